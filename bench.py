@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — GN iterations/s of the MI355X sliding-window VIO backend on BASELINE.json's headline config.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks L] [--landmark-type invdepth|xyz]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks L] [--landmark-type invdepth|xyz] [--dump-outputs DIR]
 
 One "step" = one Gauss-Newton iteration of the hot path: linearise all reprojection
 + IMU factors, reduce the landmark Schur complement, add the prior, damped pivoted LDLT of the 171x171 pose
@@ -87,6 +87,41 @@ def kernel_algorithmic_bytes(name, n, m, xyz=False):
     }[name]
 
 
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, ctx, xyz, chi2, rank, world, dist):
+    """--dump-outputs DIR: what the timed path's last step hands a caller — the window's states, the landmarks, the step it took and the
+    re-evaluated chi2 — as float64 .npy files, so that two builds run with the same arguments can be compared array for array.  N > 1:
+    the landmark arrays are gathered over the ranks in rank order (the original landmark order) and rank 0 writes.  Landmark arrays
+    larger than the 64 MB budget are replaced by a fixed, seeded sample of their rows (landmark_index.npy names the rows)."""
+    import numpy as np
+    poses, speed_bias, ext = ctx.get_window()
+    dx_pose, dx_lm = ctx.get_delta()
+    lms = ctx.get_landmarks_xyz() if xyz else ctx.get_landmarks()
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (lms, dx_lm))
+        lms = np.concatenate([p[0] for p in parts])
+        dx_lm = np.concatenate([p[1] for p in parts])
+    if rank != 0:
+        return
+    arrays = {"poses": poses, "speed_bias": speed_bias, "extrinsic": ext, "delta_pose": dx_pose, "chi2": np.array([chi2])}
+    fixed = sum(a.nbytes for a in arrays.values())
+    n = lms.shape[0]
+    row_bytes = (lms.nbytes + dx_lm.nbytes) // max(n, 1)
+    if fixed + n * row_bytes > DUMP_LIMIT_BYTES:
+        k = (DUMP_LIMIT_BYTES - fixed) // (row_bytes + 8)
+        idx = np.sort(np.random.RandomState(0).choice(n, k, replace=False))
+        lms, dx_lm = lms[idx], dx_lm[idx]
+        arrays["landmark_index"] = idx
+    arrays["landmarks_xyz" if xyz else "landmarks_inv_depth"] = lms
+    arrays["delta_landmarks"] = dx_lm
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
+
+
 def spawn_ranks(n):
     """`python bench.py --gpus N` without a launcher: start the N rank processes as children of this one — fresh interpreters,
     started before this process has made any GPU call (it never makes one) — hand them the torch.distributed environment, pass
@@ -153,7 +188,11 @@ def main():
     ap.add_argument("--replica-windows", type=int, default=16, help="N > 1: independent windows per GPU of the `replicas` block (0 skips it)")
     ap.add_argument("--replica-landmarks", type=int, default=20000)
     ap.add_argument("--no-scale-projection", action="store_true", help="N = 1: skip the scale_projection block (the sharded launch sequence on the 200 000 / N-landmark shards of configs[3], one GPU)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step handed back (window, landmarks, step, chi2) as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         sys.exit(spawn_ranks(args.gpus))          # before anything here has touched a GPU (torch is not even imported yet)
@@ -288,6 +327,8 @@ def main():
         elapsed = float(tt.item())
 
     chi2 = ctx.chi2()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, xyz, chi2, rank, world, dist)
     ms_per_step = elapsed * 1e3 / args.steps
     value = args.steps / elapsed            # iterations of THE window per second: N ranks working on one iteration count once
 

@@ -55,6 +55,42 @@ def ref_lib(vio):
     return vio.VioLib(so, "vior_")
 
 
+REF_RUNS_DIR = os.path.join(GOLDEN_DIR, "reference_runs")
+
+
+class RefRuns:
+    """What the compiled reference backend returns on a test's inputs.  Where oracle/_ref is (or can be built) it is computed live —
+    and, with VIO_RECORD_REFERENCE=1, recorded as tests/golden/reference_runs/<name>.npz (tests/golden/make_golden_reference_runs.py);
+    everywhere else it is read back from that file, so the comparison runs on every box."""
+
+    def __init__(self, vio):
+        self.lib = None
+        so = os.path.join(ORACLE_DIR, "_ref", "libvio_ref.so")
+        if not os.path.exists(so) and os.path.isdir("/root/reference/workspace"):
+            subprocess.check_call(["make", "-C", ORACLE_DIR, "-s", "ref"])
+        if os.path.exists(so):
+            self.lib = vio.VioLib(so, "vior_")
+
+    def get(self, name, fn):
+        """fn(ref_lib) -> dict of arrays, or the recorded dict of the same name."""
+        import numpy as np
+        path = os.path.join(REF_RUNS_DIR, name + ".npz")
+        if self.lib is None:
+            assert os.path.exists(path), "no recorded reference run %s: tests/golden/make_golden_reference_runs.py writes it" % name
+            with np.load(path) as z:
+                return {k: z[k] for k in z.files}
+        out = {k: np.asarray(v) for k, v in fn(self.lib).items()}
+        if os.environ.get("VIO_RECORD_REFERENCE") == "1":
+            os.makedirs(REF_RUNS_DIR, exist_ok=True)
+            np.savez_compressed(path, **out)
+        return out
+
+
+@pytest.fixture(scope="session")
+def ref_runs(vio):
+    return RefRuns(vio)
+
+
 @pytest.fixture(scope="session")
 def hip_lib(vio):
     """The product library.  No fallback: a missing build is a failure, not a skip."""

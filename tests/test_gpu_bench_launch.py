@@ -9,6 +9,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 pytestmark = pytest.mark.gpu
@@ -51,18 +52,19 @@ def test_two_ranks_launched_as_the_driver_would():
     assert abs(out["single_gpu_same_window_ms"] - one["ms_per_step"]) <= 0.25 * one["ms_per_step"], (out["single_gpu_same_window_ms"], one["ms_per_step"])
 
 
-def test_eight_ranks_launched_as_the_driver_would():
-    """The driver's own 8-GPU command — `python bench.py --gpus 8 --steps K --warmup W` — with all eight rank processes on the one device of a
-    test box: eight processes each synthesising the 200 000-landmark window, the rendezvous, 25 000 landmarks per rank (one round of
-    k_linearize workgroups), the exchange of eight 24 KB slabs summed in rank order, cpu_baseline on the shared window, the `replicas`
-    block.  The first real 8-GPU launch is then not also the first 8-process launch (VERDICT r05 weak #9)."""
-    p, out = run_bench(["--gpus", "8", "--steps", "4", "--warmup", "1", "--replica-windows", "1", "--replica-landmarks", "2000", "--cpu-baseline-steps", "1"],
+def test_four_ranks_launched_as_the_driver_would():
+    """The driver's N > 2 command — `python bench.py --gpus N --steps K --warmup W` — with all four rank processes on the one device of a
+    test box (four, not eight: with this test's own process that is five processes holding the GPU, and a shared machine allows at most
+    six): four processes each synthesising the 200 000-landmark window, the rendezvous, 50 000 landmarks per rank, the exchange of four
+    24 KB slabs summed in rank order, cpu_baseline on the shared window, the `replicas` block.  The first real multi-GPU launch is then
+    not also the first launch of more than two rank processes (VERDICT r05 weak #9)."""
+    p, out = run_bench(["--gpus", "4", "--steps", "4", "--warmup", "1", "--replica-windows", "1", "--replica-landmarks", "2000", "--cpu-baseline-steps", "1"],
                        {"VIO_BENCH_ONE_DEVICE": "1"}, timeout=1500)
     assert p.returncode == 0, p.stderr[-3000:]
     assert out is not None, p.stdout[-2000:]
-    assert out["n_gpus"] == 8 and out["steps"] == 4 and out["scaling"] == "strong"
+    assert out["n_gpus"] == 4 and out["steps"] == 4 and out["scaling"] == "strong"
     cfg = out["config"]
-    assert cfg["landmarks_total"] == 200000 and cfg["landmarks_per_gpu"] == 25000 and cfg["observations_per_gpu"] == 100000
+    assert cfg["landmarks_total"] == 200000 and cfg["landmarks_per_gpu"] == 50000 and cfg["observations_per_gpu"] == 200000
     assert cfg["exchange"] == "hook_host" and cfg["all_ranks_on_one_device"] is True
     assert abs(out["value"] * out["ms_per_step"] - 1e3) <= 1e-6 * 1e3
     assert out["final_chi2"] > 0 and out["final_chi2"] == out["final_chi2"]
@@ -113,3 +115,23 @@ def test_single_gpu_line_is_the_headline_window():
     assert out["config"]["landmarks_total"] == 20000 and out["config"]["observations_per_gpu"] == 80000
     assert out["single_gpu_same_window_ms"] is None
     assert abs(out["value"] * out["ms_per_step"] - 1e3) <= 1e-6 * 1e3
+
+
+def test_dump_outputs_are_the_last_steps_result_and_repeat_exactly(tmp_path):
+    """--dump-outputs DIR: the timed path's last step as float64 .npy files; the same arguments give the same inputs, so two runs give
+    the same arrays — and one more timed step gives a different state."""
+    base = ["--warmup", "2", "--landmarks", "3000", "--no-cpu-baseline", "--batch", "0", "--no-per-frame", "--no-small-regime", "--no-scale-projection"]
+    runs = {}
+    for tag, steps in (("a", 5), ("b", 5), ("c", 6)):
+        p, out = run_bench(base + ["--steps", str(steps), "--dump-outputs", str(tmp_path / tag)])
+        assert p.returncode == 0, p.stderr[-3000:]
+        assert out["steps"] == steps
+        runs[tag] = (out, {f[:-4]: np.load(tmp_path / tag / f) for f in sorted(os.listdir(tmp_path / tag))})
+    out, arrs = runs["a"]
+    assert set(arrs) == {"poses", "speed_bias", "extrinsic", "delta_pose", "chi2", "landmarks_inv_depth", "delta_landmarks"}
+    assert all(a.dtype == np.float64 and np.isfinite(a).all() for a in arrs.values())
+    assert arrs["landmarks_inv_depth"].shape == (3000,) and arrs["delta_landmarks"].shape == (3000,) and arrs["poses"].shape == (11, 7)
+    assert float(arrs["chi2"][0]) == out["final_chi2"]
+    for k, a in arrs.items():
+        np.testing.assert_array_equal(a, runs["b"][1][k], err_msg=k)
+    assert np.abs(runs["c"][1]["landmarks_inv_depth"] - arrs["landmarks_inv_depth"]).max() > 0

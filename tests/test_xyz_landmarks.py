@@ -79,22 +79,27 @@ def test_kind_switch_and_unsupported_calls(vio, oracle_lib):
     assert ctx.solve(10).final_chi2 == a and a != b
 
 
-@pytest.mark.ref
 @pytest.mark.parametrize("n,seed,ragged,ext_fixed,kw", [(1, 1, False, 1, {}), (12, 2, True, 1, {}), (80, 3, True, 0, {}),
                                                         (40, 4, False, 1, dict(obs_per_landmark=10))])
-def test_oracle_vs_reference_on_fresh_xyz_windows(vio, oracle_lib, ref_lib, n, seed, ragged, ext_fixed, kw):
+def test_oracle_vs_reference_on_fresh_xyz_windows(vio, oracle_lib, ref_runs, n, seed, ragged, ext_fixed, kw):
     w = vio.synth.make_window_xyz(n, seed=seed, ragged=ragged, **kw)
-    co, cr = oracle_lib.context(ext_fixed=ext_fixed), ref_lib.context(ext_fixed=ext_fixed)
+
+    def reference(ref_lib):
+        cr = ref_lib.context(ext_fixed=ext_fixed)
+        cr.load(w)
+        out = tu.run_stepwise(cr)
+        cr.load(w)
+        out.update(tu.run_solve(cr)[0])
+        return out
+    b = sb = ref_runs.get("xyz_stepwise_and_solve_n%d_s%d" % (n, seed), reference)
+    co = oracle_lib.context(ext_fixed=ext_fixed)
     co.load(w)
-    cr.load(w)
-    a, b = tu.run_stepwise(co), tu.run_stepwise(cr)
+    a = tu.run_stepwise(co)
     assert tu.scaled_sym_err(a["Hs"][np.ix_(CAM, CAM)], b["Hs"][np.ix_(CAM, CAM)]) <= 1e-9
     assert np.abs(a["dx_pose"] - b["dx_pose"]).max() <= 1e-9 and np.abs(a["dx_lm"] - b["dx_lm"]).max() <= 1e-9
     assert tu.rel_max(a["hll"], b["hll"]) <= 1e-11 and int(a["accepted"]) == int(b["accepted"])
     co.load(w)
-    cr.load(w)
     sa, _ = tu.run_solve(co)
-    sb, _ = tu.run_solve(cr)
     assert int(sa["iterations"]) == int(sb["iterations"])
     assert np.abs(sa["posesF"] - sb["posesF"]).max() <= 1e-6 and np.abs(sa["invdF"] - sb["invdF"]).max() <= 1e-6
 
@@ -282,14 +287,16 @@ def test_oracle_xyz_marginalize_against_the_reference_fixtures(vio, oracle_lib):
     check_xyz_marg0_nan(oracle_lib, vio)
 
 
-@pytest.mark.ref
-def test_reference_xyz_marginalize_reproduces_its_fixtures(vio, ref_lib):
+def test_reference_xyz_marginalize_reproduces_its_fixtures(vio, ref_runs):
     for f in MARG0_FIXTURES + ["marg0_xyz_n40_s71_tukey_nan.npz"]:
         z = np.load(os.path.join(GOLDEN_DIR, f))
         w, kw = marg0_window(vio, z)
-        ctx = ref_lib.context(**kw)
-        ctx.load(w)
-        m = ctx.marginalize(vio.MARG_OLD, allow_nonfinite=True)
+
+        def reference(ref_lib):
+            ctx = ref_lib.context(**kw)
+            ctx.load(w)
+            return ctx.marginalize(vio.MARG_OLD, allow_nonfinite=True)
+        m = ref_runs.get("xyz_marginalize_" + f[:-4], reference)
         for k in tu.PRIOR_FIELDS:
             np.testing.assert_array_equal(m[k], z["marg0_" + k])
 
