@@ -1,0 +1,217 @@
+"""numpy reference of the marginal covariances (include/vio_covariance.h), built from the oracle's own pieces:
+vioo_reproj_edge / vioo_reproj_xyz_edge for the Jacobians, vioo_robust_info2 for the robust weights, vioo_get_pose_hessian for the
+pose block of the Hessian.  Shared by test_covariance_reference.py (CPU) and test_gpu_covariance.py."""
+import ctypes as C
+
+import numpy as np
+
+PD, CD, NF = 171, 72, 11
+CAM_FULL = np.array([a if a < 6 else 6 + 15 * ((a - 6) // 6) + (a - 6) % 6 for a in range(CD)])
+
+
+def _dp(a):
+    return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def keep_index(ext_fixed, gauge, xyz=False):
+    """The 171-indices that stay variables: the extrinsic goes when fixed (always for XYZ windows), frame 0's pose under gauge 1."""
+    keep = []
+    for v in range(PD):
+        if v < 6 and (ext_fixed or xyz):
+            continue
+        if gauge == 1 and 6 <= v < 12:
+            continue
+        keep.append(v)
+    return np.array(keep)
+
+
+def _huber_beyond(cfg, r):
+    s2 = cfg.reproj_sqrt_info ** 2
+    return cfg.loss_type == 1 and r[0] * (s2 * r[0]) + r[1] * (s2 * r[1]) > cfg.loss_delta ** 2
+
+
+def robust_info(fr, cfg, r, W, drho):
+    """vioo_robust_info2 as a 2 x 2."""
+    fr(C.c_int(cfg.loss_type), C.c_double(cfg.loss_delta), C.c_double(cfg.reproj_sqrt_info), _dp(r), C.byref(drho), _dp(W))
+    return W.reshape(2, 2).copy()
+
+
+def huber_ambiguous(oracle_lib, cfg, w, poses, ext, vals):
+    """Landmarks with a Huber edge beyond delta, where each implementation's choice of the correction term is rounding noise: the GPU
+    tests compare the information and variance of the others."""
+    n = len(vals)
+    out = np.zeros(n, dtype=bool)
+    if cfg.loss_type != 1:
+        return out
+    fe, fx = oracle_lib.dll.vioo_reproj_edge, oracle_lib.dll.vioo_reproj_xyz_edge
+    fe.restype = fx.restype = None
+    r = np.zeros(2)
+    poses = np.ascontiguousarray(poses, dtype=np.float64)
+    ext = np.ascontiguousarray(ext, dtype=np.float64)
+    for e in range(len(w.lm)):
+        l = int(w.lm[e])
+        if getattr(w, "xyz", None) is not None:
+            fx(_dp(np.ascontiguousarray(poses[int(w.frame[e])])), _dp(ext), _dp(np.ascontiguousarray(vals[l], dtype=np.float64)),
+               _dp(np.ascontiguousarray(w.pts[e], dtype=np.float64)), _dp(r), None, None)
+        else:
+            fe(_dp(np.ascontiguousarray(poses[int(w.host[e])])), _dp(np.ascontiguousarray(poses[int(w.target[e])])), _dp(ext),
+               C.c_double(vals[l]), _dp(np.ascontiguousarray(w.pts_i[e], dtype=np.float64)),
+               _dp(np.ascontiguousarray(w.pts_j[e], dtype=np.float64)), _dp(r), None, None, None, None)
+        out[l] |= _huber_beyond(cfg, r)
+    return out
+
+
+def landmark_terms(oracle_lib, cfg, w, poses, ext, vals, landmarks=None):
+    """(h, Wl) of the landmarks at the state (poses, ext, vals): h (n,) and Wl (n, 72) for inverse depths, H_ll (n, 3, 3) and
+    W_l (n, 72, 3) for XYZ.  landmarks: the subset to form (default all), in that order.
+    Huber beyond delta: rho' + 2 rho'' e2 is exactly zero there, and whether Edge::RobustInfo adds its correction follows the sign of
+    the rounding; huber_ambiguous() lists the landmarks with such an edge."""
+    xyz = getattr(w, "xyz", None) is not None
+    fe, fx, fr = oracle_lib.dll.vioo_reproj_edge, oracle_lib.dll.vioo_reproj_xyz_edge, oracle_lib.dll.vioo_robust_info2
+    for f in (fe, fx, fr):
+        f.restype = None
+    n = len(vals)
+    sel = np.arange(n) if landmarks is None else np.asarray(landmarks)
+    pos = -np.ones(n, dtype=np.int64)
+    pos[sel] = np.arange(sel.size)
+    D = 3 if xyz else 1
+    h = np.zeros((sel.size, D, D))
+    Wl = np.zeros((sel.size, CD, D))
+    poses = np.ascontiguousarray(poses, dtype=np.float64)
+    ext = np.ascontiguousarray(ext, dtype=np.float64)
+    r, W, drho = np.zeros(2), np.zeros(4), C.c_double()
+    lm = np.asarray(w.lm)
+    for e in np.nonzero(pos[lm] >= 0)[0]:
+        l = int(lm[e])
+        k = pos[l]
+        if xyz:
+            f = int(w.frame[e])
+            Jf, Jp = np.zeros(6), np.zeros(12)
+            fx(_dp(np.ascontiguousarray(poses[f])), _dp(ext), _dp(np.ascontiguousarray(vals[l], dtype=np.float64)),
+               _dp(np.ascontiguousarray(w.pts[e], dtype=np.float64)), _dp(r), _dp(Jf), _dp(Jp))
+            Wm = robust_info(fr, cfg, r, W, drho)
+            Jf, Jp = Jf.reshape(2, 3), Jp.reshape(2, 6)
+            h[k] += Jf.T @ Wm @ Jf
+            Wl[k, 6 + 6 * f:12 + 6 * f, :] += Jp.T @ Wm @ Jf
+        else:
+            fi, fj = int(w.host[e]), int(w.target[e])
+            Jl, Ji, Jj, Je = np.zeros(2), np.zeros(12), np.zeros(12), np.zeros(12)
+            fe(_dp(np.ascontiguousarray(poses[fi])), _dp(np.ascontiguousarray(poses[fj])), _dp(ext), C.c_double(vals[l]),
+               _dp(np.ascontiguousarray(w.pts_i[e], dtype=np.float64)), _dp(np.ascontiguousarray(w.pts_j[e], dtype=np.float64)),
+               _dp(r), _dp(Jl), _dp(Ji), _dp(Jj), _dp(Je))
+            Wm = robust_info(fr, cfg, r, W, drho)
+            Jl = Jl.reshape(2, 1)
+            h[k] += Jl.T @ Wm @ Jl
+            Wl[k, 6 + 6 * fi:12 + 6 * fi, :] += Ji.reshape(2, 6).T @ Wm @ Jl
+            Wl[k, 6 + 6 * fj:12 + 6 * fj, :] += Jj.reshape(2, 6).T @ Wm @ Jl
+            if not cfg.ext_fixed:
+                Wl[k, 0:6, :] += Je.reshape(2, 6).T @ Wm @ Jl
+    if xyz:
+        return h, Wl
+    return h[:, 0, 0], Wl[:, :, 0]
+
+
+def pose_cov_from_schur(S, keep):
+    """inv of S restricted to `keep` (its lower triangle mirrored, as the kernel reads it), scattered into a 171 x 171 with zeros."""
+    Sl = np.tril(S)
+    Sl = Sl + np.tril(Sl, -1).T
+    out = np.zeros((PD, PD))
+    out[np.ix_(keep, keep)] = np.linalg.inv(Sl[np.ix_(keep, keep)])
+    return out
+
+
+def landmark_cov(pose_cov, h, Wl):
+    """var_l = 1/h_l + w_l^T Sigma_cc w_l / h_l^2 (n,), or Sigma_l = H^-1 + H^-1 W^T Sigma_cc W H^-1 (n, 3, 3)."""
+    Scc = pose_cov[np.ix_(CAM_FULL, CAM_FULL)]
+    if h.ndim == 1:
+        q = np.einsum("la,ab,lb->l", Wl, Scc, Wl)
+        return 1.0 / h + q / h ** 2
+    Hi = np.linalg.inv(h)
+    Q = np.einsum("lad,ab,lbe->lde", Wl, Scc, Wl)
+    return Hi + Hi @ Q @ Hi
+
+
+def full_hessian(Hpp, h, Wl, keep):
+    """The dense Hessian of the window restricted to the kept pose variables and the landmarks: [[Hpp, Hpm], [Hmp, Hmm]]."""
+    D = 1 if h.ndim == 1 else 3
+    n = h.shape[0]
+    Hpm = np.zeros((PD, n * D))
+    Hmm = np.zeros((n * D, n * D))
+    for l in range(n):
+        Hpm[CAM_FULL, D * l:D * l + D] = Wl[l].reshape(CD, D)
+        Hmm[D * l:D * l + D, D * l:D * l + D] = h[l].reshape(D, D)
+    K = np.concatenate([keep, PD + np.arange(n * D)])
+    H = np.block([[Hpp, Hpm], [Hpm.T, Hmm]])
+    return H[np.ix_(K, K)]
+
+
+def scaled_err(A, B):
+    """max |A_ij - B_ij| / sqrt(B_ii B_jj) over the entries whose diagonal is not zero."""
+    d = np.sqrt(np.abs(np.diag(B)))
+    nz = d > 0
+    s = np.outer(d[nz], d[nz])
+    return float(np.max(np.abs(A[np.ix_(nz, nz)] - B[np.ix_(nz, nz)]) / s))
+
+
+def cond_scaled(S, keep):
+    """Condition number of S[keep, keep] after symmetric diagonal scaling: what the fp64 inverse can be trusted to."""
+    A = S[np.ix_(keep, keep)]
+    d = 1.0 / np.sqrt(np.abs(np.diag(A)))
+    return float(np.linalg.cond(A * np.outer(d, d)))
+
+
+def well_posed_prior(S_diag, prior=None, rel=1e-2, anchor=False):
+    """A prior that makes a synthetic window's covariance well-posed.  The windows of synth.make_window move too little for every
+    direction of the IMU states to be observable (a common offset of the 11 accelerometer biases is a null direction of H_pp_schur
+    whatever the gauge), so frame 0's speed and biases get rel x their diagonal of H_pp_schur (S_diag, 171) as extra information;
+    anchor=True does the same for frame 0's pose (what gauge "none" needs without a marginalisation prior).
+    prior: a marginalisation prior to add them to, or None."""
+    P = 156
+    if prior is None:
+        prior = {"H": np.zeros((P, P)), "b": np.zeros(P), "err": np.zeros(P), "jt_inv": np.zeros((P, P))}
+    prior = {k: np.array(v, dtype=np.float64) for k, v in prior.items()}
+    idx = np.arange(6 if anchor else 12, 21)
+    prior["H"][idx, idx] += rel * np.asarray(S_diag)[idx]
+    return prior
+
+
+# (name, landmarks, ragged, loss, ext_fixed, marginalisation prior, gauge, xyz)
+CASES = [
+    ("plain50_cauchy", 50, False, 2, 0, False, 1, False),
+    ("ragged150_huber_extfixed", 150, True, 1, 1, False, 1, False),
+    ("ragged120_cauchy_none", 120, True, 2, 0, False, 0, False),
+    ("prior100_cauchy_fix", 100, False, 2, 0, True, 1, False),
+    ("prior100_cauchy_none", 100, False, 2, 0, True, 0, False),
+    ("prior100_ragged_extfixed_none", 100, True, 2, 1, True, 0, False),
+    ("xyz80_cauchy", 80, False, 2, 0, False, 1, True),
+    ("xyz90_huber_none", 90, False, 1, 0, False, 0, True),
+]
+
+
+def make_case(vio, oracle_lib, case):
+    """(window, context overrides, gauge) of one of CASES.  The prior is built with the oracle (MargOldFrame of a neighbouring
+    window) and topped up by well_posed_prior from the window's own H_pp_schur."""
+    name, n, ragged, loss, ext_fixed, marg, gauge, xyz = case
+    make = vio.synth.make_window_xyz if xyz else vio.synth.make_window
+    w = make(n, seed=3, ragged=ragged, t0=1.1)
+    kw = dict(ext_fixed=ext_fixed, loss_type=loss)
+    if loss == 1:
+        kw["loss_delta"] = 5.0      # (at delta = 1 every edge of these windows lies beyond delta: see huber_ambiguous)
+    mp = None
+    if marg:
+        w0 = vio.synth.make_window(n, seed=4)
+        c0 = oracle_lib.context(**kw)
+        c0.load(w0)
+        c0.solve(5)
+        mp = c0.marginalize(vio.MARG_OLD)
+    c = oracle_lib.context(**kw)
+    c.load(w)
+    c.linearize()
+    S0, _ = c.get_schur_system()
+    w.prior = well_posed_prior(np.diag(S0), mp, anchor=(gauge == 0))
+    return w, kw, gauge
+
+
+def tolerance(S, keep):
+    """What fp64 allows for an inverse of S[keep, keep] in the scaled metric: 100 eps kappa, and no less than 1e-10."""
+    return max(1e-10, 100 * np.finfo(np.float64).eps * cond_scaled(S, keep))

@@ -5,13 +5,16 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import capi, sharded, stream, synth
+from . import capi, covariance, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
+from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB = os.environ.get("VIO_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "libvio_hip.so")     # (VIO_HIP_LIB: another build, for A/B measurements)
+
+COV_LIB = os.path.join(PKG_DIR, "csrc", "libvio_cov_hip.so")     # include/vio_covariance.h, linked against libvio_hip.so
 
 _hip = None
 
@@ -45,3 +48,20 @@ def load_hip_debug():
             pass
         _hip_debug = VioLib(os.environ.get("VIO_HIP_DEBUG_LIB") or os.path.join(PKG_DIR, "csrc", "diag", "libvio_hip_debug.so"), "vio_")
     return _hip_debug
+
+
+_cov = None
+
+
+def load_cov():
+    """Load the covariance library (csrc/libvio_cov_hip.so).  It resolves libvio_hip.so through its rpath: csrc/libvio_hip.so, which
+    load_hip() loads first so that both share that one instance.  With VIO_HIP_LIB naming another build the process would hold two
+    copies and hand one's contexts to the other, so that is refused."""
+    global _cov
+    if _cov is None:
+        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
+        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
+            raise RuntimeError("load_cov: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_cov_hip.so is linked against" % (HIP_LIB, own))
+        load_hip()
+        _cov = CovLib(COV_LIB)
+    return _cov

@@ -223,8 +223,13 @@ class VioContext:
             else:
                 setattr(self.cfg, k, v)
         self._ck(self.lib.fn["set_config"](self.h, C.byref(self.cfg)), "set_config")
+        if getattr(self, "_cov", None) is not None:          # the covariance handle's copy of the loss / information / ext_fixed
+            self._cov.set_config(self.cfg)
 
     def close(self):
+        cov = self.__dict__.pop("_cov", None)
+        if cov is not None:
+            cov.close()
         if self.h:
             self.lib.fn["destroy"](self.h)
             self.h = C.c_void_p()
@@ -411,6 +416,19 @@ class VioContext:
         if not (st == -3 and allow_nonfinite):
             self._ck(st, "marginalize_end")
         return {"H": H, "b": b, "err": err, "jt_inv": jt}
+
+    def covariance(self, w, gauge="fix_oldest"):
+        """Marginal covariances at the current state (include/vio_covariance.h; HIP library only): (pose_cov (171, 171),
+        lm_var (n,) or, for an XYZ window, (n, 3, 3)).  w: the window passed to load(); gauge: "fix_oldest" (frame 0's pose held
+        fixed) or "none".  The handle of the covariance library is kept on the context from call to call."""
+        if self.lib.prefix != "vio_":
+            raise VioError(-5, self.lib.prefix + "covariance", "(the covariance library binds the HIP library's contexts only)")
+        if getattr(self, "_cov", None) is None:
+            from . import load_cov
+            self._cov = load_cov().create(self)
+        else:
+            self._cov.set_config(self.cfg)          # (set_config forwards it too; this also covers a cfg edited in place)
+        return self._cov.compute(w, gauge)
 
     # ---- read back ------------------------------------------------------------------------
     def get_window(self):

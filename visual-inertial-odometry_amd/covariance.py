@@ -1,0 +1,134 @@
+"""ctypes binding of include/vio_covariance.h (csrc/libvio_cov_hip.so): marginal covariances of a solved window.
+
+    cov = vio.load_cov()
+    pose_cov, lm_var = ctx.covariance(w)                 # VioContext of the HIP library, w: the window passed to ctx.load()
+    P_newest = vio.pose_block(pose_cov, vio.WINDOW_SIZE) # 6 x 6 covariance of the newest pose (position, rotation)
+
+Ordering of pose_cov: [ext(6) | (pose 6, speed-bias 9) x 11] (vio_get_schur_system's); fixed variables are zero rows / columns.
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from .capi import NUM_FRAMES, POSE_DIM, VioError, _dp, _f64, _ip
+
+GAUGE_NONE, GAUGE_FIX_OLDEST = 0, 1
+GAUGES = {"none": GAUGE_NONE, "fix_oldest": GAUGE_FIX_OLDEST}
+
+
+def pose_block(pose_cov, k):
+    """The 6 x 6 covariance of frame k's pose (position, then rotation) out of a 171 x 171 pose_cov."""
+    if not 0 <= k < NUM_FRAMES:
+        raise IndexError("frame %d outside the window (0 .. %d)" % (k, NUM_FRAMES - 1))
+    o = 6 + 15 * k
+    return np.array(pose_cov[o:o + 6, o:o + 6])
+
+
+def speed_bias_block(pose_cov, k):
+    """The 9 x 9 covariance of frame k's speed and biases."""
+    if not 0 <= k < NUM_FRAMES:
+        raise IndexError("frame %d outside the window (0 .. %d)" % (k, NUM_FRAMES - 1))
+    o = 12 + 15 * k
+    return np.array(pose_cov[o:o + 9, o:o + 9])
+
+
+class CovLib:
+    """libvio_cov_hip.so: vio_cov_* (it resolves libvio_hip.so's symbols from the instance already loaded in the process)."""
+
+    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "landmark_information",
+               "pivot_ratio", "timing"]
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise FileNotFoundError(
+                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
+        self.path = path
+        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
+        self.fn = {s: getattr(self.dll, "vio_cov_" + s) for s in self.SYMBOLS}
+        for s in self.SYMBOLS:
+            self.fn[s].restype = C.c_int
+        self.fn["destroy"].restype = None
+        self.fn["last_error"].restype = C.c_char_p
+        self.fn["version"].restype = C.c_int32
+
+    def create(self, ctx):
+        """A vio_cov handle bound to `ctx` (a VioContext of the HIP library)."""
+        return CovHandle(self, ctx)
+
+
+class CovHandle:
+    def __init__(self, lib, ctx):
+        self.lib = lib
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        st = lib.fn["create"](ctx.h, C.byref(ctx.cfg), C.byref(self.h))
+        if st != 0:
+            raise VioError(st, "vio_cov_create")
+
+    def close(self):
+        if self.h:
+            self.lib.fn["destroy"](self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, st, where):
+        if st != 0:
+            msg = self.lib.fn["last_error"](self.h)
+            raise VioError(st, "vio_cov_" + where, (msg or b"").decode(errors="replace"))
+
+    def set_config(self, cfg):
+        """vio_cov_set_config: the configuration the context now runs with (after VioContext.set_config)."""
+        self._ck(self.lib.fn["set_config"](self.h, C.byref(cfg)), "set_config")
+
+    def pivot_ratio(self):
+        """min_k d_k / S_kk of the last successful compute: near eps, the window barely constrains some direction."""
+        r = C.c_double()
+        self._ck(self.lib.fn["pivot_ratio"](self.h, C.byref(r)), "pivot_ratio")
+        return r.value
+
+    def compute(self, w, gauge="fix_oldest", pose_cov=None, lm_out=None):
+        """(pose_cov (171, 171), lm_var (n,) or lm_cov (n, 3, 3)) of the context's current state.  w: the window passed to load().
+        pose_cov / lm_out: optional arrays to fill (they are left untouched when the call fails)."""
+        g = (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
+        gi = GAUGES[gauge] if isinstance(gauge, str) else int(gauge)
+        xyz = (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
+        n = self.ctx.n
+        P = np.zeros((POSE_DIM, POSE_DIM)) if pose_cov is None else pose_cov
+        assert P.shape == (POSE_DIM, POSE_DIM) and P.dtype == np.float64 and P.flags.c_contiguous
+        L = (np.zeros((n, 3, 3)) if xyz else np.zeros(n)) if lm_out is None else lm_out
+        assert L.dtype == np.float64 and L.flags.c_contiguous and L.size == n * (9 if xyz else 1)
+        Lp = _dp(L) if n else None
+        lm = np.ascontiguousarray(g("lm"), dtype=np.int32)
+        m = lm.size
+        if xyz:
+            fr = np.ascontiguousarray(g("frame"), dtype=np.int32)
+            pts = _f64(g("pts"), (m, 2))
+            st = self.lib.fn["compute_xyz"](self.h, C.c_int32(gi), C.c_int64(m), _ip(lm), _ip(fr), _dp(pts), C.c_int64(n), _dp(P), Lp)
+            self._ck(st, "compute_xyz")
+        else:
+            host = np.ascontiguousarray(g("host"), dtype=np.int32)
+            tgt = np.ascontiguousarray(g("target"), dtype=np.int32)
+            pi, pj = _f64(g("pts_i"), (m, 2)), _f64(g("pts_j"), (m, 2))
+            st = self.lib.fn["compute"](self.h, C.c_int32(gi), C.c_int64(m), _ip(lm), _ip(host), _ip(tgt), _dp(pi), _dp(pj),
+                                        C.c_int64(n), _dp(P), Lp)
+            self._ck(st, "compute")
+        return P, L
+
+    def landmark_information(self, xyz=False):
+        """h_l (n,) or H_ll (n, 3, 3) as the last successful compute recomputed them."""
+        n = self.ctx.n
+        out = np.zeros((max(n, 1), 3, 3)) if xyz else np.zeros(max(n, 1))
+        self._ck(self.lib.fn["landmark_information"](self.h, C.c_int64(n), _dp(out)), "landmark_information")
+        return out[:n]
+
+    def timing(self):
+        """ms of the last compute: host (linearise + read-back + upload), k_cov_pose, k_cov_landmarks, whole call."""
+        out = (C.c_double * 4)()
+        self._ck(self.lib.fn["timing"](self.h, out), "timing")
+        return {"host_ms": out[0], "k_cov_pose_ms": out[1], "k_cov_landmarks_ms": out[2], "total_ms": out[3]}
