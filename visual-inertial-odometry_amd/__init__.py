@@ -5,16 +5,18 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import capi, covariance, sharded, stream, synth
+from . import capi, covariance, residuals, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
+from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 HIP_LIB = os.environ.get("VIO_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "libvio_hip.so")     # (VIO_HIP_LIB: another build, for A/B measurements)
 
 COV_LIB = os.path.join(PKG_DIR, "csrc", "libvio_cov_hip.so")     # include/vio_covariance.h, linked against libvio_hip.so
+RES_LIB = os.path.join(PKG_DIR, "csrc", "libvio_res_hip.so")     # include/vio_residuals.h, linked against libvio_hip.so
 
 _hip = None
 
@@ -65,3 +67,19 @@ def load_cov():
         load_hip()
         _cov = CovLib(COV_LIB)
     return _cov
+
+
+_res = None
+
+
+def load_res():
+    """Load the residual library (csrc/libvio_res_hip.so), under the same rule as load_cov: it resolves libvio_hip.so through its rpath,
+    so a VIO_HIP_LIB naming another build is refused."""
+    global _res
+    if _res is None:
+        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
+        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
+            raise RuntimeError("load_res: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_res_hip.so is linked against" % (HIP_LIB, own))
+        load_hip()
+        _res = ResLib(RES_LIB)
+    return _res

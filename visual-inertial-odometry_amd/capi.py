@@ -225,11 +225,14 @@ class VioContext:
         self._ck(self.lib.fn["set_config"](self.h, C.byref(self.cfg)), "set_config")
         if getattr(self, "_cov", None) is not None:          # the covariance handle's copy of the loss / information / ext_fixed
             self._cov.set_config(self.cfg)
+        if getattr(self, "_res", None) is not None:          # ... and the residual handle's (loss, information, gravity)
+            self._res.set_config(self.cfg)
 
     def close(self):
-        cov = self.__dict__.pop("_cov", None)
-        if cov is not None:
-            cov.close()
+        for k in ("_cov", "_res"):
+            hd = self.__dict__.pop(k, None)
+            if hd is not None:
+                hd.close()
         if self.h:
             self.lib.fn["destroy"](self.h)
             self.h = C.c_void_p()
@@ -429,6 +432,21 @@ class VioContext:
         else:
             self._cov.set_config(self.cfg)          # (set_config forwards it too; this also covers a cfg edited in place)
         return self._cov.compute(w, gauge)
+
+    def residuals(self, w, focal=None, outlier_px=3.0):
+        """Per-edge residuals, the chi2 breakdown and landmark outlier flags at the current state (include/vio_residuals.h; HIP
+        library only): a dict of obs (m, 4), lm (n, 3), flags (n,) uint8 and summary (dict).  w: the window passed to load();
+        focal: pixels per normalised-plane unit (default synth.FOCAL); outlier_px: the mean pixel error above which bit 0 is set.
+        The handle of the residual library is kept on the context from call to call."""
+        if self.lib.prefix != "vio_":
+            raise VioError(-5, self.lib.prefix + "residuals", "(the residual library binds the HIP library's contexts only)")
+        from . import synth
+        if getattr(self, "_res", None) is None:
+            from . import load_res
+            self._res = load_res().create(self)
+        else:
+            self._res.set_config(self.cfg)          # (set_config forwards it too; this also covers a cfg edited in place)
+        return self._res.compute(w, synth.FOCAL if focal is None else focal, outlier_px)
 
     # ---- read back ------------------------------------------------------------------------
     def get_window(self):

@@ -16,6 +16,7 @@
 #include <vector>
 
 #include "vio_device_math.h"
+#include "vio_obs_csr.h"
 #include "../../include/vio_covariance.h"
 
 #define PD VIO_POSE_DIM                    // 171
@@ -512,13 +513,9 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
     }
     // CSR over the landmarks (stable: a landmark's observations keep the caller's order)
     int *off = hi + iOff, *ofr = hi + iOfr, *oh = hi + iHost;
-    for (int64_t l = 0; l <= n; ++l) off[l] = 0;
-    for (int64_t e = 0; e < m; ++e) ++off[lm[e] + 1];
-    for (int64_t l = 0; l < n; ++l) off[l + 1] += off[l];
-    std::vector<int> fill(off, off + n);
     for (int64_t l = 0; l < n; ++l) oh[l] = -1;
-    for (int64_t e = 0; e < m; ++e) {
-        const int l = lm[e], q = fill[l]++;
+    int mixed = -1;                         // a landmark whose observations name different host frames
+    const bool ok = obs_csr(m, lm, n, off, [&](int64_t e, int l, int q) {
         ofr[q] = target[e];
         hd[oPj + 2 * (size_t)q] = pts_j[2 * e];
         hd[oPj + 2 * (size_t)q + 1] = pts_j[2 * e + 1];
@@ -528,10 +525,13 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
                 hd[oPi + 2 * (size_t)l] = pts_i[2 * e];
                 hd[oPi + 2 * (size_t)l + 1] = pts_i[2 * e + 1];
             } else if (oh[l] != host[e]) {
-                return fail(cv, VIO_ERR_BAD_ARG, "landmark %d has observations with different host frames", l);
+                mixed = l;
+                return false;
             }
         }
-    }
+        return true;
+    });
+    if (!ok) return fail(cv, VIO_ERR_BAD_ARG, "landmark %d has observations with different host frames", mixed);
     if (D == 1)
         for (int64_t l = 0; l < n; ++l)
             if (oh[l] < 0) { oh[l] = 0; hd[oPi + 2 * (size_t)l] = 0; hd[oPi + 2 * (size_t)l + 1] = 0; }

@@ -91,6 +91,40 @@ DEV void d_pose_plus(const double *p, const double *d, double *o) {
     o[3] = q.x; o[4] = q.y; o[5] = q.z; o[6] = q.w;
 }
 
+// EdgeReprojection::ComputeResidual (edge_reprojection.cc:18-37), the residual alone: Ri / Rj the rotations of the host and target
+// poses, ric / tic the extrinsic's, lam the inverse depth, p_i / p_j the normalised observations.  r (2); returns the point's depth in
+// the target camera.  (The same expressions as k_cov_landmarks's, which fuses them with the Jacobians.)
+DEV double d_reproj_residual(const double *Ri, const double *Pi, const double *Rj, const double *Pj, const double *ric,
+                             const double *tic, double lam, const double *p_i, const double *p_j, double *r) {
+    const double pc_i[3] = {p_i[0] / lam, p_i[1] / lam, 1.0 / lam};
+    double pb_i[3], pw[3], dd[3], pb_j[3], ee[3], pc_j[3];
+    d_m3_vec(ric, pc_i, pb_i);
+    for (int k = 0; k < 3; ++k) pb_i[k] += tic[k];
+    d_m3_vec(Ri, pb_i, pw);
+    for (int k = 0; k < 3; ++k) dd[k] = pw[k] + Pi[k] - Pj[k];
+    d_m3_tvec(Rj, dd, pb_j);
+    for (int k = 0; k < 3; ++k) ee[k] = pb_j[k] - tic[k];
+    d_m3_tvec(ric, ee, pc_j);
+    const double dep = pc_j[2];
+    r[0] = pc_j[0] / dep - p_j[0];
+    r[1] = pc_j[1] / dep - p_j[1];
+    return dep;
+}
+
+// EdgeReprojectionXYZ::ComputeResidual (edge_reprojection.cc:130-145), the residual alone: world point pw seen from the pose (Rj, Pj).
+DEV double d_reproj_xyz_residual(const double *Rj, const double *Pj, const double *ric, const double *tic, const double *pw,
+                                 const double *obs, double *r) {
+    double dd[3], pim[3], ee[3], pc[3];
+    for (int k = 0; k < 3; ++k) dd[k] = pw[k] - Pj[k];
+    d_m3_tvec(Rj, dd, pim);
+    for (int k = 0; k < 3; ++k) ee[k] = pim[k] - tic[k];
+    d_m3_tvec(ric, ee, pc);
+    const double dep = pc[2];
+    r[0] = pc[0] / dep - obs[0];
+    r[1] = pc[1] / dep - obs[1];
+    return dep;
+}
+
 // LossFunction::Compute (loss_function.cc:9-47); type 0 = no loss object
 DEV void d_loss(int type, double delta, double e2, double &r0, double &r1, double &r2) {
     if (type == 2) {            // Cauchy

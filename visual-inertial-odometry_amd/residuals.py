@@ -1,0 +1,147 @@
+"""ctypes binding of include/vio_residuals.h (csrc/libvio_res_hip.so): per-edge residuals, the chi2 breakdown and landmark outlier
+flags of a window.
+
+    r = ctx.residuals(w)                 # VioContext of the HIP library, w: the window passed to ctx.load()
+    r["obs"]      (m, 4)  r_x, r_y, e2, rho0 per edge, in w's order
+    r["lm"]       (n, 3)  mean and max pixel error, sum of rho0 per landmark
+    r["flags"]    (n,)    uint8: FLAG_REPROJ | FLAG_DEPTH | FLAG_STATE
+    r["summary"]  dict    chi2, visual_robust, visual_plain, imu, prior, imu_edge (10), frame_robust (11), frame_edges (11), n_flagged (3)
+"""
+import ctypes as C
+import os
+
+import numpy as np
+
+from . import synth
+from .capi import NUM_FRAMES, WINDOW_SIZE, VioError, VioPreint, _dp, _f64, _ip
+
+FLAG_REPROJ, FLAG_DEPTH, FLAG_STATE = 1, 2, 4
+FLAGS_ALL = FLAG_REPROJ | FLAG_DEPTH | FLAG_STATE
+
+
+class VioResSummary(C.Structure):
+    _fields_ = [("chi2", C.c_double), ("visual_robust", C.c_double), ("visual_plain", C.c_double), ("imu", C.c_double),
+                ("prior", C.c_double), ("imu_edge", C.c_double * WINDOW_SIZE), ("frame_robust", C.c_double * NUM_FRAMES),
+                ("frame_edges", C.c_int64 * NUM_FRAMES), ("n_flagged", C.c_int64 * 3)]
+
+    def as_dict(self):
+        out = {}
+        for name, _ in self._fields_:
+            v = getattr(self, name)
+            out[name] = np.array(v[:]) if hasattr(v, "_length_") else float(v)
+        return out
+
+
+class ResLib:
+    """libvio_res_hip.so: vio_res_* (it resolves libvio_hip.so's symbols from the instance already loaded in the process)."""
+
+    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "timing"]
+
+    def __init__(self, path):
+        if not os.path.exists(path):
+            raise FileNotFoundError(
+                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
+        self.path = path
+        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
+        self.fn = {s: getattr(self.dll, "vio_res_" + s) for s in self.SYMBOLS}
+        for s in self.SYMBOLS:
+            self.fn[s].restype = C.c_int
+        self.fn["destroy"].restype = None
+        self.fn["last_error"].restype = C.c_char_p
+        self.fn["version"].restype = C.c_int32
+        self.fn["compute"].argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
+        self.fn["compute_xyz"].argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
+
+    def create(self, ctx):
+        """A vio_res handle bound to `ctx` (a VioContext of the HIP library)."""
+        return ResHandle(self, ctx)
+
+
+def _pre_array(pres):
+    """The ten pointers of vio_set_imu_all (None: no edge) and the structs they point to (kept alive by the caller)."""
+    pres = list(pres)
+    if len(pres) != WINDOW_SIZE:
+        raise ValueError("the window's %d IMU edges (None for a missing one), got %d" % (WINDOW_SIZE, len(pres)))
+    keep = [None if p is None else (p if isinstance(p, VioPreint) else VioPreint.from_dict(p)) for p in pres]
+    arr = (C.POINTER(VioPreint) * WINDOW_SIZE)(*[C.pointer(p) if p is not None else C.POINTER(VioPreint)() for p in keep])
+    return arr, keep
+
+
+class ResHandle:
+    def __init__(self, lib, ctx):
+        self.lib = lib
+        self.ctx = ctx
+        self.h = C.c_void_p()
+        st = lib.fn["create"](ctx.h, C.byref(ctx.cfg), C.byref(self.h))
+        if st != 0:
+            raise VioError(st, "vio_res_create")
+
+    def close(self):
+        if self.h:
+            self.lib.fn["destroy"](self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _ck(self, st, where):
+        if st != 0:
+            msg = self.lib.fn["last_error"](self.h)
+            raise VioError(st, "vio_res_" + where, (msg or b"").decode(errors="replace"))
+
+    def set_config(self, cfg):
+        """vio_res_set_config: the configuration the context now runs with (after VioContext.set_config)."""
+        self._ck(self.lib.fn["set_config"](self.h, C.byref(cfg)), "set_config")
+
+    def compute(self, w, focal=synth.FOCAL, outlier_px=3.0, n=None, outputs=("obs", "lm", "flags", "summary"), out=None, imu=True):
+        """The residual query at the context's current state.  w: the window passed to load().  n: the landmark count passed to the
+        library (default: the context's).  outputs: which outputs to ask for (the others are passed as NULL and come back None).
+        out: optional dict of caller-owned arrays to fill ("obs" (m, 4), "lm" (n, 3), "flags" (n,) uint8); they are left untouched
+        when the call fails.  imu=False passes pre = NULL (the IMU terms and chi2 come back NaN)."""
+        g = (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
+        xyz = (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
+        n = self.ctx.n if n is None else int(n)
+        lm = np.ascontiguousarray(g("lm"), dtype=np.int32)
+        m = lm.size
+        if m != self.ctx.m:
+            raise VioError(-1, "vio_res_compute", "(the window has %d edges, the context %d)" % (m, self.ctx.m))
+        out = dict(out or {})
+        want = set(outputs)
+        arrs = {}
+        if "obs" in want:
+            arrs["obs"] = out.get("obs", np.zeros((m, 4)))
+        if "lm" in want:
+            arrs["lm"] = out.get("lm", np.zeros((max(n, 0), 3)))
+        if "flags" in want:
+            arrs["flags"] = out.get("flags", np.zeros(max(n, 0), dtype=np.uint8))
+        for a in arrs.values():
+            assert a.flags.c_contiguous
+        summ = VioResSummary() if "summary" in want else None
+        ptr = lambda k: arrs[k].ctypes.data if k in arrs and arrs[k].size else None
+        pre, _keep = _pre_array(g("preint")) if imu else (None, None)
+        tail = [C.c_int64(n), pre, C.c_double(focal), C.c_double(outlier_px), ptr("obs"), ptr("lm"), ptr("flags"),
+                C.addressof(summ) if summ is not None else None]
+        if xyz:
+            fr = np.ascontiguousarray(g("frame"), dtype=np.int32)
+            pts = _f64(g("pts"), (m, 2))
+            st = self.lib.fn["compute_xyz"](self.h, C.c_int64(m), lm.ctypes.data, fr.ctypes.data, pts.ctypes.data, *tail)
+            self._ck(st, "compute_xyz")
+        else:
+            host = np.ascontiguousarray(g("host"), dtype=np.int32)
+            tgt = np.ascontiguousarray(g("target"), dtype=np.int32)
+            pi, pj = _f64(g("pts_i"), (m, 2)), _f64(g("pts_j"), (m, 2))
+            st = self.lib.fn["compute"](self.h, C.c_int64(m), lm.ctypes.data, host.ctypes.data, tgt.ctypes.data, pi.ctypes.data,
+                                        pj.ctypes.data, *tail)
+            self._ck(st, "compute")
+        res = {k: arrs.get(k) for k in ("obs", "lm", "flags")}
+        res["summary"] = summ.as_dict() if summ is not None else None
+        return res
+
+    def timing(self):
+        """ms of the last compute: host (read-back of the states + packing + upload), the three kernels, whole call."""
+        out = (C.c_double * 5)()
+        self._ck(self.lib.fn["timing"](self.h, out), "timing")
+        return {"host_ms": out[0], "k_res_obs_ms": out[1], "k_res_lm_ms": out[2], "k_res_tail_ms": out[3], "total_ms": out[4]}

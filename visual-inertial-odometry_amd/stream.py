@@ -327,12 +327,16 @@ class SimulatorFileStream:
 
 class StreamDriver:
     def __init__(self, lib, stream, ctx_kwargs=None, pos_noise=0.02, rot_noise=0.005, depth_noise=0.05, seed=1,
-                 triangulate=False, nonkey_every=0):
+                 triangulate=False, nonkey_every=0, outlier_px=None):
         """triangulate=True: a landmark's first depth comes from FeatureManager::triangulate (vio_triangulate, on the
         current pose estimates, feature_manager.cpp:203-257) the first time it enters a solve, as in
         Estimator::solveOdometry (estimator.cpp:489-503), instead of from the perturbed ground truth.
         nonkey_every=n > 0: every n-th frame is not a keyframe: when it is the second-newest frame of the window it is
-        marginalised (MARGIN_SECOND_NEW) instead of the oldest one."""
+        marginalised (MARGIN_SECOND_NEW) instead of the oldest one.
+        outlier_px=x (HIP library only): after every solve the residual query (include/vio_residuals.h) flags the landmarks whose
+        mean reprojection error exceeds x pixels, that have a point behind a camera, or whose inverse depth is not positive and finite;
+        their tracks are erased after the marginalisation and before the slide — what removeOutlier (feature_manager.cpp:259-275) and
+        removeFailures (:161-171) would do if they were active.  self.rejected: the count of every step.  None: no query."""
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -369,6 +373,9 @@ class StreamDriver:
         self.reports = []
         self.flags = []             # marginalisation flag of every step
         self.n_triangulated = 0
+        self.outlier_px = outlier_px
+        self.rejected = []          # tracks erased at every step (outlier_px set)
+        self.rejected_ids = []      # ... and which
 
     # ---- feature bookkeeping (FeatureManager) ---------------------------------------------------------
     def add_frame_observations(self, f):
@@ -463,6 +470,10 @@ class StreamDriver:
         newest = self.frames[WINDOW_SIZE]
         self.trajectory.append((st.times[newest], self.poses[WINDOW_SIZE].copy()))
         self.reports.append(rep)
+        bad = []
+        if self.outlier_px is not None:         # FeaturePerId::is_outlier / solve_flag = 2 from the solved window
+            flags = self.ctx.residuals(w, outlier_px=self.outlier_px)["flags"]
+            bad = [ids[k] for k in np.nonzero(flags & 7)[0]]
         second_new = self.frames[WINDOW_SIZE - 1]
         margin_old = not (self.nonkey_every and second_new % self.nonkey_every == self.nonkey_every - 1)
         self.flags.append(MARG_OLD if margin_old else MARG_SECOND_NEW)
@@ -470,6 +481,12 @@ class StreamDriver:
         w2, _ = self.window_arrays()
         self.ctx.load(w2)
         self.prior = self.ctx.marginalize(MARG_OLD if margin_old else MARG_SECOND_NEW)
+        if self.outlier_px is not None:         # removeOutlier + removeFailures, before the slide
+            for l in bad:
+                del self.tracks[l]
+                self.depth.pop(l, None)
+            self.rejected.append(len(bad))
+            self.rejected_ids.extend(bad)
         if self.next_frame >= st.n_frames:
             return False
         if margin_old:
