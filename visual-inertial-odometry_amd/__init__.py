@@ -5,11 +5,12 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import capi, covariance, residuals, sharded, stream, synth
+from . import capi, covariance, imu, residuals, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
+from .imu import ImuHandle, ImuLib
 from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -17,6 +18,7 @@ HIP_LIB = os.environ.get("VIO_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "libvio
 
 COV_LIB = os.path.join(PKG_DIR, "csrc", "libvio_cov_hip.so")     # include/vio_covariance.h, linked against libvio_hip.so
 RES_LIB = os.path.join(PKG_DIR, "csrc", "libvio_res_hip.so")     # include/vio_residuals.h, linked against libvio_hip.so
+IMU_LIB = os.path.join(PKG_DIR, "csrc", "libvio_imu_hip.so")     # include/vio_imu.h, linked against libvio_hip.so
 
 _hip = None
 
@@ -83,3 +85,19 @@ def load_res():
         load_hip()
         _res = ResLib(RES_LIB)
     return _res
+
+
+_imu = None
+
+
+def load_imu():
+    """Load the IMU pre-integration library (csrc/libvio_imu_hip.so), under the same rule as load_cov: it is linked against
+    csrc/libvio_hip.so, so a VIO_HIP_LIB naming another build is refused."""
+    global _imu
+    if _imu is None:
+        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
+        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
+            raise RuntimeError("load_imu: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_imu_hip.so is linked against" % (HIP_LIB, own))
+        load_hip()
+        _imu = ImuLib(IMU_LIB)
+    return _imu

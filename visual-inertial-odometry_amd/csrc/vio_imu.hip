@@ -1,0 +1,466 @@
+// vio_imu.hip — batched IMU pre-integration and bias re-propagation (include/vio_imu.h).
+//
+// The raw samples of n intervals are uploaded once (vio_imu_load) and stay on the device; vio_imu_propagate runs IntegrationBase
+// (VM/include/factor/integration_base.h:13-158) over any subset of them at new biases in one launch of k_imu_propagate:
+//   one wavefront (one 64-thread workgroup) per interval, the intervals independent across the grid.
+//   The mid-point state (delta_p, delta_q, delta_v and the 3 x 3 blocks of F and V) is wave-uniform: every lane computes it in the
+//   host routine's operation order (vio_host::preintegrate, host_dense.cpp), with contraction off, and keeps it in registers.
+//   J and C are 16 x 16 zero-padded tiles held in registers in the accumulator layout of v_mfma_f64_16x16x4_f64 (lane l, register
+//   q: row (l >> 4) + 4q, column l & 15).  Each sample writes F (15 x 15) and G = V sqrt(N) (15 x 18, padded to 16 x 20) into LDS
+//   from their 3 x 3 blocks, every lane reads its A/B fragments of them back (row l & 15, k = 4s + (l >> 4)), and
+//     J <- F J                       4 MFMAs (J's accumulator registers are the B fragments as they stand)
+//     U <- C F^T                     4 MFMAs (C is symmetric: its accumulator registers are also its A fragments)
+//     C <- G G^T + F U               5 + 4 MFMAs (G's fragment is its own A and B operand)
+//   17 MFMAs per sample, one dependent chain per wave.
+// No atomics; every sum has a fixed order, so two identical calls give bitwise the same records.
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <cstdarg>
+#include <cstdio>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/vio_imu.h"
+
+#define IMU_NT 64                          // one wavefront per interval
+#define IMU_LDF 17                         // F tile: 16 rows, row stride 17 doubles
+#define IMU_LDG 21                         // G tile: 16 rows x 20 columns, row stride 21 doubles
+#define IMU_REC 467                        // doubles of one vio_preint
+#define R_SUMDT 0
+#define R_DP 1
+#define R_DQ 4
+#define R_DV 8
+#define R_BA 11
+#define R_BG 14
+#define R_JAC 17
+#define R_COV (R_JAC + 225)
+static_assert(sizeof(vio_preint) == IMU_REC * sizeof(double), "vio_preint is 467 contiguous doubles");
+
+typedef double imu_v4d __attribute__((ext_vector_type(4)));     // accumulator of v_mfma_f64_16x16x4_f64
+
+struct ImuArgs {
+    const int64_t *off;        // [n + 1]
+    const double *first;       // [n][6] acc0 | gyr0
+    const double *dt;          // [S]
+    const double *acc;         // [S][3]
+    const double *gyr;         // [S][3]
+    const double *bias;        // [count][6] ba | bg of the k-th listed interval
+    const int *which;          // [count] interval of output k
+    double *out;               // [count][IMU_REC]
+    double sn[4];              // sqrt of the noise diagonal: acc_n, gyr_n, acc_w, gyr_w
+};
+
+#pragma clang fp contract(off)     // the state recurrence and the blocks of F and V: products and sums as the host routine rounds them
+
+struct dm3 { double m[9]; };
+
+__device__ __forceinline__ dm3 m3_mul(const dm3 &a, const dm3 &b) {
+    dm3 c;
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) c.m[3 * i + j] = a.m[3 * i] * b.m[j] + a.m[3 * i + 1] * b.m[3 + j] + a.m[3 * i + 2] * b.m[6 + j];
+    return c;
+}
+__device__ __forceinline__ dm3 m3_hat(const double *v) { return dm3{{0, -v[2], v[1], v[2], 0, -v[0], -v[1], v[0], 0}}; }
+__device__ __forceinline__ dm3 m3_rot(const double *q) {        // Eigen toRotationMatrix on (x,y,z,w), no normalisation
+    const double x = q[0], y = q[1], z = q[2], w = q[3];
+    const double tx = 2 * x, ty = 2 * y, tz = 2 * z, twx = tx * w, twy = ty * w, twz = tz * w;
+    const double txx = tx * x, txy = ty * x, txz = tz * x, tyy = ty * y, tyz = tz * y, tzz = tz * z;
+    return dm3{{1 - (tyy + tzz), txy - twz, txz + twy, txy + twz, 1 - (txx + tzz), tyz - twx, txz - twy, tyz + twx, 1 - (txx + tyy)}};
+}
+__device__ __forceinline__ void m3_apply(const dm3 &R, const double *v, double *o) {
+#pragma unroll
+    for (int i = 0; i < 3; ++i) o[i] = R.m[3 * i] * v[0] + R.m[3 * i + 1] * v[1] + R.m[3 * i + 2] * v[2];
+}
+// element e of a wave-uniform 3 x 3 as a select chain (the empty asm keeps the compiler from turning the chain back into an indexed
+// load of the array, which would put every block in scratch)
+__device__ __forceinline__ double m3_pick(const dm3 &B, int e) {
+    double v = B.m[0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) {
+        double x = B.m[k];
+        asm volatile("" : "+v"(x));
+        v = e == k ? x : v;
+    }
+    return v;
+}
+// lanes 0..8 store the block B * s at (r0, c0) of a tile
+__device__ __forceinline__ void put_block(double *T, int ld, int r0, int c0, const dm3 &B, double s, int lane) {
+    if (lane < 9) T[(r0 + lane / 3) * ld + c0 + lane % 3] = m3_pick(B, lane) * s;
+}
+// lanes 0..2 store the diagonal of d * I at (r0, c0)
+__device__ __forceinline__ void put_diag(double *T, int ld, int r0, int c0, double d, int lane) {
+    if (lane < 3) T[(r0 + lane) * ld + c0 + lane] = d;
+}
+
+__global__ __launch_bounds__(IMU_NT) void k_imu_propagate(ImuArgs a) {
+    __shared__ double sF[16 * IMU_LDF];
+    __shared__ double sG[16 * IMU_LDG];
+    const int lane = threadIdx.x;
+    const int k = blockIdx.x;
+    const int iv = a.which[k];
+    const int64_t s0 = a.off[iv], s1 = a.off[iv + 1];
+    double ba[3], bg[3], a0[3], g0[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        ba[c] = a.bias[6 * k + c]; bg[c] = a.bias[6 * k + 3 + c];
+        a0[c] = a.first[6 * (int64_t)iv + c]; g0[c] = a.first[6 * (int64_t)iv + 3 + c];
+    }
+    for (int e = lane; e < 16 * IMU_LDF; e += IMU_NT) sF[e] = 0.0;
+    for (int e = lane; e < 16 * IMU_LDG; e += IMU_NT) sG[e] = 0.0;
+    __syncthreads();
+    put_diag(sF, IMU_LDF, 0, 0, 1.0, lane);                // the constant identity blocks of F
+    put_diag(sF, IMU_LDF, 6, 6, 1.0, lane);
+    put_diag(sF, IMU_LDF, 9, 9, 1.0, lane);
+    put_diag(sF, IMU_LDF, 12, 12, 1.0, lane);
+
+    const int col = lane & 15, rb = lane >> 4;
+    imu_v4d J, C;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = rb + 4 * q;
+        J[q] = (row == col && row < 15) ? 1.0 : 0.0;
+        C[q] = 0.0;
+    }
+    double dp[3] = {0, 0, 0}, dv[3] = {0, 0, 0}, dq[4] = {0, 0, 0, 1}, sum_dt = 0;
+    const double sn0 = a.sn[0], sn1 = a.sn[1], sn2 = a.sn[2], sn3 = a.sn[3];
+    const dm3 I3{{1, 0, 0, 0, 1, 0, 0, 0, 1}};
+    for (int64_t s = s0; s < s1; ++s) {
+        const double h = a.dt[s];
+        double a1[3], g1[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { a1[c] = a.acc[3 * s + c]; g1[c] = a.gyr[3 * s + c]; }
+        double ua0[3], ua1[3], w[3], x0[3], x1[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { x0[c] = a0[c] - ba[c]; x1[c] = a1[c] - ba[c]; w[c] = 0.5 * (g0[c] + g1[c]) - bg[c]; }
+        const dm3 Rd = m3_rot(dq);
+        m3_apply(Rd, x0, ua0);
+        const double iq[4] = {w[0] * h / 2, w[1] * h / 2, w[2] * h / 2, 1.0};
+        const double rq[4] = {dq[3] * iq[0] + dq[0] * iq[3] + dq[1] * iq[2] - dq[2] * iq[1],
+                              dq[3] * iq[1] + dq[1] * iq[3] + dq[2] * iq[0] - dq[0] * iq[2],
+                              dq[3] * iq[2] + dq[2] * iq[3] + dq[0] * iq[1] - dq[1] * iq[0],
+                              dq[3] * iq[3] - dq[0] * iq[0] - dq[1] * iq[1] - dq[2] * iq[2]};
+        const dm3 Rr = m3_rot(rq);
+        m3_apply(Rr, x1, ua1);
+        double rp[3], rv[3];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const double ua = 0.5 * (ua0[c] + ua1[c]);
+            rp[c] = dp[c] + dv[c] * h + 0.5 * ua * h * h;
+            rv[c] = dv[c] + ua * h;
+        }
+        const dm3 Rw = m3_hat(w), Ra0 = m3_hat(x0), Ra1 = m3_hat(x1);
+        dm3 ImW;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) ImW.m[c] = I3.m[c] - Rw.m[c] * h;
+        const dm3 RdA0 = m3_mul(Rd, Ra0), RrA1 = m3_mul(Rr, Ra1), RrA1I = m3_mul(RrA1, ImW);
+
+        // F (the blocks the host's put() writes, same values) and G = V sqrt(N), column block by column block
+        dm3 B;
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = -0.25 * RdA0.m[c] * h * h + -0.25 * RrA1I.m[c] * h * h;
+        put_block(sF, IMU_LDF, 0, 3, B, 1.0, lane);
+        put_diag(sF, IMU_LDF, 0, 6, h, lane);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = -0.25 * (Rd.m[c] + Rr.m[c]) * h * h;
+        put_block(sF, IMU_LDF, 0, 9, B, 1.0, lane);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = -0.25 * RrA1.m[c] * h * h * -h;
+        put_block(sF, IMU_LDF, 0, 12, B, 1.0, lane);
+        put_block(sF, IMU_LDF, 3, 3, ImW, 1.0, lane);
+        put_diag(sF, IMU_LDF, 3, 12, -1.0 * h, lane);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = -0.5 * RdA0.m[c] * h + -0.5 * RrA1I.m[c] * h;
+        put_block(sF, IMU_LDF, 6, 3, B, 1.0, lane);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = -0.5 * (Rd.m[c] + Rr.m[c]) * h;
+        put_block(sF, IMU_LDF, 6, 9, B, 1.0, lane);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = -0.5 * RrA1.m[c] * h * -h;
+        put_block(sF, IMU_LDF, 6, 12, B, 1.0, lane);
+
+        const double v00 = 0.25 * h * h, v33 = 0.5 * h, v60 = 0.5 * h;
+        put_block(sG, IMU_LDG, 0, 0, Rd, v00 * sn0, lane);     // V(0, 0) = Rd h^2 / 4, column block 0: acc_n
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = 0.25 * -RrA1.m[c] * h * h * 0.5 * h;
+        put_block(sG, IMU_LDG, 0, 3, B, sn1, lane);             // column blocks 3, 9: gyr_n
+        put_block(sG, IMU_LDG, 0, 9, B, sn1, lane);
+        put_block(sG, IMU_LDG, 0, 6, Rr, v00 * sn0, lane);      // column block 6: acc_n
+        put_diag(sG, IMU_LDG, 3, 3, v33 * sn1, lane);
+        put_diag(sG, IMU_LDG, 3, 9, v33 * sn1, lane);
+        put_block(sG, IMU_LDG, 6, 0, Rd, v60 * sn0, lane);
+#pragma unroll
+        for (int c = 0; c < 9; ++c) B.m[c] = 0.5 * -RrA1.m[c] * h * 0.5 * h;
+        put_block(sG, IMU_LDG, 6, 3, B, sn1, lane);
+        put_block(sG, IMU_LDG, 6, 9, B, sn1, lane);
+        put_block(sG, IMU_LDG, 6, 6, Rr, v60 * sn0, lane);
+        put_diag(sG, IMU_LDG, 9, 12, h * sn2, lane);            // column block 12: acc_w
+        put_diag(sG, IMU_LDG, 12, 15, h * sn3, lane);           // column block 15: gyr_w
+        __syncthreads();
+        double fa[4], ga[5];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) fa[q] = sF[col * IMU_LDF + 4 * q + rb];
+#pragma unroll
+        for (int q = 0; q < 5; ++q) ga[q] = sG[col * IMU_LDG + 4 * q + rb];
+        __syncthreads();                                        // (the next sample's blocks overwrite the tiles)
+
+        imu_v4d Jn = {0, 0, 0, 0}, U = {0, 0, 0, 0}, Cn = {0, 0, 0, 0};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) Jn = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[q], J[q], Jn, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) U = __builtin_amdgcn_mfma_f64_16x16x4f64(C[q], fa[q], U, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 5; ++q) Cn = __builtin_amdgcn_mfma_f64_16x16x4f64(ga[q], ga[q], Cn, 0, 0, 0);
+#pragma unroll
+        for (int q = 0; q < 4; ++q) Cn = __builtin_amdgcn_mfma_f64_16x16x4f64(fa[q], U[q], Cn, 0, 0, 0);
+        J = Jn;
+        C = Cn;
+
+        const double nq = sqrt(rq[0] * rq[0] + rq[1] * rq[1] + rq[2] * rq[2] + rq[3] * rq[3]);
+#pragma unroll
+        for (int c = 0; c < 4; ++c) dq[c] = rq[c] / nq;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { dp[c] = rp[c]; dv[c] = rv[c]; a0[c] = a1[c]; g0[c] = g1[c]; }
+        sum_dt += h;
+    }
+
+    double *o = a.out + (int64_t)k * IMU_REC;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const int row = rb + 4 * q;
+        if (row < 15 && col < 15) {
+            o[R_JAC + 15 * row + col] = J[q];
+            o[R_COV + 15 * row + col] = C[q];
+        }
+    }
+    if (lane == 0) {
+        o[R_SUMDT] = sum_dt;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) { o[R_DP + c] = dp[c]; o[R_DV + c] = dv[c]; o[R_BA + c] = ba[c]; o[R_BG + c] = bg[c]; }
+#pragma unroll
+        for (int c = 0; c < 4; ++c) o[R_DQ + c] = dq[c];
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------------------------------
+struct vio_imu {
+    int device = 0;
+    hipStream_t stream = nullptr;
+    bool own_stream = false;
+    hipEvent_t ev[2] = {nullptr, nullptr};
+    char err[512] = {0};
+    int32_t n = -1;                                 // intervals loaded (-1: nothing yet)
+    vio_imu_noise noise = {0, 0, 0, 0};
+    // device: off | first | dt | acc | gyr, one allocation replaced by every load
+    char *d_data = nullptr;
+    int64_t *d_off = nullptr;
+    double *d_first = nullptr, *d_dt = nullptr, *d_acc = nullptr, *d_gyr = nullptr;
+    // per call: bias | which up, the records down (pinned host twins; grow only)
+    char *d_in = nullptr, *h_in = nullptr;
+    size_t in_cap = 0;
+    char *d_out = nullptr, *h_out = nullptr;
+    size_t out_cap = 0;
+    double timing[3] = {0, 0, 0};
+};
+
+namespace {
+
+// The calling thread's current device is the caller's: switched to the handle's for the library's calls, put back on the way out.
+struct DeviceScope {
+    int prev = -1;
+    bool ok = false;
+    explicit DeviceScope(int dev) {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(dev) == hipSuccess;
+    }
+    ~DeviceScope() {
+        if (prev >= 0) (void)hipSetDevice(prev);
+    }
+};
+
+vio_status fail(vio_imu *h, vio_status st, const char *fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(h->err, sizeof(h->err), fmt, ap);
+    va_end(ap);
+    return st;
+}
+
+vio_status hip_ck(vio_imu *h, hipError_t e, const char *what) {
+    if (e == hipSuccess) return VIO_OK;
+    return fail(h, VIO_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
+}
+
+// grow a pinned host buffer and its device twin to hold `bytes` (never shrinks)
+vio_status ensure(vio_imu *h, char **d, char **hb, size_t *cap, size_t bytes) {
+    if (bytes <= *cap) return VIO_OK;
+    if (*d) hipFree(*d);
+    if (*hb) hipHostFree(*hb);
+    *d = nullptr; *hb = nullptr; *cap = 0;
+    size_t want = bytes + bytes / 4 + 4096;
+    vio_status st = hip_ck(h, hipMalloc((void **)d, want), "hipMalloc");
+    if (st != VIO_OK) return st;
+    st = hip_ck(h, hipHostMalloc((void **)hb, want, hipHostMallocDefault), "hipHostMalloc");
+    if (st != VIO_OK) return st;
+    *cap = want;
+    return VIO_OK;
+}
+
+size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
+
+}   // namespace
+
+extern "C" {
+
+vio_status vio_imu_create(int32_t device, void *stream, vio_imu **out) {
+    if (!out) return VIO_ERR_BAD_ARG;
+    *out = nullptr;
+    if (device < 0) return VIO_ERR_BAD_ARG;
+    vio_imu *h = new (std::nothrow) vio_imu;
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->device = device;
+    DeviceScope dev(device);
+    if (!dev.ok) { delete h; return VIO_ERR_HIP; }
+    if (stream) {
+        h->stream = (hipStream_t)stream;
+    } else {
+        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return VIO_ERR_HIP; }
+        h->own_stream = true;
+    }
+    for (int k = 0; k < 2; ++k)
+        if (hipEventCreate(&h->ev[k]) != hipSuccess) { vio_imu_destroy(h); return VIO_ERR_HIP; }
+    *out = h;
+    return VIO_OK;
+}
+
+void vio_imu_destroy(vio_imu *h) {
+    if (!h) return;
+    DeviceScope dev(h->device);
+    if (h->stream) hipStreamSynchronize(h->stream);
+    for (int k = 0; k < 2; ++k) if (h->ev[k]) hipEventDestroy(h->ev[k]);
+    if (h->d_data) hipFree(h->d_data);
+    if (h->d_in) hipFree(h->d_in);
+    if (h->d_out) hipFree(h->d_out);
+    if (h->h_in) hipHostFree(h->h_in);
+    if (h->h_out) hipHostFree(h->h_out);
+    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
+    delete h;
+}
+
+const char *vio_imu_last_error(const vio_imu *h) { return h ? h->err : "null handle"; }
+
+int32_t vio_imu_version(void) { return VIO_IMU_VERSION; }
+
+vio_status vio_imu_load(vio_imu *h, int32_t n, const int64_t *offset, const double *first, const double *dt, const double *acc,
+                        const double *gyr, const vio_imu_noise *noise) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (n < 0 || !offset || !noise || (n > 0 && !first)) return fail(h, VIO_ERR_BAD_ARG, "n=%d, or offset / first / noise is NULL", n);
+    if (offset[0] != 0) return fail(h, VIO_ERR_BAD_ARG, "offset[0] = %lld, not 0", (long long)offset[0]);
+    for (int32_t i = 0; i < n; ++i)
+        if (offset[i + 1] < offset[i])
+            return fail(h, VIO_ERR_BAD_ARG, "offset decreases at interval %d (%lld -> %lld)", i, (long long)offset[i], (long long)offset[i + 1]);
+    const int64_t S = offset[n];
+    if (S > 0 && (!dt || !acc || !gyr)) return fail(h, VIO_ERR_BAD_ARG, "%lld samples and dt / acc / gyr is NULL", (long long)S);
+    DeviceScope dev(h->device);
+    if (!dev.ok) return fail(h, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+    vio_status st;
+    if ((st = hip_ck(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    if (h->d_data) hipFree(h->d_data);
+    h->d_data = nullptr;
+    h->n = -1;
+    const size_t oOff = 0, oFirst = align256(oOff + 8 * ((size_t)n + 1)), oDt = align256(oFirst + 48 * (size_t)n),
+                 oAcc = align256(oDt + 8 * (size_t)S), oGyr = align256(oAcc + 24 * (size_t)S), total = align256(oGyr + 24 * (size_t)S);
+    if ((st = hip_ck(h, hipMalloc((void **)&h->d_data, total), "hipMalloc")) != VIO_OK) return st;
+    h->d_off = (int64_t *)(h->d_data + oOff);
+    h->d_first = (double *)(h->d_data + oFirst);
+    h->d_dt = (double *)(h->d_data + oDt);
+    h->d_acc = (double *)(h->d_data + oAcc);
+    h->d_gyr = (double *)(h->d_data + oGyr);
+    struct { void *d; const void *s; size_t b; } cp[5] = {{h->d_off, offset, 8 * ((size_t)n + 1)}, {h->d_first, first, 48 * (size_t)n},
+                                                          {h->d_dt, dt, 8 * (size_t)S}, {h->d_acc, acc, 24 * (size_t)S},
+                                                          {h->d_gyr, gyr, 24 * (size_t)S}};
+    for (auto &c : cp)
+        if (c.b && (st = hip_ck(h, hipMemcpyAsync(c.d, c.s, c.b, hipMemcpyHostToDevice, h->stream), "upload")) != VIO_OK) return st;
+    if ((st = hip_ck(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    h->n = n;
+    h->noise = *noise;
+    return VIO_OK;
+}
+
+vio_status vio_imu_propagate(vio_imu *h, int32_t count, const int32_t *which, const double *ba, const double *bg, vio_preint *out) {
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (h->n < 0) return fail(h, VIO_ERR_BAD_ARG, "nothing loaded");
+    const int32_t n = h->n;
+    if (!which && count != n) return fail(h, VIO_ERR_BAD_ARG, "which = NULL and count %d is not the %d intervals loaded", count, n);
+    if (count < 0) return fail(h, VIO_ERR_BAD_ARG, "count %d", count);
+    if (count == 0) return VIO_OK;
+    if (!ba || !bg || !out) return fail(h, VIO_ERR_BAD_ARG, "ba / bg / out is NULL");
+    if (which)
+        for (int32_t k = 0; k < count; ++k)
+            if (which[k] < 0 || which[k] >= n) return fail(h, VIO_ERR_BAD_ARG, "which[%d] = %d is not an interval (n = %d)", k, which[k], n);
+    DeviceScope dev(h->device);
+    if (!dev.ok) return fail(h, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+    vio_status st;
+    const size_t oB = 0, oW = align256(oB + 48 * (size_t)count), nin = align256(oW + 4 * (size_t)count);
+    const size_t nout = (size_t)IMU_REC * 8 * count;
+    if ((st = ensure(h, &h->d_in, &h->h_in, &h->in_cap, nin)) != VIO_OK) return st;
+    if ((st = ensure(h, &h->d_out, &h->h_out, &h->out_cap, nout)) != VIO_OK) return st;
+    double *hb = (double *)(h->h_in + oB);
+    int *hw = (int *)(h->h_in + oW);
+    for (int32_t k = 0; k < count; ++k) {
+        const int32_t i = which ? which[k] : k;
+        hw[k] = i;
+        for (int c = 0; c < 3; ++c) { hb[6 * k + c] = ba[3 * (size_t)i + c]; hb[6 * k + 3 + c] = bg[3 * (size_t)i + c]; }
+    }
+    if ((st = hip_ck(h, hipMemcpyAsync(h->d_in, h->h_in, nin, hipMemcpyHostToDevice, h->stream), "upload")) != VIO_OK) return st;
+    const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+
+    ImuArgs a;
+    a.off = h->d_off; a.first = h->d_first; a.dt = h->d_dt; a.acc = h->d_acc; a.gyr = h->d_gyr;
+    a.bias = (const double *)(h->d_in + oB);
+    a.which = (const int *)(h->d_in + oW);
+    a.out = (double *)h->d_out;
+    a.sn[0] = h->noise.acc_n; a.sn[1] = h->noise.gyr_n; a.sn[2] = h->noise.acc_w; a.sn[3] = h->noise.gyr_w;
+    hipEventRecord(h->ev[0], h->stream);
+    hipLaunchKernelGGL(k_imu_propagate, dim3(count), dim3(IMU_NT), 0, h->stream, a);
+    if ((st = hip_ck(h, hipGetLastError(), "k_imu_propagate launch")) != VIO_OK) return st;
+    hipEventRecord(h->ev[1], h->stream);
+    if ((st = hip_ck(h, hipMemcpyAsync(h->h_out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream), "read-back")) != VIO_OK) return st;
+    if ((st = hip_ck(h, hipStreamSynchronize(h->stream), "k_imu_propagate")) != VIO_OK) return st;
+
+    const double *rec = (const double *)h->h_out;
+    int32_t bad = -1;
+    for (int32_t k = 0; k < count; ++k) {
+        const int32_t i = hw[k];
+        const double *r = rec + (size_t)IMU_REC * k;
+        std::memcpy(&out[i], r, sizeof(vio_preint));
+        if (bad < 0 || i < bad)
+            for (int e = 0; e < IMU_REC; ++e)
+                if (!std::isfinite(r[e])) { bad = i; break; }
+    }
+    float kms = 0.f;
+    hipEventElapsedTime(&kms, h->ev[0], h->ev[1]);
+    h->timing[0] = t_host;
+    h->timing[1] = kms;
+    h->timing[2] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    if (bad >= 0) return fail(h, VIO_ERR_NOT_FINITE, "interval %d: non-finite pre-integration (a non-finite sample or bias)", bad);
+    return VIO_OK;
+}
+
+vio_status vio_imu_timing(const vio_imu *h, double *out3) {
+    if (!h || !out3) return VIO_ERR_BAD_ARG;
+    std::memcpy(out3, h->timing, sizeof(h->timing));
+    return VIO_OK;
+}
+
+}   // extern "C"

@@ -22,6 +22,7 @@ import math
 import numpy as np
 
 from . import synth
+from .imu import record_dict
 from .capi import MARG_OLD, MARG_SECOND_NEW, NUM_FRAMES, WINDOW_SIZE
 
 
@@ -327,7 +328,7 @@ class SimulatorFileStream:
 
 class StreamDriver:
     def __init__(self, lib, stream, ctx_kwargs=None, pos_noise=0.02, rot_noise=0.005, depth_noise=0.05, seed=1,
-                 triangulate=False, nonkey_every=0, outlier_px=None):
+                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None):
         """triangulate=True: a landmark's first depth comes from FeatureManager::triangulate (vio_triangulate, on the
         current pose estimates, feature_manager.cpp:203-257) the first time it enters a solve, as in
         Estimator::solveOdometry (estimator.cpp:489-503), instead of from the perturbed ground truth.
@@ -336,7 +337,13 @@ class StreamDriver:
         outlier_px=x (HIP library only): after every solve the residual query (include/vio_residuals.h) flags the landmarks whose
         mean reprojection error exceeds x pixels, that have a point behind a camera, or whose inverse depth is not positive and finite;
         their tracks are erased after the marginalisation and before the slide — what removeOutlier (feature_manager.cpp:259-275) and
-        removeFailures (:161-171) would do if they were active.  self.rejected: the count of every step.  None: no query."""
+        removeFailures (:161-171) would do if they were active.  self.rejected: the count of every step.  None: no query.
+        bias_relinearize=(ba_thresh, bg_thresh) (needs the GPU): the pre-integrations follow the bias estimates through the IMU
+        library (include/vio_imu.h).  Every new interval, the merged one of a non-keyframe slide included, is pre-integrated at the bias
+        of the frame it starts from (new IntegrationBase{acc_0, gyr_0, Bas[..], Bgs[..]}, estimator.cpp:116, 159, 1178, 1229), and
+        before every solve the intervals whose start frame's bias moved more than the threshold (max-abs, per axis) from their
+        linearized_ba / linearized_bg are re-propagated (repropagate, integration_base.h:38-52).  self.repropagated: the count of every
+        step.  None: every interval stays at zero bias and the library is not loaded."""
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -376,6 +383,13 @@ class StreamDriver:
         self.outlier_px = outlier_px
         self.rejected = []          # tracks erased at every step (outlier_px set)
         self.rejected_ids = []      # ... and which
+        self.bias_relinearize = None if bias_relinearize is None else (float(bias_relinearize[0]), float(bias_relinearize[1]))
+        self.repropagated = []      # intervals re-propagated before every solve (bias_relinearize set)
+        if self.bias_relinearize is not None:
+            from . import load_imu
+            self.imu_h = load_imu().create(device=self.ctx.cfg.device)
+            self._imu_stale = True              # the handle does not hold self.intervals
+            self._repropagate(list(range(WINDOW_SIZE)))
 
     # ---- feature bookkeeping (FeatureManager) ---------------------------------------------------------
     def add_frame_observations(self, f):
@@ -451,10 +465,33 @@ class StreamDriver:
         out[list(self.depth.keys())] = True
         return out
 
+    # ---- IMU pre-integration at the bias estimates (bias_relinearize) ---------------------------------
+    def _repropagate(self, ks):
+        """Pre-integrate intervals ks of the window at the bias of the frame each starts from (interval k: frame k -> k + 1)."""
+        if self._imu_stale:
+            self.imu_h.load(self.intervals, self.noise)
+            self._imu_stale = False
+        n = len(self.intervals)
+        recs = self.imu_h.propagate(self.sb[:n, 3:6], self.sb[:n, 6:9], which=ks)
+        for k, r in zip(ks, recs):
+            self.preint[k] = record_dict(r)
+
+    def relinearize_biases(self):
+        """repropagate the intervals whose start frame's bias moved past the thresholds; returns how many."""
+        tba, tbg = self.bias_relinearize
+        ks = [k for k in range(WINDOW_SIZE)
+              if np.abs(self.sb[k, 3:6] - self.preint[k]["linearized_ba"]).max() > tba
+              or np.abs(self.sb[k, 6:9] - self.preint[k]["linearized_bg"]).max() > tbg]
+        if ks:
+            self._repropagate(ks)
+        return len(ks)
+
     # ---- one frame ------------------------------------------------------------------------------------
     def step(self):
         """Solve the current window, marginalise, slide, take in the next frame.  Returns False at the end."""
         st = self.s
+        if self.bias_relinearize is not None:
+            self.repropagated.append(self.relinearize_biases())
         self.ensure_depths()
         w, ids = self.window_arrays()
         self.ctx.load(w)
@@ -518,6 +555,8 @@ class StreamDriver:
         self.frames.pop(0)
         self.intervals.pop(0)
         self.preint.pop(0)
+        if self.bias_relinearize is not None:
+            self._imu_stale = True
         self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
 
     def slide_window_new(self):
@@ -534,8 +573,13 @@ class StreamDriver:
         a, b = self.intervals[WINDOW_SIZE - 2], self.intervals[WINDOW_SIZE - 1]
         merged = dict(acc0=a["acc0"], gyr0=a["gyr0"], dt=a["dt"] + b["dt"], acc=a["acc"] + b["acc"], gyr=a["gyr"] + b["gyr"])
         self.intervals[WINDOW_SIZE - 2:] = [merged]
-        self.preint[WINDOW_SIZE - 2:] = [synth.preintegrate(merged["acc0"], merged["gyr0"], np.zeros(3), np.zeros(3),
-                                                           merged["dt"], merged["acc"], merged["gyr"], **self.noise)]
+        if self.bias_relinearize is None:
+            self.preint[WINDOW_SIZE - 2:] = [synth.preintegrate(merged["acc0"], merged["gyr0"], np.zeros(3), np.zeros(3),
+                                                               merged["dt"], merged["acc"], merged["gyr"], **self.noise)]
+        else:
+            self.preint[WINDOW_SIZE - 2:] = [None]
+            self._imu_stale = True
+            self._repropagate([WINDOW_SIZE - 2])
         self.frames.pop(WINDOW_SIZE - 1)
         self.poses[WINDOW_SIZE - 1], self.sb[WINDOW_SIZE - 1] = self.poses[WINDOW_SIZE].copy(), self.sb[WINDOW_SIZE].copy()
 
@@ -551,6 +595,10 @@ class StreamDriver:
         self.frames.append(f)
         self.intervals.append(iv)
         self.preint.append(pre)
+        if self.bias_relinearize is not None:
+            self._imu_stale = True
+            self._repropagate([WINDOW_SIZE - 1])
+            pre = self.preint[WINDOW_SIZE - 1]
         dt = pre["sum_dt"]
         i = WINDOW_SIZE - 1
         Ri = synth.quat_to_rot(self.poses[i, 3:7])
