@@ -40,7 +40,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define VIO_COV_VERSION 1
+#define VIO_COV_VERSION 2
 
 typedef enum {
     VIO_COV_GAUGE_NONE = 0,         /* invert H_pp_schur as it is (a window without a prior has 4 unobservable directions) */
@@ -67,6 +67,30 @@ vio_status vio_cov_compute(vio_cov *cv, int32_t gauge, int64_t m, const int32_t 
 /* XYZ window.  m, lm, frame, pts: what vio_set_observations_xyz was given.  lm_cov: n x 3 x 3 or NULL. */
 vio_status vio_cov_compute_xyz(vio_cov *cv, int32_t gauge, int64_t m, const int32_t *lm, const int32_t *frame, const double *pts,
                                int64_t n, double *pose_cov, double *lm_cov);
+
+/* Many windows at once: what vio_cov_compute / vio_cov_compute_xyz give for each window, bitwise, with one
+ * launch of each kernel for the whole batch and one synchronisation.  cvs[i]: one handle per window, no handle twice; their contexts
+ * share one device and one stream (vio_config.stream) and all hold the kind of landmark `xyz` names (0: inverse depths, 1: XYZ).
+ * items[i]: window i's arguments, those of the single call.  For an XYZ window `target` is the observing frame and `pts_j` the
+ * observation (what vio_set_observations_xyz took as frame / pts); host and pts_i are ignored.
+ * Errors of the batch, with nothing written and no kernel launched: VIO_ERR_BAD_ARG for a mismatch of device, stream or landmark kind,
+ * a handle given twice, or a window whose arguments the single call refuses; VIO_ERR_UNSUPPORTED for a sharded context.  The message
+ * is on cvs[0] (vio_cov_last_error) and names the window.  count = 0 is a no-op that returns VIO_OK.
+ * Per window: window_status[i] (may be NULL) is VIO_OK or VIO_ERR_NOT_FINITE.  A window that fails has its outputs left untouched and
+ * its handle's vio_cov_last_error naming the variable; the others are still computed and written, and the call then returns
+ * VIO_ERR_NOT_FINITE.  Afterwards vio_cov_landmark_information / vio_cov_pivot_ratio of each successful window's handle are those of
+ * its window, and vio_cov_timing of every handle of the batch gives the batch's times (host = every window's linearise + read-back +
+ * upload, then the kernels over all windows, then the whole call).  No context's state changes. */
+typedef struct vio_cov_batch_item {
+    int64_t m;
+    const int32_t *lm, *host, *target;
+    const double *pts_i, *pts_j;
+    int64_t n;
+    double *pose_cov;               /* 171 x 171 or NULL */
+    double *lm_out;                 /* lm_var (n) / lm_cov (n x 3 x 3) or NULL */
+} vio_cov_batch_item;
+vio_status vio_cov_compute_batch(vio_cov *const *cvs, int32_t count, int32_t gauge, int32_t xyz, const vio_cov_batch_item *items,
+                                 vio_status *window_status);
 
 /* h_l (n doubles) or H_ll (n x 3 x 3) as the last successful compute recomputed them. */
 vio_status vio_cov_landmark_information(vio_cov *cv, int64_t n, double *info);

@@ -41,7 +41,7 @@ extern "C" {
 #pragma GCC visibility push(default)
 #endif
 
-#define VIO_RES_VERSION 1
+#define VIO_RES_VERSION 2
 
 /* bits of lm_flags */
 #define VIO_RES_FLAG_REPROJ 1u     /* the mean pixel error is above outlier_px (a NaN mean counts as above): FeaturePerId::is_outlier */
@@ -80,6 +80,30 @@ vio_status vio_res_compute(vio_res *rs, int64_t m, const int32_t *lm, const int3
 vio_status vio_res_compute_xyz(vio_res *rs, int64_t m, const int32_t *lm, const int32_t *frame, const double *pts, int64_t n,
                                const vio_preint *const *pre, double focal, double outlier_px, double *obs_out, double *lm_out,
                                uint8_t *lm_flags, vio_res_summary *summary);
+
+/* Many windows at once: what vio_res_compute / vio_res_compute_xyz give for each window, bitwise, with one
+ * launch of each kernel for the whole batch (every window's edges and landmarks tiled from a workgroup boundary, one k_res_tail
+ * workgroup per window) and one synchronisation.  rss[i]: one handle per window, no handle twice; their contexts share one device and
+ * one stream (vio_config.stream) and all hold the kind of landmark `xyz` names (0: inverse depths, 1: XYZ).  items[i]: window i's
+ * arguments and outputs, those of the single call (each output may be NULL); focal and outlier_px are the batch's.  For an XYZ window
+ * `target` is the observing frame and `pts_j` the observation (vio_set_observations_xyz's frame / pts); host and pts_i are ignored.
+ * Errors, with nothing written and no kernel launched: VIO_ERR_BAD_ARG for a mismatch of device, stream or landmark kind, a handle
+ * given twice, or a window whose arguments the single call refuses; VIO_ERR_UNSUPPORTED for a sharded context.  The message is on
+ * rss[0] (vio_res_last_error) and names the window.  count = 0 is a no-op that returns VIO_OK.  Afterwards vio_res_timing of every
+ * handle of the batch gives the batch's times (host = every window's read-back + packing + upload). */
+typedef struct vio_res_batch_item {
+    int64_t m;
+    const int32_t *lm, *host, *target;
+    const double *pts_i, *pts_j;
+    int64_t n;
+    const vio_preint *const *pre;   /* the ten pointers of vio_set_imu_all, or NULL (IMU fields and chi2 NaN) */
+    double *obs_out;                /* m x 4 or NULL */
+    double *lm_out;                 /* n x 3 or NULL */
+    uint8_t *lm_flags;              /* n or NULL */
+    vio_res_summary *summary;       /* or NULL */
+} vio_res_batch_item;
+vio_status vio_res_compute_batch(vio_res *const *rss, int32_t count, int32_t xyz, const vio_res_batch_item *items, double focal,
+                                 double outlier_px);
 
 /* Times of the last successful compute, ms: [0] read-back of the states + packing + upload, host wall clock; [1] k_res_obs,
  * [2] k_res_lm, [3] k_res_tail (HIP events on the context's stream); [4] the whole call, wall clock.  NaN when the events could not

@@ -176,6 +176,20 @@ class VioLib:
             raise VioError(st, self.prefix + "batch_solve", (msg or b"").decode(errors="replace"))
         return list(reps)
 
+    def batch_covariance(self, ctxs, windows, gauge="fix_oldest"):
+        """VioContext.covariance of every window of `ctxs` (a batch vio_batch_solve takes) with one launch per kernel for the batch
+        (vio_cov_compute_batch): one (pose_cov, lm) per window, bitwise what the single call gives.  windows: what each context was
+        loaded with.  A window whose system is not positive definite raises a VioError whose .window_status lists every window's
+        status and whose .results holds the other windows' results (None for a failed one)."""
+        from . import load_cov
+        return load_cov().compute_batch(ctxs, windows, gauge)
+
+    def batch_residuals(self, ctxs, windows, focal=None, outlier_px=3.0):
+        """VioContext.residuals of every window of `ctxs` with one launch per kernel for the batch (vio_res_compute_batch): one dict
+        per window, bitwise what the single call gives."""
+        from . import load_res, synth
+        return load_res().compute_batch(ctxs, windows, synth.FOCAL if focal is None else focal, outlier_px)
+
     def has(self, name):
         return hasattr(self.dll, self.prefix + name)
 
@@ -424,6 +438,10 @@ class VioContext:
         """Marginal covariances at the current state (include/vio_covariance.h; HIP library only): (pose_cov (171, 171),
         lm_var (n,) or, for an XYZ window, (n, 3, 3)).  w: the window passed to load(); gauge: "fix_oldest" (frame 0's pose held
         fixed) or "none".  The handle of the covariance library is kept on the context from call to call."""
+        return self.cov_handle().compute(w, gauge)
+
+    def cov_handle(self):
+        """The context's handle of the covariance library, made on first use and kept from call to call."""
         if self.lib.prefix != "vio_":
             raise VioError(-5, self.lib.prefix + "covariance", "(the covariance library binds the HIP library's contexts only)")
         if getattr(self, "_cov", None) is None:
@@ -431,22 +449,26 @@ class VioContext:
             self._cov = load_cov().create(self)
         else:
             self._cov.set_config(self.cfg)          # (set_config forwards it too; this also covers a cfg edited in place)
-        return self._cov.compute(w, gauge)
+        return self._cov
 
     def residuals(self, w, focal=None, outlier_px=3.0):
         """Per-edge residuals, the chi2 breakdown and landmark outlier flags at the current state (include/vio_residuals.h; HIP
         library only): a dict of obs (m, 4), lm (n, 3), flags (n,) uint8 and summary (dict).  w: the window passed to load();
         focal: pixels per normalised-plane unit (default synth.FOCAL); outlier_px: the mean pixel error above which bit 0 is set.
         The handle of the residual library is kept on the context from call to call."""
+        from . import synth
+        return self.res_handle().compute(w, synth.FOCAL if focal is None else focal, outlier_px)
+
+    def res_handle(self):
+        """The context's handle of the residual library, made on first use and kept from call to call."""
         if self.lib.prefix != "vio_":
             raise VioError(-5, self.lib.prefix + "residuals", "(the residual library binds the HIP library's contexts only)")
-        from . import synth
         if getattr(self, "_res", None) is None:
             from . import load_res
             self._res = load_res().create(self)
         else:
             self._res.set_config(self.cfg)          # (set_config forwards it too; this also covers a cfg edited in place)
-        return self._res.compute(w, synth.FOCAL if focal is None else focal, outlier_px)
+        return self._res
 
     # ---- read back ------------------------------------------------------------------------
     def get_window(self):

@@ -2,6 +2,7 @@
 
     cov = vio.load_cov()
     pose_cov, lm_var = ctx.covariance(w)                 # VioContext of the HIP library, w: the window passed to ctx.load()
+    [(pose_cov, lm_var), ...] = hip.batch_covariance(ctxs, windows)     # many windows, one launch per kernel
     P_newest = vio.pose_block(pose_cov, vio.WINDOW_SIZE) # 6 x 6 covariance of the newest pose (position, rotation)
 
 Ordering of pose_cov: [ext(6) | (pose 6, speed-bias 9) x 11] (vio_get_schur_system's); fixed variables are zero rows / columns.
@@ -36,8 +37,8 @@ def speed_bias_block(pose_cov, k):
 class CovLib:
     """libvio_cov_hip.so: vio_cov_* (it resolves libvio_hip.so's symbols from the instance already loaded in the process)."""
 
-    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "landmark_information",
-               "pivot_ratio", "timing"]
+    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "compute_batch",
+               "landmark_information", "pivot_ratio", "timing"]
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -48,6 +49,7 @@ class CovLib:
         self.fn = {s: getattr(self.dll, "vio_cov_" + s) for s in self.SYMBOLS}
         for s in self.SYMBOLS:
             self.fn[s].restype = C.c_int
+        self.fn["compute_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["destroy"].restype = None
         self.fn["last_error"].restype = C.c_char_p
         self.fn["version"].restype = C.c_int32
@@ -55,6 +57,70 @@ class CovLib:
     def create(self, ctx):
         """A vio_cov handle bound to `ctx` (a VioContext of the HIP library)."""
         return CovHandle(self, ctx)
+
+    def compute_batch(self, ctxs, windows, gauge="fix_oldest", out=None):
+        """vio_cov_compute_batch over the windows of `ctxs` (VioContexts of the HIP library on one device and one stream, one kind of
+        landmark), each with the handle VioContext.covariance uses.  windows: what each context was loaded with.  out: optional list
+        of (pose_cov, lm) arrays to fill, one pair per window.  Returns one (pose_cov, lm) per window.
+        A batch-level error raises VioError.  When some windows fail (VIO_ERR_NOT_FINITE) the others are still computed: the VioError
+        raised then carries .window_status (every window's status), .results (None for a failed window) and names each failed window
+        with its handle's message; a failed window's arrays are left untouched."""
+        ctxs, windows = list(ctxs), list(windows)
+        if len(ctxs) != len(windows):
+            raise ValueError("%d contexts, %d windows" % (len(ctxs), len(windows)))
+        B = len(ctxs)
+        gi = GAUGES[gauge] if isinstance(gauge, str) else int(gauge)
+        handles = [c.cov_handle() for c in ctxs]
+        xyz0 = bool(B) and _is_xyz(windows[0])          # the batch's kind: the library refuses a context holding the other
+        items = (VioCovBatchItem * max(B, 1))()
+        keep, res = [], []
+        for i, (c, w) in enumerate(zip(ctxs, windows)):
+            g = _getter(w)
+            n = c.n
+            xyz = _is_xyz(w)
+            P, L = out[i] if out is not None else (np.zeros((POSE_DIM, POSE_DIM)), np.zeros((n, 3, 3)) if xyz else np.zeros(n))
+            assert P.shape == (POSE_DIM, POSE_DIM) and P.dtype == np.float64 and P.flags.c_contiguous
+            assert L.dtype == np.float64 and L.flags.c_contiguous and L.size == n * (9 if xyz else 1)
+            lm = np.ascontiguousarray(g("lm"), dtype=np.int32)
+            m = lm.size
+            if xyz:
+                arrs = [lm, None, np.ascontiguousarray(g("frame"), dtype=np.int32), None, _f64(g("pts"), (m, 2))]
+            else:
+                arrs = [lm, np.ascontiguousarray(g("host"), dtype=np.int32), np.ascontiguousarray(g("target"), dtype=np.int32),
+                        _f64(g("pts_i"), (m, 2)), _f64(g("pts_j"), (m, 2))]
+            it = items[i]
+            it.m, it.n = m, n
+            it.lm, it.host, it.target, it.pts_i, it.pts_j = [a.ctypes.data if a is not None else None for a in arrs]
+            it.pose_cov, it.lm_out = P.ctypes.data, (L.ctypes.data if n else None)
+            keep.append(arrs)
+            res.append((P, L))
+        status = (C.c_int32 * max(B, 1))()
+        hs = (C.c_void_p * max(B, 1))(*[h.h.value for h in handles])
+        st = self.fn["compute_batch"](hs, C.c_int32(B), C.c_int32(gi), C.c_int32(1 if xyz0 else 0), items, status)
+        if st == 0:
+            return res
+        if st != -3 or B == 0:
+            handles[0]._ck(st, "compute_batch")
+        ws = [int(status[i]) for i in range(B)]
+        msgs = ["window %d: %s" % (i, (self.fn["last_error"](handles[i].h) or b"").decode(errors="replace"))
+                for i in range(B) if ws[i] != 0]
+        e = VioError(st, "vio_cov_compute_batch", "; ".join(msgs))
+        e.window_status = ws
+        e.results = [r if s == 0 else None for r, s in zip(res, ws)]
+        raise e
+
+
+class VioCovBatchItem(C.Structure):
+    _fields_ = [("m", C.c_int64), ("lm", C.c_void_p), ("host", C.c_void_p), ("target", C.c_void_p), ("pts_i", C.c_void_p),
+                ("pts_j", C.c_void_p), ("n", C.c_int64), ("pose_cov", C.c_void_p), ("lm_out", C.c_void_p)]
+
+
+def _getter(w):
+    return (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
+
+
+def _is_xyz(w):
+    return (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
 
 
 class CovHandle:
@@ -128,7 +194,8 @@ class CovHandle:
         return out[:n]
 
     def timing(self):
-        """ms of the last compute: host (linearise + read-back + upload), k_cov_pose, k_cov_landmarks, whole call."""
+        """ms of the last compute: host (linearise + read-back + upload), k_cov_pose, k_cov_landmarks, whole call.  After a
+        compute_batch: the batch's times, on every handle of the batch."""
         out = (C.c_double * 4)()
         self._ck(self.lib.fn["timing"](self.h, out), "timing")
         return {"host_ms": out[0], "k_cov_pose_ms": out[1], "k_cov_landmarks_ms": out[2], "total_ms": out[3]}

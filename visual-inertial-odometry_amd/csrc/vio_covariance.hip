@@ -1,7 +1,8 @@
-// vio_covariance.hip — marginal covariances of a solved window (include/vio_covariance.h).
+// vio_covariance.hip — marginal covariances of a solved window (include/vio_covariance.h; DESIGN.md sections 10 and 13).
 //
 // A companion of libvio_hip.so that uses nothing but its C ABI: the system and the states are read back through the getters, and
-// the two kernels below run on the context's stream.
+// the two kernels below run on the context's stream.  vio_cov_compute_batch runs each of them once for many windows
+// (k_cov_pose_batch, k_cov_landmarks_batch: the same bodies, vio_cov_*_body.inc, one window per workgroup).
 //   k_cov_pose          one workgroup: the reduced H_pp_schur (fixed variables removed) as a packed lower triangle in LDS, inverted
 //                       in place by the symmetric sweep; Sigma written once as a full 171 x 171 and as the 72 x 72 camera block.
 //   k_cov_landmarks<D>  one lane per landmark: its observations' reprojection Jacobians and robust weights recomputed, h_l and w_l
@@ -15,6 +16,7 @@
 #include <cstring>
 #include <vector>
 
+#include "vio_batch_grid.h"
 #include "vio_device_math.h"
 #include "vio_obs_csr.h"
 #include "../../include/vio_covariance.h"
@@ -46,65 +48,32 @@ __device__ inline int tri(int i, int j) { return i * (i + 1) / 2 + j; }         
 __global__ void __launch_bounds__(POSE_NT) k_cov_pose(const double *__restrict__ S, const int *__restrict__ keep, int n,
                                                        double *__restrict__ cov, double *__restrict__ cc, int *__restrict__ status,
                                                        double *__restrict__ ratio) {
-    __shared__ double A[TRI_MAX];
-    __shared__ double col[PD + 1];           // pivot column k
-    __shared__ double dg[PD];                // diagonal of S (the pivot ratio)
-    __shared__ int red[PD];                  // 171-index -> reduced index, -1: held fixed
-    const int tid = threadIdx.x;
-    const int ntri = n * (n + 1) / 2;
+#include "vio_cov_pose_body.inc"
+}
 
-    for (int q = tid; q < PD; q += POSE_NT) red[q] = -1;
-    __syncthreads();
-    for (int q = tid; q < n; q += POSE_NT) { red[keep[q]] = q; dg[q] = S[(size_t)keep[q] * PD + keep[q]]; }
+// one window of k_cov_pose_batch: k_cov_pose's arguments, in the window's own buffers
+struct CovPoseItem {
+    const double *S;
+    const int *keep;
+    double *cov;
+    double *cc;
+    int *status;
+    double *ratio;
+    int n;
+};
 
-    // the thread's packed entries and their (row, column), found once
-    int ij[POSE_PER];                        // row << 16 | column
-#pragma unroll
-    for (int s = 0; s < POSE_PER; ++s) {
-        const int p = tid + s * POSE_NT;
-        int i = (int)((sqrt(8.0 * p + 1.0) - 1.0) * 0.5);
-        while ((i + 1) * (i + 2) / 2 <= p) ++i;
-        while (i * (i + 1) / 2 > p) --i;
-        const int j = p - i * (i + 1) / 2;
-        ij[s] = (i << 16) | j;
-        if (p < ntri) A[p] = S[(size_t)keep[i] * PD + keep[j]];          // lower triangle of S (keep is ascending)
-    }
-    __syncthreads();
-
-    double rmin = 1.0;
-    for (int k = 0; k < n; ++k) {
-        if (tid < n) col[tid] = A[tid >= k ? tri(tid, k) : tri(k, tid)];
-        __syncthreads();
-        const double d = col[k];
-        if (!(d > 0.0) || !isfinite(d)) {          // uniform: every thread read the same pivot
-            if (tid == 0) status[0] = k;
-            return;
-        }
-        rmin = fmin(rmin, d / dg[k]);
-        const double dinv = 1.0 / d;
-#pragma unroll
-        for (int s = 0; s < POSE_PER; ++s) {
-            const int p = tid + s * POSE_NT;
-            if (p < ntri) {
-                const int i = ij[s] >> 16, j = ij[s] & 0xffff;
-                if (i == k && j == k) A[p] = -dinv;
-                else if (i == k) A[p] = col[j] * dinv;
-                else if (j == k) A[p] = col[i] * dinv;
-                else A[p] = A[p] - (col[i] * dinv) * col[j];
-            }
-        }
-        __syncthreads();
-    }
-    if (tid == 0) { status[0] = -1; ratio[0] = rmin; }
-
-    for (int q = tid; q < PD * PD; q += POSE_NT) {
-        const int r = red[q / PD], c = red[q % PD];
-        cov[q] = (r >= 0 && c >= 0) ? -A[r >= c ? tri(r, c) : tri(c, r)] : 0.0;
-    }
-    for (int q = tid; q < CD * CD; q += POSE_NT) {
-        const int r = red[cam_to_full(q / CD)], c = red[cam_to_full(q % CD)];
-        cc[q] = (r >= 0 && c >= 0) ? -A[r >= c ? tri(r, c) : tri(c, r)] : 0.0;
-    }
+// k_cov_pose for a batch: workgroup w inverts window w's system, with k_cov_pose's code (vio_cov_pose_body.inc), so each window gets
+// the bits the single call gives it.  117 KB of LDS: one workgroup per CU, the windows side by side.
+__global__ void __launch_bounds__(POSE_NT) k_cov_pose_batch(const CovPoseItem *__restrict__ items) {
+    const CovPoseItem it = items[blockIdx.x];
+    const double *__restrict__ S = it.S;
+    const int *__restrict__ keep = it.keep;
+    const int n = it.n;
+    double *__restrict__ cov = it.cov;
+    double *__restrict__ cc = it.cc;
+    int *__restrict__ status = it.status;
+    double *__restrict__ ratio = it.ratio;
+#include "vio_cov_pose_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -169,217 +138,19 @@ DEV void reduce_mul(const double *red, const double *M, double *J, int c0) {
 
 template <int D>
 __global__ void __launch_bounds__(LmNT<D>::v) k_cov_landmarks(CovLmArgs a) {
-    constexpr int NT = LmNT<D>::v;
-    __shared__ double sc[CD * CD];
-    __shared__ double wl[CD * D * NT];          // the lane's coupling column, variable-major: [(72 * d + var) * NT + lane]
-    __shared__ double sR[(NF + 1) * 9];         // rotations of the 11 poses and (slot 11) of the extrinsic
-    const int tid = threadIdx.x;
-    for (int q = tid; q < CD * CD; q += NT) sc[q] = a.cc[q];
-    for (int f = tid; f <= NF; f += NT) d_quat_to_R(f < NF ? a.poses + 7 * f + 3 : a.ext + 3, sR + 9 * f);
-    for (int q = 0; q < CD * D; ++q) wl[q * NT + tid] = 0.0;
-    __syncthreads();
-    const int l = blockIdx.x * NT + tid;
-    if (l >= a.n) return;
+    const unsigned blk = blockIdx.x;
+#include "vio_cov_landmarks_body.inc"
+}
 
-    const double *ric = sR + 9 * NF, *tic = a.ext;
-    double ricT[9];
-#pragma unroll
-    for (int r = 0; r < 3; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) ricT[3 * r + c] = ric[3 * c + r];
-    const double s = a.sqrt_info;
-    double h[D * D];
-#pragma unroll
-    for (int q = 0; q < D * D; ++q) h[q] = 0.0;
-    unsigned mask = 0;                          // camera blocks the landmark couples to: bit 0 ext, bit 1 + f pose f
-    double *w = wl + tid;
-
-    for (int e = a.off[l]; e < a.off[l + 1]; ++e) {
-        const int fj = a.ofr[e];
-        const double *Rj = sR + 9 * fj, *Pj = a.poses + 7 * fj;
-        double r[2], W[4];
-        if (D == 1) {
-            // EdgeReprojection (edge_reprojection.cc:18-109)
-            const int fi = a.ohost[l];
-            const double *Ri = sR + 9 * fi, *Pi = a.poses + 7 * fi;
-            const double lam = a.val[l];
-            const double pts_i[3] = {a.pts_i[2 * l], a.pts_i[2 * l + 1], 1.0};
-            const double pc_i[3] = {pts_i[0] / lam, pts_i[1] / lam, pts_i[2] / lam};
-            double pb_i[3], pw[3], dd[3], pb_j[3], ee[3], pc_j[3];
-            d_m3_vec(ric, pc_i, pb_i);
-            for (int k = 0; k < 3; ++k) pb_i[k] += tic[k];
-            d_m3_vec(Ri, pb_i, pw);
-            for (int k = 0; k < 3; ++k) dd[k] = pw[k] + Pi[k] - Pj[k];
-            d_m3_tvec(Rj, dd, pb_j);
-            for (int k = 0; k < 3; ++k) ee[k] = pb_j[k] - tic[k];
-            d_m3_tvec(ric, ee, pc_j);
-            const double dep = pc_j[2];
-            r[0] = pc_j[0] / dep - a.pts_j[2 * e];
-            r[1] = pc_j[1] / dep - a.pts_j[2 * e + 1];
-            robust_info2(a.loss_type, a.loss_delta, s, r, W);
-            const double red[6] = {1. / dep, 0, -pc_j[0] / (dep * dep), 0, 1. / dep, -pc_j[1] / (dep * dep)};
-            double A[9], ARi[9], T[9], M[9], Ji[12], Jj[12], Je[12];
-            double RjT[9];
-#pragma unroll
-            for (int r2 = 0; r2 < 3; ++r2)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) RjT[3 * r2 + c] = Rj[3 * c + r2];
-            d_m3_mul(ricT, RjT, A);                                  // ric^T Rj^T
-            d_m3_mul(A, Ri, ARi);                                    // ric^T Rj^T Ri
-            d_m3_mul(ARi, ric, T);                                   // ric^T Rj^T Ri ric
-            double v[3];
-            d_m3_vec(T, pts_i, v);
-            double Jl[2];
-            for (int r2 = 0; r2 < 2; ++r2)
-                Jl[r2] = (red[3 * r2] * v[0] + red[3 * r2 + 1] * v[1] + red[3 * r2 + 2] * v[2]) * -1.0 / (lam * lam);
-            // J_pose_i = reduce [ric^T Rj^T | -ric^T Rj^T Ri hat(pb_i)]
-            reduce_mul(red, A, Ji, 0);
-            skew3(pb_i, M);
-            double Mm[9];
-            d_m3_mul(ARi, M, Mm);
-            for (int k = 0; k < 9; ++k) Mm[k] = -Mm[k];
-            reduce_mul(red, Mm, Ji, 3);
-            // J_pose_j = reduce [-ric^T Rj^T | ric^T hat(pb_j)]
-            for (int k = 0; k < 9; ++k) M[k] = -A[k];
-            reduce_mul(red, M, Jj, 0);
-            skew3(pb_j, M);
-            d_m3_mul(ricT, M, Mm);
-            reduce_mul(red, Mm, Jj, 3);
-            // J_ext = reduce [ric^T (Rj^T Ri - I) | -T hat(pc_i) + hat(T pc_i) + hat(ric^T (Rj^T (Ri tic + Pi - Pj) - tic))]
-            if (a.ext_free) {
-                d_m3_mul(RjT, Ri, M);
-                M[0] -= 1; M[4] -= 1; M[8] -= 1;
-                d_m3_mul(ricT, M, Mm);
-                reduce_mul(red, Mm, Je, 0);
-                double S1[9], t1[9], v2[3], S2[9], u[3], ww[3], x[3], S3[9];
-                skew3(pc_i, S1);
-                d_m3_mul(T, S1, t1);
-                d_m3_vec(T, pc_i, v2);
-                skew3(v2, S2);
-                d_m3_vec(Ri, tic, u);
-                for (int k = 0; k < 3; ++k) u[k] = u[k] + Pi[k] - Pj[k];
-                d_m3_tvec(Rj, u, ww);
-                for (int k = 0; k < 3; ++k) ww[k] -= tic[k];
-                d_m3_tvec(ric, ww, x);
-                skew3(x, S3);
-                for (int k = 0; k < 9; ++k) M[k] = -t1[k] + S2[k] + S3[k];
-                reduce_mul(red, M, Je, 3);
-            }
-            // h_l += J_l^T W J_l;  w_l += (J_l^T W) [J_i | J_j | J_ext] on the host / target / extrinsic blocks
-            const double t0 = Jl[0] * W[0] + Jl[1] * W[2], t1 = Jl[0] * W[1] + Jl[1] * W[3];
-            h[0] += t0 * Jl[0] + t1 * Jl[1];
-            const int ii = 6 + 6 * fi, jj = 6 + 6 * fj;
-            for (int k = 0; k < 6; ++k) {
-                w[(ii + k) * NT] += t0 * Ji[k] + t1 * Ji[6 + k];
-                w[(jj + k) * NT] += t0 * Jj[k] + t1 * Jj[6 + k];
-                if (a.ext_free) w[k * NT] += t0 * Je[k] + t1 * Je[6 + k];
-            }
-            mask |= (2u << fi) | (2u << fj) | (a.ext_free ? 1u : 0u);
-        } else {
-            // EdgeReprojectionXYZ (edge_reprojection.cc:130-180)
-            const double *pw = a.val + 3 * l;
-            double dd[3], pim[3], ee[3], pc[3];
-            for (int k = 0; k < 3; ++k) dd[k] = pw[k] - Pj[k];
-            d_m3_tvec(Rj, dd, pim);                                  // Rj^T (pw - Pj): pts_imu in the observing frame
-            for (int k = 0; k < 3; ++k) ee[k] = pim[k] - tic[k];
-            d_m3_tvec(ric, ee, pc);
-            const double dep = pc[2];
-            r[0] = pc[0] / dep - a.pts_j[2 * e];
-            r[1] = pc[1] / dep - a.pts_j[2 * e + 1];
-            robust_info2(a.loss_type, a.loss_delta, s, r, W);
-            const double red[6] = {1. / dep, 0, -pc[0] / (dep * dep), 0, 1. / dep, -pc[1] / (dep * dep)};
-            double RT[9], M[9], Mm[9], Jp[12], Jf[6];
-#pragma unroll
-            for (int r2 = 0; r2 < 3; ++r2)
-#pragma unroll
-                for (int c = 0; c < 3; ++c) RT[3 * r2 + c] = Rj[3 * c + r2];
-            // J_pose = reduce [ric^T (-Ri^T) | ric^T hat(pts_imu)],  J_feature = reduce ric^T Ri^T
-            d_m3_mul(ricT, RT, Mm);
-            for (int k = 0; k < 9; ++k) M[k] = -Mm[k];
-            reduce_mul(red, M, Jp, 0);
-            skew3(pim, M);
-            double Mh[9];
-            d_m3_mul(ricT, M, Mh);
-            reduce_mul(red, Mh, Jp, 3);
-            for (int r2 = 0; r2 < 2; ++r2)
-                for (int c = 0; c < 3; ++c)
-                    Jf[3 * r2 + c] = red[3 * r2] * Mm[c] + red[3 * r2 + 1] * Mm[3 + c] + red[3 * r2 + 2] * Mm[6 + c];
-            const int ip = 6 + 6 * fj;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) {
-                const double t0 = Jf[d] * W[0] + Jf[3 + d] * W[2], t1 = Jf[d] * W[1] + Jf[3 + d] * W[3];     // (J_f^T W) row d
-#pragma unroll
-                for (int c = 0; c < 3; ++c) h[3 * d + c] += t0 * Jf[c] + t1 * Jf[3 + c];
-                for (int k = 0; k < 6; ++k) w[(CD * d + ip + k) * NT] += t0 * Jp[k] + t1 * Jp[6 + k];
-            }
-            mask |= 2u << fj;
-        }
-    }
-
-    // q = w^T Sigma_cc w over the blocks the landmark touches (D x D), block rows P, block columns Q in ascending order
-    double q[D * D];
-#pragma unroll
-    for (int k = 0; k < D * D; ++k) q[k] = 0.0;
-    for (unsigned mp = mask; mp; mp &= mp - 1) {
-        const int P = __builtin_ctz(mp);
-        double t[6 * D];                                               // (Sigma_cc w)_P
-#pragma unroll
-        for (int k = 0; k < 6 * D; ++k) t[k] = 0.0;
-        for (unsigned mq = mask; mq; mq &= mq - 1) {
-            const int Q = __builtin_ctz(mq);
-            for (int c = 0; c < 6; ++c) {
-                double wq[D];
-#pragma unroll
-                for (int d = 0; d < D; ++d) wq[d] = w[(CD * d + 6 * Q + c) * NT];
-#pragma unroll
-                for (int r2 = 0; r2 < 6; ++r2) {
-                    const double sv = sc[(6 * P + r2) * CD + 6 * Q + c];
-#pragma unroll
-                    for (int d = 0; d < D; ++d) t[D * r2 + d] += sv * wq[d];
-                }
-            }
-        }
-#pragma unroll
-        for (int r2 = 0; r2 < 6; ++r2) {
-            double wp[D];
-#pragma unroll
-            for (int d = 0; d < D; ++d) wp[d] = w[(CD * d + 6 * P + r2) * NT];
-#pragma unroll
-            for (int d = 0; d < D; ++d)
-#pragma unroll
-                for (int d2 = 0; d2 < D; ++d2) q[D * d + d2] += wp[d] * t[D * r2 + d2];
-        }
-    }
-
-    if (D == 1) {
-        const double hl = h[0];
-        a.info[l] = hl;
-        if (!(hl > 0.0) || !isfinite(hl)) { atomicMin(a.bad, l); a.out[l] = NAN; return; }
-        const double hinv = 1.0 / hl;
-        a.out[l] = hinv + q[0] * hinv * hinv;
-    } else {
-        // H_ll^-1 by the adjugate; positive definite by Sylvester's criterion (the leading minors), else reported
-        const double *H = h;
-        const double m0 = H[0], m1 = H[0] * H[4] - H[1] * H[3];
-        const double c00 = H[4] * H[8] - H[5] * H[7], c01 = H[2] * H[7] - H[1] * H[8], c02 = H[1] * H[5] - H[2] * H[4];
-        const double c11 = H[0] * H[8] - H[2] * H[6], c12 = H[2] * H[3] - H[0] * H[5], c22 = H[0] * H[4] - H[1] * H[3];
-        const double det = H[0] * c00 + H[1] * (H[5] * H[6] - H[3] * H[8]) + H[2] * (H[3] * H[7] - H[4] * H[6]);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) a.info[9 * l + k] = H[k];
-        if (!(m0 > 0.0) || !(m1 > 0.0) || !(det > 0.0) || !isfinite(det)) {
-            atomicMin(a.bad, l);
-#pragma unroll
-            for (int k = 0; k < 9; ++k) a.out[9 * l + k] = NAN;
-            return;
-        }
-        const double id = 1.0 / det;
-        const double Hi[9] = {c00 * id, c01 * id, c02 * id, c01 * id, c11 * id, c12 * id, c02 * id, c12 * id, c22 * id};
-        double T[9], O[9];
-        d_m3_mul(Hi, q, T);
-        d_m3_mul(T, Hi, O);
-#pragma unroll
-        for (int k = 0; k < 9; ++k) a.out[9 * l + k] = Hi[k] + O[k];
-    }
+// k_cov_landmarks for a batch: window w owns the workgroups [blk0[w], blk0[w + 1]), which restart at its landmark 0 and stage its
+// Sigma_cc and rotations, so each lane runs what it runs in k_cov_landmarks on that window alone.
+template <int D>
+__global__ void __launch_bounds__(LmNT<D>::v) k_cov_landmarks_batch(const CovLmArgs *__restrict__ items, const int *__restrict__ blk0,
+                                                                    int count) {
+    const int win = batch_window(blk0, count, blockIdx.x);
+    const CovLmArgs a = items[win];
+    const unsigned blk = blockIdx.x - (unsigned)blk0[win];
+#include "vio_cov_landmarks_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -399,6 +170,10 @@ struct vio_cov {
     double *d_out = nullptr;
     size_t out_cap = 0;
     double *h_out = nullptr;
+    // device: the batch tables of a vio_cov_compute_batch whose first handle this is (CovPoseItem | CovLmArgs | workgroup starts)
+    double *d_tab = nullptr;
+    size_t tab_cap = 0;
+    double *h_tab = nullptr;
     int64_t last_n = -1;
     int last_dim = 0;
     std::vector<double> info;               // of the last successful compute
@@ -463,11 +238,22 @@ static const char *var_name(int full, char *buf, size_t len) {
 
 static size_t align8(size_t x) { return (x + 7) & ~(size_t)7; }
 
+// One window staged for the kernels: its upload enqueued on the context's stream, and where everything lies in the handle's buffers.
+struct Staged {
+    int D = 1;
+    int nk = 0;                             // variables kept
+    int ext_fixed = 1;
+    int64_t n = 0;
+    size_t oS = 0, oP = 0, oE = 0, oV = 0, oPi = 0, oPj = 0, nd = 0;            // doubles of d_in
+    size_t iKeep = 0, iOff = 0, iOfr = 0, iHost = 0, ni = 0;                   // ints after them
+    size_t o_cov = 0, o_cc = 0, o_out = 0, o_info = 0, nout = 0;               // doubles of d_out, then the status ints
+};
+
+// Validation, linearisation when needed, read-back of the system and the states, the CSR, and the upload (enqueued on the context's
+// stream, with the status words reset).  Nothing is launched and no output is written.  The caller holds the context's device.
 // D = 1: obs (host, target, pts_i, pts_j); D = 3: obs (frame, pts) in `target` / `pts_j`
-static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
-                          const double *pts_i, const double *pts_j, int64_t n, double *pose_cov, double *lm_out) {
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
+static vio_status stage(vio_cov *cv, int D, int32_t gauge, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
+                        const double *pts_i, const double *pts_j, int64_t n, Staged &sg) {
     if (gauge != VIO_COV_GAUGE_NONE && gauge != VIO_COV_GAUGE_FIX_OLDEST) return fail(cv, VIO_ERR_BAD_ARG, "unknown gauge %d", gauge);
     if (m < 0 || n < 0 || n > INT32_MAX / 9 || m > INT32_MAX) return fail(cv, VIO_ERR_BAD_ARG, "bad sizes m=%lld n=%lld", (long long)m, (long long)n);
     if (m > 0 && (!lm || !target || !pts_j || (D == 1 && (!host || !pts_i)))) return fail(cv, VIO_ERR_BAD_ARG, "observation array is NULL");
@@ -475,14 +261,16 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
         if (lm[e] < 0 || lm[e] >= n || target[e] < 0 || target[e] >= NF || (D == 1 && (host[e] < 0 || host[e] >= NF)))
             return fail(cv, VIO_ERR_BAD_ARG, "observation %lld refers to landmark %d / frame out of range", (long long)e, lm[e]);
     }
-    DeviceScope dev(cv->cfg.device);
-    if (!dev.ok) return fail(cv, VIO_ERR_HIP, "hipSetDevice(%d)", cv->cfg.device);
     vio_status st = VIO_OK;
 
     // layout of the upload
+    sg.D = D;
+    sg.n = n;
     const size_t oS = 0, oP = oS + PD * PD, oE = oP + NF * 7, oV = align8(oE + 7), oPi = align8(oV + (size_t)n * D),
                  oPj = align8(oPi + (D == 1 ? 2 * (size_t)n : 0)), nd = align8(oPj + 2 * (size_t)m);
     const size_t iKeep = 0, iOff = iKeep + PD + 1, iOfr = iOff + (size_t)n + 1, iHost = iOfr + (size_t)m, ni = iHost + (size_t)n + 2;
+    sg.oS = oS; sg.oP = oP; sg.oE = oE; sg.oV = oV; sg.oPi = oPi; sg.oPj = oPj; sg.nd = nd;
+    sg.iKeep = iKeep; sg.iOff = iOff; sg.iOfr = iOfr; sg.iHost = iHost; sg.ni = ni;
     if ((st = ensure(cv, &cv->d_in, &cv->h_in, &cv->in_cap, nd * sizeof(double) + ni * sizeof(int))) != VIO_OK) return st;
     double *hd = cv->h_in;
     int *hi = (int *)(cv->h_in + nd);
@@ -511,6 +299,8 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
         if (gauge == VIO_COV_GAUGE_FIX_OLDEST && v >= 6 && v < 12) continue;
         hi[iKeep + nk++] = v;
     }
+    sg.nk = nk;
+    sg.ext_fixed = ext_fixed;
     // CSR over the landmarks (stable: a landmark's observations keep the caller's order)
     int *off = hi + iOff, *ofr = hi + iOfr, *oh = hi + iHost;
     for (int64_t l = 0; l < n; ++l) oh[l] = -1;
@@ -541,47 +331,89 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
     cv->stream = (hipStream_t)sp;
 
     const size_t o_cov = 0, o_cc = PD * PD, o_out = o_cc + CD * CD, o_info = o_out + (size_t)n * D * D, nout = align8(o_info + (size_t)n * D * D);
+    sg.o_cov = o_cov; sg.o_cc = o_cc; sg.o_out = o_out; sg.o_info = o_info; sg.nout = nout;
     if ((st = ensure(cv, &cv->d_out, &cv->h_out, &cv->out_cap, nout * sizeof(double) + 8 * sizeof(int))) != VIO_OK) return st;
-    int *d_status = (int *)(cv->d_out + nout), *h_status = (int *)(cv->h_out + nout);
-    int *di = (int *)(cv->d_in + nd);
+    int *d_status = (int *)(cv->d_out + nout);
 
     if ((st = hip_ck(cv, hipMemcpyAsync(cv->d_in, cv->h_in, nd * sizeof(double) + ni * sizeof(int), hipMemcpyHostToDevice, cv->stream), "upload")) != VIO_OK) return st;
     // status[0]: failing pivot (-1: none); status[1]: smallest landmark without a positive definite information (NO_BAD_LM: none)
     if ((st = hip_ck(cv, hipMemsetAsync(d_status, 0xff, sizeof(int), cv->stream), "hipMemsetAsync")) != VIO_OK) return st;
     if ((st = hip_ck(cv, hipMemsetAsync(d_status + 1, 0x7f, sizeof(int), cv->stream), "hipMemsetAsync")) != VIO_OK) return st;
+    return VIO_OK;
+}
+
+// k_cov_pose's and k_cov_landmarks' arguments for a staged window
+static CovPoseItem pose_item(vio_cov *cv, const Staged &sg) {
+    int *di = (int *)(cv->d_in + sg.nd), *d_status = (int *)(cv->d_out + sg.nout);
+    CovPoseItem it;
+    it.S = cv->d_in + sg.oS; it.keep = di + sg.iKeep; it.n = sg.nk; it.cov = cv->d_out + sg.o_cov; it.cc = cv->d_out + sg.o_cc;
+    it.status = d_status; it.ratio = (double *)(d_status + 2);
+    return it;
+}
+
+static CovLmArgs lm_args(vio_cov *cv, const Staged &sg) {
+    int *di = (int *)(cv->d_in + sg.nd), *d_status = (int *)(cv->d_out + sg.nout);
+    CovLmArgs a;
+    a.cc = cv->d_out + sg.o_cc; a.poses = cv->d_in + sg.oP; a.ext = cv->d_in + sg.oE; a.val = cv->d_in + sg.oV; a.pts_i = cv->d_in + sg.oPi;
+    a.pts_j = cv->d_in + sg.oPj; a.off = di + sg.iOff; a.ofr = di + sg.iOfr; a.ohost = di + sg.iHost; a.n = (int)sg.n;
+    a.ext_free = !sg.ext_fixed; a.loss_type = cv->cfg.loss_type; a.loss_delta = cv->cfg.loss_delta; a.sqrt_info = cv->cfg.reproj_sqrt_info;
+    a.out = cv->d_out + sg.o_out; a.info = cv->d_out + sg.o_info; a.bad = d_status + 1;
+    return a;
+}
+
+static vio_status read_back(vio_cov *cv, const Staged &sg) {
+    return hip_ck(cv, hipMemcpyAsync(cv->h_out, cv->d_out, sg.nout * sizeof(double) + 8 * sizeof(int), hipMemcpyDeviceToHost, cv->stream), "read-back");
+}
+
+// After the read-back has completed: the window's verdict, and on success its outputs and the handle's landmark information and
+// pivot ratio.  On failure nothing is written.
+static vio_status finish(vio_cov *cv, const Staged &sg, double *pose_cov, double *lm_out) {
+    const int64_t n = sg.n;
+    const int D = sg.D;
+    const int *h_status = (const int *)(cv->h_out + sg.nout);
+    const int *hi = (const int *)(cv->h_in + sg.nd);
+    char nm[64];
+    if (h_status[0] >= 0)
+        return fail(cv, VIO_ERR_NOT_FINITE, "pose covariance: pivot %d (%s) of the reduced H_pp_schur is not positive and finite",
+                    h_status[0], var_name(hi[sg.iKeep + h_status[0]], nm, sizeof(nm)));
+    if (n > 0 && h_status[1] != NO_BAD_LM)
+        return fail(cv, VIO_ERR_NOT_FINITE, "landmark %d: its information is not positive definite and finite", h_status[1]);
+    if (pose_cov) memcpy(pose_cov, cv->h_out + sg.o_cov, sizeof(double) * PD * PD);
+    if (lm_out && n > 0) memcpy(lm_out, cv->h_out + sg.o_out, sizeof(double) * (size_t)n * D * D);
+    cv->info.assign(cv->h_out + sg.o_info, cv->h_out + sg.o_info + (size_t)n * D * D);
+    cv->last_n = n;
+    cv->last_dim = D;
+    cv->pivot_ratio = *(const double *)(h_status + 2);
+    return VIO_OK;
+}
+
+static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
+                          const double *pts_i, const double *pts_j, int64_t n, double *pose_cov, double *lm_out) {
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    DeviceScope dev(cv->cfg.device);
+    if (!dev.ok) return fail(cv, VIO_ERR_HIP, "hipSetDevice(%d)", cv->cfg.device);
+    Staged sg;
+    vio_status st = stage(cv, D, gauge, m, lm, host, target, pts_i, pts_j, n, sg);
+    if (st != VIO_OK) return st;
     const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
     if ((st = hip_ck(cv, hipEventRecord(cv->ev[0], cv->stream), "hipEventRecord")) != VIO_OK) return st;
-    k_cov_pose<<<1, POSE_NT, 0, cv->stream>>>(cv->d_in + oS, di + iKeep, nk, cv->d_out + o_cov, cv->d_out + o_cc, d_status,
-                                              (double *)(d_status + 2));
+    const CovPoseItem it = pose_item(cv, sg);
+    k_cov_pose<<<1, POSE_NT, 0, cv->stream>>>(it.S, it.keep, it.n, it.cov, it.cc, it.status, it.ratio);
     if ((st = hip_ck(cv, hipGetLastError(), "k_cov_pose launch")) != VIO_OK) return st;
     if ((st = hip_ck(cv, hipEventRecord(cv->ev[1], cv->stream), "hipEventRecord")) != VIO_OK) return st;
     if (n > 0) {
-        CovLmArgs a;
-        a.cc = cv->d_out + o_cc; a.poses = cv->d_in + oP; a.ext = cv->d_in + oE; a.val = cv->d_in + oV; a.pts_i = cv->d_in + oPi;
-        a.pts_j = cv->d_in + oPj; a.off = di + iOff; a.ofr = di + iOfr; a.ohost = di + iHost; a.n = (int)n;
-        a.ext_free = !ext_fixed; a.loss_type = cv->cfg.loss_type; a.loss_delta = cv->cfg.loss_delta; a.sqrt_info = cv->cfg.reproj_sqrt_info;
-        a.out = cv->d_out + o_out; a.info = cv->d_out + o_info; a.bad = d_status + 1;
+        const CovLmArgs a = lm_args(cv, sg);
         if (D == 1) k_cov_landmarks<1><<<(unsigned)((n + LmNT<1>::v - 1) / LmNT<1>::v), LmNT<1>::v, 0, cv->stream>>>(a);
         else k_cov_landmarks<3><<<(unsigned)((n + LmNT<3>::v - 1) / LmNT<3>::v), LmNT<3>::v, 0, cv->stream>>>(a);
         if ((st = hip_ck(cv, hipGetLastError(), "k_cov_landmarks launch")) != VIO_OK) return st;
     }
     if ((st = hip_ck(cv, hipEventRecord(cv->ev[2], cv->stream), "hipEventRecord")) != VIO_OK) return st;
-    if ((st = hip_ck(cv, hipMemcpyAsync(cv->h_out, cv->d_out, nout * sizeof(double) + 8 * sizeof(int), hipMemcpyDeviceToHost, cv->stream), "read-back")) != VIO_OK) return st;
+    if ((st = read_back(cv, sg)) != VIO_OK) return st;
     if ((st = hip_ck(cv, hipStreamSynchronize(cv->stream), "hipStreamSynchronize")) != VIO_OK) return st;
 
-    char nm[64];
-    if (h_status[0] >= 0)
-        return fail(cv, VIO_ERR_NOT_FINITE, "pose covariance: pivot %d (%s) of the reduced H_pp_schur is not positive and finite",
-                    h_status[0], var_name(hi[iKeep + h_status[0]], nm, sizeof(nm)));
-    if (n > 0 && h_status[1] != NO_BAD_LM)
-        return fail(cv, VIO_ERR_NOT_FINITE, "landmark %d: its information is not positive definite and finite", h_status[1]);
-    if (pose_cov) memcpy(pose_cov, cv->h_out + o_cov, sizeof(double) * PD * PD);
-    if (lm_out && n > 0) memcpy(lm_out, cv->h_out + o_out, sizeof(double) * (size_t)n * D * D);
-    cv->info.assign(cv->h_out + o_info, cv->h_out + o_info + (size_t)n * D * D);
-    cv->last_n = n;
-    cv->last_dim = D;
-    cv->pivot_ratio = *(const double *)(h_status + 2);
+    if ((st = finish(cv, sg, pose_cov, lm_out)) != VIO_OK) return st;
     float ms1 = 0, ms2 = 0;
     if ((st = hip_ck(cv, hipEventElapsedTime(&ms1, cv->ev[0], cv->ev[1]), "hipEventElapsedTime")) != VIO_OK ||
         (st = hip_ck(cv, hipEventElapsedTime(&ms2, cv->ev[1], cv->ev[2]), "hipEventElapsedTime")) != VIO_OK) {
@@ -593,6 +425,106 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
     cv->timing[2] = ms2;
     cv->timing[3] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     return VIO_OK;
+}
+
+// a window's error, reported on the batch's first handle as well
+static vio_status batch_fail(vio_cov *c0, vio_status st, int i, const vio_cov *cv) {
+    char msg[sizeof(cv->err)];
+    memcpy(msg, cv->err, sizeof(msg));
+    return fail(c0, st, "vio_cov_compute_batch: window %d: %s", i, msg);
+}
+
+// The batch: every window staged in its own handle's buffers (one upload each), one table upload, k_cov_pose_batch and
+// k_cov_landmarks_batch once for all windows, one read-back per window, one synchronisation.
+static vio_status compute_batch(vio_cov *const *cvs, int32_t count, int32_t gauge, int32_t xyz, const vio_cov_batch_item *items,
+                                vio_status *window_status) {
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    vio_cov *c0 = cvs[0];
+    const int D = xyz ? 3 : 1;
+    if (gauge != VIO_COV_GAUGE_NONE && gauge != VIO_COV_GAUGE_FIX_OLDEST) return fail(c0, VIO_ERR_BAD_ARG, "unknown gauge %d", gauge);
+    // one device, one stream, no handle twice (a handle's buffers hold one window), no shard
+    void *s0 = nullptr;
+    for (int32_t i = 0; i < count; ++i) {
+        vio_cov *cv = cvs[i];
+        if (!cv) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d: null handle", i);
+        cv->err[0] = 0;
+        if (cv->cfg.shard_count > 1) return fail(c0, VIO_ERR_UNSUPPORTED, "vio_cov_compute_batch: window %d: sharded context", i);
+        if (cv->cfg.device != c0->cfg.device)
+            return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d is on device %d, window 0 on %d: the contexts must share one device and one stream", i, cv->cfg.device, c0->cfg.device);
+        for (int32_t j = 0; j < i; ++j)
+            if (cvs[j] == cv) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: windows %d and %d are the same handle", j, i);
+    }
+    DeviceScope dev(c0->cfg.device);
+    if (!dev.ok) return fail(c0, VIO_ERR_HIP, "hipSetDevice(%d)", c0->cfg.device);
+    for (int32_t i = 0; i < count; ++i) {
+        void *sp = nullptr;
+        if (vio_get_stream(cvs[i]->ctx, &sp) != VIO_OK) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d: vio_get_stream", i);
+        if (i == 0) s0 = sp;
+        else if (sp != s0) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d is on another stream than window 0: the contexts must share one device and one stream", i);
+    }
+    vio_status st = VIO_OK;
+    std::vector<Staged> sg(count);
+    for (int32_t i = 0; i < count; ++i) {
+        const vio_cov_batch_item &it = items[i];
+        st = stage(cvs[i], D, gauge, it.m, it.lm, D == 1 ? it.host : nullptr, it.target, D == 1 ? it.pts_i : nullptr, it.pts_j, it.n, sg[i]);
+        if (st != VIO_OK) return batch_fail(c0, st, i, cvs[i]);
+    }
+    // the tables: CovPoseItem[count] | CovLmArgs[count] | blk0[count + 1]
+    const int lnt = D == 1 ? LmNT<1>::v : LmNT<3>::v;
+    const size_t bPose = 0, bLm = align8(bPose + sizeof(CovPoseItem) * count), bBlk = align8(bLm + sizeof(CovLmArgs) * count),
+                 nbytes = bBlk + sizeof(int) * ((size_t)count + 1);
+    if ((st = ensure(c0, &c0->d_tab, &c0->h_tab, &c0->tab_cap, nbytes)) != VIO_OK) return st;
+    char *ht = (char *)c0->h_tab;
+    CovPoseItem *tp = (CovPoseItem *)(ht + bPose);
+    CovLmArgs *tl = (CovLmArgs *)(ht + bLm);
+    int *blk0 = (int *)(ht + bBlk);
+    int64_t nblk = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        tp[i] = pose_item(cvs[i], sg[i]);
+        tl[i] = lm_args(cvs[i], sg[i]);
+        blk0[i] = (int)nblk;
+        nblk += (sg[i].n + lnt - 1) / lnt;
+        if (nblk > INT32_MAX) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: too many landmarks in the batch");
+    }
+    blk0[count] = (int)nblk;
+    hipStream_t stream = (hipStream_t)s0;
+    const char *dt = (const char *)c0->d_tab;
+    if ((st = hip_ck(c0, hipMemcpyAsync(c0->d_tab, c0->h_tab, nbytes, hipMemcpyHostToDevice, stream), "table upload")) != VIO_OK) return st;
+    const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+
+    if ((st = hip_ck(c0, hipEventRecord(c0->ev[0], stream), "hipEventRecord")) != VIO_OK) return st;
+    k_cov_pose_batch<<<(unsigned)count, POSE_NT, 0, stream>>>((const CovPoseItem *)(dt + bPose));
+    if ((st = hip_ck(c0, hipGetLastError(), "k_cov_pose_batch launch")) != VIO_OK) return st;
+    if ((st = hip_ck(c0, hipEventRecord(c0->ev[1], stream), "hipEventRecord")) != VIO_OK) return st;
+    if (nblk > 0) {
+        const CovLmArgs *dl = (const CovLmArgs *)(dt + bLm);
+        const int *db = (const int *)(dt + bBlk);
+        if (D == 1) k_cov_landmarks_batch<1><<<(unsigned)nblk, LmNT<1>::v, 0, stream>>>(dl, db, count);
+        else k_cov_landmarks_batch<3><<<(unsigned)nblk, LmNT<3>::v, 0, stream>>>(dl, db, count);
+        if ((st = hip_ck(c0, hipGetLastError(), "k_cov_landmarks_batch launch")) != VIO_OK) return st;
+    }
+    if ((st = hip_ck(c0, hipEventRecord(c0->ev[2], stream), "hipEventRecord")) != VIO_OK) return st;
+    for (int32_t i = 0; i < count; ++i)
+        if ((st = read_back(cvs[i], sg[i])) != VIO_OK) return batch_fail(c0, st, i, cvs[i]);
+    if ((st = hip_ck(c0, hipStreamSynchronize(stream), "hipStreamSynchronize")) != VIO_OK) return st;
+
+    vio_status ret = VIO_OK;
+    for (int32_t i = 0; i < count; ++i) {
+        const vio_status wst = finish(cvs[i], sg[i], items[i].pose_cov, items[i].lm_out);
+        if (window_status) window_status[i] = wst;
+        if (wst != VIO_OK) ret = wst;
+    }
+    float ms1 = 0, ms2 = 0;
+    double tm[4] = {NAN, NAN, NAN, NAN};
+    if (hipEventElapsedTime(&ms1, c0->ev[0], c0->ev[1]) == hipSuccess && hipEventElapsedTime(&ms2, c0->ev[1], c0->ev[2]) == hipSuccess) {
+        tm[0] = t_host;
+        tm[1] = ms1;
+        tm[2] = ms2;
+        tm[3] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    }
+    for (int32_t i = 0; i < count; ++i) memcpy(cvs[i]->timing, tm, sizeof(tm));
+    return ret;
 }
 
 extern "C" {
@@ -621,8 +553,10 @@ void vio_cov_destroy(vio_cov *cv) {
     for (int k = 0; k < 3; ++k) if (cv->ev[k]) hipEventDestroy(cv->ev[k]);
     if (cv->d_in) hipFree(cv->d_in);
     if (cv->d_out) hipFree(cv->d_out);
+    if (cv->d_tab) hipFree(cv->d_tab);
     if (cv->h_in) hipHostFree(cv->h_in);
     if (cv->h_out) hipHostFree(cv->h_out);
+    if (cv->h_tab) hipHostFree(cv->h_tab);
     delete cv;
 }
 
@@ -663,6 +597,15 @@ vio_status vio_cov_compute_xyz(vio_cov *cv, int32_t gauge, int64_t m, const int3
     return compute(cv, 3, gauge, m, lm, nullptr, frame, nullptr, pts, n, pose_cov, lm_cov);
 }
 
+vio_status vio_cov_compute_batch(vio_cov *const *cvs, int32_t count, int32_t gauge, int32_t xyz, const vio_cov_batch_item *items,
+                                 vio_status *window_status) {
+    if (count < 0 || (count > 0 && (!cvs || !items))) return VIO_ERR_BAD_ARG;
+    if (count == 0) return VIO_OK;
+    if (!cvs[0]) return VIO_ERR_BAD_ARG;
+    cvs[0]->err[0] = 0;
+    return compute_batch(cvs, count, gauge, xyz, items, window_status);
+}
+
 vio_status vio_cov_landmark_information(vio_cov *cv, int64_t n, double *info) {
     if (!cv) return VIO_ERR_BAD_ARG;
     if (cv->last_n < 0 || n != cv->last_n) return fail(cv, VIO_ERR_BAD_ARG, "no compute with n=%lld to read back", (long long)n);
@@ -677,3 +620,4 @@ vio_status vio_cov_timing(vio_cov *cv, double *out4) {
 }
 
 }   // extern "C"
+

@@ -1,8 +1,9 @@
 // vio_residuals.hip — per-edge residuals, the chi2 breakdown and landmark outlier flags (include/vio_residuals.h; DESIGN.md
-// section 11).
+// sections 11 and 13).
 //
 // A companion of libvio_hip.so that uses nothing but its C ABI: the states are read back through the getters, and the three kernels
-// below run on the context's stream.
+// below run on the context's stream.  vio_res_compute_batch runs each of them once for many windows (k_res_*_batch: the same bodies,
+// vio_res_*_body.inc; every window's edges and landmarks tiled from a workgroup boundary, one tail workgroup per window).
 //   k_res_obs<D>  one thread per edge, in the caller's order: the reprojection residual, e2 and rho0, stored as one row of obs.
 //   k_res_lm      one thread per landmark: its edges walked in CSR order -> mean / max pixel error, sum of rho0, flags; per-workgroup
 //                 partials of the visual totals, the 11 frame sums and the flag counts (DPP wave sums, waves in order).
@@ -18,6 +19,7 @@
 #include <cstring>
 #include <vector>
 
+#include "vio_batch_grid.h"
 #include "vio_device_math.h"
 #include "vio_imu_math.h"
 #include "vio_obs_csr.h"
@@ -89,29 +91,17 @@ struct ResArgs {
 
 template <int D>
 __global__ void __launch_bounds__(OBS_NT) k_res_obs(ResArgs a) {
-    __shared__ double sR[(NF + 1) * 9];         // rotations of the 11 poses and (slot 11) of the extrinsic
-    const int tid = threadIdx.x;
-    for (int f = tid; f <= NF; f += OBS_NT) d_quat_to_R(f < NF ? a.poses + 7 * f + 3 : a.ext + 3, sR + 9 * f);
-    __syncthreads();
-    const long long e = (long long)blockIdx.x * OBS_NT + tid;
-    if (e >= a.m) return;
-    const int l = a.lm[e], fj = a.fr[e];
-    double r[2], dep;
-    if (D == 1) {
-        const int fi = a.host[e];
-        dep = d_reproj_residual(sR + 9 * fi, a.poses + 7 * fi, sR + 9 * fj, a.poses + 7 * fj, sR + 9 * NF, a.ext, a.val[l],
-                                a.pts_i + 2 * e, a.pts_j + 2 * e, r);
-    } else {
-        dep = d_reproj_xyz_residual(sR + 9 * fj, a.poses + 7 * fj, sR + 9 * NF, a.ext, a.val + 3 * (size_t)l, a.pts_j + 2 * e, r);
-    }
-    const double info = a.sqrt_info * a.sqrt_info;
-    const double e2 = r[0] * (info * r[0]) + r[1] * (info * r[1]);          // Edge::Chi2 (edge.cc:33-37)
-    double r0, r1, r2;
-    d_loss(a.loss_type, a.loss_delta, e2, r0, r1, r2);                       // RobustChi2: rho[0] (e2 itself without a loss)
-    double2 *o = (double2 *)(a.obs + 4 * e);
-    o[0] = make_double2(r[0], r[1]);
-    o[1] = make_double2(e2, r0);
-    a.dneg[e] = dep <= 0.0;
+    const unsigned blk = blockIdx.x;
+#include "vio_res_obs_body.inc"
+}
+
+// k_res_obs for a batch: window w owns the workgroups [blk0[w], blk0[w + 1]) (vio_batch_grid.h), which restart at its edge 0.
+template <int D>
+__global__ void __launch_bounds__(OBS_NT) k_res_obs_batch(const ResArgs *__restrict__ items, const int *__restrict__ blk0, int count) {
+    const int win = batch_window(blk0, count, blockIdx.x);
+    const ResArgs a = items[win];
+    const unsigned blk = blockIdx.x - (unsigned)blk0[win];
+#include "vio_res_obs_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -119,72 +109,18 @@ __global__ void __launch_bounds__(OBS_NT) k_res_obs(ResArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------------
 template <int D>
 __global__ void __launch_bounds__(LM_NT) k_res_lm(ResArgs a) {
-    __shared__ double red[P_N * (LM_NT / 64)];
-    const int tid = threadIdx.x;
-    const int l = blockIdx.x * LM_NT + tid;
-    double vr = 0.0, vp = 0.0, fr[NF], fe[NF], fl[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-    for (int f = 0; f < NF; ++f) { fr[f] = 0.0; fe[f] = 0.0; }
-    if (l < a.n) {
-        double spx = 0.0, mpx = 0.0, srho = 0.0;
-        unsigned flag = 0;
-        const int q0 = a.off[l], q1 = a.off[l + 1];
-        for (int q = q0; q < q1; ++q) {
-            const int e = a.eidx[q];
-            const double2 *o = (const double2 *)(a.obs + 4 * (size_t)e);
-            const double2 rr = o[0], er = o[1];
-            const double px = a.focal * sqrt(rr.x * rr.x + rr.y * rr.y);
-            spx += px;
-            if (!isnan(mpx) && !(px <= mpx)) mpx = px;                      // max; a NaN sticks
-            srho += er.y;
-            vr += er.y;
-            vp += er.x;
-            const int f = a.fr[e];
-#pragma unroll
-            for (int k = 0; k < NF; ++k) {                       // (selects, not a register array indexed at run time)
-                fr[k] += (f == k) ? er.y : 0.0;
-                fe[k] += (f == k) ? 1.0 : 0.0;
-            }
-            if (a.dneg[e]) flag |= VIO_RES_FLAG_DEPTH;
-        }
-        const int cnt = q1 - q0;
-        const double mean = cnt ? spx / cnt : 0.0;
-        if (cnt && !(mean <= a.outlier_px)) flag |= VIO_RES_FLAG_REPROJ;
-        if (D == 1) {
-            const double lam = a.val[l];
-            if (!(lam > 0.0) || !isfinite(lam)) flag |= VIO_RES_FLAG_STATE;
-        } else {
-            const double *p = a.val + 3 * (size_t)l;
-            if (!isfinite(p[0]) || !isfinite(p[1]) || !isfinite(p[2])) flag |= VIO_RES_FLAG_STATE;
-        }
-        a.lm_out[3 * (size_t)l] = mean;
-        a.lm_out[3 * (size_t)l + 1] = mpx;
-        a.lm_out[3 * (size_t)l + 2] = srho;
-        a.flags[l] = (unsigned char)flag;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) fl[k] = (flag >> k) & 1u ? 1.0 : 0.0;
-    }
-    // workgroup partials: DPP sum inside each wave, the waves added in order
-    const int w = tid >> 6;
-    double v;
-#define RES_WAVE_SUM(slot, x) v = d_wave_sum_to_lane63(x); if ((tid & 63) == 63) red[(slot) * (LM_NT / 64) + w] = v;
-    RES_WAVE_SUM(P_VR, vr)
-    RES_WAVE_SUM(P_VP, vp)
-#pragma unroll
-    for (int k = 0; k < NF; ++k) {
-        RES_WAVE_SUM(P_FR + k, fr[k])
-        RES_WAVE_SUM(P_FE + k, fe[k])
-    }
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { RES_WAVE_SUM(P_FL + k, fl[k]) }
-#undef RES_WAVE_SUM
-    __syncthreads();
-    if (tid < P_N) {
-        double s = 0.0;
-#pragma unroll
-        for (int k = 0; k < LM_NT / 64; ++k) s += red[tid * (LM_NT / 64) + k];
-        a.part[(size_t)blockIdx.x * P_STRIDE + tid] = s;
-    }
+    const unsigned blk = blockIdx.x;
+#include "vio_res_lm_body.inc"
+}
+
+// k_res_lm for a batch: window w owns the workgroups [blk0[w], blk0[w + 1]), which restart at its landmark 0 and write its partial
+// rows 0 .. n_wg - 1, so its DPP sums see the segments they see in k_res_lm.
+template <int D>
+__global__ void __launch_bounds__(LM_NT) k_res_lm_batch(const ResArgs *__restrict__ items, const int *__restrict__ blk0, int count) {
+    const int win = batch_window(blk0, count, blockIdx.x);
+    const ResArgs a = items[win];
+    const unsigned blk = blockIdx.x - (unsigned)blk0[win];
+#include "vio_res_lm_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -192,53 +128,13 @@ __global__ void __launch_bounds__(LM_NT) k_res_lm(ResArgs a) {
 // workgroups, then a DPP sum); wave 3: ||err_prior||.
 // ---------------------------------------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(TAIL_NT) k_res_tail(ResArgs a) {
-    __shared__ double simu[NW];
-    __shared__ double scol[P_N];
-    __shared__ double sprior;
-    const int tid = threadIdx.x, w = tid >> 6, lane = tid & 63;
-    if (tid < NW) {
-        const int k = tid;
-        double chi = 0.0;
-        if (!a.have_pre) chi = NAN;
-        else if (a.pre_ok[k]) {
-            const double *pre = a.pre + k * PRE_STRIDE;
-            const double *pi = a.poses + 7 * k, *pj = pi + 7, *si = a.sb + 9 * k, *sj = si + 9;
-            ImuCommon c;
-            d_imu_common(pre, pi, si, pj, c);
-            double r[15];
-            d_imu_residual(pre, a.gravity, pi, si, pj, sj, c, r);
-            for (int i = 0; i < 15; ++i) {                 // r^T Info r in the order of the solver's chi2 (d_backsub_imu_block)
-                double t = 0;
-                for (int j = 0; j < 15; ++j) t += pre[PRE_INFO + 15 * i + j] * r[j];
-                chi += r[i] * t;
-            }
-        }
-        simu[k] = chi;
-    }
-    for (int col = w; col < P_N; col += TAIL_NT / 64) {
-        double s = 0.0;
-        for (int b = lane; b < a.n_wg; b += 64) s += a.part[(size_t)b * P_STRIDE + col];
-        s = d_wave_sum_to_lane63(s);
-        if (lane == 63) scol[col] = s;
-    }
-    if (w == TAIL_NT / 64 - 1) {
-        double s = 0.0;
-        for (int i = lane; i < PRD; i += 64) s += a.errp[i] * a.errp[i];
-        s = d_wave_sum_to_lane63(s);
-        if (lane == 63) sprior = sqrt(s);
-    }
-    __syncthreads();
-    if (tid == 0) {
-        double imu = 0.0;
-        for (int k = 0; k < NW; ++k) { imu += simu[k]; a.sum[S_IMUE + k] = simu[k]; }
-        a.sum[S_VR] = scol[P_VR];
-        a.sum[S_VP] = scol[P_VP];
-        a.sum[S_IMU] = imu;
-        a.sum[S_PRIOR] = sprior;
-        a.sum[S_CHI] = 0.5 * (scol[P_VR] + (imu + sprior));         // vio_chi2: 0.5 * (visual + (imu + prior))
-        for (int f = 0; f < NF; ++f) { a.sum[S_FR + f] = scol[P_FR + f]; a.sum[S_FE + f] = scol[P_FE + f]; }
-        for (int k = 0; k < 3; ++k) a.sum[S_FL + k] = scol[P_FL + k];
-    }
+#include "vio_res_tail_body.inc"
+}
+
+// k_res_tail for a batch: workgroup w is window w's tail.
+__global__ void __launch_bounds__(TAIL_NT) k_res_tail_batch(const ResArgs *__restrict__ items) {
+    const ResArgs a = items[blockIdx.x];
+#include "vio_res_tail_body.inc"
 }
 
 // ---------------------------------------------------------------------------------------------------------------------------------
@@ -256,6 +152,9 @@ struct vio_res {
     // device: obs | lm_out | part | sum (doubles), then dneg | flags (bytes); the requested parts come back through h_out (pinned)
     char *d_out = nullptr, *h_out = nullptr;
     size_t out_cap = 0;
+    // device: the batch tables of a vio_res_compute_batch whose first handle this is (ResArgs | workgroup starts)
+    char *d_tab = nullptr, *h_tab = nullptr;
+    size_t tab_cap = 0;
     double timing[5] = {0, 0, 0, 0, 0};
 };
 
@@ -338,12 +237,20 @@ static void inverse15(const double *cov, double *info) {
     }
 }
 
+// One window staged for the kernels: its upload enqueued on the context's stream, its kernel arguments, its read-back layout.
+struct Staged {
+    ResArgs a;
+    int64_t m = 0, n = 0;
+    int D = 1;
+    size_t qObs = 0, qLm = 0, qSum = 0, qFl = 0, nout = 0;      // bytes of d_out
+};
+
+// Validation, read-back of the states, packing, and the upload (enqueued on the context's stream).  Nothing is launched and no output
+// is written.  The caller holds the context's device.
 // D = 1: obs (host, target, pts_i, pts_j); D = 3: obs (frame, pts) in `target` / `pts_j`
-static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
-                          const double *pts_i, const double *pts_j, int64_t n, const vio_preint *const *pre, double focal,
-                          double outlier_px, double *obs_out, double *lm_out, uint8_t *lm_flags, vio_res_summary *summary) {
-    using clk = std::chrono::steady_clock;
-    const auto t0 = clk::now();
+static vio_status stage(vio_res *rs, int D, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
+                        const double *pts_i, const double *pts_j, int64_t n, const vio_preint *const *pre, double focal,
+                        double outlier_px, Staged &sg) {
     if (m < 0 || n < 0 || n >= INT32_MAX || m >= INT32_MAX) return fail(rs, VIO_ERR_BAD_ARG, "bad sizes m=%lld n=%lld", (long long)m, (long long)n);
     if (!(focal > 0.0)) return fail(rs, VIO_ERR_BAD_ARG, "focal %g is not positive", focal);
     if (m > 0 && (!lm || !target || !pts_j || (D == 1 && (!host || !pts_i)))) return fail(rs, VIO_ERR_BAD_ARG, "observation array is NULL");
@@ -351,8 +258,6 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
         if (lm[e] < 0 || lm[e] >= n || target[e] < 0 || target[e] >= NF || (D == 1 && (host[e] < 0 || host[e] >= NF)))
             return fail(rs, VIO_ERR_BAD_ARG, "observation %lld refers to landmark %d / a frame out of range", (long long)e, lm[e]);
     }
-    DeviceScope dev(rs->cfg.device);
-    if (!dev.ok) return fail(rs, VIO_ERR_HIP, "hipSetDevice(%d)", rs->cfg.device);
     vio_status st = VIO_OK;
 
     // layout of the upload (bytes; every array 256-aligned)
@@ -412,9 +317,8 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
     if ((st = ensure(rs, &rs->d_out, &rs->h_out, &rs->out_cap, nout)) != VIO_OK) return st;
 
     if ((st = hip_ck(rs, hipMemcpyAsync(rs->d_in, rs->h_in, nin, hipMemcpyHostToDevice, rs->stream), "upload")) != VIO_OK) return st;
-    const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
-    ResArgs a;
+    ResArgs &a = sg.a;
     char *di = rs->d_in, *dq = rs->d_out;
     a.poses = (const double *)(di + oP); a.sb = (const double *)(di + oS); a.ext = (const double *)(di + oE);
     a.errp = (const double *)(di + oErr); a.pre = (const double *)(di + oPre); a.pre_ok = (const int *)(di + oOk);
@@ -427,6 +331,42 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
     for (int k = 0; k < 3; ++k) a.gravity[k] = rs->cfg.gravity[k];
     a.obs = (double *)(dq + qObs); a.dneg = (unsigned char *)(dq + qDn); a.lm_out = (double *)(dq + qLm);
     a.flags = (unsigned char *)(dq + qFl); a.part = (double *)(dq + qPart); a.sum = (double *)(dq + qSum);
+    sg.m = m; sg.n = n; sg.D = D;
+    sg.qObs = qObs; sg.qLm = qLm; sg.qSum = qSum; sg.qFl = qFl; sg.nout = nout;
+    return VIO_OK;
+}
+
+// After the read-back has completed: the requested outputs, from h_out at the offsets the device used
+static void finish(vio_res *rs, const Staged &sg, double *obs_out, double *lm_out, uint8_t *lm_flags, vio_res_summary *summary) {
+    if (obs_out && sg.m > 0) std::memcpy(obs_out, rs->h_out + sg.qObs, 32 * (size_t)sg.m);
+    if (lm_out && sg.n > 0) std::memcpy(lm_out, rs->h_out + sg.qLm, 24 * (size_t)sg.n);
+    if (lm_flags && sg.n > 0) std::memcpy(lm_flags, rs->h_out + sg.qFl, (size_t)sg.n);
+    if (summary) {
+        const double *s = (const double *)(rs->h_out + sg.qSum);
+        vio_res_summary o;
+        std::memset(&o, 0, sizeof(o));
+        o.chi2 = s[S_CHI]; o.visual_robust = s[S_VR]; o.visual_plain = s[S_VP]; o.imu = s[S_IMU]; o.prior = s[S_PRIOR];
+        for (int k = 0; k < NW; ++k) o.imu_edge[k] = s[S_IMUE + k];
+        for (int f = 0; f < NF; ++f) { o.frame_robust[f] = s[S_FR + f]; o.frame_edges[f] = (int64_t)s[S_FE + f]; }
+        for (int k = 0; k < 3; ++k) o.n_flagged[k] = (int64_t)s[S_FL + k];
+        *summary = o;
+    }
+}
+
+static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
+                          const double *pts_i, const double *pts_j, int64_t n, const vio_preint *const *pre, double focal,
+                          double outlier_px, double *obs_out, double *lm_out, uint8_t *lm_flags, vio_res_summary *summary) {
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    DeviceScope dev(rs->cfg.device);
+    if (!dev.ok) return fail(rs, VIO_ERR_HIP, "hipSetDevice(%d)", rs->cfg.device);
+    Staged sg;
+    vio_status st = stage(rs, D, m, lm, host, target, pts_i, pts_j, n, pre, focal, outlier_px, sg);
+    if (st != VIO_OK) return st;
+    const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    const ResArgs &a = sg.a;
+    const int n_wg = a.n_wg;
+    char *dq = rs->d_out;
 
     if ((st = hip_ck(rs, hipEventRecord(rs->ev[0], rs->stream), "hipEventRecord")) != VIO_OK) return st;
     if (m > 0) {
@@ -447,26 +387,14 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
     if ((st = hip_ck(rs, hipEventRecord(rs->ev[3], rs->stream), "hipEventRecord")) != VIO_OK) return st;
     // read back what was asked for
     struct Part { bool want; size_t off, bytes; } parts[4] = {
-        {obs_out != nullptr && m > 0, qObs, 32 * (size_t)m}, {lm_out != nullptr && n > 0, qLm, 24 * (size_t)n},
-        {lm_flags != nullptr && n > 0, qFl, (size_t)n}, {summary != nullptr, qSum, 8 * S_N}};
+        {obs_out != nullptr && m > 0, sg.qObs, 32 * (size_t)m}, {lm_out != nullptr && n > 0, sg.qLm, 24 * (size_t)n},
+        {lm_flags != nullptr && n > 0, sg.qFl, (size_t)n}, {summary != nullptr, sg.qSum, 8 * S_N}};
     for (const Part &p : parts)
         if (p.want && (st = hip_ck(rs, hipMemcpyAsync(rs->h_out + p.off, dq + p.off, p.bytes, hipMemcpyDeviceToHost, rs->stream), "read-back")) != VIO_OK)
             return st;
     if ((st = hip_ck(rs, hipStreamSynchronize(rs->stream), "hipStreamSynchronize")) != VIO_OK) return st;
 
-    if (parts[0].want) std::memcpy(obs_out, rs->h_out + qObs, parts[0].bytes);
-    if (parts[1].want) std::memcpy(lm_out, rs->h_out + qLm, parts[1].bytes);
-    if (parts[2].want) std::memcpy(lm_flags, rs->h_out + qFl, parts[2].bytes);
-    if (summary) {
-        const double *s = (const double *)(rs->h_out + qSum);
-        vio_res_summary o;
-        std::memset(&o, 0, sizeof(o));
-        o.chi2 = s[S_CHI]; o.visual_robust = s[S_VR]; o.visual_plain = s[S_VP]; o.imu = s[S_IMU]; o.prior = s[S_PRIOR];
-        for (int k = 0; k < NW; ++k) o.imu_edge[k] = s[S_IMUE + k];
-        for (int f = 0; f < NF; ++f) { o.frame_robust[f] = s[S_FR + f]; o.frame_edges[f] = (int64_t)s[S_FE + f]; }
-        for (int k = 0; k < 3; ++k) o.n_flagged[k] = (int64_t)s[S_FL + k];
-        *summary = o;
-    }
+    finish(rs, sg, obs_out, lm_out, lm_flags, summary);
     float ms[3] = {0, 0, 0};
     for (int k = 0; k < 3; ++k)
         if (hipEventElapsedTime(&ms[k], rs->ev[k], rs->ev[k + 1]) != hipSuccess) {
@@ -476,6 +404,108 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
     rs->timing[0] = t_host;
     for (int k = 0; k < 3; ++k) rs->timing[1 + k] = ms[k];
     rs->timing[4] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    return VIO_OK;
+}
+
+// a window's error, reported on the batch's first handle as well
+static vio_status batch_fail(vio_res *r0, vio_status st, int i, const vio_res *rs) {
+    char msg[sizeof(rs->err)];
+    memcpy(msg, rs->err, sizeof(msg));
+    return fail(r0, st, "vio_res_compute_batch: window %d: %s", i, msg);
+}
+
+// The batch: every window staged in its own handle's buffers (one upload each), one table upload, k_res_obs_batch, k_res_lm_batch
+// and k_res_tail_batch once for all windows, one read-back per window (its whole output block), one synchronisation.
+static vio_status compute_batch(vio_res *const *rss, int32_t count, int32_t xyz, const vio_res_batch_item *items, double focal,
+                                double outlier_px) {
+    using clk = std::chrono::steady_clock;
+    const auto t0 = clk::now();
+    vio_res *r0 = rss[0];
+    const int D = xyz ? 3 : 1;
+    void *s0 = nullptr;
+    for (int32_t i = 0; i < count; ++i) {
+        vio_res *rs = rss[i];
+        if (!rs) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d: null handle", i);
+        rs->err[0] = 0;
+        if (rs->cfg.shard_count > 1) return fail(r0, VIO_ERR_UNSUPPORTED, "vio_res_compute_batch: window %d: sharded context", i);
+        if (rs->cfg.device != r0->cfg.device)
+            return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d is on device %d, window 0 on %d: the contexts must share one device and one stream", i, rs->cfg.device, r0->cfg.device);
+        for (int32_t j = 0; j < i; ++j)
+            if (rss[j] == rs) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: windows %d and %d are the same handle", j, i);
+    }
+    DeviceScope dev(r0->cfg.device);
+    if (!dev.ok) return fail(r0, VIO_ERR_HIP, "hipSetDevice(%d)", r0->cfg.device);
+    for (int32_t i = 0; i < count; ++i) {
+        void *sp = nullptr;
+        if (vio_get_stream(rss[i]->ctx, &sp) != VIO_OK) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d: vio_get_stream", i);
+        if (i == 0) s0 = sp;
+        else if (sp != s0) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d is on another stream than window 0: the contexts must share one device and one stream", i);
+    }
+    vio_status st = VIO_OK;
+    std::vector<Staged> sg(count);
+    for (int32_t i = 0; i < count; ++i) {
+        const vio_res_batch_item &it = items[i];
+        st = stage(rss[i], D, it.m, it.lm, D == 1 ? it.host : nullptr, it.target, D == 1 ? it.pts_i : nullptr, it.pts_j, it.n, it.pre,
+                   focal, outlier_px, sg[i]);
+        if (st != VIO_OK) return batch_fail(r0, st, i, rss[i]);
+    }
+    // the tables: ResArgs[count] | obs workgroup starts[count + 1] | lm workgroup starts[count + 1]
+    const size_t bArgs = 0, bObs = align256(sizeof(ResArgs) * count), bLm = bObs + sizeof(int) * ((size_t)count + 1),
+                 nbytes = bLm + sizeof(int) * ((size_t)count + 1);
+    if ((st = ensure(r0, &r0->d_tab, &r0->h_tab, &r0->tab_cap, nbytes)) != VIO_OK) return st;
+    char *ht = r0->h_tab;
+    ResArgs *ta = (ResArgs *)(ht + bArgs);
+    int *blk_obs = (int *)(ht + bObs), *blk_lm = (int *)(ht + bLm);
+    int64_t nobs = 0, nlm = 0;
+    for (int32_t i = 0; i < count; ++i) {
+        ta[i] = sg[i].a;
+        blk_obs[i] = (int)nobs;
+        blk_lm[i] = (int)nlm;
+        nobs += (sg[i].m + OBS_NT - 1) / OBS_NT;
+        nlm += sg[i].a.n_wg;
+        if (nobs > INT32_MAX || nlm > INT32_MAX) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: too many edges in the batch");
+    }
+    blk_obs[count] = (int)nobs;
+    blk_lm[count] = (int)nlm;
+    hipStream_t stream = (hipStream_t)s0;
+    const char *dt = r0->d_tab;
+    if ((st = hip_ck(r0, hipMemcpyAsync(r0->d_tab, r0->h_tab, nbytes, hipMemcpyHostToDevice, stream), "table upload")) != VIO_OK) return st;
+    const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+
+    const ResArgs *da = (const ResArgs *)(dt + bArgs);
+    if ((st = hip_ck(r0, hipEventRecord(r0->ev[0], stream), "hipEventRecord")) != VIO_OK) return st;
+    if (nobs > 0) {
+        if (D == 1) k_res_obs_batch<1><<<(unsigned)nobs, OBS_NT, 0, stream>>>(da, (const int *)(dt + bObs), count);
+        else k_res_obs_batch<3><<<(unsigned)nobs, OBS_NT, 0, stream>>>(da, (const int *)(dt + bObs), count);
+        if ((st = hip_ck(r0, hipGetLastError(), "k_res_obs_batch launch")) != VIO_OK) return st;
+    }
+    if ((st = hip_ck(r0, hipEventRecord(r0->ev[1], stream), "hipEventRecord")) != VIO_OK) return st;
+    if (nlm > 0) {
+        if (D == 1) k_res_lm_batch<1><<<(unsigned)nlm, LM_NT, 0, stream>>>(da, (const int *)(dt + bLm), count);
+        else k_res_lm_batch<3><<<(unsigned)nlm, LM_NT, 0, stream>>>(da, (const int *)(dt + bLm), count);
+        if ((st = hip_ck(r0, hipGetLastError(), "k_res_lm_batch launch")) != VIO_OK) return st;
+    }
+    if ((st = hip_ck(r0, hipEventRecord(r0->ev[2], stream), "hipEventRecord")) != VIO_OK) return st;
+    k_res_tail_batch<<<(unsigned)count, TAIL_NT, 0, stream>>>(da);
+    if ((st = hip_ck(r0, hipGetLastError(), "k_res_tail_batch launch")) != VIO_OK) return st;
+    if ((st = hip_ck(r0, hipEventRecord(r0->ev[3], stream), "hipEventRecord")) != VIO_OK) return st;
+    for (int32_t i = 0; i < count; ++i)
+        if ((st = hip_ck(rss[i], hipMemcpyAsync(rss[i]->h_out, rss[i]->d_out, sg[i].nout, hipMemcpyDeviceToHost, stream), "read-back")) != VIO_OK)
+            return batch_fail(r0, st, i, rss[i]);
+    if ((st = hip_ck(r0, hipStreamSynchronize(stream), "hipStreamSynchronize")) != VIO_OK) return st;
+
+    for (int32_t i = 0; i < count; ++i)
+        finish(rss[i], sg[i], items[i].obs_out, items[i].lm_out, items[i].lm_flags, items[i].summary);
+    float ms[3] = {0, 0, 0};
+    double tm[5] = {NAN, NAN, NAN, NAN, NAN};
+    bool ev_ok = true;
+    for (int k = 0; k < 3; ++k) ev_ok = ev_ok && hipEventElapsedTime(&ms[k], r0->ev[k], r0->ev[k + 1]) == hipSuccess;
+    if (ev_ok) {
+        tm[0] = t_host;
+        for (int k = 0; k < 3; ++k) tm[1 + k] = ms[k];
+        tm[4] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    }
+    for (int32_t i = 0; i < count; ++i) memcpy(rss[i]->timing, tm, sizeof(tm));
     return VIO_OK;
 }
 
@@ -505,8 +535,10 @@ void vio_res_destroy(vio_res *rs) {
     for (int k = 0; k < 4; ++k) if (rs->ev[k]) hipEventDestroy(rs->ev[k]);
     if (rs->d_in) hipFree(rs->d_in);
     if (rs->d_out) hipFree(rs->d_out);
+    if (rs->d_tab) hipFree(rs->d_tab);
     if (rs->h_in) hipHostFree(rs->h_in);
     if (rs->h_out) hipHostFree(rs->h_out);
+    if (rs->h_tab) hipHostFree(rs->h_tab);
     delete rs;
 }
 
@@ -538,6 +570,15 @@ vio_status vio_res_compute_xyz(vio_res *rs, int64_t m, const int32_t *lm, const 
     return compute(rs, 3, m, lm, nullptr, frame, nullptr, pts, n, pre, focal, outlier_px, obs_out, lm_out, lm_flags, summary);
 }
 
+vio_status vio_res_compute_batch(vio_res *const *rss, int32_t count, int32_t xyz, const vio_res_batch_item *items, double focal,
+                                 double outlier_px) {
+    if (count < 0 || (count > 0 && (!rss || !items))) return VIO_ERR_BAD_ARG;
+    if (count == 0) return VIO_OK;
+    if (!rss[0]) return VIO_ERR_BAD_ARG;
+    rss[0]->err[0] = 0;
+    return compute_batch(rss, count, xyz, items, focal, outlier_px);
+}
+
 vio_status vio_res_timing(vio_res *rs, double *out5) {
     if (!rs || !out5) return VIO_ERR_BAD_ARG;
     memcpy(out5, rs->timing, sizeof(rs->timing));
@@ -545,3 +586,4 @@ vio_status vio_res_timing(vio_res *rs, double *out5) {
 }
 
 }   // extern "C"
+

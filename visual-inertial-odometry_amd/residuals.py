@@ -6,6 +6,7 @@ flags of a window.
     r["lm"]       (n, 3)  mean and max pixel error, sum of rho0 per landmark
     r["flags"]    (n,)    uint8: FLAG_REPROJ | FLAG_DEPTH | FLAG_STATE
     r["summary"]  dict    chi2, visual_robust, visual_plain, imu, prior, imu_edge (10), frame_robust (11), frame_edges (11), n_flagged (3)
+    [r, ...] = hip.batch_residuals(ctxs, windows)        # many windows, one launch per kernel
 """
 import ctypes as C
 import os
@@ -35,7 +36,7 @@ class VioResSummary(C.Structure):
 class ResLib:
     """libvio_res_hip.so: vio_res_* (it resolves libvio_hip.so's symbols from the instance already loaded in the process)."""
 
-    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "timing"]
+    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "compute_batch", "timing"]
 
     def __init__(self, path):
         if not os.path.exists(path):
@@ -51,10 +52,86 @@ class ResLib:
         self.fn["version"].restype = C.c_int32
         self.fn["compute"].argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
         self.fn["compute_xyz"].argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
+        self.fn["compute_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double]
 
     def create(self, ctx):
         """A vio_res handle bound to `ctx` (a VioContext of the HIP library)."""
         return ResHandle(self, ctx)
+
+    def compute_batch(self, ctxs, windows, focal=synth.FOCAL, outlier_px=3.0, outputs=("obs", "lm", "flags", "summary"), out=None,
+                      imu=True):
+        """vio_res_compute_batch over the windows of `ctxs` (VioContexts of the HIP library on one device and one stream, one kind of
+        landmark), each with the handle VioContext.residuals uses.  windows: what each context was loaded with.  outputs / imu: as
+        ResHandle.compute, for every window; out: optional list of such dicts of caller-owned arrays, one per window.  Returns one
+        dict per window, in ResHandle.compute's shape.  Errors raise VioError (nothing is written then)."""
+        ctxs, windows = list(ctxs), list(windows)
+        if len(ctxs) != len(windows):
+            raise ValueError("%d contexts, %d windows" % (len(ctxs), len(windows)))
+        B = len(ctxs)
+        handles = [c.res_handle() for c in ctxs]
+        xyz0 = bool(B) and _is_xyz(windows[0])          # the batch's kind: the library refuses a context holding the other
+        items = (VioResBatchItem * max(B, 1))()
+        keep, res = [], []
+        want = set(outputs)
+        for i, (c, w) in enumerate(zip(ctxs, windows)):
+            g = _getter(w)
+            n = c.n
+            lm = np.ascontiguousarray(g("lm"), dtype=np.int32)
+            m = lm.size
+            if m != c.m:
+                raise VioError(-1, "vio_res_compute_batch", "(window %d has %d edges, its context %d)" % (i, m, c.m))
+            if _is_xyz(w):
+                arrs = [lm, None, np.ascontiguousarray(g("frame"), dtype=np.int32), None, _f64(g("pts"), (m, 2))]
+            else:
+                arrs = [lm, np.ascontiguousarray(g("host"), dtype=np.int32), np.ascontiguousarray(g("target"), dtype=np.int32),
+                        _f64(g("pts_i"), (m, 2)), _f64(g("pts_j"), (m, 2))]
+            o = dict((out[i] if out is not None else None) or {})
+            outs = {}
+            if "obs" in want:
+                outs["obs"] = o.get("obs", np.zeros((m, 4)))
+            if "lm" in want:
+                outs["lm"] = o.get("lm", np.zeros((n, 3)))
+            if "flags" in want:
+                outs["flags"] = o.get("flags", np.zeros(n, dtype=np.uint8))
+            for a in outs.values():
+                assert a.flags.c_contiguous
+            summ = VioResSummary() if "summary" in want else None
+            pre = _pre_array(g("preint")) if imu else (None, None)
+            it = items[i]
+            it.m, it.n = m, n
+            it.lm, it.host, it.target, it.pts_i, it.pts_j = [a.ctypes.data if a is not None else None for a in arrs]
+            it.pre = C.addressof(pre[0]) if pre[0] is not None else None
+            ptr = lambda k: outs[k].ctypes.data if k in outs and outs[k].size else None
+            it.obs_out, it.lm_out, it.lm_flags = ptr("obs"), ptr("lm"), ptr("flags")
+            it.summary = C.addressof(summ) if summ is not None else None
+            keep.append((arrs, pre))
+            res.append((outs, summ))
+        hs = (C.c_void_p * max(B, 1))(*[h.h.value for h in handles])
+        st = self.fn["compute_batch"](hs, C.c_int32(B), C.c_int32(1 if xyz0 else 0), items, C.c_double(focal), C.c_double(outlier_px))
+        if B:
+            handles[0]._ck(st, "compute_batch")
+        elif st != 0:
+            raise VioError(st, "vio_res_compute_batch")
+        out_list = []
+        for outs, summ in res:
+            r = {k: outs.get(k) for k in ("obs", "lm", "flags")}
+            r["summary"] = summ.as_dict() if summ is not None else None
+            out_list.append(r)
+        return out_list
+
+
+class VioResBatchItem(C.Structure):
+    _fields_ = [("m", C.c_int64), ("lm", C.c_void_p), ("host", C.c_void_p), ("target", C.c_void_p), ("pts_i", C.c_void_p),
+                ("pts_j", C.c_void_p), ("n", C.c_int64), ("pre", C.c_void_p), ("obs_out", C.c_void_p), ("lm_out", C.c_void_p),
+                ("lm_flags", C.c_void_p), ("summary", C.c_void_p)]
+
+
+def _getter(w):
+    return (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
+
+
+def _is_xyz(w):
+    return (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
 
 
 def _pre_array(pres):
@@ -141,7 +218,8 @@ class ResHandle:
         return res
 
     def timing(self):
-        """ms of the last compute: host (read-back of the states + packing + upload), the three kernels, whole call."""
+        """ms of the last compute: host (read-back of the states + packing + upload), the three kernels, whole call.  After a
+        compute_batch: the batch's times, on every handle of the batch."""
         out = (C.c_double * 5)()
         self._ck(self.lib.fn["timing"](self.h, out), "timing")
         return {"host_ms": out[0], "k_res_obs_ms": out[1], "k_res_lm_ms": out[2], "k_res_tail_ms": out[3], "total_ms": out[4]}
