@@ -5,12 +5,13 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import capi, covariance, imu, residuals, sharded, stream, synth
+from . import batch_stream, capi, covariance, imu, marg, residuals, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
 from .imu import ImuHandle, ImuLib
+from .marg import MargHandle, MargLib
 from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -19,6 +20,7 @@ HIP_LIB = os.environ.get("VIO_HIP_LIB") or os.path.join(PKG_DIR, "csrc", "libvio
 COV_LIB = os.path.join(PKG_DIR, "csrc", "libvio_cov_hip.so")     # include/vio_covariance.h, linked against libvio_hip.so
 RES_LIB = os.path.join(PKG_DIR, "csrc", "libvio_res_hip.so")     # include/vio_residuals.h, linked against libvio_hip.so
 IMU_LIB = os.path.join(PKG_DIR, "csrc", "libvio_imu_hip.so")     # include/vio_imu.h, linked against libvio_hip.so
+MARG_LIB = os.path.join(PKG_DIR, "csrc", "libvio_marg_hip.so")   # include/vio_marg.h, linked against libvio_hip.so
 
 _hip = None
 
@@ -101,3 +103,19 @@ def load_imu():
         load_hip()
         _imu = ImuLib(IMU_LIB)
     return _imu
+
+
+_marg = None
+
+
+def load_marg():
+    """Load the batched marginalisation library (csrc/libvio_marg_hip.so), under the same rule as load_cov: it is linked against
+    csrc/libvio_hip.so, so a VIO_HIP_LIB naming another build is refused."""
+    global _marg
+    if _marg is None:
+        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
+        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
+            raise RuntimeError("load_marg: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_marg_hip.so is linked against" % (HIP_LIB, own))
+        load_hip()
+        _marg = MargLib(MARG_LIB)
+    return _marg

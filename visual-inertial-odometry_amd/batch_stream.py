@@ -1,0 +1,86 @@
+"""B stream drivers advanced in lockstep, with the frame's two heavy calls batched over them: one vio_batch_solve for every window's
+Problem::Solve(10) and one vio_marg_compute_batch (include/vio_marg.h) for every window's MargOldFrame / MargNewFrame.
+
+    drivers = [StreamDriver(hip, SyntheticStream(seed=s), ctx_kwargs=dict(stream=stream)) for s in seeds]   # contexts on one stream
+    trajectories = run_batched(drivers, vio.load_marg().create(stream=stream))
+
+Each driver keeps its own bookkeeping (FeatureManager, slide, the next frame) exactly as StreamDriver.step does it; what changes is
+that the marginalisation takes the re-anchored window's host arrays directly (as MargOldFrame builds a fresh Problem from para_*,
+estimator.cpp:693-829) instead of reloading the context and calling vio_marginalize.  Results agree with StreamDriver.run to the
+rounding of the two marginalisation tails.
+"""
+import numpy as np
+
+from .capi import MARG_OLD, MARG_SECOND_NEW, WINDOW_SIZE
+from .stream import anchor_gauge
+
+
+def _check(drivers):
+    for i, d in enumerate(drivers):
+        if d.outlier_px is not None:
+            raise ValueError("run_batched: driver %d was created with outlier_px (the residual query is not batched here)" % i)
+        if d.bias_relinearize is not None:
+            raise ValueError("run_batched: driver %d was created with bias_relinearize (not batched here)" % i)
+    libs = {id(d.lib) for d in drivers}
+    if len(libs) > 1:
+        raise ValueError("run_batched: the drivers' contexts belong to different libraries")
+    streams = {d.ctx.get_stream() for d in drivers}
+    if len(streams) > 1:
+        raise ValueError("run_batched: the drivers' contexts must share one stream (ctx_kwargs=dict(stream=...))")
+
+
+def step_batched(drivers, marg):
+    """One frame of every driver in `drivers` (all not finished).  Returns, per driver, whether it has another frame."""
+    for d in drivers:
+        d.ensure_depths()
+    loaded = []
+    for d in drivers:
+        w, ids = d.window_arrays()
+        d.ctx.load(w)
+        loaded.append((w, ids))
+    reps = drivers[0].lib.batch_solve([d.ctx for d in drivers], 10)
+    jobs = []
+    for d, (w, ids), rep in zip(drivers, loaded, reps):
+        poses, sb, _ = d.ctx.get_window()
+        invd = d.ctx.get_landmarks()
+        if d.prior is not None:      # estimator.cpp:1040-1049: b/err prior come back updated, H/Jt stay
+            b, e = d.ctx.get_prior()
+            d.prior = dict(d.prior, b=b[:156].copy(), err=e.copy())
+        d.poses, d.sb = anchor_gauge(w.poses, poses, sb)
+        for l, v in zip(ids, invd):
+            d.depth[l] = 1.0 / v
+        newest = d.frames[WINDOW_SIZE]
+        d.trajectory.append((d.s.times[newest], d.poses[WINDOW_SIZE].copy()))
+        d.reports.append(rep)
+        second_new = d.frames[WINDOW_SIZE - 1]
+        margin_old = not (d.nonkey_every and second_new % d.nonkey_every == d.nonkey_every - 1)
+        kind = MARG_OLD if margin_old else MARG_SECOND_NEW
+        d.flags.append(kind)
+        w2, _ = d.window_arrays()       # the re-anchored states (estimator.cpp:1086-1102)
+        jobs.append((kind, w2, d.prior))
+    priors = marg.compute_batch(jobs)
+    more = []
+    for d, p, (kind, _, _) in zip(drivers, priors, jobs):
+        d.prior = p
+        if d.next_frame >= d.s.n_frames:
+            more.append(False)
+            continue
+        if kind == MARG_OLD:
+            d.slide_window_old()
+        else:
+            d.slide_window_new()
+        d.take_next_frame()
+        more.append(True)
+    return more
+
+
+def run_batched(drivers, marg):
+    """Run every driver to the end of its stream (StreamDriver.run, batched).  Returns each driver's trajectory as StreamDriver.run
+    does.  marg: a MargHandle on the contexts' device and stream."""
+    drivers = list(drivers)
+    _check(drivers)
+    active = list(drivers)
+    while active:
+        more = step_batched(active, marg)
+        active = [d for d, m in zip(active, more) if m]
+    return [np.array([np.concatenate([[t], p]) for t, p in d.trajectory]) for d in drivers]
