@@ -5,12 +5,13 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, imu, marg, residuals, sharded, stream, synth
+from . import batch_stream, capi, covariance, imu, init, marg, residuals, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
 from .imu import ImuHandle, ImuLib
+from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
 from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
@@ -21,6 +22,7 @@ COV_LIB = os.path.join(PKG_DIR, "csrc", "libvio_cov_hip.so")     # include/vio_c
 RES_LIB = os.path.join(PKG_DIR, "csrc", "libvio_res_hip.so")     # include/vio_residuals.h, linked against libvio_hip.so
 IMU_LIB = os.path.join(PKG_DIR, "csrc", "libvio_imu_hip.so")     # include/vio_imu.h, linked against libvio_hip.so
 MARG_LIB = os.path.join(PKG_DIR, "csrc", "libvio_marg_hip.so")   # include/vio_marg.h, linked against libvio_hip.so
+INIT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_init_hip.so")   # include/vio_init.h, linked against libvio_hip.so
 
 _hip = None
 
@@ -119,3 +121,19 @@ def load_marg():
         load_hip()
         _marg = MargLib(MARG_LIB)
     return _marg
+
+
+_init = None
+
+
+def load_init():
+    """Load the visual-inertial alignment library (csrc/libvio_init_hip.so), under the same rule as load_cov: it is linked against
+    csrc/libvio_hip.so, so a VIO_HIP_LIB naming another build is refused."""
+    global _init
+    if _init is None:
+        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
+        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
+            raise RuntimeError("load_init: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_init_hip.so is linked against" % (HIP_LIB, own))
+        load_hip()
+        _init = InitLib(INIT_LIB)
+    return _init

@@ -74,11 +74,41 @@ def step_batched(drivers, marg):
     return more
 
 
+def _init_group_key(d):
+    """What one alignment call shares across its windows: the extrinsic translation (TIC[0]), G, the IMU noise of the re-propagation
+    and the aligner.  Drivers that differ in any of them are aligned in separate calls."""
+    noise = tuple(sorted((k, float(v)) for k, v in d.noise.items()))
+    return (tuple(float(v) for v in d.ext[0:3]), float(d.g_norm), noise, id(d.initialize.get("aligner")))
+
+
+def initialize_batched(drivers):
+    """The initialisation tries of every driver created with `initialize` that is not initialised yet, in batched rounds: each round
+    makes one alignment call (InitHandle.initialize_batch: one gyro launch, one re-propagation, one align launch) for every group of
+    drivers still trying that share an extrinsic, G, IMU noise and aligner (usually one group), then applies each outcome as
+    StreamDriver.ensure_initialized does.  Returns the number of rounds."""
+    pending = [d for d in drivers if not d.initialized]
+    rounds = 0
+    while pending:
+        groups = {}
+        for d in pending:
+            groups.setdefault(_init_group_key(d), []).append(d)
+        for group in groups.values():
+            reqs = [d.init_request() for d in group]
+            res = group[0].init_align([r[0] for r in reqs], [r[1] for r in reqs])
+            for d, (item, _), r in zip(group, reqs, res):
+                d.init_apply(item, r)
+        pending = [d for d in pending if not d.initialized]
+        rounds += 1
+    return rounds
+
+
 def run_batched(drivers, marg):
     """Run every driver to the end of its stream (StreamDriver.run, batched).  Returns each driver's trajectory as StreamDriver.run
-    does.  marg: a MargHandle on the contexts' device and stream."""
+    does.  marg: a MargHandle on the contexts' device and stream.  Drivers created with `initialize` first run their tries in batched
+    rounds (initialize_batched); the others start at once."""
     drivers = list(drivers)
     _check(drivers)
+    initialize_batched(drivers)
     active = list(drivers)
     while active:
         more = step_batched(active, marg)

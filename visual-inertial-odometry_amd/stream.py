@@ -61,6 +61,36 @@ def anchor_gauge(poses_before, poses_after, sb_after):
     return poses, sb
 
 
+def visual_trajectory(stream, frames, l=0, scale=1.0, rot_noise=0.0, pos_noise=0.0, seed=0):
+    """The SfM stand-in of the initialisation: ImageFrame::R / T of the global frames `frames` as initialStructure leaves them
+    (estimator.cpp:224-382) — camera frame frames[l] is the origin, R = R_{c_l c_k} RIC^T (the body's rotation in c_l) and
+    T = p_{c_l c_k} / scale (the camera centre, up to the unknown scale).  It replaces relativePose + GlobalSFM + solvePnP, which need
+    OpenCV and Ceres.  rot_noise: std (rad) of a right-multiplied rotation per frame; pos_noise: std (m, metric) added to every camera
+    centre before the division by scale.  Returns (R (F, 3, 3), T (F, 3))."""
+    rng = np.random.RandomState(seed)
+    ric = np.asarray(getattr(stream, "ric", synth.R_IC), dtype=np.float64)
+    tic = np.asarray(getattr(stream, "tic", synth.T_IC), dtype=np.float64)
+    fl = frames[l]
+    Rcl = stream.R[fl] @ ric
+    pcl = stream.P[fl] + stream.R[fl] @ tic
+    R, T = np.zeros((len(frames), 3, 3)), np.zeros((len(frames), 3))
+    for k, f in enumerate(frames):
+        Rb = Rcl.T @ stream.R[f]
+        if rot_noise:
+            Rb = Rb @ _small_rot(rng.normal(0.0, rot_noise, 3))
+        R[k] = Rb
+        p = Rcl.T @ (stream.P[f] + stream.R[f] @ tic - pcl)
+        if pos_noise:
+            p = p + rng.normal(0.0, pos_noise, 3)
+        T[k] = p / scale
+    return R, T
+
+
+def _small_rot(th):
+    q = np.array([th[0] / 2, th[1] / 2, th[2] / 2, 1.0])
+    return synth.quat_to_rot(q / np.linalg.norm(q))
+
+
 class SyntheticStream:
     """Ground truth + measurements of `n_frames` keyframes on the simulator's trajectory."""
 
@@ -328,7 +358,7 @@ class SimulatorFileStream:
 
 class StreamDriver:
     def __init__(self, lib, stream, ctx_kwargs=None, pos_noise=0.02, rot_noise=0.005, depth_noise=0.05, seed=1,
-                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None):
+                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None, initialize=None):
         """triangulate=True: a landmark's first depth comes from FeatureManager::triangulate (vio_triangulate, on the
         current pose estimates, feature_manager.cpp:203-257) the first time it enters a solve, as in
         Estimator::solveOdometry (estimator.cpp:489-503), instead of from the perturbed ground truth.
@@ -343,7 +373,16 @@ class StreamDriver:
         of the frame it starts from (new IntegrationBase{acc_0, gyr_0, Bas[..], Bgs[..]}, estimator.cpp:116, 159, 1178, 1229), and
         before every solve the intervals whose start frame's bias moved more than the threshold (max-abs, per axis) from their
         linearized_ba / linearized_bg are re-propagated (repropagate, integration_base.h:38-52).  self.repropagated: the count of every
-        step.  None: every interval stays at zero bias and the library is not loaded."""
+        step.  None: every interval stays at zero bias and the library is not loaded.
+        initialize=dict(scale=, rot_noise=, pos_noise=, max_tries=, seed=) (needs the GPU): the window starts in the INITIAL state
+        with no ground-truth state.  Each try aligns the current 11-frame window (every frame a keyframe) through the alignment
+        library (include/vio_init.h) on visual_trajectory's SfM stand-in: gyro bias, re-propagation, LinearAlignment,
+        RefineGravity (visualInitialAlign, estimator.cpp:384-460).  On success the state change is applied, the window's
+        pre-integrations become the re-propagated ones, and the depths are triangulated on the un-scaled SfM poses with tic = 0 and
+        then multiplied by s.  On failure the oldest frame leaves without a prior (the INITIAL slideWindow) and the next frame comes
+        in; max_tries failures raise.  self.init_tries, self.init_frame (the newest frame at success) and self.init_result record it.
+        An `aligner` entry (a callable(items, intervals, tic, g_norm, noise) returning the dicts InitHandle.initialize_batch returns)
+        replaces the library (the CPU tests pass the numpy restatement).  None: the ground-truth start below."""
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -360,7 +399,7 @@ class StreamDriver:
         self.nonkey_every = nonkey_every
         self.poses = np.zeros((NUM_FRAMES, 7))
         self.sb = np.zeros((NUM_FRAMES, 9))
-        for i in range(NUM_FRAMES):
+        for i in range(NUM_FRAMES if initialize is None else 0):
             th = rng.normal(0.0, rot_noise, 3)
             dq = np.array([th[0] / 2, th[1] / 2, th[2] / 2, 1.0])
             dq /= np.linalg.norm(dq)
@@ -390,6 +429,86 @@ class StreamDriver:
             self.imu_h = load_imu().create(device=self.ctx.cfg.device)
             self._imu_stale = True              # the handle does not hold self.intervals
             self._repropagate(list(range(WINDOW_SIZE)))
+        self.initialize = None if initialize is None else dict(initialize)
+        self.initialized = initialize is None
+        self.init_tries, self.init_frame, self.init_result = 0, None, None
+        if self.initialize is not None:
+            cfg = dict(scale=1.0, rot_noise=0.0, pos_noise=0.0, max_tries=10, seed=0)
+            cfg.update(self.initialize)
+            self.initialize = cfg
+            self._init_h = self._init_imu = None
+
+    # ---- initialisation (initialize) ------------------------------------------------------------------
+    def init_request(self):
+        """The current window as an alignment item (visual_trajectory's R / T, the zero-bias records) and its raw intervals."""
+        c = self.initialize
+        R, T = visual_trajectory(self.s, self.frames, 0, c["scale"], c["rot_noise"], c["pos_noise"], c["seed"] + self.init_tries)
+        return dict(R=R, T=T, pre=list(self.preint), is_key=None), list(self.intervals)
+
+    def init_align(self, items, intervals):
+        """The alignment of `items` on this driver's backend: the library (one handle pair per driver), or the `aligner` given."""
+        c = self.initialize
+        if c.get("aligner") is not None:
+            return c["aligner"](items, intervals, self.ext[0:3].copy(), self.g_norm, self.noise)
+        if self._init_h is None:
+            from . import load_imu, load_init
+            self._init_h = load_init().create(device=self.ctx.cfg.device)
+            self._init_imu = load_imu().create(device=self.ctx.cfg.device)
+        return self._init_h.initialize_batch(items, intervals, self._init_imu, self.ext[0:3].copy(), self.g_norm, self.noise)
+
+    def init_apply(self, item, res):
+        """One try's outcome: visualInitialAlign's state change on success, else the INITIAL slide and the next frame."""
+        self.init_tries += 1
+        if res["status"] == 0:
+            s = float(res["s"])
+            self.poses = np.asarray(res["poses"], dtype=np.float64).reshape(NUM_FRAMES, 7).copy()
+            self.sb = np.asarray(res["speed_bias"], dtype=np.float64).reshape(NUM_FRAMES, 9).copy()
+            self.preint = list(res["pre"])
+            # f_manager.clearDepth; triangulate on the SfM poses with TIC_TMP = 0 and RIC; estimated_depth *= s (estimator.cpp:407-439)
+            self.depth = {}
+            sfm = np.zeros((NUM_FRAMES, 7))
+            sfm[:, 0:3] = item["T"]
+            for i in range(NUM_FRAMES):
+                sfm[i, 3:7] = synth.rot_to_quat(item["R"][i])
+            todo = self.usable()
+            if todo:
+                sf, off, pts = [], [0], []
+                for l, start in todo:
+                    sf.append(start); pts.extend(p for _, p in self.tracks[l]); off.append(off[-1] + len(self.tracks[l]))
+                ext0 = np.concatenate([np.zeros(3), self.ext[3:7]])
+                d = self.ctx.triangulate(np.array(sf, dtype=np.int32), np.array(off, dtype=np.int64), np.array(pts).reshape(-1, 2),
+                                         sfm, ext0, -np.ones(len(todo)))
+                for (l, _), v in zip(todo, d):
+                    self.depth[l] = float(v) * s
+                self.n_triangulated += len(todo)
+            self.init_result = res
+            self.init_frame = self.frames[WINDOW_SIZE]
+            self.initialized = True
+            return True
+        if self.init_tries >= self.initialize["max_tries"]:
+            raise RuntimeError("StreamDriver: no initialisation after %d tries (last status %d)" % (self.init_tries, res["status"]))
+        if self.next_frame >= self.s.n_frames:
+            raise RuntimeError("StreamDriver: the stream ended before the initialisation succeeded")
+        # slideWindow in the INITIAL state: the oldest frame leaves, no prior, no depth shift (f_manager.removeBack)
+        gone = self.frames[0]
+        for l in list(self.tracks.keys()):
+            tr = self.tracks[l]
+            if tr[0][0] == gone:
+                del tr[0]
+                if not tr:
+                    del self.tracks[l]
+        self.frames.pop(0)
+        self.intervals.pop(0)
+        self.preint.pop(0)
+        self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
+        self.take_next_frame()
+        return False
+
+    def ensure_initialized(self):
+        """Tries until the window is initialised (a no-op for a driver created without `initialize`, or already initialised)."""
+        while not self.initialized:
+            item, ivs = self.init_request()
+            self.init_apply(item, self.init_align([item], [ivs])[0])
 
     # ---- feature bookkeeping (FeatureManager) ---------------------------------------------------------
     def add_frame_observations(self, f):
@@ -490,6 +609,8 @@ class StreamDriver:
     def step(self):
         """Solve the current window, marginalise, slide, take in the next frame.  Returns False at the end."""
         st = self.s
+        if not self.initialized:
+            self.ensure_initialized()
         if self.bias_relinearize is not None:
             self.repropagated.append(self.relinearize_biases())
         self.ensure_depths()
@@ -618,7 +739,8 @@ class StreamDriver:
     def ground_truth(self):
         st = self.s
         return np.array([np.concatenate([[t], st.P[k], st.Q[k]])
-                         for k, t in enumerate(st.times) if k >= WINDOW_SIZE])[:len(self.trajectory)]
+                         for k, t in enumerate(st.times)
+                         if k >= (WINDOW_SIZE if self.init_frame is None else self.init_frame)])[:len(self.trajectory)]
 
 
 def ate_rmse(traj, gt):
