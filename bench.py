@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — GN iterations/s of the MI355X sliding-window VIO backend on BASELINE.json's headline config.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks L] [--landmark-type invdepth|xyz] [--dump-outputs DIR]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--landmarks L] [--landmark-type invdepth|xyz] [--dump-outputs DIR] [--full]
 
 One "step" = one Gauss-Newton iteration of the hot path: linearise all reprojection
 + IMU factors, reduce the landmark Schur complement, add the prior, damped pivoted LDLT of the 171x171 pose
@@ -15,21 +15,26 @@ N > 1: BASELINE.json configs[3] — ONE 200 000-landmark / 800 000-observation w
        the rendezvous, the barriers and the 128-byte communicator id); per iteration the library itself issues ONE RCCL
        all-gather of the shards' 24 KB partial reduced systems on its stream and adds them in rank order (SURVEY.md
        section 8e).  `value` = GN iterations/s of THAT window (steps / elapsed — N ranks working on
-       one iteration count once); `single_gpu_same_window_ms` is the same window unsharded on rank 0's GPU, measured in the
-       same run, so the speed-up is in the line.
+       one iteration count once); with --full, `single_gpu_same_window_ms` is the same window unsharded on rank 0's GPU,
+       measured in the same run, so the speed-up is in the line.
        Launch: `python bench.py --gpus N` spawns its N rank processes itself (the parent never touches a GPU), or
        `python -m torch.distributed.run --nproc-per-node N bench.py --gpus N` (RANK / WORLD_SIZE from the environment).
        VIO_BENCH_ONE_DEVICE=1 puts every rank on device 0 with the exchange staged through host memory over gloo (RCCL
        refuses two ranks on one device): the N > 1 code path on a one-GPU box (tests/test_gpu_bench_launch.py).
 
-The JSON line also carries
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line.  Its JSON line also carries
   roofline      achieved = algorithmic bytes per launch / measured launch duration of the dominant kernel
                 (HIP event pairs on the library's stream around about ten launches spread over the timed steps),
                 peak = 8 TB/s HBM
-  cpu_baseline  the oracle's (oracle/vio_oracle.c, plain C, 1 thread) GN iteration on the same window,
-                timed on this box's host cores on a bounded sample (rank 0, N = 1 only)
+
+--full adds, after the timed steps (each block can be left out with its --no-* / size option):
+  cpu_baseline  the oracle's (oracle/vio_oracle.c, plain C, 1 thread) GN iteration on the same window, timed on the
+                host on a bounded sample; with cpu_baseline_all_cores (OpenMP build) and cpu_reference (oracle/_ref)
   per_frame     what surrounds the inner iteration once per frame: vio_set_*, plan + upload + first linearisation,
-                Solve(10), MargOldFrame — host wall clock, for the HIP library and for the CPU port
+                Solve(10), MargOldFrame — host wall clock, for the HIP library and for the CPU port; per_frame_small
+                the same in the reference's regime (N = 150 / 300, the MH_05 real-IMU windows, four backends)
+  scale_projection, batched (N = 1), single_gpu_same_window_ms and replicas (N > 1)
+Without --full these keys are null.
 """
 import argparse
 import importlib.util
@@ -188,6 +193,9 @@ def main():
     ap.add_argument("--replica-windows", type=int, default=16, help="N > 1: independent windows per GPU of the `replicas` block (0 skips it)")
     ap.add_argument("--replica-landmarks", type=int, default=20000)
     ap.add_argument("--no-scale-projection", action="store_true", help="N = 1: skip the scale_projection block (the sharded launch sequence on the 200 000 / N-landmark shards of configs[3], one GPU)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure the CPU baselines, per-frame costs, scale projection, batched windows (N = 1) "
+                         "and the unsharded / replicated windows (N > 1); a plain run measures the headline only")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last step handed back (window, landmarks, step, chi2) as DIR/<name>.npy")
     args = ap.parse_args()
@@ -297,7 +305,8 @@ def main():
         ctx.gn_iteration(lam)
     ctx.synchronize()
 
-    # which kernel dominates?  one short profiled pass per kernel (outside the timed region)
+    # which kernel dominates?  one short profiled pass per kernel (outside the timed region).  Every run makes it, --full or not: the
+    # timed loop brackets the kernel it finds, and its iterations are part of the state the timed steps start from
     per_kernel = {}
     for kid, name in enumerate(hip.KERNELS):
         ctx.profile_begin(kid)
@@ -334,7 +343,7 @@ def main():
 
     # N > 1: the same window unsharded on rank 0's GPU, in the same run (the others wait at the barrier)
     single_gpu = None
-    if world > 1:
+    if world > 1 and args.full:
         if rank == 0:
             c1 = hip.context(device=local_rank)
             c1.load(full)
@@ -355,7 +364,7 @@ def main():
     # N > 1, the regime that scales: every GPU runs its own batch of independent windows (vio_batch_gn_iteration), no collective in
     # the data path; the job's figure is the sum over the ranks of windows x iterations / the slowest rank's time
     replicas = None
-    if world > 1 and args.replica_windows > 0:
+    if world > 1 and args.full and args.replica_windows > 0:
         rw, rn = args.replica_windows, args.replica_landmarks
         rkw = dict(device=local_rank, item_policy=vio.capi.ITEMS_THROUGHPUT)
         lead = hip.context(**rkw)
@@ -434,7 +443,7 @@ def main():
     # ---- what one frame costs around the inner iteration (Estimator::backendOptimization, estimator.cpp:1075-1141):
     #      vio_set_* of a fresh window, plan + upload + first linearisation, Solve(10), MargOldFrame — host wall clock
     per_frame = None
-    if rank == 0 and world == 1 and not args.no_per_frame:
+    if rank == 0 and world == 1 and args.full and not args.no_per_frame:
         # a stream of windows, one frame (0.1 s) apart on the generator's trajectory, each with fresh landmarks: frame r + 1 is set with
         # THE PRIOR FRAME r's MargOldFrame RETURNED (estimator.cpp:693-901 -> :1020-1034), so vio_set_prior copies and uploads its
         # 430 KB in every timed frame (round 3 alternated two windows that shared one prior, and the library's keep-if-equal test
@@ -631,7 +640,7 @@ def main():
     #      communicator: the collective's launch is in the figure, its xGMI latency between real ranks is not), against the whole window
     #      unsharded (three launches) in the same run.  projected_speedup = unsharded / shard: an UPPER bound.
     scale_projection = None
-    if rank == 0 and world == 1 and not xyz and not args.no_scale_projection:
+    if rank == 0 and world == 1 and not xyz and args.full and not args.no_scale_projection:
         try:
             n_sp = args.landmarks_total
             big = make(n_sp, seed=42, obs_per_landmark=k_obs)
@@ -677,7 +686,7 @@ def main():
     # ---- B independent windows per launch (vio_batch_gn_iteration): the regime in which the device is full.  Same window
     #      size as the headline, different seeds; reported beside the single-window line, never instead of it
     batched = None
-    if rank == 0 and world == 1 and args.batch > 0:
+    if rank == 0 and world == 1 and args.full and args.batch > 0:
         B = args.batch
         # (many windows share the device: items as large as the LDS holds, vio_config.item_policy)
         lead = hip.context(device=local_rank, item_policy=vio.capi.ITEMS_THROUGHPUT)
@@ -792,7 +801,7 @@ def main():
         del cb, extra, members, lead          # (members first: they run on the leader's stream)
 
     cpu_baseline = None
-    if rank == 0 and world > 1 and not args.no_cpu_baseline:
+    if rank == 0 and world > 1 and args.full and not args.no_cpu_baseline:
         # the CPU port on the WHOLE window the ranks share (the reference's dense solver would need 320 GB for it): a bounded sample
         import subprocess
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s"])
@@ -812,7 +821,7 @@ def main():
                         "sample": "%d GN iterations of the whole %d-landmark / %d-observation window the %d ranks share, "
                                   "oracle/vio_oracle.c (plain C, -O2, 1 thread), rank 0's host" % (steps, full.n_landmarks, full.n_observations, world)}
         del co
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         import subprocess
         subprocess.check_call(["make", "-C", os.path.join(ROOT, "oracle"), "-s"])
         orc = vio.VioLib(os.path.join(ROOT, "oracle", "liboracle.so"), "vioo_")
