@@ -88,6 +88,16 @@ def test_hip_library_fails_loudly_without_a_gpu(vio):
     assert e.value.status in (-6, -2)      # VIO_ERR_NO_DEVICE / VIO_ERR_HIP, never a silent CPU path
 
 
+def test_companion_handles_fail_loudly_without_a_gpu(vio):
+    import torch
+    if torch.cuda.is_available():
+        pytest.skip("a GPU is present")
+    for load in (vio.load_imu, vio.load_marg, vio.load_init):
+        with pytest.raises(vio.VioError) as e:
+            load().create()
+        assert e.value.status in (-6, -2), load.__name__      # VIO_ERR_NO_DEVICE / VIO_ERR_HIP from the device scope
+
+
 def test_oracle_exports_the_same_surface(vio, oracle_lib):
     for f in header_functions():
         if f == "vio_preintegrate":

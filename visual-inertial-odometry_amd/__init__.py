@@ -58,82 +58,43 @@ def load_hip_debug():
     return _hip_debug
 
 
-_cov = None
+_companions = {}
+
+
+def _load_companion(key, cls, path):
+    """A companion library, loaded once.  It resolves libvio_hip.so through its rpath: csrc/libvio_hip.so, which load_hip() loads
+    first so that both share that one instance.  With VIO_HIP_LIB naming another build the process would hold two copies and hand
+    one's contexts to the other, so that is refused."""
+    if key not in _companions:
+        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
+        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
+            raise RuntimeError("load_%s: VIO_HIP_LIB=%s is not %s, the libvio_hip.so %s is linked against"
+                               % (key, HIP_LIB, own, os.path.basename(path)))
+        load_hip()
+        _companions[key] = cls(path)
+    return _companions[key]
 
 
 def load_cov():
-    """Load the covariance library (csrc/libvio_cov_hip.so).  It resolves libvio_hip.so through its rpath: csrc/libvio_hip.so, which
-    load_hip() loads first so that both share that one instance.  With VIO_HIP_LIB naming another build the process would hold two
-    copies and hand one's contexts to the other, so that is refused."""
-    global _cov
-    if _cov is None:
-        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
-        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
-            raise RuntimeError("load_cov: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_cov_hip.so is linked against" % (HIP_LIB, own))
-        load_hip()
-        _cov = CovLib(COV_LIB)
-    return _cov
-
-
-_res = None
+    """Load the covariance library (csrc/libvio_cov_hip.so)."""
+    return _load_companion("cov", CovLib, COV_LIB)
 
 
 def load_res():
-    """Load the residual library (csrc/libvio_res_hip.so), under the same rule as load_cov: it resolves libvio_hip.so through its rpath,
-    so a VIO_HIP_LIB naming another build is refused."""
-    global _res
-    if _res is None:
-        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
-        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
-            raise RuntimeError("load_res: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_res_hip.so is linked against" % (HIP_LIB, own))
-        load_hip()
-        _res = ResLib(RES_LIB)
-    return _res
-
-
-_imu = None
+    """Load the residual library (csrc/libvio_res_hip.so)."""
+    return _load_companion("res", ResLib, RES_LIB)
 
 
 def load_imu():
-    """Load the IMU pre-integration library (csrc/libvio_imu_hip.so), under the same rule as load_cov: it is linked against
-    csrc/libvio_hip.so, so a VIO_HIP_LIB naming another build is refused."""
-    global _imu
-    if _imu is None:
-        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
-        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
-            raise RuntimeError("load_imu: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_imu_hip.so is linked against" % (HIP_LIB, own))
-        load_hip()
-        _imu = ImuLib(IMU_LIB)
-    return _imu
-
-
-_marg = None
+    """Load the IMU pre-integration library (csrc/libvio_imu_hip.so)."""
+    return _load_companion("imu", ImuLib, IMU_LIB)
 
 
 def load_marg():
-    """Load the batched marginalisation library (csrc/libvio_marg_hip.so), under the same rule as load_cov: it is linked against
-    csrc/libvio_hip.so, so a VIO_HIP_LIB naming another build is refused."""
-    global _marg
-    if _marg is None:
-        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
-        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
-            raise RuntimeError("load_marg: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_marg_hip.so is linked against" % (HIP_LIB, own))
-        load_hip()
-        _marg = MargLib(MARG_LIB)
-    return _marg
-
-
-_init = None
+    """Load the batched marginalisation library (csrc/libvio_marg_hip.so)."""
+    return _load_companion("marg", MargLib, MARG_LIB)
 
 
 def load_init():
-    """Load the visual-inertial alignment library (csrc/libvio_init_hip.so), under the same rule as load_cov: it is linked against
-    csrc/libvio_hip.so, so a VIO_HIP_LIB naming another build is refused."""
-    global _init
-    if _init is None:
-        own = os.path.join(PKG_DIR, "csrc", "libvio_hip.so")
-        if os.path.realpath(HIP_LIB) != os.path.realpath(own):
-            raise RuntimeError("load_init: VIO_HIP_LIB=%s is not %s, the libvio_hip.so libvio_init_hip.so is linked against" % (HIP_LIB, own))
-        load_hip()
-        _init = InitLib(INIT_LIB)
-    return _init
+    """Load the visual-inertial alignment library (csrc/libvio_init_hip.so)."""
+    return _load_companion("init", InitLib, INIT_LIB)

@@ -40,6 +40,9 @@ class VioPreint(C.Structure):
 
     @classmethod
     def from_dict(cls, d):
+        """A VioPreint from synth.preintegrate's dict; a VioPreint passes through as it is."""
+        if isinstance(d, cls):
+            return d
         p = cls()
         v = np.frombuffer(p, dtype=np.float64)       # the struct is 467 contiguous doubles: filled through a view (a ctypes array
         v[0] = float(d["sum_dt"])                    # assigned from a list costs 10 us per pre-integration, 0.1 ms per frame)
@@ -81,6 +84,64 @@ def _f64(a, shape=None):
     return a
 
 
+def window_field(w, k, default=None):
+    """Field k of a window: a dict's entry or an object's attribute (synth.Window, StreamDriver's windows); default when absent."""
+    return w.get(k, default) if isinstance(w, dict) else getattr(w, k, default)
+
+
+def preint_pointers(pres):
+    """The ten pointers of vio_set_imu_all (None: no edge; dicts or VioPreint) and the structs they point to (kept alive by the
+    caller).  The caller checks that there are ten."""
+    keep = [None if p is None else VioPreint.from_dict(p) for p in pres]
+    arr = (C.POINTER(VioPreint) * WINDOW_SIZE)(*[C.pointer(p) if p is not None else C.POINTER(VioPreint)() for p in keep])
+    return arr, keep
+
+
+# the entry points every library shares a signature of; the others return a vio_status
+_SHARED_SIGNATURES = {"destroy": (None, [C.c_void_p]), "last_error": (C.c_char_p, [C.c_void_p]), "version": (C.c_int32, [])}
+
+
+def open_lib(path, prefix, symbols):
+    """(dll, fn): the built library at `path` and its entry points prefix + s for s in `symbols`, fn[s] returning a vio_status
+    (c_int) unless the signature is a shared one (destroy, last_error, version).  A missing export raises AttributeError."""
+    if not os.path.exists(path):
+        raise FileNotFoundError(
+            "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
+    dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
+    fn = {}
+    for s in symbols:
+        f = fn[s] = getattr(dll, prefix + s)
+        f.restype, argtypes = _SHARED_SIGNATURES.get(s, (C.c_int, None))
+        if argtypes is not None:
+            f.argtypes = argtypes
+    return dll, fn
+
+
+class CompanionHandle:
+    """What the handles of the companion libraries (vio_cov, vio_res, vio_imu, vio_marg, vio_init) share: .lib (the *Lib),
+    .h (the handle), their entry points named PREFIX + name."""
+
+    PREFIX = None
+
+    def close(self):
+        if self.h:
+            self.lib.fn["destroy"](self.h)
+            self.h = C.c_void_p()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def last_error(self):
+        return (self.lib.fn["last_error"](self.h) or b"").decode(errors="replace")
+
+    def _ck(self, st, where):
+        if st != 0:
+            raise VioError(st, self.PREFIX + where, self.last_error())
+
+
 class VioLib:
     """One shared library exporting the vio_backend.h surface under `prefix`."""
 
@@ -109,15 +170,10 @@ class VioLib:
     KERNELS = ["k_linearize", "k_reduce", "k_assemble", "k_pose_solve", "k_backsub", "k_lm_decide"]
 
     def __init__(self, path, prefix="vio_"):
-        if not os.path.exists(path):
-            raise FileNotFoundError(
-                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
         self.path = path
         self.prefix = prefix
-        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        self.fn = {}
-        for s in self.SYMBOLS:
-            self.fn[s] = getattr(self.dll, prefix + s)     # raises AttributeError on a missing export
+        self.dll, self.fn = open_lib(path, prefix, self.SYMBOLS)     # raises AttributeError on a missing export
+        self.fn["default_config"].restype = None
         for s in self.OPTIONAL:
             if hasattr(self.dll, prefix + s):
                 self.fn[s] = getattr(self.dll, prefix + s)
@@ -131,12 +187,6 @@ class VioLib:
                 if hasattr(self.dll, prefix + s):
                     self.fn[s] = getattr(self.dll, prefix + s)
                     self.fn[s].restype = C.c_int
-        self.fn["last_error"].restype = C.c_char_p
-        self.fn["destroy"].restype = None
-        self.fn["default_config"].restype = None
-        for s in self.SYMBOLS:
-            if s not in ("last_error", "destroy", "default_config"):
-                self.fn[s].restype = C.c_int
 
     def preintegrate(self, acc0, gyr0, ba, bg, dts, accs, gyrs, acc_n, gyr_n, acc_w, gyr_w):
         """IntegrationBase on the host through the ABI (vio_preintegrate); returns a VioPreint."""
@@ -317,8 +367,7 @@ class VioContext:
         if pre is None:
             self._ck(self.lib.fn["set_imu"](self.h, C.c_int32(k), None), "set_imu")
         else:
-            p = pre if isinstance(pre, VioPreint) else VioPreint.from_dict(pre)
-            self._ck(self.lib.fn["set_imu"](self.h, C.c_int32(k), C.byref(p)), "set_imu")
+            self._ck(self.lib.fn["set_imu"](self.h, C.c_int32(k), C.byref(VioPreint.from_dict(pre))), "set_imu")
 
     def set_imu_all(self, pres):
         """vio_set_imu_all: the ten edges (dicts, VioPreint or None) in one crossing of the boundary; libraries without it: ten calls."""
@@ -329,8 +378,7 @@ class VioContext:
             for k, pre in enumerate(pres):
                 self.set_imu(k, pre)
             return
-        keep = [None if p is None else (p if isinstance(p, VioPreint) else VioPreint.from_dict(p)) for p in pres]
-        arr = (C.POINTER(VioPreint) * WINDOW_SIZE)(*[C.pointer(p) if p is not None else C.POINTER(VioPreint)() for p in keep])
+        arr, _keep = preint_pointers(pres)
         self._ck(self.lib.fn["set_imu_all"](self.h, arr), "set_imu_all")
 
     def set_prior(self, prior):

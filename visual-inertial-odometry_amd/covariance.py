@@ -8,11 +8,10 @@
 Ordering of pose_cov: [ext(6) | (pose 6, speed-bias 9) x 11] (vio_get_schur_system's); fixed variables are zero rows / columns.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-from .capi import NUM_FRAMES, POSE_DIM, VioError, _dp, _f64, _ip
+from .capi import NUM_FRAMES, POSE_DIM, CompanionHandle, VioError, _dp, _f64, _ip, open_lib, window_field
 
 GAUGE_NONE, GAUGE_FIX_OLDEST = 0, 1
 GAUGES = {"none": GAUGE_NONE, "fix_oldest": GAUGE_FIX_OLDEST}
@@ -41,18 +40,9 @@ class CovLib:
                "landmark_information", "pivot_ratio", "timing"]
 
     def __init__(self, path):
-        if not os.path.exists(path):
-            raise FileNotFoundError(
-                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
         self.path = path
-        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        self.fn = {s: getattr(self.dll, "vio_cov_" + s) for s in self.SYMBOLS}
-        for s in self.SYMBOLS:
-            self.fn[s].restype = C.c_int
+        self.dll, self.fn = open_lib(path, "vio_cov_", self.SYMBOLS)
         self.fn["compute_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p]
-        self.fn["destroy"].restype = None
-        self.fn["last_error"].restype = C.c_char_p
-        self.fn["version"].restype = C.c_int32
 
     def create(self, ctx):
         """A vio_cov handle bound to `ctx` (a VioContext of the HIP library)."""
@@ -71,13 +61,13 @@ class CovLib:
         B = len(ctxs)
         gi = GAUGES[gauge] if isinstance(gauge, str) else int(gauge)
         handles = [c.cov_handle() for c in ctxs]
-        xyz0 = bool(B) and _is_xyz(windows[0])          # the batch's kind: the library refuses a context holding the other
+        xyz0 = bool(B) and window_field(windows[0], "xyz") is not None          # the batch's kind: the library refuses a context holding the other
         items = (VioCovBatchItem * max(B, 1))()
         keep, res = [], []
         for i, (c, w) in enumerate(zip(ctxs, windows)):
-            g = _getter(w)
+            g = lambda k: window_field(w, k)
             n = c.n
-            xyz = _is_xyz(w)
+            xyz = g("xyz") is not None
             P, L = out[i] if out is not None else (np.zeros((POSE_DIM, POSE_DIM)), np.zeros((n, 3, 3)) if xyz else np.zeros(n))
             assert P.shape == (POSE_DIM, POSE_DIM) and P.dtype == np.float64 and P.flags.c_contiguous
             assert L.dtype == np.float64 and L.flags.c_contiguous and L.size == n * (9 if xyz else 1)
@@ -115,15 +105,9 @@ class VioCovBatchItem(C.Structure):
                 ("pts_j", C.c_void_p), ("n", C.c_int64), ("pose_cov", C.c_void_p), ("lm_out", C.c_void_p)]
 
 
-def _getter(w):
-    return (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
+class CovHandle(CompanionHandle):
+    PREFIX = "vio_cov_"
 
-
-def _is_xyz(w):
-    return (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
-
-
-class CovHandle:
     def __init__(self, lib, ctx):
         self.lib = lib
         self.ctx = ctx
@@ -132,21 +116,6 @@ class CovHandle:
         if st != 0:
             raise VioError(st, "vio_cov_create")
 
-    def close(self):
-        if self.h:
-            self.lib.fn["destroy"](self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, st, where):
-        if st != 0:
-            msg = self.lib.fn["last_error"](self.h)
-            raise VioError(st, "vio_cov_" + where, (msg or b"").decode(errors="replace"))
 
     def set_config(self, cfg):
         """vio_cov_set_config: the configuration the context now runs with (after VioContext.set_config)."""
@@ -161,9 +130,9 @@ class CovHandle:
     def compute(self, w, gauge="fix_oldest", pose_cov=None, lm_out=None):
         """(pose_cov (171, 171), lm_var (n,) or lm_cov (n, 3, 3)) of the context's current state.  w: the window passed to load().
         pose_cov / lm_out: optional arrays to fill (they are left untouched when the call fails)."""
-        g = (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
+        g = lambda k: window_field(w, k)
         gi = GAUGES[gauge] if isinstance(gauge, str) else int(gauge)
-        xyz = (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
+        xyz = g("xyz") is not None
         n = self.ctx.n
         P = np.zeros((POSE_DIM, POSE_DIM)) if pose_cov is None else pose_cov
         assert P.shape == (POSE_DIM, POSE_DIM) and P.dtype == np.float64 and P.flags.c_contiguous

@@ -11,12 +11,12 @@
 
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "vio_batch_grid.h"
+#include "vio_companion.h"
 #include "vio_device_math.h"
 #include "vio_obs_csr.h"
 #include "../../include/vio_covariance.h"
@@ -159,21 +159,14 @@ __global__ void __launch_bounds__(LmNT<D>::v) k_cov_landmarks_batch(const CovLmA
 struct vio_cov {
     vio_ctx *ctx = nullptr;
     vio_config cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};
-    char err[512] = {0};
-    // device: S | poses | ext | val | pts_i | pts_j (doubles), then keep | off | ofr | ohost | status (ints): one upload
-    double *d_in = nullptr;
-    size_t in_cap = 0;
-    double *h_in = nullptr;                 // pinned mirror of d_in
-    // device: cov | cc | out | info (doubles), then status (2 ints): one read-back
-    double *d_out = nullptr;
-    size_t out_cap = 0;
-    double *h_out = nullptr;
-    // device: the batch tables of a vio_cov_compute_batch whose first handle this is (CovPoseItem | CovLmArgs | workgroup starts)
-    double *d_tab = nullptr;
-    size_t tab_cap = 0;
-    double *h_tab = nullptr;
+    StreamEvents<3> q;                      // the context's stream (borrowed, set by stage()) and the timing events
+    ErrText err = {0};
+    // S | poses | ext | val | pts_i | pts_j (doubles), then keep | off | ofr | ohost | status (ints): one upload
+    Twin<double> in;
+    // cov | cc | out | info (doubles), then status (2 ints): one read-back
+    Twin<double> out;
+    // the batch tables of a vio_cov_compute_batch whose first handle this is (CovPoseItem | CovLmArgs | workgroup starts)
+    Twin<char> tab;
     int64_t last_n = -1;
     int last_dim = 0;
     std::vector<double> info;               // of the last successful compute
@@ -182,47 +175,6 @@ struct vio_cov {
     bool relinearize = false;               // vio_cov_set_config changed what the system depends on: the context's linearisation, if it
                                             // holds one, is of the old configuration (vio_set_config keeps it), so linearise first
 };
-
-// The calling thread's current device is the caller's: switched to the context's for the library's calls, put back on the way out.
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-static vio_status fail(vio_cov *cv, vio_status st, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(cv->err, sizeof(cv->err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-static vio_status hip_ck(vio_cov *cv, hipError_t e, const char *what) {
-    if (e == hipSuccess) return VIO_OK;
-    return fail(cv, VIO_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-// grow a pinned host buffer and its device twin to hold `bytes`
-static vio_status ensure(vio_cov *cv, double **d, double **h, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return VIO_OK;
-    if (*d) hipFree(*d);
-    if (*h) hipHostFree(*h);
-    *d = nullptr; *h = nullptr; *cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    vio_status st = hip_ck(cv, hipMalloc((void **)d, want), "hipMalloc");
-    if (st != VIO_OK) return st;
-    st = hip_ck(cv, hipHostMalloc((void **)h, want, hipHostMallocDefault), "hipHostMalloc");
-    if (st != VIO_OK) return st;
-    *cap = want;
-    return VIO_OK;
-}
 
 static const char *var_name(int full, char *buf, size_t len) {
     if (full < 6) snprintf(buf, len, "extrinsic component %d", full);
@@ -254,12 +206,12 @@ struct Staged {
 // D = 1: obs (host, target, pts_i, pts_j); D = 3: obs (frame, pts) in `target` / `pts_j`
 static vio_status stage(vio_cov *cv, int D, int32_t gauge, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
                         const double *pts_i, const double *pts_j, int64_t n, Staged &sg) {
-    if (gauge != VIO_COV_GAUGE_NONE && gauge != VIO_COV_GAUGE_FIX_OLDEST) return fail(cv, VIO_ERR_BAD_ARG, "unknown gauge %d", gauge);
-    if (m < 0 || n < 0 || n > INT32_MAX / 9 || m > INT32_MAX) return fail(cv, VIO_ERR_BAD_ARG, "bad sizes m=%lld n=%lld", (long long)m, (long long)n);
-    if (m > 0 && (!lm || !target || !pts_j || (D == 1 && (!host || !pts_i)))) return fail(cv, VIO_ERR_BAD_ARG, "observation array is NULL");
+    if (gauge != VIO_COV_GAUGE_NONE && gauge != VIO_COV_GAUGE_FIX_OLDEST) return fail(cv->err, VIO_ERR_BAD_ARG, "unknown gauge %d", gauge);
+    if (m < 0 || n < 0 || n > INT32_MAX / 9 || m > INT32_MAX) return fail(cv->err, VIO_ERR_BAD_ARG, "bad sizes m=%lld n=%lld", (long long)m, (long long)n);
+    if (m > 0 && (!lm || !target || !pts_j || (D == 1 && (!host || !pts_i)))) return fail(cv->err, VIO_ERR_BAD_ARG, "observation array is NULL");
     for (int64_t e = 0; e < m; ++e) {
         if (lm[e] < 0 || lm[e] >= n || target[e] < 0 || target[e] >= NF || (D == 1 && (host[e] < 0 || host[e] >= NF)))
-            return fail(cv, VIO_ERR_BAD_ARG, "observation %lld refers to landmark %d / frame out of range", (long long)e, lm[e]);
+            return fail(cv->err, VIO_ERR_BAD_ARG, "observation %lld refers to landmark %d / frame out of range", (long long)e, lm[e]);
     }
     vio_status st = VIO_OK;
 
@@ -271,25 +223,25 @@ static vio_status stage(vio_cov *cv, int D, int32_t gauge, int64_t m, const int3
     const size_t iKeep = 0, iOff = iKeep + PD + 1, iOfr = iOff + (size_t)n + 1, iHost = iOfr + (size_t)m, ni = iHost + (size_t)n + 2;
     sg.oS = oS; sg.oP = oP; sg.oE = oE; sg.oV = oV; sg.oPi = oPi; sg.oPj = oPj; sg.nd = nd;
     sg.iKeep = iKeep; sg.iOff = iOff; sg.iOfr = iOfr; sg.iHost = iHost; sg.ni = ni;
-    if ((st = ensure(cv, &cv->d_in, &cv->h_in, &cv->in_cap, nd * sizeof(double) + ni * sizeof(int))) != VIO_OK) return st;
-    double *hd = cv->h_in;
-    int *hi = (int *)(cv->h_in + nd);
+    if ((st = cv->in.ensure(cv->err, nd * sizeof(double) + ni * sizeof(int))) != VIO_OK) return st;
+    double *hd = cv->in.h;
+    int *hi = (int *)(cv->in.h + nd);
 
     // H_pp_schur at the current state: linearise first when the context says it holds none, or holds one of an older configuration
     if (cv->relinearize) {
-        if ((st = vio_linearize(cv->ctx)) != VIO_OK) return fail(cv, st, "vio_linearize: %s", vio_last_error(cv->ctx));
+        if ((st = vio_linearize(cv->ctx)) != VIO_OK) return fail(cv->err, st, "vio_linearize: %s", vio_last_error(cv->ctx));
         cv->relinearize = false;
     }
     st = vio_get_schur_system(cv->ctx, hd + oS, nullptr);
     if (st == VIO_ERR_BAD_ARG) {
-        if ((st = vio_linearize(cv->ctx)) != VIO_OK) return fail(cv, st, "vio_linearize: %s", vio_last_error(cv->ctx));
+        if ((st = vio_linearize(cv->ctx)) != VIO_OK) return fail(cv->err, st, "vio_linearize: %s", vio_last_error(cv->ctx));
         st = vio_get_schur_system(cv->ctx, hd + oS, nullptr);
     }
-    if (st != VIO_OK) return fail(cv, st, "vio_get_schur_system: %s", vio_last_error(cv->ctx));
+    if (st != VIO_OK) return fail(cv->err, st, "vio_get_schur_system: %s", vio_last_error(cv->ctx));
     double sb[NF * 9];
-    if ((st = vio_get_window(cv->ctx, hd + oP, sb, hd + oE)) != VIO_OK) return fail(cv, st, "vio_get_window: %s", vio_last_error(cv->ctx));
+    if ((st = vio_get_window(cv->ctx, hd + oP, sb, hd + oE)) != VIO_OK) return fail(cv->err, st, "vio_get_window: %s", vio_last_error(cv->ctx));
     st = D == 1 ? vio_get_landmarks(cv->ctx, n, hd + oV) : vio_get_landmarks_xyz(cv->ctx, n, hd + oV);
-    if (st != VIO_OK) return fail(cv, st, "vio_get_landmarks%s(n=%lld): %s", D == 1 ? "" : "_xyz", (long long)n, vio_last_error(cv->ctx));
+    if (st != VIO_OK) return fail(cv->err, st, "vio_get_landmarks%s(n=%lld): %s", D == 1 ? "" : "_xyz", (long long)n, vio_last_error(cv->ctx));
 
     // variables kept: everything but the extrinsic (fixed, or not a variable of XYZ edges) and frame 0's pose (gauge)
     const int ext_fixed = D == 3 || cv->cfg.ext_fixed;
@@ -321,48 +273,48 @@ static vio_status stage(vio_cov *cv, int D, int32_t gauge, int64_t m, const int3
         }
         return true;
     });
-    if (!ok) return fail(cv, VIO_ERR_BAD_ARG, "landmark %d has observations with different host frames", mixed);
+    if (!ok) return fail(cv->err, VIO_ERR_BAD_ARG, "landmark %d has observations with different host frames", mixed);
     if (D == 1)
         for (int64_t l = 0; l < n; ++l)
             if (oh[l] < 0) { oh[l] = 0; hd[oPi + 2 * (size_t)l] = 0; hd[oPi + 2 * (size_t)l + 1] = 0; }
 
     void *sp = nullptr;
-    if ((st = vio_get_stream(cv->ctx, &sp)) != VIO_OK) return fail(cv, st, "vio_get_stream");
-    cv->stream = (hipStream_t)sp;
+    if ((st = vio_get_stream(cv->ctx, &sp)) != VIO_OK) return fail(cv->err, st, "vio_get_stream");
+    cv->q.stream = (hipStream_t)sp;
 
     const size_t o_cov = 0, o_cc = PD * PD, o_out = o_cc + CD * CD, o_info = o_out + (size_t)n * D * D, nout = align8(o_info + (size_t)n * D * D);
     sg.o_cov = o_cov; sg.o_cc = o_cc; sg.o_out = o_out; sg.o_info = o_info; sg.nout = nout;
-    if ((st = ensure(cv, &cv->d_out, &cv->h_out, &cv->out_cap, nout * sizeof(double) + 8 * sizeof(int))) != VIO_OK) return st;
-    int *d_status = (int *)(cv->d_out + nout);
+    if ((st = cv->out.ensure(cv->err, nout * sizeof(double) + 8 * sizeof(int))) != VIO_OK) return st;
+    int *d_status = (int *)(cv->out.d + nout);
 
-    if ((st = hip_ck(cv, hipMemcpyAsync(cv->d_in, cv->h_in, nd * sizeof(double) + ni * sizeof(int), hipMemcpyHostToDevice, cv->stream), "upload")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipMemcpyAsync(cv->in.d, cv->in.h, nd * sizeof(double) + ni * sizeof(int), hipMemcpyHostToDevice, cv->q.stream), "upload")) != VIO_OK) return st;
     // status[0]: failing pivot (-1: none); status[1]: smallest landmark without a positive definite information (NO_BAD_LM: none)
-    if ((st = hip_ck(cv, hipMemsetAsync(d_status, 0xff, sizeof(int), cv->stream), "hipMemsetAsync")) != VIO_OK) return st;
-    if ((st = hip_ck(cv, hipMemsetAsync(d_status + 1, 0x7f, sizeof(int), cv->stream), "hipMemsetAsync")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipMemsetAsync(d_status, 0xff, sizeof(int), cv->q.stream), "hipMemsetAsync")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipMemsetAsync(d_status + 1, 0x7f, sizeof(int), cv->q.stream), "hipMemsetAsync")) != VIO_OK) return st;
     return VIO_OK;
 }
 
 // k_cov_pose's and k_cov_landmarks' arguments for a staged window
 static CovPoseItem pose_item(vio_cov *cv, const Staged &sg) {
-    int *di = (int *)(cv->d_in + sg.nd), *d_status = (int *)(cv->d_out + sg.nout);
+    int *di = (int *)(cv->in.d + sg.nd), *d_status = (int *)(cv->out.d + sg.nout);
     CovPoseItem it;
-    it.S = cv->d_in + sg.oS; it.keep = di + sg.iKeep; it.n = sg.nk; it.cov = cv->d_out + sg.o_cov; it.cc = cv->d_out + sg.o_cc;
+    it.S = cv->in.d + sg.oS; it.keep = di + sg.iKeep; it.n = sg.nk; it.cov = cv->out.d + sg.o_cov; it.cc = cv->out.d + sg.o_cc;
     it.status = d_status; it.ratio = (double *)(d_status + 2);
     return it;
 }
 
 static CovLmArgs lm_args(vio_cov *cv, const Staged &sg) {
-    int *di = (int *)(cv->d_in + sg.nd), *d_status = (int *)(cv->d_out + sg.nout);
+    int *di = (int *)(cv->in.d + sg.nd), *d_status = (int *)(cv->out.d + sg.nout);
     CovLmArgs a;
-    a.cc = cv->d_out + sg.o_cc; a.poses = cv->d_in + sg.oP; a.ext = cv->d_in + sg.oE; a.val = cv->d_in + sg.oV; a.pts_i = cv->d_in + sg.oPi;
-    a.pts_j = cv->d_in + sg.oPj; a.off = di + sg.iOff; a.ofr = di + sg.iOfr; a.ohost = di + sg.iHost; a.n = (int)sg.n;
+    a.cc = cv->out.d + sg.o_cc; a.poses = cv->in.d + sg.oP; a.ext = cv->in.d + sg.oE; a.val = cv->in.d + sg.oV; a.pts_i = cv->in.d + sg.oPi;
+    a.pts_j = cv->in.d + sg.oPj; a.off = di + sg.iOff; a.ofr = di + sg.iOfr; a.ohost = di + sg.iHost; a.n = (int)sg.n;
     a.ext_free = !sg.ext_fixed; a.loss_type = cv->cfg.loss_type; a.loss_delta = cv->cfg.loss_delta; a.sqrt_info = cv->cfg.reproj_sqrt_info;
-    a.out = cv->d_out + sg.o_out; a.info = cv->d_out + sg.o_info; a.bad = d_status + 1;
+    a.out = cv->out.d + sg.o_out; a.info = cv->out.d + sg.o_info; a.bad = d_status + 1;
     return a;
 }
 
 static vio_status read_back(vio_cov *cv, const Staged &sg) {
-    return hip_ck(cv, hipMemcpyAsync(cv->h_out, cv->d_out, sg.nout * sizeof(double) + 8 * sizeof(int), hipMemcpyDeviceToHost, cv->stream), "read-back");
+    return hip_ck(cv->err, hipMemcpyAsync(cv->out.h, cv->out.d, sg.nout * sizeof(double) + 8 * sizeof(int), hipMemcpyDeviceToHost, cv->q.stream), "read-back");
 }
 
 // After the read-back has completed: the window's verdict, and on success its outputs and the handle's landmark information and
@@ -370,17 +322,17 @@ static vio_status read_back(vio_cov *cv, const Staged &sg) {
 static vio_status finish(vio_cov *cv, const Staged &sg, double *pose_cov, double *lm_out) {
     const int64_t n = sg.n;
     const int D = sg.D;
-    const int *h_status = (const int *)(cv->h_out + sg.nout);
-    const int *hi = (const int *)(cv->h_in + sg.nd);
+    const int *h_status = (const int *)(cv->out.h + sg.nout);
+    const int *hi = (const int *)(cv->in.h + sg.nd);
     char nm[64];
     if (h_status[0] >= 0)
-        return fail(cv, VIO_ERR_NOT_FINITE, "pose covariance: pivot %d (%s) of the reduced H_pp_schur is not positive and finite",
+        return fail(cv->err, VIO_ERR_NOT_FINITE, "pose covariance: pivot %d (%s) of the reduced H_pp_schur is not positive and finite",
                     h_status[0], var_name(hi[sg.iKeep + h_status[0]], nm, sizeof(nm)));
     if (n > 0 && h_status[1] != NO_BAD_LM)
-        return fail(cv, VIO_ERR_NOT_FINITE, "landmark %d: its information is not positive definite and finite", h_status[1]);
-    if (pose_cov) memcpy(pose_cov, cv->h_out + sg.o_cov, sizeof(double) * PD * PD);
-    if (lm_out && n > 0) memcpy(lm_out, cv->h_out + sg.o_out, sizeof(double) * (size_t)n * D * D);
-    cv->info.assign(cv->h_out + sg.o_info, cv->h_out + sg.o_info + (size_t)n * D * D);
+        return fail(cv->err, VIO_ERR_NOT_FINITE, "landmark %d: its information is not positive definite and finite", h_status[1]);
+    if (pose_cov) memcpy(pose_cov, cv->out.h + sg.o_cov, sizeof(double) * PD * PD);
+    if (lm_out && n > 0) memcpy(lm_out, cv->out.h + sg.o_out, sizeof(double) * (size_t)n * D * D);
+    cv->info.assign(cv->out.h + sg.o_info, cv->out.h + sg.o_info + (size_t)n * D * D);
     cv->last_n = n;
     cv->last_dim = D;
     cv->pivot_ratio = *(const double *)(h_status + 2);
@@ -392,31 +344,31 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     DeviceScope dev(cv->cfg.device);
-    if (!dev.ok) return fail(cv, VIO_ERR_HIP, "hipSetDevice(%d)", cv->cfg.device);
+    if (!dev.ok) return fail(cv->err, VIO_ERR_HIP, "hipSetDevice(%d)", cv->cfg.device);
     Staged sg;
     vio_status st = stage(cv, D, gauge, m, lm, host, target, pts_i, pts_j, n, sg);
     if (st != VIO_OK) return st;
     const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
-    if ((st = hip_ck(cv, hipEventRecord(cv->ev[0], cv->stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipEventRecord(cv->q.ev[0], cv->q.stream), "hipEventRecord")) != VIO_OK) return st;
     const CovPoseItem it = pose_item(cv, sg);
-    k_cov_pose<<<1, POSE_NT, 0, cv->stream>>>(it.S, it.keep, it.n, it.cov, it.cc, it.status, it.ratio);
-    if ((st = hip_ck(cv, hipGetLastError(), "k_cov_pose launch")) != VIO_OK) return st;
-    if ((st = hip_ck(cv, hipEventRecord(cv->ev[1], cv->stream), "hipEventRecord")) != VIO_OK) return st;
+    k_cov_pose<<<1, POSE_NT, 0, cv->q.stream>>>(it.S, it.keep, it.n, it.cov, it.cc, it.status, it.ratio);
+    if ((st = hip_ck(cv->err, hipGetLastError(), "k_cov_pose launch")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipEventRecord(cv->q.ev[1], cv->q.stream), "hipEventRecord")) != VIO_OK) return st;
     if (n > 0) {
         const CovLmArgs a = lm_args(cv, sg);
-        if (D == 1) k_cov_landmarks<1><<<(unsigned)((n + LmNT<1>::v - 1) / LmNT<1>::v), LmNT<1>::v, 0, cv->stream>>>(a);
-        else k_cov_landmarks<3><<<(unsigned)((n + LmNT<3>::v - 1) / LmNT<3>::v), LmNT<3>::v, 0, cv->stream>>>(a);
-        if ((st = hip_ck(cv, hipGetLastError(), "k_cov_landmarks launch")) != VIO_OK) return st;
+        if (D == 1) k_cov_landmarks<1><<<(unsigned)((n + LmNT<1>::v - 1) / LmNT<1>::v), LmNT<1>::v, 0, cv->q.stream>>>(a);
+        else k_cov_landmarks<3><<<(unsigned)((n + LmNT<3>::v - 1) / LmNT<3>::v), LmNT<3>::v, 0, cv->q.stream>>>(a);
+        if ((st = hip_ck(cv->err, hipGetLastError(), "k_cov_landmarks launch")) != VIO_OK) return st;
     }
-    if ((st = hip_ck(cv, hipEventRecord(cv->ev[2], cv->stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipEventRecord(cv->q.ev[2], cv->q.stream), "hipEventRecord")) != VIO_OK) return st;
     if ((st = read_back(cv, sg)) != VIO_OK) return st;
-    if ((st = hip_ck(cv, hipStreamSynchronize(cv->stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    if ((st = hip_ck(cv->err, hipStreamSynchronize(cv->q.stream), "hipStreamSynchronize")) != VIO_OK) return st;
 
     if ((st = finish(cv, sg, pose_cov, lm_out)) != VIO_OK) return st;
     float ms1 = 0, ms2 = 0;
-    if ((st = hip_ck(cv, hipEventElapsedTime(&ms1, cv->ev[0], cv->ev[1]), "hipEventElapsedTime")) != VIO_OK ||
-        (st = hip_ck(cv, hipEventElapsedTime(&ms2, cv->ev[1], cv->ev[2]), "hipEventElapsedTime")) != VIO_OK) {
+    if ((st = hip_ck(cv->err, hipEventElapsedTime(&ms1, cv->q.ev[0], cv->q.ev[1]), "hipEventElapsedTime")) != VIO_OK ||
+        (st = hip_ck(cv->err, hipEventElapsedTime(&ms2, cv->q.ev[1], cv->q.ev[2]), "hipEventElapsedTime")) != VIO_OK) {
         for (double &t : cv->timing) t = NAN;   // (the outputs are written: only the timings are unknown)
         return VIO_OK;
     }
@@ -431,7 +383,7 @@ static vio_status compute(vio_cov *cv, int D, int32_t gauge, int64_t m, const in
 static vio_status batch_fail(vio_cov *c0, vio_status st, int i, const vio_cov *cv) {
     char msg[sizeof(cv->err)];
     memcpy(msg, cv->err, sizeof(msg));
-    return fail(c0, st, "vio_cov_compute_batch: window %d: %s", i, msg);
+    return fail(c0->err, st, "vio_cov_compute_batch: window %d: %s", i, msg);
 }
 
 // The batch: every window staged in its own handle's buffers (one upload each), one table upload, k_cov_pose_batch and
@@ -442,26 +394,26 @@ static vio_status compute_batch(vio_cov *const *cvs, int32_t count, int32_t gaug
     const auto t0 = clk::now();
     vio_cov *c0 = cvs[0];
     const int D = xyz ? 3 : 1;
-    if (gauge != VIO_COV_GAUGE_NONE && gauge != VIO_COV_GAUGE_FIX_OLDEST) return fail(c0, VIO_ERR_BAD_ARG, "unknown gauge %d", gauge);
+    if (gauge != VIO_COV_GAUGE_NONE && gauge != VIO_COV_GAUGE_FIX_OLDEST) return fail(c0->err, VIO_ERR_BAD_ARG, "unknown gauge %d", gauge);
     // one device, one stream, no handle twice (a handle's buffers hold one window), no shard
     void *s0 = nullptr;
     for (int32_t i = 0; i < count; ++i) {
         vio_cov *cv = cvs[i];
-        if (!cv) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d: null handle", i);
+        if (!cv) return fail(c0->err, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d: null handle", i);
         cv->err[0] = 0;
-        if (cv->cfg.shard_count > 1) return fail(c0, VIO_ERR_UNSUPPORTED, "vio_cov_compute_batch: window %d: sharded context", i);
+        if (cv->cfg.shard_count > 1) return fail(c0->err, VIO_ERR_UNSUPPORTED, "vio_cov_compute_batch: window %d: sharded context", i);
         if (cv->cfg.device != c0->cfg.device)
-            return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d is on device %d, window 0 on %d: the contexts must share one device and one stream", i, cv->cfg.device, c0->cfg.device);
+            return fail(c0->err, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d is on device %d, window 0 on %d: the contexts must share one device and one stream", i, cv->cfg.device, c0->cfg.device);
         for (int32_t j = 0; j < i; ++j)
-            if (cvs[j] == cv) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: windows %d and %d are the same handle", j, i);
+            if (cvs[j] == cv) return fail(c0->err, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: windows %d and %d are the same handle", j, i);
     }
     DeviceScope dev(c0->cfg.device);
-    if (!dev.ok) return fail(c0, VIO_ERR_HIP, "hipSetDevice(%d)", c0->cfg.device);
+    if (!dev.ok) return fail(c0->err, VIO_ERR_HIP, "hipSetDevice(%d)", c0->cfg.device);
     for (int32_t i = 0; i < count; ++i) {
         void *sp = nullptr;
-        if (vio_get_stream(cvs[i]->ctx, &sp) != VIO_OK) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d: vio_get_stream", i);
+        if (vio_get_stream(cvs[i]->ctx, &sp) != VIO_OK) return fail(c0->err, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d: vio_get_stream", i);
         if (i == 0) s0 = sp;
-        else if (sp != s0) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d is on another stream than window 0: the contexts must share one device and one stream", i);
+        else if (sp != s0) return fail(c0->err, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: window %d is on another stream than window 0: the contexts must share one device and one stream", i);
     }
     vio_status st = VIO_OK;
     std::vector<Staged> sg(count);
@@ -474,8 +426,8 @@ static vio_status compute_batch(vio_cov *const *cvs, int32_t count, int32_t gaug
     const int lnt = D == 1 ? LmNT<1>::v : LmNT<3>::v;
     const size_t bPose = 0, bLm = align8(bPose + sizeof(CovPoseItem) * count), bBlk = align8(bLm + sizeof(CovLmArgs) * count),
                  nbytes = bBlk + sizeof(int) * ((size_t)count + 1);
-    if ((st = ensure(c0, &c0->d_tab, &c0->h_tab, &c0->tab_cap, nbytes)) != VIO_OK) return st;
-    char *ht = (char *)c0->h_tab;
+    if ((st = c0->tab.ensure(c0->err, nbytes)) != VIO_OK) return st;
+    char *ht = c0->tab.h;
     CovPoseItem *tp = (CovPoseItem *)(ht + bPose);
     CovLmArgs *tl = (CovLmArgs *)(ht + bLm);
     int *blk0 = (int *)(ht + bBlk);
@@ -485,29 +437,29 @@ static vio_status compute_batch(vio_cov *const *cvs, int32_t count, int32_t gaug
         tl[i] = lm_args(cvs[i], sg[i]);
         blk0[i] = (int)nblk;
         nblk += (sg[i].n + lnt - 1) / lnt;
-        if (nblk > INT32_MAX) return fail(c0, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: too many landmarks in the batch");
+        if (nblk > INT32_MAX) return fail(c0->err, VIO_ERR_BAD_ARG, "vio_cov_compute_batch: too many landmarks in the batch");
     }
     blk0[count] = (int)nblk;
     hipStream_t stream = (hipStream_t)s0;
-    const char *dt = (const char *)c0->d_tab;
-    if ((st = hip_ck(c0, hipMemcpyAsync(c0->d_tab, c0->h_tab, nbytes, hipMemcpyHostToDevice, stream), "table upload")) != VIO_OK) return st;
+    const char *dt = c0->tab.d;
+    if ((st = hip_ck(c0->err, hipMemcpyAsync(c0->tab.d, c0->tab.h, nbytes, hipMemcpyHostToDevice, stream), "table upload")) != VIO_OK) return st;
     const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
-    if ((st = hip_ck(c0, hipEventRecord(c0->ev[0], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(c0->err, hipEventRecord(c0->q.ev[0], stream), "hipEventRecord")) != VIO_OK) return st;
     k_cov_pose_batch<<<(unsigned)count, POSE_NT, 0, stream>>>((const CovPoseItem *)(dt + bPose));
-    if ((st = hip_ck(c0, hipGetLastError(), "k_cov_pose_batch launch")) != VIO_OK) return st;
-    if ((st = hip_ck(c0, hipEventRecord(c0->ev[1], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(c0->err, hipGetLastError(), "k_cov_pose_batch launch")) != VIO_OK) return st;
+    if ((st = hip_ck(c0->err, hipEventRecord(c0->q.ev[1], stream), "hipEventRecord")) != VIO_OK) return st;
     if (nblk > 0) {
         const CovLmArgs *dl = (const CovLmArgs *)(dt + bLm);
         const int *db = (const int *)(dt + bBlk);
         if (D == 1) k_cov_landmarks_batch<1><<<(unsigned)nblk, LmNT<1>::v, 0, stream>>>(dl, db, count);
         else k_cov_landmarks_batch<3><<<(unsigned)nblk, LmNT<3>::v, 0, stream>>>(dl, db, count);
-        if ((st = hip_ck(c0, hipGetLastError(), "k_cov_landmarks_batch launch")) != VIO_OK) return st;
+        if ((st = hip_ck(c0->err, hipGetLastError(), "k_cov_landmarks_batch launch")) != VIO_OK) return st;
     }
-    if ((st = hip_ck(c0, hipEventRecord(c0->ev[2], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(c0->err, hipEventRecord(c0->q.ev[2], stream), "hipEventRecord")) != VIO_OK) return st;
     for (int32_t i = 0; i < count; ++i)
         if ((st = read_back(cvs[i], sg[i])) != VIO_OK) return batch_fail(c0, st, i, cvs[i]);
-    if ((st = hip_ck(c0, hipStreamSynchronize(stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    if ((st = hip_ck(c0->err, hipStreamSynchronize(stream), "hipStreamSynchronize")) != VIO_OK) return st;
 
     vio_status ret = VIO_OK;
     for (int32_t i = 0; i < count; ++i) {
@@ -515,9 +467,9 @@ static vio_status compute_batch(vio_cov *const *cvs, int32_t count, int32_t gaug
         if (window_status) window_status[i] = wst;
         if (wst != VIO_OK) ret = wst;
     }
-    float ms1 = 0, ms2 = 0;
+    const float ms1 = elapsed_ms(c0->q.ev[0], c0->q.ev[1]), ms2 = elapsed_ms(c0->q.ev[1], c0->q.ev[2]);
     double tm[4] = {NAN, NAN, NAN, NAN};
-    if (hipEventElapsedTime(&ms1, c0->ev[0], c0->ev[1]) == hipSuccess && hipEventElapsedTime(&ms2, c0->ev[1], c0->ev[2]) == hipSuccess) {
+    if (!std::isnan(ms1) && !std::isnan(ms2)) {
         tm[0] = t_host;
         tm[1] = ms1;
         tm[2] = ms2;
@@ -540,8 +492,7 @@ vio_status vio_cov_create(struct vio_ctx *ctx, const vio_config *cfg, vio_cov **
     cv->cfg = *cfg;
     DeviceScope dev(cfg->device);
     if (!dev.ok) { delete cv; return VIO_ERR_HIP; }
-    for (int k = 0; k < 3; ++k)
-        if (hipEventCreate(&cv->ev[k]) != hipSuccess) { vio_cov_destroy(cv); return VIO_ERR_HIP; }
+    if (cv->q.create_events() != hipSuccess) { vio_cov_destroy(cv); return VIO_ERR_HIP; }
     *out = cv;
     return VIO_OK;
 }
@@ -549,21 +500,14 @@ vio_status vio_cov_create(struct vio_ctx *ctx, const vio_config *cfg, vio_cov **
 void vio_cov_destroy(vio_cov *cv) {
     if (!cv) return;
     DeviceScope dev(cv->cfg.device);
-    if (cv->stream) hipStreamSynchronize(cv->stream);
-    for (int k = 0; k < 3; ++k) if (cv->ev[k]) hipEventDestroy(cv->ev[k]);
-    if (cv->d_in) hipFree(cv->d_in);
-    if (cv->d_out) hipFree(cv->d_out);
-    if (cv->d_tab) hipFree(cv->d_tab);
-    if (cv->h_in) hipHostFree(cv->h_in);
-    if (cv->h_out) hipHostFree(cv->h_out);
-    if (cv->h_tab) hipHostFree(cv->h_tab);
-    delete cv;
+    cv->q.release();
+    delete cv;                              // (the buffers free themselves)
 }
 
 vio_status vio_cov_set_config(vio_cov *cv, const vio_config *cfg) {
     if (!cv || !cfg) return VIO_ERR_BAD_ARG;
-    if (cfg->device != cv->cfg.device) return fail(cv, VIO_ERR_BAD_ARG, "device %d: the handle was made for device %d", cfg->device, cv->cfg.device);
-    if (cfg->shard_count > 1) return fail(cv, VIO_ERR_UNSUPPORTED, "sharded context");
+    if (cfg->device != cv->cfg.device) return fail(cv->err, VIO_ERR_BAD_ARG, "device %d: the handle was made for device %d", cfg->device, cv->cfg.device);
+    if (cfg->shard_count > 1) return fail(cv->err, VIO_ERR_UNSUPPORTED, "sharded context");
     const vio_config &o = cv->cfg;
     if (cfg->ext_fixed != o.ext_fixed || cfg->loss_type != o.loss_type || cfg->loss_delta != o.loss_delta ||
         cfg->reproj_sqrt_info != o.reproj_sqrt_info || memcmp(cfg->gravity, o.gravity, sizeof(o.gravity)) != 0 || cfg->item_policy != o.item_policy)
@@ -574,7 +518,7 @@ vio_status vio_cov_set_config(vio_cov *cv, const vio_config *cfg) {
 
 vio_status vio_cov_pivot_ratio(vio_cov *cv, double *ratio) {
     if (!cv || !ratio) return VIO_ERR_BAD_ARG;
-    if (cv->last_n < 0) return fail(cv, VIO_ERR_BAD_ARG, "no successful compute yet");
+    if (cv->last_n < 0) return fail(cv->err, VIO_ERR_BAD_ARG, "no successful compute yet");
     *ratio = cv->pivot_ratio;
     return VIO_OK;
 }
@@ -608,7 +552,7 @@ vio_status vio_cov_compute_batch(vio_cov *const *cvs, int32_t count, int32_t gau
 
 vio_status vio_cov_landmark_information(vio_cov *cv, int64_t n, double *info) {
     if (!cv) return VIO_ERR_BAD_ARG;
-    if (cv->last_n < 0 || n != cv->last_n) return fail(cv, VIO_ERR_BAD_ARG, "no compute with n=%lld to read back", (long long)n);
+    if (cv->last_n < 0 || n != cv->last_n) return fail(cv->err, VIO_ERR_BAD_ARG, "no compute with n=%lld to read back", (long long)n);
     if (info && n > 0) memcpy(info, cv->info.data(), sizeof(double) * cv->info.size());
     return VIO_OK;
 }

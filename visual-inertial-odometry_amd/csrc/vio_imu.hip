@@ -17,13 +17,13 @@
 
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <new>
 #include <vector>
 
 #include "../../include/vio_imu.h"
+#include "vio_companion.h"
 
 #define IMU_NT 64                          // one wavefront per interval
 #define IMU_LDF 17                         // F tile: 16 rows, row stride 17 doubles
@@ -251,70 +251,18 @@ __global__ __launch_bounds__(IMU_NT) void k_imu_propagate(ImuArgs a) {
 // ---------------------------------------------------------------------------------------------------------------------------------
 struct vio_imu {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    hipEvent_t ev[2] = {nullptr, nullptr};
-    char err[512] = {0};
+    StreamEvents<2> q;                              // the caller's stream or an owned one, and the timing events
+    ErrText err = {0};
     int32_t n = -1;                                 // intervals loaded (-1: nothing yet)
     vio_imu_noise noise = {0, 0, 0, 0};
     // device: off | first | dt | acc | gyr, one allocation replaced by every load
-    char *d_data = nullptr;
+    DevBuf<char> data;
     int64_t *d_off = nullptr;
     double *d_first = nullptr, *d_dt = nullptr, *d_acc = nullptr, *d_gyr = nullptr;
-    // per call: bias | which up, the records down (pinned host twins; grow only)
-    char *d_in = nullptr, *h_in = nullptr;
-    size_t in_cap = 0;
-    char *d_out = nullptr, *h_out = nullptr;
-    size_t out_cap = 0;
+    // per call: bias | which up, the records down
+    Twin<char> in, out;
     double timing[3] = {0, 0, 0};
 };
-
-namespace {
-
-// The calling thread's current device is the caller's: switched to the handle's for the library's calls, put back on the way out.
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-vio_status fail(vio_imu *h, vio_status st, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(h->err, sizeof(h->err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-vio_status hip_ck(vio_imu *h, hipError_t e, const char *what) {
-    if (e == hipSuccess) return VIO_OK;
-    return fail(h, VIO_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-// grow a pinned host buffer and its device twin to hold `bytes` (never shrinks)
-vio_status ensure(vio_imu *h, char **d, char **hb, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return VIO_OK;
-    if (*d) hipFree(*d);
-    if (*hb) hipHostFree(*hb);
-    *d = nullptr; *hb = nullptr; *cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    vio_status st = hip_ck(h, hipMalloc((void **)d, want), "hipMalloc");
-    if (st != VIO_OK) return st;
-    st = hip_ck(h, hipHostMalloc((void **)hb, want, hipHostMallocDefault), "hipHostMalloc");
-    if (st != VIO_OK) return st;
-    *cap = want;
-    return VIO_OK;
-}
-
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
-}   // namespace
 
 extern "C" {
 
@@ -327,14 +275,8 @@ vio_status vio_imu_create(int32_t device, void *stream, vio_imu **out) {
     h->device = device;
     DeviceScope dev(device);
     if (!dev.ok) { delete h; return VIO_ERR_HIP; }
-    if (stream) {
-        h->stream = (hipStream_t)stream;
-    } else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-        h->own_stream = true;
-    }
-    for (int k = 0; k < 2; ++k)
-        if (hipEventCreate(&h->ev[k]) != hipSuccess) { vio_imu_destroy(h); return VIO_ERR_HIP; }
+    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
+    if (h->q.create_events() != hipSuccess) { vio_imu_destroy(h); return VIO_ERR_HIP; }
     *out = h;
     return VIO_OK;
 }
@@ -342,15 +284,8 @@ vio_status vio_imu_create(int32_t device, void *stream, vio_imu **out) {
 void vio_imu_destroy(vio_imu *h) {
     if (!h) return;
     DeviceScope dev(h->device);
-    if (h->stream) hipStreamSynchronize(h->stream);
-    for (int k = 0; k < 2; ++k) if (h->ev[k]) hipEventDestroy(h->ev[k]);
-    if (h->d_data) hipFree(h->d_data);
-    if (h->d_in) hipFree(h->d_in);
-    if (h->d_out) hipFree(h->d_out);
-    if (h->h_in) hipHostFree(h->h_in);
-    if (h->h_out) hipHostFree(h->h_out);
-    if (h->own_stream && h->stream) hipStreamDestroy(h->stream);
-    delete h;
+    h->q.release();
+    delete h;                                       // (the buffers free themselves)
 }
 
 const char *vio_imu_last_error(const vio_imu *h) { return h ? h->err : "null handle"; }
@@ -361,34 +296,33 @@ vio_status vio_imu_load(vio_imu *h, int32_t n, const int64_t *offset, const doub
                         const double *gyr, const vio_imu_noise *noise) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    if (n < 0 || !offset || !noise || (n > 0 && !first)) return fail(h, VIO_ERR_BAD_ARG, "n=%d, or offset / first / noise is NULL", n);
-    if (offset[0] != 0) return fail(h, VIO_ERR_BAD_ARG, "offset[0] = %lld, not 0", (long long)offset[0]);
+    if (n < 0 || !offset || !noise || (n > 0 && !first)) return fail(h->err, VIO_ERR_BAD_ARG, "n=%d, or offset / first / noise is NULL", n);
+    if (offset[0] != 0) return fail(h->err, VIO_ERR_BAD_ARG, "offset[0] = %lld, not 0", (long long)offset[0]);
     for (int32_t i = 0; i < n; ++i)
         if (offset[i + 1] < offset[i])
-            return fail(h, VIO_ERR_BAD_ARG, "offset decreases at interval %d (%lld -> %lld)", i, (long long)offset[i], (long long)offset[i + 1]);
+            return fail(h->err, VIO_ERR_BAD_ARG, "offset decreases at interval %d (%lld -> %lld)", i, (long long)offset[i], (long long)offset[i + 1]);
     const int64_t S = offset[n];
-    if (S > 0 && (!dt || !acc || !gyr)) return fail(h, VIO_ERR_BAD_ARG, "%lld samples and dt / acc / gyr is NULL", (long long)S);
+    if (S > 0 && (!dt || !acc || !gyr)) return fail(h->err, VIO_ERR_BAD_ARG, "%lld samples and dt / acc / gyr is NULL", (long long)S);
     DeviceScope dev(h->device);
-    if (!dev.ok) return fail(h, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     vio_status st;
-    if ((st = hip_ck(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize")) != VIO_OK) return st;
-    if (h->d_data) hipFree(h->d_data);
-    h->d_data = nullptr;
+    if ((st = hip_ck(h->err, hipStreamSynchronize(h->q.stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    h->data.release();
     h->n = -1;
     const size_t oOff = 0, oFirst = align256(oOff + 8 * ((size_t)n + 1)), oDt = align256(oFirst + 48 * (size_t)n),
                  oAcc = align256(oDt + 8 * (size_t)S), oGyr = align256(oAcc + 24 * (size_t)S), total = align256(oGyr + 24 * (size_t)S);
-    if ((st = hip_ck(h, hipMalloc((void **)&h->d_data, total), "hipMalloc")) != VIO_OK) return st;
-    h->d_off = (int64_t *)(h->d_data + oOff);
-    h->d_first = (double *)(h->d_data + oFirst);
-    h->d_dt = (double *)(h->d_data + oDt);
-    h->d_acc = (double *)(h->d_data + oAcc);
-    h->d_gyr = (double *)(h->d_data + oGyr);
+    if ((st = hip_ck(h->err, hipMalloc((void **)&h->data.d, total), "hipMalloc")) != VIO_OK) return st;
+    h->d_off = (int64_t *)(h->data.d + oOff);
+    h->d_first = (double *)(h->data.d + oFirst);
+    h->d_dt = (double *)(h->data.d + oDt);
+    h->d_acc = (double *)(h->data.d + oAcc);
+    h->d_gyr = (double *)(h->data.d + oGyr);
     struct { void *d; const void *s; size_t b; } cp[5] = {{h->d_off, offset, 8 * ((size_t)n + 1)}, {h->d_first, first, 48 * (size_t)n},
                                                           {h->d_dt, dt, 8 * (size_t)S}, {h->d_acc, acc, 24 * (size_t)S},
                                                           {h->d_gyr, gyr, 24 * (size_t)S}};
     for (auto &c : cp)
-        if (c.b && (st = hip_ck(h, hipMemcpyAsync(c.d, c.s, c.b, hipMemcpyHostToDevice, h->stream), "upload")) != VIO_OK) return st;
-    if ((st = hip_ck(h, hipStreamSynchronize(h->stream), "hipStreamSynchronize")) != VIO_OK) return st;
+        if (c.b && (st = hip_ck(h->err, hipMemcpyAsync(c.d, c.s, c.b, hipMemcpyHostToDevice, h->q.stream), "upload")) != VIO_OK) return st;
+    if ((st = hip_ck(h->err, hipStreamSynchronize(h->q.stream), "hipStreamSynchronize")) != VIO_OK) return st;
     h->n = n;
     h->noise = *noise;
     return VIO_OK;
@@ -399,46 +333,46 @@ vio_status vio_imu_propagate(vio_imu *h, int32_t count, const int32_t *which, co
     const auto t0 = clk::now();
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    if (h->n < 0) return fail(h, VIO_ERR_BAD_ARG, "nothing loaded");
+    if (h->n < 0) return fail(h->err, VIO_ERR_BAD_ARG, "nothing loaded");
     const int32_t n = h->n;
-    if (!which && count != n) return fail(h, VIO_ERR_BAD_ARG, "which = NULL and count %d is not the %d intervals loaded", count, n);
-    if (count < 0) return fail(h, VIO_ERR_BAD_ARG, "count %d", count);
+    if (!which && count != n) return fail(h->err, VIO_ERR_BAD_ARG, "which = NULL and count %d is not the %d intervals loaded", count, n);
+    if (count < 0) return fail(h->err, VIO_ERR_BAD_ARG, "count %d", count);
     if (count == 0) return VIO_OK;
-    if (!ba || !bg || !out) return fail(h, VIO_ERR_BAD_ARG, "ba / bg / out is NULL");
+    if (!ba || !bg || !out) return fail(h->err, VIO_ERR_BAD_ARG, "ba / bg / out is NULL");
     if (which)
         for (int32_t k = 0; k < count; ++k)
-            if (which[k] < 0 || which[k] >= n) return fail(h, VIO_ERR_BAD_ARG, "which[%d] = %d is not an interval (n = %d)", k, which[k], n);
+            if (which[k] < 0 || which[k] >= n) return fail(h->err, VIO_ERR_BAD_ARG, "which[%d] = %d is not an interval (n = %d)", k, which[k], n);
     DeviceScope dev(h->device);
-    if (!dev.ok) return fail(h, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     vio_status st;
     const size_t oB = 0, oW = align256(oB + 48 * (size_t)count), nin = align256(oW + 4 * (size_t)count);
     const size_t nout = (size_t)IMU_REC * 8 * count;
-    if ((st = ensure(h, &h->d_in, &h->h_in, &h->in_cap, nin)) != VIO_OK) return st;
-    if ((st = ensure(h, &h->d_out, &h->h_out, &h->out_cap, nout)) != VIO_OK) return st;
-    double *hb = (double *)(h->h_in + oB);
-    int *hw = (int *)(h->h_in + oW);
+    if ((st = h->in.ensure(h->err, nin)) != VIO_OK) return st;
+    if ((st = h->out.ensure(h->err, nout)) != VIO_OK) return st;
+    double *hb = (double *)(h->in.h + oB);
+    int *hw = (int *)(h->in.h + oW);
     for (int32_t k = 0; k < count; ++k) {
         const int32_t i = which ? which[k] : k;
         hw[k] = i;
         for (int c = 0; c < 3; ++c) { hb[6 * k + c] = ba[3 * (size_t)i + c]; hb[6 * k + 3 + c] = bg[3 * (size_t)i + c]; }
     }
-    if ((st = hip_ck(h, hipMemcpyAsync(h->d_in, h->h_in, nin, hipMemcpyHostToDevice, h->stream), "upload")) != VIO_OK) return st;
+    if ((st = hip_ck(h->err, hipMemcpyAsync(h->in.d, h->in.h, nin, hipMemcpyHostToDevice, h->q.stream), "upload")) != VIO_OK) return st;
     const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
     ImuArgs a;
     a.off = h->d_off; a.first = h->d_first; a.dt = h->d_dt; a.acc = h->d_acc; a.gyr = h->d_gyr;
-    a.bias = (const double *)(h->d_in + oB);
-    a.which = (const int *)(h->d_in + oW);
-    a.out = (double *)h->d_out;
+    a.bias = (const double *)(h->in.d + oB);
+    a.which = (const int *)(h->in.d + oW);
+    a.out = (double *)h->out.d;
     a.sn[0] = h->noise.acc_n; a.sn[1] = h->noise.gyr_n; a.sn[2] = h->noise.acc_w; a.sn[3] = h->noise.gyr_w;
-    hipEventRecord(h->ev[0], h->stream);
-    hipLaunchKernelGGL(k_imu_propagate, dim3(count), dim3(IMU_NT), 0, h->stream, a);
-    if ((st = hip_ck(h, hipGetLastError(), "k_imu_propagate launch")) != VIO_OK) return st;
-    hipEventRecord(h->ev[1], h->stream);
-    if ((st = hip_ck(h, hipMemcpyAsync(h->h_out, h->d_out, nout, hipMemcpyDeviceToHost, h->stream), "read-back")) != VIO_OK) return st;
-    if ((st = hip_ck(h, hipStreamSynchronize(h->stream), "k_imu_propagate")) != VIO_OK) return st;
+    hipEventRecord(h->q.ev[0], h->q.stream);
+    hipLaunchKernelGGL(k_imu_propagate, dim3(count), dim3(IMU_NT), 0, h->q.stream, a);
+    if ((st = hip_ck(h->err, hipGetLastError(), "k_imu_propagate launch")) != VIO_OK) return st;
+    hipEventRecord(h->q.ev[1], h->q.stream);
+    if ((st = hip_ck(h->err, hipMemcpyAsync(h->out.h, h->out.d, nout, hipMemcpyDeviceToHost, h->q.stream), "read-back")) != VIO_OK) return st;
+    if ((st = hip_ck(h->err, hipStreamSynchronize(h->q.stream), "k_imu_propagate")) != VIO_OK) return st;
 
-    const double *rec = (const double *)h->h_out;
+    const double *rec = (const double *)h->out.h;
     int32_t bad = -1;
     for (int32_t k = 0; k < count; ++k) {
         const int32_t i = hw[k];
@@ -449,11 +383,11 @@ vio_status vio_imu_propagate(vio_imu *h, int32_t count, const int32_t *which, co
                 if (!std::isfinite(r[e])) { bad = i; break; }
     }
     float kms = 0.f;
-    hipEventElapsedTime(&kms, h->ev[0], h->ev[1]);
+    hipEventElapsedTime(&kms, h->q.ev[0], h->q.ev[1]);
     h->timing[0] = t_host;
     h->timing[1] = kms;
     h->timing[2] = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    if (bad >= 0) return fail(h, VIO_ERR_NOT_FINITE, "interval %d: non-finite pre-integration (a non-finite sample or bias)", bad);
+    if (bad >= 0) return fail(h->err, VIO_ERR_NOT_FINITE, "interval %d: non-finite pre-integration (a non-finite sample or bias)", bad);
     return VIO_OK;
 }
 

@@ -22,10 +22,11 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <string>
+#include <new>
 #include <vector>
 
 #include "../../include/vio_init.h"
+#include "vio_companion.h"
 
 #pragma clang fp contract(off)
 
@@ -619,55 +620,26 @@ __global__ __launch_bounds__(ALIGN_NT) void k_init_align(AlignArgs a) {
 // ---------------------------------------------------------------------------------------------------------
 struct vio_init {
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string err;
-    char *h_stage = nullptr; size_t stage_cap = 0;       // pinned: descriptors | doubles
-    char *d_stage = nullptr; size_t dstage_cap = 0;
-    double *d_scr = nullptr; size_t scr_cap = 0;
-    double *h_out = nullptr, *d_out = nullptr; size_t hout_cap = 0, dout_cap = 0;
-    hipEvent_t ev[3] = {nullptr, nullptr, nullptr};      // upload start, kernel start, kernel end
+    ErrText err = {0};
+    Twin<char> staging;                                  // descriptors | doubles
+    DevBuf<double> scr;
+    Twin<double> out;
+    StreamEvents<3> q;                                   // events: upload start, kernel start, kernel end
     double timing[3] = {NAN, NAN, NAN};
 };
 
 namespace {
 
-struct DeviceGuard {          // the caller's current device, restored on every way out
-    int prev = -1;
-    explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-vio_status fail(vio_init *h, vio_status st, const std::string &msg) { h->err = msg; return st; }
 // a failure after work was enqueued: wait for the stream first, so that no copy still reads the pinned staging buffer the next call fills
-vio_status fail_synced(vio_init *h, const std::string &msg) { (void)hipStreamSynchronize(h->stream); h->err = msg; return VIO_ERR_HIP; }
-
-template <class T> bool grow_pinned(T *&p, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    if (hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-    cap = bytes;
-    return true;
-}
-template <class T> bool grow_device(T *&p, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc((void **)&p, bytes) != hipSuccess) { p = nullptr; return false; }
-    cap = bytes;
-    return true;
-}
-
-std::string win(int i) { return "window " + std::to_string(i) + ": "; }
+vio_status fail_synced(vio_init *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
 
 vio_status check_item(vio_init *h, int i, const vio_init_item &it, int &K) {
     if (it.n_frames < 2 || it.n_frames > VIO_INIT_MAX_FRAMES)
-        return fail(h, VIO_ERR_BAD_ARG, win(i) + "n_frames must be in [2, " + std::to_string(VIO_INIT_MAX_FRAMES) + "]");
-    if (!it.R || !it.T || !it.pre) return fail(h, VIO_ERR_BAD_ARG, win(i) + "R, T and pre are required");
+        return fail(h->err, VIO_ERR_BAD_ARG, "window %d: n_frames must be in [2, %d]", i, VIO_INIT_MAX_FRAMES);
+    if (!it.R || !it.T || !it.pre) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: R, T and pre are required", i);
     K = 0;
     for (int f = 0; f < it.n_frames; ++f) K += it.is_key ? (it.is_key[f] != 0) : 1;
-    if (K < 2) return fail(h, VIO_ERR_BAD_ARG, win(i) + "fewer than two keyframes");
+    if (K < 2) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: fewer than two keyframes", i);
     return VIO_OK;
 }
 
@@ -679,7 +651,7 @@ vio_status stage(vio_init *h, int count, const vio_init_item *items, const doubl
         const vio_status st = check_item(h, i, items[i], Ks[(size_t)i]);
         if (st != VIO_OK) return st;
     }
-    b_desc = ((sizeof(InitWin) * (size_t)count + 255) / 256) * 256;
+    b_desc = align256(sizeof(InitWin) * (size_t)count);
     int64_t nd = 0;
     scr = 0;
     fmax = 2;
@@ -695,10 +667,10 @@ vio_status stage(vio_init *h, int count, const vio_init_item *items, const doubl
         if (w.F > fmax) fmax = w.F;
     }
     bytes = b_desc + sizeof(double) * (size_t)nd;
-    if (!grow_pinned(h->h_stage, h->stage_cap, bytes) || !grow_device(h->d_stage, h->dstage_cap, bytes))
-        return fail(h, VIO_ERR_HIP, "out of memory");
-    std::memcpy(h->h_stage, wins.data(), sizeof(InitWin) * (size_t)count);
-    double *hd = (double *)(h->h_stage + b_desc);
+    const vio_status st = h->staging.ensure(h->err, bytes);
+    if (st != VIO_OK) return st;
+    std::memcpy(h->staging.h, wins.data(), sizeof(InitWin) * (size_t)count);
+    double *hd = (double *)(h->staging.h + b_desc);
     for (int i = 0; i < count; ++i) {
         const vio_init_item &it = items[i];
         const InitWin &w = wins[(size_t)i];
@@ -722,9 +694,7 @@ vio_status stage(vio_init *h, int count, const vio_init_item *items, const doubl
 }
 
 void finish_timing(vio_init *h, std::chrono::steady_clock::time_point t0, std::chrono::steady_clock::time_point t1) {
-    float ms0 = NAN, ms1 = NAN;
-    if (hipEventElapsedTime(&ms0, h->ev[0], h->ev[1]) != hipSuccess) ms0 = NAN;
-    if (hipEventElapsedTime(&ms1, h->ev[1], h->ev[2]) != hipSuccess) ms1 = NAN;
+    const float ms0 = elapsed_ms(h->q.ev[0], h->q.ev[1]), ms1 = elapsed_ms(h->q.ev[1], h->q.ev[2]);
     const auto t2 = std::chrono::steady_clock::now();
     h->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count() + ms0;
     h->timing[1] = ms1;
@@ -737,7 +707,7 @@ extern "C" {
 
 int32_t vio_init_version(void) { return VIO_INIT_VERSION; }
 
-const char *vio_init_last_error(const vio_init *h) { return h ? h->err.c_str() : "NULL handle"; }
+const char *vio_init_last_error(const vio_init *h) { return h ? h->err : "NULL handle"; }
 
 vio_status vio_init_create(int32_t device, void *stream, vio_init **out) {
     if (!out) return VIO_ERR_BAD_ARG;
@@ -745,16 +715,13 @@ vio_status vio_init_create(int32_t device, void *stream, vio_init **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
     if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceGuard dg(device);
-    vio_init *h = new vio_init();
+    DeviceScope dev(device);
+    if (!dev.ok) return VIO_ERR_HIP;
+    vio_init *h = new (std::nothrow) vio_init();
+    if (!h) return VIO_ERR_BAD_ARG;
     h->device = device;
-    if (stream) h->stream = (hipStream_t)stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-        h->own_stream = true;
-    }
-    for (auto &e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) { vio_init_destroy(h); return VIO_ERR_HIP; }
+    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
+    if (h->q.create_events() != hipSuccess) { vio_init_destroy(h); return VIO_ERR_HIP; }
     if (hipFuncSetAttribute((const void *)k_init_align, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) {
         vio_init_destroy(h);
         return VIO_ERR_HIP;
@@ -765,16 +732,9 @@ vio_status vio_init_create(int32_t device, void *stream, vio_init **out) {
 
 void vio_init_destroy(vio_init *h) {
     if (!h) return;
-    DeviceGuard dg(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->d_scr) (void)hipFree(h->d_scr);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    DeviceScope dev(h->device);
+    h->q.release();
+    delete h;                                            // (the buffers free themselves)
 }
 
 vio_status vio_init_timing(const vio_init *h, double *out3) {
@@ -786,41 +746,41 @@ vio_status vio_init_timing(const vio_init *h, double *out3) {
 vio_status vio_init_gyro_bias_batch(vio_init *h, int32_t count, const vio_init_item *items, const double *bg_in, double *bg_out,
                                     int32_t *status) {
     if (!h) return VIO_ERR_BAD_ARG;
-    h->err.clear();
+    h->err[0] = 0;
     if (count < 0 || (count > 0 && (!items || !bg_in || !bg_out)))
-        return fail(h, VIO_ERR_BAD_ARG, "vio_init_gyro_bias_batch: negative count or a NULL array");
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_init_gyro_bias_batch: negative count or a NULL array");
     if (count == 0) return VIO_OK;
     const auto t0 = std::chrono::steady_clock::now();
     size_t b_desc = 0, bytes = 0;
     int fmax = 0;
     int64_t scr = 0;
-    DeviceGuard dg(h->device);                      // before stage(): its buffers belong on the handle's device
+    DeviceScope dev(h->device);                     // before stage(): its buffers belong on the handle's device
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     vio_status st = stage(h, count, items, bg_in, b_desc, bytes, fmax, scr);
     if (st != VIO_OK) return st;
     const size_t outb = sizeof(double) * 4 * (size_t)count;
-    if (!grow_pinned(h->h_out, h->hout_cap, outb) || !grow_device(h->d_out, h->dout_cap, outb))
-        return fail(h, VIO_ERR_HIP, "vio_init_gyro_bias_batch: out of memory");
+    if ((st = h->out.ensure(h->err, outb)) != VIO_OK) return st;
     const auto t1 = std::chrono::steady_clock::now();
-    (void)hipEventRecord(h->ev[0], h->stream);
-    if (hipMemcpyAsync(h->d_stage, h->h_stage, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+    (void)hipEventRecord(h->q.ev[0], h->q.stream);
+    if (hipMemcpyAsync(h->staging.d, h->staging.h, bytes, hipMemcpyHostToDevice, h->q.stream) != hipSuccess)
         return fail_synced(h, "vio_init_gyro_bias_batch: upload failed");
-    (void)hipEventRecord(h->ev[1], h->stream);
-    hipLaunchKernelGGL(k_init_gyro, dim3((count + GYRO_NT - 1) / GYRO_NT), dim3(GYRO_NT), 0, h->stream, count,
-                       (const InitWin *)h->d_stage, (const double *)(h->d_stage + b_desc), h->d_out);
-    (void)hipEventRecord(h->ev[2], h->stream);
+    (void)hipEventRecord(h->q.ev[1], h->q.stream);
+    hipLaunchKernelGGL(k_init_gyro, dim3((count + GYRO_NT - 1) / GYRO_NT), dim3(GYRO_NT), 0, h->q.stream, count,
+                       (const InitWin *)h->staging.d, (const double *)(h->staging.d + b_desc), h->out.d);
+    (void)hipEventRecord(h->q.ev[2], h->q.stream);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "vio_init_gyro_bias_batch: kernel launch failed");
-    if (hipMemcpyAsync(h->h_out, h->d_out, outb, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
+    if (hipMemcpyAsync(h->out.h, h->out.d, outb, hipMemcpyDeviceToHost, h->q.stream) != hipSuccess ||
+        hipStreamSynchronize(h->q.stream) != hipSuccess)
         return fail_synced(h, "vio_init_gyro_bias_batch: kernel or read-back failed");
     vio_status ret = VIO_OK;
     for (int i = 0; i < count; ++i) {
-        const double *o = h->h_out + 4 * (size_t)i;
+        const double *o = h->out.h + 4 * (size_t)i;
         for (int k = 0; k < 3; ++k) bg_out[3 * i + k] = o[k];
         const int32_t ws = (int32_t)o[3];
         if (status) status[i] = ws;
         if (ws != VIO_OK) {
             ret = VIO_ERR_NOT_FINITE;
-            if (h->err.empty()) h->err = win(i) + "non-finite input or result";
+            if (!h->err[0]) fail(h->err, ret, "window %d: non-finite input or result", i);
         }
     }
     finish_timing(h, t0, t1);
@@ -830,45 +790,44 @@ vio_status vio_init_gyro_bias_batch(vio_init *h, int32_t count, const vio_init_i
 vio_status vio_init_align_batch(vio_init *h, int32_t count, const vio_init_item *items, const double *tic, double g_norm,
                                 const double *bg, vio_init_result *res, double *x, double *poses, double *speed_bias) {
     if (!h) return VIO_ERR_BAD_ARG;
-    h->err.clear();
+    h->err[0] = 0;
     if (count < 0 || (count > 0 && (!items || !tic || !bg || !res)))
-        return fail(h, VIO_ERR_BAD_ARG, "vio_init_align_batch: negative count or a NULL array");
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_init_align_batch: negative count or a NULL array");
     if (count == 0) return VIO_OK;
     const auto t0 = std::chrono::steady_clock::now();
     size_t b_desc = 0, bytes = 0;
     int fmax = 0;
     int64_t scr = 0;
-    DeviceGuard dg(h->device);                      // before stage(): its buffers belong on the handle's device
+    DeviceScope dev(h->device);                     // before stage(): its buffers belong on the handle's device
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     vio_status st = stage(h, count, items, bg, b_desc, bytes, fmax, scr);
     if (st != VIO_OK) return st;
     const size_t outb = sizeof(double) * OUT_STRIDE * (size_t)count;
-    if (!grow_pinned(h->h_out, h->hout_cap, outb) || !grow_device(h->d_out, h->dout_cap, outb) ||
-        !grow_device(h->d_scr, h->scr_cap, sizeof(double) * (size_t)scr))
-        return fail(h, VIO_ERR_HIP, "vio_init_align_batch: out of memory");
+    if ((st = h->out.ensure(h->err, outb)) != VIO_OK || (st = h->scr.ensure(h->err, sizeof(double) * (size_t)scr)) != VIO_OK) return st;
     AlignArgs a;
-    a.wins = (const InitWin *)h->d_stage;
-    a.dd = (const double *)(h->d_stage + b_desc);
-    a.scr = h->d_scr;
-    a.out = h->d_out;
+    a.wins = (const InitWin *)h->staging.d;
+    a.dd = (const double *)(h->staging.d + b_desc);
+    a.scr = h->scr.d;
+    a.out = h->out.d;
     for (int k = 0; k < 3; ++k) a.tic[k] = tic[k];
     a.G = g_norm;
     a.nmax = 3 * fmax + 4;
     a.fmax = fmax;
     const size_t lds = sizeof(double) * ((size_t)tri(a.nmax) + 2 * (size_t)a.nmax + (size_t)RAB * (fmax - 1)) + sizeof(int) * (size_t)a.nmax;
     const auto t1 = std::chrono::steady_clock::now();
-    (void)hipEventRecord(h->ev[0], h->stream);
-    if (hipMemcpyAsync(h->d_stage, h->h_stage, bytes, hipMemcpyHostToDevice, h->stream) != hipSuccess)
+    (void)hipEventRecord(h->q.ev[0], h->q.stream);
+    if (hipMemcpyAsync(h->staging.d, h->staging.h, bytes, hipMemcpyHostToDevice, h->q.stream) != hipSuccess)
         return fail_synced(h, "vio_init_align_batch: upload failed");
-    (void)hipEventRecord(h->ev[1], h->stream);
-    hipLaunchKernelGGL(k_init_align, dim3(count), dim3(ALIGN_NT), lds, h->stream, a);
-    (void)hipEventRecord(h->ev[2], h->stream);
+    (void)hipEventRecord(h->q.ev[1], h->q.stream);
+    hipLaunchKernelGGL(k_init_align, dim3(count), dim3(ALIGN_NT), lds, h->q.stream, a);
+    (void)hipEventRecord(h->q.ev[2], h->q.stream);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "vio_init_align_batch: kernel launch failed");
-    if (hipMemcpyAsync(h->h_out, h->d_out, outb, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
+    if (hipMemcpyAsync(h->out.h, h->out.d, outb, hipMemcpyDeviceToHost, h->q.stream) != hipSuccess ||
+        hipStreamSynchronize(h->q.stream) != hipSuccess)
         return fail_synced(h, "vio_init_align_batch: kernel or read-back failed");
     vio_status ret = VIO_OK;
     for (int i = 0; i < count; ++i) {
-        const double *o = h->h_out + (size_t)OUT_STRIDE * i;
+        const double *o = h->out.h + (size_t)OUT_STRIDE * i;
         vio_init_result &r = res[i];
         r.status = (int32_t)o[0];
         r.n_key = (int32_t)o[1];
@@ -883,7 +842,7 @@ vio_status vio_init_align_batch(vio_init *h, int32_t count, const vio_init_item 
             std::memcpy(speed_bias + (size_t)VIO_INIT_SB_STRIDE * i, o + OREC + VIO_INIT_X_STRIDE + VIO_INIT_POSE_STRIDE, sizeof(double) * 9 * K);
         if (r.status == VIO_ERR_NOT_FINITE) {
             ret = VIO_ERR_NOT_FINITE;
-            if (h->err.empty()) h->err = win(i) + "non-finite input or result";
+            if (!h->err[0]) fail(h->err, ret, "window %d: non-finite input or result", i);
         }
     }
     finish_timing(h, t0, t1);

@@ -19,11 +19,12 @@
 #include <cmath>
 #include <cstdio>
 #include <cstring>
-#include <string>
+#include <new>
 #include <vector>
 
 #include "../../include/vio_marg.h"
 #include "host_dense.h"
+#include "vio_companion.h"
 #include "vio_device_math.h"
 #include "vio_types.h"
 
@@ -684,74 +685,44 @@ __global__ void __launch_bounds__(TAIL_NT) k_marg_tail(const MargWin *__restrict
 struct vio_marg {
     vio_config cfg;
     int device = 0;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
-    std::string err;
-    char *h_stage = nullptr; size_t stage_cap = 0;        // pinned: descriptors | ints | doubles
-    char *d_stage = nullptr; size_t dstage_cap = 0;
-    double *d_scr = nullptr; size_t scr_cap = 0;
-    double *h_out = nullptr, *d_out = nullptr; size_t hout_cap = 0, dout_cap = 0;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};      // upload start, build, tail, end
+    ErrText err = {0};
+    Twin<char> staging;                                   // descriptors | ints | doubles
+    DevBuf<double> scr;
+    Twin<double> out;
+    StreamEvents<4> q;                                    // events: upload start, build, tail, end
     double timing[4] = {NAN, NAN, NAN, NAN};
     std::vector<int32_t> live;
 };
 
 namespace {
 
-struct DeviceGuard {          // the caller's current device, restored on every way out
-    int prev = -1;
-    explicit DeviceGuard(int dev) { if (hipGetDevice(&prev) != hipSuccess) prev = -1; (void)hipSetDevice(dev); }
-    ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
-};
-
-vio_status fail(vio_marg *h, vio_status st, const std::string &msg) { h->err = msg; return st; }
-
-template <class T> bool grow_pinned(T *&p, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipHostFree(p);
-    p = nullptr; cap = 0;
-    if (hipHostMalloc((void **)&p, bytes, hipHostMallocDefault) != hipSuccess) { p = nullptr; return false; }
-    cap = bytes;
-    return true;
-}
-template <class T> bool grow_device(T *&p, size_t &cap, size_t bytes) {
-    if (bytes <= cap) return true;
-    if (p) (void)hipFree(p);
-    p = nullptr; cap = 0;
-    if (hipMalloc((void **)&p, bytes) != hipSuccess) { p = nullptr; return false; }
-    cap = bytes;
-    return true;
-}
-
 // the graph of one window: the landmarks hosted in frame 0 (MargOldFrame, estimator.cpp:762-764) with their edges in the caller's order
 struct Graph {
     std::vector<int32_t> lms, eoff, edges;
 };
 
-std::string win(int i) { return "window " + std::to_string(i) + ": "; }
-
 // argument checks of one item (nothing is written); the graph of a VIO_MARG_OLD window
 vio_status check_item(vio_marg *h, int i, const vio_marg_item &it, Graph &g) {
-    if (it.kind != VIO_MARG_OLD && it.kind != VIO_MARG_SECOND_NEW) return fail(h, VIO_ERR_BAD_ARG, win(i) + "kind is neither VIO_MARG_OLD nor VIO_MARG_SECOND_NEW");
-    if (!it.H || !it.b || !it.err || !it.jt_inv) return fail(h, VIO_ERR_BAD_ARG, win(i) + "an output array is NULL");
-    if ((it.H_prior == nullptr) != (it.b_prior == nullptr)) return fail(h, VIO_ERR_BAD_ARG, win(i) + "H_prior and b_prior must both be given or both be NULL");
+    if (it.kind != VIO_MARG_OLD && it.kind != VIO_MARG_SECOND_NEW) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: kind is neither VIO_MARG_OLD nor VIO_MARG_SECOND_NEW", i);
+    if (!it.H || !it.b || !it.err || !it.jt_inv) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: an output array is NULL", i);
+    if ((it.H_prior == nullptr) != (it.b_prior == nullptr)) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: H_prior and b_prior must both be given or both be NULL", i);
     if (it.kind == VIO_MARG_SECOND_NEW) return VIO_OK;
-    if (!it.poses || !it.speed_bias || !it.ext) return fail(h, VIO_ERR_BAD_ARG, win(i) + "poses, speed_bias and ext are required");
-    if (it.n < 0 || it.m < 0 || it.n > INT32_MAX || it.m > INT32_MAX) return fail(h, VIO_ERR_BAD_ARG, win(i) + "negative or too large n / m");
-    if (it.n > 0 && !it.inv_depth) return fail(h, VIO_ERR_BAD_ARG, win(i) + "inv_depth is NULL");
-    if (it.m > 0 && (!it.lm || !it.host || !it.target || !it.pts_i || !it.pts_j)) return fail(h, VIO_ERR_BAD_ARG, win(i) + "an observation array is NULL");
+    if (!it.poses || !it.speed_bias || !it.ext) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: poses, speed_bias and ext are required", i);
+    if (it.n < 0 || it.m < 0 || it.n > INT32_MAX || it.m > INT32_MAX) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: negative or too large n / m", i);
+    if (it.n > 0 && !it.inv_depth) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: inv_depth is NULL", i);
+    if (it.m > 0 && (!it.lm || !it.host || !it.target || !it.pts_i || !it.pts_j)) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: an observation array is NULL", i);
     std::vector<int32_t> lhost((size_t)it.n, -1), cnt((size_t)it.n + 1, 0);
     std::vector<int64_t> first((size_t)it.n, -1);
     std::vector<uint32_t> seen((size_t)it.n, 0u);
     for (int64_t e = 0; e < it.m; ++e) {
         const int32_t l = it.lm[e], ho = it.host[e], t = it.target[e];
-        if (l < 0 || l >= it.n) return fail(h, VIO_ERR_BAD_ARG, win(i) + "observation " + std::to_string(e) + ": landmark index out of range");
-        if (ho < 0 || ho >= NF || t < 0 || t >= NF) return fail(h, VIO_ERR_BAD_ARG, win(i) + "observation " + std::to_string(e) + ": frame index out of range");
-        if (ho == t) return fail(h, VIO_ERR_BAD_ARG, win(i) + "observation " + std::to_string(e) + ": host == target");
+        if (l < 0 || l >= it.n) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: observation %lld: landmark index out of range", i, (long long)e);
+        if (ho < 0 || ho >= NF || t < 0 || t >= NF) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: observation %lld: frame index out of range", i, (long long)e);
+        if (ho == t) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: observation %lld: host == target", i, (long long)e);
         if (first[l] < 0) { first[l] = e; lhost[l] = ho; }
         else if (lhost[l] != ho || it.pts_i[2 * e] != it.pts_i[2 * first[l]] || it.pts_i[2 * e + 1] != it.pts_i[2 * first[l] + 1])
-            return fail(h, VIO_ERR_BAD_ARG, win(i) + "landmark " + std::to_string(l) + ": its observations disagree on the host frame or pts_i");
-        if (seen[l] & (1u << t)) return fail(h, VIO_ERR_BAD_ARG, win(i) + "landmark " + std::to_string(l) + ": two observations in one frame");
+            return fail(h->err, VIO_ERR_BAD_ARG, "window %d: landmark %d: its observations disagree on the host frame or pts_i", i, l);
+        if (seen[l] & (1u << t)) return fail(h->err, VIO_ERR_BAD_ARG, "window %d: landmark %d: two observations in one frame", i, l);
         seen[l] |= 1u << t;
         ++cnt[l + 1];
     }
@@ -775,12 +746,12 @@ extern "C" {
 
 int32_t vio_marg_version(void) { return VIO_MARG_VERSION; }
 
-const char *vio_marg_last_error(const vio_marg *h) { return h ? h->err.c_str() : "NULL handle"; }
+const char *vio_marg_last_error(const vio_marg *h) { return h ? h->err : "NULL handle"; }
 
 vio_status vio_marg_set_config(vio_marg *h, const vio_config *cfg) {
     if (!h || !cfg) return VIO_ERR_BAD_ARG;
-    if (cfg->device != h->cfg.device || (cfg->stream && cfg->stream != (void *)h->stream) || (!cfg->stream && !h->own_stream))
-        return fail(h, VIO_ERR_BAD_ARG, "vio_marg_set_config: device and stream must be those of vio_marg_create");
+    if (cfg->device != h->cfg.device || (cfg->stream && cfg->stream != (void *)h->q.stream) || (!cfg->stream && !h->q.own_stream))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_marg_set_config: device and stream must be those of vio_marg_create");
     void *st = h->cfg.stream;
     h->cfg = *cfg;
     h->cfg.stream = st;
@@ -793,18 +764,15 @@ vio_status vio_marg_create(const vio_config *cfg, vio_marg **out) {
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
     if (cfg->device < 0 || cfg->device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceGuard dg(cfg->device);
-    vio_marg *h = new vio_marg();
+    DeviceScope dev(cfg->device);
+    if (!dev.ok) return VIO_ERR_HIP;
+    vio_marg *h = new (std::nothrow) vio_marg();
+    if (!h) return VIO_ERR_BAD_ARG;
     h->cfg = *cfg;
     h->device = cfg->device;
-    if (cfg->stream) h->stream = (hipStream_t)cfg->stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-        h->own_stream = true;
-        h->cfg.stream = h->stream;
-    }
-    for (auto &e : h->ev)
-        if (hipEventCreate(&e) != hipSuccess) { vio_marg_destroy(h); return VIO_ERR_HIP; }
+    if (h->q.open_stream(cfg->stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
+    h->cfg.stream = h->q.stream;
+    if (h->q.create_events() != hipSuccess) { vio_marg_destroy(h); return VIO_ERR_HIP; }
     if (hipFuncSetAttribute((const void *)k_marg_tail, hipFuncAttributeMaxDynamicSharedMemorySize, (int)TAIL_LDS) != hipSuccess) {
         vio_marg_destroy(h);
         return VIO_ERR_HIP;
@@ -815,16 +783,9 @@ vio_status vio_marg_create(const vio_config *cfg, vio_marg **out) {
 
 void vio_marg_destroy(vio_marg *h) {
     if (!h) return;
-    DeviceGuard dg(h->device);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (auto &e : h->ev) if (e) (void)hipEventDestroy(e);
-    if (h->h_stage) (void)hipHostFree(h->h_stage);
-    if (h->h_out) (void)hipHostFree(h->h_out);
-    if (h->d_stage) (void)hipFree(h->d_stage);
-    if (h->d_scr) (void)hipFree(h->d_scr);
-    if (h->d_out) (void)hipFree(h->d_out);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-    delete h;
+    DeviceScope dev(h->device);
+    h->q.release();
+    delete h;                                             // (the buffers free themselves)
 }
 
 vio_status vio_marg_timing(vio_marg *h, double *out4) {
@@ -848,8 +809,8 @@ vio_status vio_marg_compute(vio_marg *h, const vio_marg_item *item) {
 
 vio_status vio_marg_compute_batch(vio_marg *h, int32_t count, const vio_marg_item *items, vio_status *window_status) {
     if (!h) return VIO_ERR_BAD_ARG;
-    h->err.clear();
-    if (count < 0 || (count > 0 && !items)) return fail(h, VIO_ERR_BAD_ARG, "vio_marg_compute_batch: negative count or NULL items");
+    h->err[0] = 0;
+    if (count < 0 || (count > 0 && !items)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_marg_compute_batch: negative count or NULL items");
     if (count == 0) return VIO_OK;
     const auto t0 = std::chrono::steady_clock::now();
     std::vector<Graph> graphs((size_t)count);
@@ -857,7 +818,8 @@ vio_status vio_marg_compute_batch(vio_marg *h, int32_t count, const vio_marg_ite
         const vio_status st = check_item(h, i, items[i], graphs[(size_t)i]);
         if (st != VIO_OK) return st;
     }
-    DeviceGuard dg(h->device);
+    DeviceScope dev(h->device);
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     // layout of the staging buffer (descriptors | ints | doubles) and of the scratch
     std::vector<MargWin> wins((size_t)count);
     int64_t nd = 0, ni = 0, ns = 0;
@@ -885,18 +847,18 @@ vio_status vio_marg_compute_batch(vio_marg *h, int32_t count, const vio_marg_ite
         w.s_hpc = ns; ns += (int64_t)PRD * PRD;
         w.s_vt = ns; ns += (int64_t)PRD * PRD;
     }
-    const size_t b_desc = ((sizeof(MargWin) * (size_t)count + 255) / 256) * 256;
-    const size_t b_ints = ((sizeof(int32_t) * (size_t)ni + 255) / 256) * 256;
+    const size_t b_desc = align256(sizeof(MargWin) * (size_t)count);
+    const size_t b_ints = align256(sizeof(int32_t) * (size_t)ni);
     const size_t stage = b_desc + b_ints + sizeof(double) * (size_t)nd;
     const size_t outb = sizeof(double) * OUT_STRIDE * (size_t)count;
-    if (!grow_pinned(h->h_stage, h->stage_cap, stage) || !grow_device(h->d_stage, h->dstage_cap, stage) ||
-        !grow_device(h->d_scr, h->scr_cap, sizeof(double) * (size_t)ns) || !grow_pinned(h->h_out, h->hout_cap, outb) ||
-        !grow_device(h->d_out, h->dout_cap, outb))
-        return fail(h, VIO_ERR_HIP, "vio_marg_compute_batch: out of memory");
+    vio_status rc;
+    if ((rc = h->staging.ensure(h->err, stage)) != VIO_OK || (rc = h->scr.ensure(h->err, sizeof(double) * (size_t)ns)) != VIO_OK ||
+        (rc = h->out.ensure(h->err, outb)) != VIO_OK)
+        return rc;
     // pack
-    std::memcpy(h->h_stage, wins.data(), sizeof(MargWin) * (size_t)count);
-    int32_t *hi = (int32_t *)(h->h_stage + b_desc);
-    double *hd = (double *)(h->h_stage + b_desc + b_ints);
+    std::memcpy(h->staging.h, wins.data(), sizeof(MargWin) * (size_t)count);
+    int32_t *hi = (int32_t *)(h->staging.h + b_desc);
+    double *hd = (double *)(h->staging.h + b_desc + b_ints);
     for (int i = 0; i < count; ++i) {
         const vio_marg_item &it = items[i];
         const Graph &g = graphs[(size_t)i];
@@ -934,28 +896,28 @@ vio_status vio_marg_compute_batch(vio_marg *h, int32_t count, const vio_marg_ite
     MargCfg mc;
     mc.loss_type = h->cfg.loss_type; mc.loss_delta = h->cfg.loss_delta; mc.sqrt_info = h->cfg.reproj_sqrt_info;
     for (int k = 0; k < 3; ++k) mc.gravity[k] = h->cfg.gravity[k];
-    const MargWin *dw = (const MargWin *)h->d_stage;
-    const int32_t *di = (const int32_t *)(h->d_stage + b_desc);
-    const double *dd = (const double *)(h->d_stage + b_desc + b_ints);
+    const MargWin *dw = (const MargWin *)h->staging.d;
+    const int32_t *di = (const int32_t *)(h->staging.d + b_desc);
+    const double *dd = (const double *)(h->staging.d + b_desc + b_ints);
     const auto t1 = std::chrono::steady_clock::now();
-    (void)hipEventRecord(h->ev[0], h->stream);
-    if (hipMemcpyAsync(h->d_stage, h->h_stage, stage, hipMemcpyHostToDevice, h->stream) != hipSuccess)
-        return fail(h, VIO_ERR_HIP, "vio_marg_compute_batch: upload failed");
-    (void)hipEventRecord(h->ev[1], h->stream);
-    hipLaunchKernelGGL(k_marg_build, dim3(count), dim3(BUILD_NT), 0, h->stream, dw, di, dd, h->d_scr, mc);
-    (void)hipEventRecord(h->ev[2], h->stream);
-    hipLaunchKernelGGL(k_marg_tail, dim3(count), dim3(TAIL_NT), TAIL_LDS, h->stream, dw, h->d_scr, h->d_out);
-    (void)hipEventRecord(h->ev[3], h->stream);
-    if (hipGetLastError() != hipSuccess) return fail(h, VIO_ERR_HIP, "vio_marg_compute_batch: kernel launch failed");
-    if (hipMemcpyAsync(h->h_out, h->d_out, outb, hipMemcpyDeviceToHost, h->stream) != hipSuccess ||
-        hipStreamSynchronize(h->stream) != hipSuccess)
-        return fail(h, VIO_ERR_HIP, "vio_marg_compute_batch: kernels or read-back failed");
+    (void)hipEventRecord(h->q.ev[0], h->q.stream);
+    if (hipMemcpyAsync(h->staging.d, h->staging.h, stage, hipMemcpyHostToDevice, h->q.stream) != hipSuccess)
+        return fail(h->err, VIO_ERR_HIP, "vio_marg_compute_batch: upload failed");
+    (void)hipEventRecord(h->q.ev[1], h->q.stream);
+    hipLaunchKernelGGL(k_marg_build, dim3(count), dim3(BUILD_NT), 0, h->q.stream, dw, di, dd, h->scr.d, mc);
+    (void)hipEventRecord(h->q.ev[2], h->q.stream);
+    hipLaunchKernelGGL(k_marg_tail, dim3(count), dim3(TAIL_NT), TAIL_LDS, h->q.stream, dw, h->scr.d, h->out.d);
+    (void)hipEventRecord(h->q.ev[3], h->q.stream);
+    if (hipGetLastError() != hipSuccess) return fail(h->err, VIO_ERR_HIP, "vio_marg_compute_batch: kernel launch failed");
+    if (hipMemcpyAsync(h->out.h, h->out.d, outb, hipMemcpyDeviceToHost, h->q.stream) != hipSuccess ||
+        hipStreamSynchronize(h->q.stream) != hipSuccess)
+        return fail(h->err, VIO_ERR_HIP, "vio_marg_compute_batch: kernels or read-back failed");
     // hand out
     vio_status ret = VIO_OK;
     h->live.assign((size_t)count, 0);
     for (int i = 0; i < count; ++i) {
         const vio_marg_item &it = items[i];
-        const double *o = h->h_out + OUT_STRIDE * (size_t)i;
+        const double *o = h->out.h + OUT_STRIDE * (size_t)i;
         std::memcpy(it.H, o, (size_t)PRD * PRD * 8);
         std::memcpy(it.jt_inv, o + (size_t)PRD * PRD, (size_t)PRD * PRD * 8);
         std::memcpy(it.b, o + (size_t)2 * PRD * PRD, PRD * 8);
@@ -965,13 +927,11 @@ vio_status vio_marg_compute_batch(vio_marg *h, int32_t count, const vio_marg_ite
         if (window_status) window_status[i] = ws;
         if (ws != VIO_OK) {
             ret = ws;
-            if (h->err.empty()) h->err = win(i) + "a landmark block has no inverse; the prior is the reference's outcome for that case (H_prior 0, the rest NaN)";
+            if (!h->err[0])
+                fail(h->err, ws, "window %d: a landmark block has no inverse; the prior is the reference's outcome for that case (H_prior 0, the rest NaN)", i);
         }
     }
-    float ms0 = NAN, ms1 = NAN, ms2 = NAN;
-    if (hipEventElapsedTime(&ms0, h->ev[0], h->ev[1]) != hipSuccess) ms0 = NAN;
-    if (hipEventElapsedTime(&ms1, h->ev[1], h->ev[2]) != hipSuccess) ms1 = NAN;
-    if (hipEventElapsedTime(&ms2, h->ev[2], h->ev[3]) != hipSuccess) ms2 = NAN;
+    const float ms0 = elapsed_ms(h->q.ev[0], h->q.ev[1]), ms1 = elapsed_ms(h->q.ev[1], h->q.ev[2]), ms2 = elapsed_ms(h->q.ev[2], h->q.ev[3]);
     const auto t2 = std::chrono::steady_clock::now();
     h->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count() + ms0;     // host pack, then the H2D copy on the stream
     h->timing[1] = ms1; h->timing[2] = ms2;

@@ -14,12 +14,12 @@
 
 #include <chrono>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstring>
 #include <vector>
 
 #include "vio_batch_grid.h"
+#include "vio_companion.h"
 #include "vio_device_math.h"
 #include "vio_imu_math.h"
 #include "vio_obs_csr.h"
@@ -143,63 +143,16 @@ __global__ void __launch_bounds__(TAIL_NT) k_res_tail_batch(const ResArgs *__res
 struct vio_res {
     vio_ctx *ctx = nullptr;
     vio_config cfg;
-    hipStream_t stream = nullptr;
-    hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
-    char err[512] = {0};
-    // device: poses | sb | ext | errp | pre | val | pts_i | pts_j (doubles), then pre_ok | lm | host | fr | off | eidx (ints): one upload
-    char *d_in = nullptr, *h_in = nullptr;          // (h_in: pinned, grows only)
-    size_t in_cap = 0;
-    // device: obs | lm_out | part | sum (doubles), then dneg | flags (bytes); the requested parts come back through h_out (pinned)
-    char *d_out = nullptr, *h_out = nullptr;
-    size_t out_cap = 0;
-    // device: the batch tables of a vio_res_compute_batch whose first handle this is (ResArgs | workgroup starts)
-    char *d_tab = nullptr, *h_tab = nullptr;
-    size_t tab_cap = 0;
+    StreamEvents<4> q;                              // the context's stream (borrowed, set by stage()) and the timing events
+    ErrText err = {0};
+    // poses | sb | ext | errp | pre | val | pts_i | pts_j (doubles), then pre_ok | lm | host | fr | off | eidx (ints): one upload
+    Twin<char> in;
+    // obs | lm_out | part | sum (doubles), then dneg | flags (bytes); the requested parts come back through out.h
+    Twin<char> out;
+    // the batch tables of a vio_res_compute_batch whose first handle this is (ResArgs | workgroup starts)
+    Twin<char> tab;
     double timing[5] = {0, 0, 0, 0, 0};
 };
-
-// The calling thread's current device is the caller's: switched to the context's for the library's calls, put back on the way out.
-struct DeviceScope {
-    int prev = -1;
-    bool ok = false;
-    explicit DeviceScope(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        ok = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DeviceScope() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
-};
-
-static vio_status fail(vio_res *rs, vio_status st, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(rs->err, sizeof(rs->err), fmt, ap);
-    va_end(ap);
-    return st;
-}
-
-static vio_status hip_ck(vio_res *rs, hipError_t e, const char *what) {
-    if (e == hipSuccess) return VIO_OK;
-    return fail(rs, VIO_ERR_HIP, "%s: %s", what, hipGetErrorString(e));
-}
-
-// grow a pinned host buffer and its device twin to hold `bytes` (never shrinks)
-static vio_status ensure(vio_res *rs, char **d, char **h, size_t *cap, size_t bytes) {
-    if (bytes <= *cap) return VIO_OK;
-    if (*d) hipFree(*d);
-    if (*h) hipHostFree(*h);
-    *d = nullptr; *h = nullptr; *cap = 0;
-    size_t want = bytes + bytes / 4 + 4096;
-    vio_status st = hip_ck(rs, hipMalloc((void **)d, want), "hipMalloc");
-    if (st != VIO_OK) return st;
-    st = hip_ck(rs, hipHostMalloc((void **)h, want, hipHostMallocDefault), "hipHostMalloc");
-    if (st != VIO_OK) return st;
-    *cap = want;
-    return VIO_OK;
-}
-
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 // covariance.inverse() (edge_imu.cc:35): LU with partial pivoting of the 15 x 15, then the two triangular solves of the identity
 static void inverse15(const double *cov, double *info) {
@@ -251,12 +204,12 @@ struct Staged {
 static vio_status stage(vio_res *rs, int D, int64_t m, const int32_t *lm, const int32_t *host, const int32_t *target,
                         const double *pts_i, const double *pts_j, int64_t n, const vio_preint *const *pre, double focal,
                         double outlier_px, Staged &sg) {
-    if (m < 0 || n < 0 || n >= INT32_MAX || m >= INT32_MAX) return fail(rs, VIO_ERR_BAD_ARG, "bad sizes m=%lld n=%lld", (long long)m, (long long)n);
-    if (!(focal > 0.0)) return fail(rs, VIO_ERR_BAD_ARG, "focal %g is not positive", focal);
-    if (m > 0 && (!lm || !target || !pts_j || (D == 1 && (!host || !pts_i)))) return fail(rs, VIO_ERR_BAD_ARG, "observation array is NULL");
+    if (m < 0 || n < 0 || n >= INT32_MAX || m >= INT32_MAX) return fail(rs->err, VIO_ERR_BAD_ARG, "bad sizes m=%lld n=%lld", (long long)m, (long long)n);
+    if (!(focal > 0.0)) return fail(rs->err, VIO_ERR_BAD_ARG, "focal %g is not positive", focal);
+    if (m > 0 && (!lm || !target || !pts_j || (D == 1 && (!host || !pts_i)))) return fail(rs->err, VIO_ERR_BAD_ARG, "observation array is NULL");
     for (int64_t e = 0; e < m; ++e) {
         if (lm[e] < 0 || lm[e] >= n || target[e] < 0 || target[e] >= NF || (D == 1 && (host[e] < 0 || host[e] >= NF)))
-            return fail(rs, VIO_ERR_BAD_ARG, "observation %lld refers to landmark %d / a frame out of range", (long long)e, lm[e]);
+            return fail(rs->err, VIO_ERR_BAD_ARG, "observation %lld refers to landmark %d / a frame out of range", (long long)e, lm[e]);
     }
     vio_status st = VIO_OK;
 
@@ -266,17 +219,17 @@ static vio_status stage(vio_res *rs, int D, int64_t m, const int32_t *lm, const 
                  oPj = align256(oPi + (D == 1 ? 16 * (size_t)m : 0)), oOk = align256(oPj + 16 * (size_t)m), oLm = align256(oOk + 4 * NW),
                  oH = align256(oLm + 4 * (size_t)m), oF = align256(oH + (D == 1 ? 4 * (size_t)m : 0)), oOff = align256(oF + 4 * (size_t)m),
                  oEi = align256(oOff + 4 * ((size_t)n + 1)), nin = align256(oEi + 4 * (size_t)m);
-    if ((st = ensure(rs, &rs->d_in, &rs->h_in, &rs->in_cap, nin)) != VIO_OK) return st;
-    char *hb = rs->h_in;
+    if ((st = rs->in.ensure(rs->err, nin)) != VIO_OK) return st;
+    char *hb = rs->in.h;
 
     // the states (n is checked against the context here: vio_get_landmarks refuses another count, before anything is written)
     if ((st = vio_get_window(rs->ctx, (double *)(hb + oP), (double *)(hb + oS), (double *)(hb + oE))) != VIO_OK)
-        return fail(rs, st, "vio_get_window: %s", vio_last_error(rs->ctx));
+        return fail(rs->err, st, "vio_get_window: %s", vio_last_error(rs->ctx));
     st = D == 1 ? vio_get_landmarks(rs->ctx, n, (double *)(hb + oV)) : vio_get_landmarks_xyz(rs->ctx, n, (double *)(hb + oV));
     if (st == VIO_ERR_BAD_ARG)
-        return fail(rs, st, "n=%lld is not the context's %s landmark count", (long long)n, D == 1 ? "inverse-depth" : "XYZ");
-    if (st != VIO_OK) return fail(rs, st, "vio_get_landmarks%s: %s", D == 1 ? "" : "_xyz", vio_last_error(rs->ctx));
-    if ((st = vio_get_prior(rs->ctx, nullptr, (double *)(hb + oErr))) != VIO_OK) return fail(rs, st, "vio_get_prior: %s", vio_last_error(rs->ctx));
+        return fail(rs->err, st, "n=%lld is not the context's %s landmark count", (long long)n, D == 1 ? "inverse-depth" : "XYZ");
+    if (st != VIO_OK) return fail(rs->err, st, "vio_get_landmarks%s: %s", D == 1 ? "" : "_xyz", vio_last_error(rs->ctx));
+    if ((st = vio_get_prior(rs->ctx, nullptr, (double *)(hb + oErr))) != VIO_OK) return fail(rs->err, st, "vio_get_prior: %s", vio_last_error(rs->ctx));
 
     // IMU edges: the pre-integration packed as the solver packs it (vio_types.h PRE_*), the information formed here
     int *ok = (int *)(hb + oOk);
@@ -307,19 +260,19 @@ static vio_status stage(vio_res *rs, int D, int64_t m, const int32_t *lm, const 
     obs_csr(m, lm, n, (int *)(hb + oOff), [&](int64_t e, int, int q) { eidx[q] = (int)e; return true; });
 
     void *sp = nullptr;
-    if ((st = vio_get_stream(rs->ctx, &sp)) != VIO_OK) return fail(rs, st, "vio_get_stream");
-    rs->stream = (hipStream_t)sp;
+    if ((st = vio_get_stream(rs->ctx, &sp)) != VIO_OK) return fail(rs->err, st, "vio_get_stream");
+    rs->q.stream = (hipStream_t)sp;
 
     const int n_wg = (int)((n + LM_NT - 1) / LM_NT);
     const size_t qObs = 0, qLm = align256(qObs + 32 * (size_t)m), qPart = align256(qLm + 24 * (size_t)n),
                  qSum = align256(qPart + 8 * (size_t)P_STRIDE * (n_wg > 0 ? n_wg : 1)), qDn = align256(qSum + 8 * S_N),
                  qFl = align256(qDn + (size_t)m), nout = align256(qFl + (size_t)n);
-    if ((st = ensure(rs, &rs->d_out, &rs->h_out, &rs->out_cap, nout)) != VIO_OK) return st;
+    if ((st = rs->out.ensure(rs->err, nout)) != VIO_OK) return st;
 
-    if ((st = hip_ck(rs, hipMemcpyAsync(rs->d_in, rs->h_in, nin, hipMemcpyHostToDevice, rs->stream), "upload")) != VIO_OK) return st;
+    if ((st = hip_ck(rs->err, hipMemcpyAsync(rs->in.d, rs->in.h, nin, hipMemcpyHostToDevice, rs->q.stream), "upload")) != VIO_OK) return st;
 
     ResArgs &a = sg.a;
-    char *di = rs->d_in, *dq = rs->d_out;
+    char *di = rs->in.d, *dq = rs->out.d;
     a.poses = (const double *)(di + oP); a.sb = (const double *)(di + oS); a.ext = (const double *)(di + oE);
     a.errp = (const double *)(di + oErr); a.pre = (const double *)(di + oPre); a.pre_ok = (const int *)(di + oOk);
     a.val = (const double *)(di + oV); a.pts_i = (const double *)(di + oPi); a.pts_j = (const double *)(di + oPj);
@@ -338,11 +291,11 @@ static vio_status stage(vio_res *rs, int D, int64_t m, const int32_t *lm, const 
 
 // After the read-back has completed: the requested outputs, from h_out at the offsets the device used
 static void finish(vio_res *rs, const Staged &sg, double *obs_out, double *lm_out, uint8_t *lm_flags, vio_res_summary *summary) {
-    if (obs_out && sg.m > 0) std::memcpy(obs_out, rs->h_out + sg.qObs, 32 * (size_t)sg.m);
-    if (lm_out && sg.n > 0) std::memcpy(lm_out, rs->h_out + sg.qLm, 24 * (size_t)sg.n);
-    if (lm_flags && sg.n > 0) std::memcpy(lm_flags, rs->h_out + sg.qFl, (size_t)sg.n);
+    if (obs_out && sg.m > 0) std::memcpy(obs_out, rs->out.h + sg.qObs, 32 * (size_t)sg.m);
+    if (lm_out && sg.n > 0) std::memcpy(lm_out, rs->out.h + sg.qLm, 24 * (size_t)sg.n);
+    if (lm_flags && sg.n > 0) std::memcpy(lm_flags, rs->out.h + sg.qFl, (size_t)sg.n);
     if (summary) {
-        const double *s = (const double *)(rs->h_out + sg.qSum);
+        const double *s = (const double *)(rs->out.h + sg.qSum);
         vio_res_summary o;
         std::memset(&o, 0, sizeof(o));
         o.chi2 = s[S_CHI]; o.visual_robust = s[S_VR]; o.visual_plain = s[S_VP]; o.imu = s[S_IMU]; o.prior = s[S_PRIOR];
@@ -359,45 +312,45 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
     using clk = std::chrono::steady_clock;
     const auto t0 = clk::now();
     DeviceScope dev(rs->cfg.device);
-    if (!dev.ok) return fail(rs, VIO_ERR_HIP, "hipSetDevice(%d)", rs->cfg.device);
+    if (!dev.ok) return fail(rs->err, VIO_ERR_HIP, "hipSetDevice(%d)", rs->cfg.device);
     Staged sg;
     vio_status st = stage(rs, D, m, lm, host, target, pts_i, pts_j, n, pre, focal, outlier_px, sg);
     if (st != VIO_OK) return st;
     const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
     const ResArgs &a = sg.a;
     const int n_wg = a.n_wg;
-    char *dq = rs->d_out;
+    char *dq = rs->out.d;
 
-    if ((st = hip_ck(rs, hipEventRecord(rs->ev[0], rs->stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(rs->err, hipEventRecord(rs->q.ev[0], rs->q.stream), "hipEventRecord")) != VIO_OK) return st;
     if (m > 0) {
         const unsigned g = (unsigned)((m + OBS_NT - 1) / OBS_NT);
-        if (D == 1) k_res_obs<1><<<g, OBS_NT, 0, rs->stream>>>(a);
-        else k_res_obs<3><<<g, OBS_NT, 0, rs->stream>>>(a);
-        if ((st = hip_ck(rs, hipGetLastError(), "k_res_obs launch")) != VIO_OK) return st;
+        if (D == 1) k_res_obs<1><<<g, OBS_NT, 0, rs->q.stream>>>(a);
+        else k_res_obs<3><<<g, OBS_NT, 0, rs->q.stream>>>(a);
+        if ((st = hip_ck(rs->err, hipGetLastError(), "k_res_obs launch")) != VIO_OK) return st;
     }
-    if ((st = hip_ck(rs, hipEventRecord(rs->ev[1], rs->stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(rs->err, hipEventRecord(rs->q.ev[1], rs->q.stream), "hipEventRecord")) != VIO_OK) return st;
     if (n_wg > 0) {
-        if (D == 1) k_res_lm<1><<<(unsigned)n_wg, LM_NT, 0, rs->stream>>>(a);
-        else k_res_lm<3><<<(unsigned)n_wg, LM_NT, 0, rs->stream>>>(a);
-        if ((st = hip_ck(rs, hipGetLastError(), "k_res_lm launch")) != VIO_OK) return st;
+        if (D == 1) k_res_lm<1><<<(unsigned)n_wg, LM_NT, 0, rs->q.stream>>>(a);
+        else k_res_lm<3><<<(unsigned)n_wg, LM_NT, 0, rs->q.stream>>>(a);
+        if ((st = hip_ck(rs->err, hipGetLastError(), "k_res_lm launch")) != VIO_OK) return st;
     }
-    if ((st = hip_ck(rs, hipEventRecord(rs->ev[2], rs->stream), "hipEventRecord")) != VIO_OK) return st;
-    k_res_tail<<<1, TAIL_NT, 0, rs->stream>>>(a);
-    if ((st = hip_ck(rs, hipGetLastError(), "k_res_tail launch")) != VIO_OK) return st;
-    if ((st = hip_ck(rs, hipEventRecord(rs->ev[3], rs->stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(rs->err, hipEventRecord(rs->q.ev[2], rs->q.stream), "hipEventRecord")) != VIO_OK) return st;
+    k_res_tail<<<1, TAIL_NT, 0, rs->q.stream>>>(a);
+    if ((st = hip_ck(rs->err, hipGetLastError(), "k_res_tail launch")) != VIO_OK) return st;
+    if ((st = hip_ck(rs->err, hipEventRecord(rs->q.ev[3], rs->q.stream), "hipEventRecord")) != VIO_OK) return st;
     // read back what was asked for
     struct Part { bool want; size_t off, bytes; } parts[4] = {
         {obs_out != nullptr && m > 0, sg.qObs, 32 * (size_t)m}, {lm_out != nullptr && n > 0, sg.qLm, 24 * (size_t)n},
         {lm_flags != nullptr && n > 0, sg.qFl, (size_t)n}, {summary != nullptr, sg.qSum, 8 * S_N}};
     for (const Part &p : parts)
-        if (p.want && (st = hip_ck(rs, hipMemcpyAsync(rs->h_out + p.off, dq + p.off, p.bytes, hipMemcpyDeviceToHost, rs->stream), "read-back")) != VIO_OK)
+        if (p.want && (st = hip_ck(rs->err, hipMemcpyAsync(rs->out.h + p.off, dq + p.off, p.bytes, hipMemcpyDeviceToHost, rs->q.stream), "read-back")) != VIO_OK)
             return st;
-    if ((st = hip_ck(rs, hipStreamSynchronize(rs->stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    if ((st = hip_ck(rs->err, hipStreamSynchronize(rs->q.stream), "hipStreamSynchronize")) != VIO_OK) return st;
 
     finish(rs, sg, obs_out, lm_out, lm_flags, summary);
-    float ms[3] = {0, 0, 0};
+    float ms[3];
     for (int k = 0; k < 3; ++k)
-        if (hipEventElapsedTime(&ms[k], rs->ev[k], rs->ev[k + 1]) != hipSuccess) {
+        if (std::isnan(ms[k] = elapsed_ms(rs->q.ev[k], rs->q.ev[k + 1]))) {
             for (double &t : rs->timing) t = NAN;   // (the outputs are written: only the timings are unknown)
             return VIO_OK;
         }
@@ -411,7 +364,7 @@ static vio_status compute(vio_res *rs, int D, int64_t m, const int32_t *lm, cons
 static vio_status batch_fail(vio_res *r0, vio_status st, int i, const vio_res *rs) {
     char msg[sizeof(rs->err)];
     memcpy(msg, rs->err, sizeof(msg));
-    return fail(r0, st, "vio_res_compute_batch: window %d: %s", i, msg);
+    return fail(r0->err, st, "vio_res_compute_batch: window %d: %s", i, msg);
 }
 
 // The batch: every window staged in its own handle's buffers (one upload each), one table upload, k_res_obs_batch, k_res_lm_batch
@@ -425,21 +378,21 @@ static vio_status compute_batch(vio_res *const *rss, int32_t count, int32_t xyz,
     void *s0 = nullptr;
     for (int32_t i = 0; i < count; ++i) {
         vio_res *rs = rss[i];
-        if (!rs) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d: null handle", i);
+        if (!rs) return fail(r0->err, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d: null handle", i);
         rs->err[0] = 0;
-        if (rs->cfg.shard_count > 1) return fail(r0, VIO_ERR_UNSUPPORTED, "vio_res_compute_batch: window %d: sharded context", i);
+        if (rs->cfg.shard_count > 1) return fail(r0->err, VIO_ERR_UNSUPPORTED, "vio_res_compute_batch: window %d: sharded context", i);
         if (rs->cfg.device != r0->cfg.device)
-            return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d is on device %d, window 0 on %d: the contexts must share one device and one stream", i, rs->cfg.device, r0->cfg.device);
+            return fail(r0->err, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d is on device %d, window 0 on %d: the contexts must share one device and one stream", i, rs->cfg.device, r0->cfg.device);
         for (int32_t j = 0; j < i; ++j)
-            if (rss[j] == rs) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: windows %d and %d are the same handle", j, i);
+            if (rss[j] == rs) return fail(r0->err, VIO_ERR_BAD_ARG, "vio_res_compute_batch: windows %d and %d are the same handle", j, i);
     }
     DeviceScope dev(r0->cfg.device);
-    if (!dev.ok) return fail(r0, VIO_ERR_HIP, "hipSetDevice(%d)", r0->cfg.device);
+    if (!dev.ok) return fail(r0->err, VIO_ERR_HIP, "hipSetDevice(%d)", r0->cfg.device);
     for (int32_t i = 0; i < count; ++i) {
         void *sp = nullptr;
-        if (vio_get_stream(rss[i]->ctx, &sp) != VIO_OK) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d: vio_get_stream", i);
+        if (vio_get_stream(rss[i]->ctx, &sp) != VIO_OK) return fail(r0->err, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d: vio_get_stream", i);
         if (i == 0) s0 = sp;
-        else if (sp != s0) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d is on another stream than window 0: the contexts must share one device and one stream", i);
+        else if (sp != s0) return fail(r0->err, VIO_ERR_BAD_ARG, "vio_res_compute_batch: window %d is on another stream than window 0: the contexts must share one device and one stream", i);
     }
     vio_status st = VIO_OK;
     std::vector<Staged> sg(count);
@@ -452,8 +405,8 @@ static vio_status compute_batch(vio_res *const *rss, int32_t count, int32_t xyz,
     // the tables: ResArgs[count] | obs workgroup starts[count + 1] | lm workgroup starts[count + 1]
     const size_t bArgs = 0, bObs = align256(sizeof(ResArgs) * count), bLm = bObs + sizeof(int) * ((size_t)count + 1),
                  nbytes = bLm + sizeof(int) * ((size_t)count + 1);
-    if ((st = ensure(r0, &r0->d_tab, &r0->h_tab, &r0->tab_cap, nbytes)) != VIO_OK) return st;
-    char *ht = r0->h_tab;
+    if ((st = r0->tab.ensure(r0->err, nbytes)) != VIO_OK) return st;
+    char *ht = r0->tab.h;
     ResArgs *ta = (ResArgs *)(ht + bArgs);
     int *blk_obs = (int *)(ht + bObs), *blk_lm = (int *)(ht + bLm);
     int64_t nobs = 0, nlm = 0;
@@ -463,43 +416,43 @@ static vio_status compute_batch(vio_res *const *rss, int32_t count, int32_t xyz,
         blk_lm[i] = (int)nlm;
         nobs += (sg[i].m + OBS_NT - 1) / OBS_NT;
         nlm += sg[i].a.n_wg;
-        if (nobs > INT32_MAX || nlm > INT32_MAX) return fail(r0, VIO_ERR_BAD_ARG, "vio_res_compute_batch: too many edges in the batch");
+        if (nobs > INT32_MAX || nlm > INT32_MAX) return fail(r0->err, VIO_ERR_BAD_ARG, "vio_res_compute_batch: too many edges in the batch");
     }
     blk_obs[count] = (int)nobs;
     blk_lm[count] = (int)nlm;
     hipStream_t stream = (hipStream_t)s0;
-    const char *dt = r0->d_tab;
-    if ((st = hip_ck(r0, hipMemcpyAsync(r0->d_tab, r0->h_tab, nbytes, hipMemcpyHostToDevice, stream), "table upload")) != VIO_OK) return st;
+    const char *dt = r0->tab.d;
+    if ((st = hip_ck(r0->err, hipMemcpyAsync(r0->tab.d, r0->tab.h, nbytes, hipMemcpyHostToDevice, stream), "table upload")) != VIO_OK) return st;
     const double t_host = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
 
     const ResArgs *da = (const ResArgs *)(dt + bArgs);
-    if ((st = hip_ck(r0, hipEventRecord(r0->ev[0], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(r0->err, hipEventRecord(r0->q.ev[0], stream), "hipEventRecord")) != VIO_OK) return st;
     if (nobs > 0) {
         if (D == 1) k_res_obs_batch<1><<<(unsigned)nobs, OBS_NT, 0, stream>>>(da, (const int *)(dt + bObs), count);
         else k_res_obs_batch<3><<<(unsigned)nobs, OBS_NT, 0, stream>>>(da, (const int *)(dt + bObs), count);
-        if ((st = hip_ck(r0, hipGetLastError(), "k_res_obs_batch launch")) != VIO_OK) return st;
+        if ((st = hip_ck(r0->err, hipGetLastError(), "k_res_obs_batch launch")) != VIO_OK) return st;
     }
-    if ((st = hip_ck(r0, hipEventRecord(r0->ev[1], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(r0->err, hipEventRecord(r0->q.ev[1], stream), "hipEventRecord")) != VIO_OK) return st;
     if (nlm > 0) {
         if (D == 1) k_res_lm_batch<1><<<(unsigned)nlm, LM_NT, 0, stream>>>(da, (const int *)(dt + bLm), count);
         else k_res_lm_batch<3><<<(unsigned)nlm, LM_NT, 0, stream>>>(da, (const int *)(dt + bLm), count);
-        if ((st = hip_ck(r0, hipGetLastError(), "k_res_lm_batch launch")) != VIO_OK) return st;
+        if ((st = hip_ck(r0->err, hipGetLastError(), "k_res_lm_batch launch")) != VIO_OK) return st;
     }
-    if ((st = hip_ck(r0, hipEventRecord(r0->ev[2], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(r0->err, hipEventRecord(r0->q.ev[2], stream), "hipEventRecord")) != VIO_OK) return st;
     k_res_tail_batch<<<(unsigned)count, TAIL_NT, 0, stream>>>(da);
-    if ((st = hip_ck(r0, hipGetLastError(), "k_res_tail_batch launch")) != VIO_OK) return st;
-    if ((st = hip_ck(r0, hipEventRecord(r0->ev[3], stream), "hipEventRecord")) != VIO_OK) return st;
+    if ((st = hip_ck(r0->err, hipGetLastError(), "k_res_tail_batch launch")) != VIO_OK) return st;
+    if ((st = hip_ck(r0->err, hipEventRecord(r0->q.ev[3], stream), "hipEventRecord")) != VIO_OK) return st;
     for (int32_t i = 0; i < count; ++i)
-        if ((st = hip_ck(rss[i], hipMemcpyAsync(rss[i]->h_out, rss[i]->d_out, sg[i].nout, hipMemcpyDeviceToHost, stream), "read-back")) != VIO_OK)
+        if ((st = hip_ck(rss[i]->err, hipMemcpyAsync(rss[i]->out.h, rss[i]->out.d, sg[i].nout, hipMemcpyDeviceToHost, stream), "read-back")) != VIO_OK)
             return batch_fail(r0, st, i, rss[i]);
-    if ((st = hip_ck(r0, hipStreamSynchronize(stream), "hipStreamSynchronize")) != VIO_OK) return st;
+    if ((st = hip_ck(r0->err, hipStreamSynchronize(stream), "hipStreamSynchronize")) != VIO_OK) return st;
 
     for (int32_t i = 0; i < count; ++i)
         finish(rss[i], sg[i], items[i].obs_out, items[i].lm_out, items[i].lm_flags, items[i].summary);
-    float ms[3] = {0, 0, 0};
+    float ms[3];
     double tm[5] = {NAN, NAN, NAN, NAN, NAN};
     bool ev_ok = true;
-    for (int k = 0; k < 3; ++k) ev_ok = ev_ok && hipEventElapsedTime(&ms[k], r0->ev[k], r0->ev[k + 1]) == hipSuccess;
+    for (int k = 0; k < 3; ++k) ev_ok = ev_ok && !std::isnan(ms[k] = elapsed_ms(r0->q.ev[k], r0->q.ev[k + 1]));
     if (ev_ok) {
         tm[0] = t_host;
         for (int k = 0; k < 3; ++k) tm[1 + k] = ms[k];
@@ -522,8 +475,7 @@ vio_status vio_res_create(struct vio_ctx *ctx, const vio_config *cfg, vio_res **
     rs->cfg = *cfg;
     DeviceScope dev(cfg->device);
     if (!dev.ok) { delete rs; return VIO_ERR_HIP; }
-    for (int k = 0; k < 4; ++k)
-        if (hipEventCreate(&rs->ev[k]) != hipSuccess) { vio_res_destroy(rs); return VIO_ERR_HIP; }
+    if (rs->q.create_events() != hipSuccess) { vio_res_destroy(rs); return VIO_ERR_HIP; }
     *out = rs;
     return VIO_OK;
 }
@@ -531,21 +483,14 @@ vio_status vio_res_create(struct vio_ctx *ctx, const vio_config *cfg, vio_res **
 void vio_res_destroy(vio_res *rs) {
     if (!rs) return;
     DeviceScope dev(rs->cfg.device);
-    if (rs->stream) hipStreamSynchronize(rs->stream);
-    for (int k = 0; k < 4; ++k) if (rs->ev[k]) hipEventDestroy(rs->ev[k]);
-    if (rs->d_in) hipFree(rs->d_in);
-    if (rs->d_out) hipFree(rs->d_out);
-    if (rs->d_tab) hipFree(rs->d_tab);
-    if (rs->h_in) hipHostFree(rs->h_in);
-    if (rs->h_out) hipHostFree(rs->h_out);
-    if (rs->h_tab) hipHostFree(rs->h_tab);
-    delete rs;
+    rs->q.release();
+    delete rs;                                      // (the buffers free themselves)
 }
 
 vio_status vio_res_set_config(vio_res *rs, const vio_config *cfg) {
     if (!rs || !cfg) return VIO_ERR_BAD_ARG;
-    if (cfg->device != rs->cfg.device) return fail(rs, VIO_ERR_BAD_ARG, "device %d: the handle was made for device %d", cfg->device, rs->cfg.device);
-    if (cfg->shard_count > 1) return fail(rs, VIO_ERR_UNSUPPORTED, "sharded context");
+    if (cfg->device != rs->cfg.device) return fail(rs->err, VIO_ERR_BAD_ARG, "device %d: the handle was made for device %d", cfg->device, rs->cfg.device);
+    if (cfg->shard_count > 1) return fail(rs->err, VIO_ERR_UNSUPPORTED, "sharded context");
     rs->cfg = *cfg;
     return VIO_OK;
 }

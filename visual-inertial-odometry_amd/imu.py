@@ -8,12 +8,11 @@
 The records are what VioContext.set_imu_all takes.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import synth
-from .capi import VioError, VioPreint
+from .capi import CompanionHandle, VioError, VioPreint, open_lib
 
 
 class VioImuNoise(C.Structure):
@@ -26,19 +25,8 @@ class ImuLib:
     SYMBOLS = ["create", "destroy", "last_error", "version", "load", "propagate", "timing"]
 
     def __init__(self, path):
-        if not os.path.exists(path):
-            raise FileNotFoundError(
-                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
         self.path = path
-        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        self.fn = {s: getattr(self.dll, "vio_imu_" + s) for s in self.SYMBOLS}
-        for s in self.SYMBOLS:
-            self.fn[s].restype = C.c_int
-        self.fn["destroy"].restype = None
-        self.fn["destroy"].argtypes = [C.c_void_p]
-        self.fn["last_error"].restype = C.c_char_p
-        self.fn["last_error"].argtypes = [C.c_void_p]
-        self.fn["version"].restype = C.c_int32
+        self.dll, self.fn = open_lib(path, "vio_imu_", self.SYMBOLS)
         self.fn["create"].argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["load"].argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 6
         self.fn["propagate"].argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 4
@@ -73,7 +61,9 @@ def record_dict(p):
             "linearized_bg": v[14:17], "jacobian": v[17:242].reshape(15, 15), "covariance": v[242:467].reshape(15, 15)}
 
 
-class ImuHandle:
+class ImuHandle(CompanionHandle):
+    PREFIX = "vio_imu_"
+
     def __init__(self, lib, device=0, stream=None):
         self.lib = lib
         self.h = C.c_void_p()
@@ -81,22 +71,6 @@ class ImuHandle:
         st = lib.fn["create"](C.c_int32(device), C.c_void_p(stream) if stream else None, C.byref(self.h))
         if st != 0:
             raise VioError(st, "vio_imu_create")
-
-    def close(self):
-        if self.h:
-            self.lib.fn["destroy"](self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, st, where):
-        if st != 0:
-            msg = self.lib.fn["last_error"](self.h)
-            raise VioError(st, "vio_imu_" + where, (msg or b"").decode(errors="replace"))
 
     def load(self, intervals, noise=None):
         """Upload the raw samples of `intervals` (dicts with acc0, gyr0, dt, acc, gyr).  noise: dict acc_n, gyr_n, acc_w, gyr_w

@@ -10,11 +10,10 @@ synth.preintegrate returns; pre[k] is interval k -> k+1), is_key (F,) or None (e
 R / T from a stream's ground truth, as initialStructure would leave them.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-from .capi import VioError, VioPreint
+from .capi import CompanionHandle, VioError, VioPreint, open_lib
 from .imu import record_dict
 
 MAX_FRAMES = 32
@@ -36,43 +35,14 @@ class VioInitResult(C.Structure):
                 ("s_linear", C.c_double), ("g_linear", C.c_double * 3), ("rot", C.c_double * 9)]
 
 
-def _preint(p):
-    """A VioPreint from a record or from synth.preintegrate's dict."""
-    if isinstance(p, VioPreint):
-        return p
-    r = VioPreint()
-    r.sum_dt = float(p["sum_dt"])
-    for k in range(3):
-        r.delta_p[k] = float(p["delta_p"][k]); r.delta_v[k] = float(p["delta_v"][k])
-        r.linearized_ba[k] = float(p["linearized_ba"][k]); r.linearized_bg[k] = float(p["linearized_bg"][k])
-    for k in range(4):
-        r.delta_q[k] = float(p["delta_q"][k])
-    J = np.ascontiguousarray(p["jacobian"], dtype=np.float64).reshape(225)
-    P = np.ascontiguousarray(p["covariance"], dtype=np.float64).reshape(225)
-    C.memmove(r.jacobian, J.ctypes.data, 225 * 8)
-    C.memmove(r.covariance, P.ctypes.data, 225 * 8)
-    return r
-
-
 class InitLib:
     """libvio_init_hip.so: vio_init_*."""
 
     SYMBOLS = ["create", "destroy", "last_error", "version", "gyro_bias_batch", "align_batch", "timing"]
 
     def __init__(self, path):
-        if not os.path.exists(path):
-            raise FileNotFoundError(
-                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
         self.path = path
-        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        self.fn = {s: getattr(self.dll, "vio_init_" + s) for s in self.SYMBOLS}
-        for s in self.SYMBOLS:
-            self.fn[s].restype = C.c_int
-        self.fn["destroy"].restype = None
-        self.fn["destroy"].argtypes = [C.c_void_p]
-        self.fn["last_error"].restype = C.c_char_p
-        self.fn["last_error"].argtypes = [C.c_void_p]
-        self.fn["version"].restype = C.c_int32
+        self.dll, self.fn = open_lib(path, "vio_init_", self.SYMBOLS)
         self.fn["create"].argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["gyro_bias_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self.fn["align_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_void_p,
@@ -96,7 +66,7 @@ class _Packed:
             F = len(R)
             pre = (VioPreint * max(1, F - 1))()
             for k, p in enumerate(it["pre"][:F - 1]):
-                pre[k] = _preint(p)
+                pre[k] = VioPreint.from_dict(p)
             key = it.get("is_key")
             key = None if key is None else np.ascontiguousarray(np.asarray(key, dtype=bool), dtype=np.uint8)
             self.keep += [R, T, pre, key]
@@ -104,7 +74,9 @@ class _Packed:
                                         C.addressof(pre))
 
 
-class InitHandle:
+class InitHandle(CompanionHandle):
+    PREFIX = "vio_init_"
+
     def __init__(self, lib, device=0, stream=None):
         self.lib = lib
         self.h = C.c_void_p()
@@ -112,21 +84,9 @@ class InitHandle:
         if st != 0:
             raise VioError(st, "vio_init_create")
 
-    def close(self):
-        if self.h:
-            self.lib.fn["destroy"](self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
     def _ck(self, st, where, allow_not_finite=False):
-        if st != 0 and not (allow_not_finite and st == NOT_FINITE):
-            msg = self.lib.fn["last_error"](self.h)
-            raise VioError(st, "vio_init_" + where, (msg or b"").decode(errors="replace"))
+        if not (allow_not_finite and st == NOT_FINITE):
+            super()._ck(st, where)
 
     def gyro_bias_batch(self, items, bg_in=None, status=False):
         """solveGyroscopeBias of every window: bg_in + delta_bg, (B, 3) (bg_in default zero: Bgs[] at the start).  status=True: also

@@ -9,11 +9,10 @@ prior: a dict with H (156 x 156) and b (156: vio_get_prior's b after a solve), o
 returns: H, b, err, jt_inv.
 """
 import ctypes as C
-import os
 
 import numpy as np
 
-from .capi import MARG_OLD, MARG_SECOND_NEW, PRIOR_DIM, VioConfig, VioError, VioPreint, _dp, _f64, _ip
+from .capi import MARG_OLD, MARG_SECOND_NEW, PRIOR_DIM, CompanionHandle, VioConfig, VioError, VioPreint, _f64, open_lib, window_field
 
 
 class VioMargItem(C.Structure):
@@ -24,33 +23,16 @@ class VioMargItem(C.Structure):
                 ("H", C.c_void_p), ("b", C.c_void_p), ("err", C.c_void_p), ("jt_inv", C.c_void_p)]
 
 
-def _get(w, k, default=None):
-    if isinstance(w, dict):
-        return w.get(k, default)
-    return getattr(w, k, default)
-
-
 class MargLib:
     """libvio_marg_hip.so: vio_marg_*."""
 
     SYMBOLS = ["create", "set_config", "destroy", "last_error", "version", "compute_batch", "compute", "timing", "live_rows"]
 
     def __init__(self, path):
-        if not os.path.exists(path):
-            raise FileNotFoundError(
-                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
         self.path = path
-        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        self.fn = {s: getattr(self.dll, "vio_marg_" + s) for s in self.SYMBOLS}
-        for s in self.SYMBOLS:
-            self.fn[s].restype = C.c_int
-        self.fn["destroy"].restype = None
-        self.fn["last_error"].restype = C.c_char_p
-        self.fn["last_error"].argtypes = [C.c_void_p]
-        self.fn["version"].restype = C.c_int32
+        self.dll, self.fn = open_lib(path, "vio_marg_", self.SYMBOLS)
         self.fn["create"].argtypes = [C.POINTER(VioConfig), C.POINTER(C.c_void_p)]
         self.fn["set_config"].argtypes = [C.c_void_p, C.POINTER(VioConfig)]
-        self.fn["destroy"].argtypes = [C.c_void_p]
         self.fn["compute_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["compute"].argtypes = [C.c_void_p, C.c_void_p]
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
@@ -77,7 +59,9 @@ class MargLib:
         return MargHandle(self, cfg)
 
 
-class MargHandle:
+class MargHandle(CompanionHandle):
+    PREFIX = "vio_marg_"
+
     def __init__(self, lib, cfg):
         self.lib, self.cfg = lib, cfg
         self.h = C.c_void_p()
@@ -85,24 +69,8 @@ class MargHandle:
         if st != 0:
             raise VioError(st, "vio_marg_create")
 
-    def close(self):
-        if self.h:
-            self.lib.fn["destroy"](self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def last_error(self):
-        return (self.lib.fn["last_error"](self.h) or b"").decode()
-
     def set_config(self, cfg):
-        st = self.lib.fn["set_config"](self.h, C.byref(cfg))
-        if st != 0:
-            raise VioError(st, "vio_marg_set_config", self.last_error())
+        self._ck(self.lib.fn["set_config"](self.h, C.byref(cfg)), "set_config")
         self.cfg = cfg
 
     def _item(self, kind, w, prior, keep):
@@ -116,18 +84,18 @@ class MargHandle:
             H, b = _f64(prior["H"], (PRIOR_DIM, PRIOR_DIM)), _f64(np.asarray(prior["b"])[:PRIOR_DIM], (PRIOR_DIM,))
             keep += [H, b]
             it.H_prior, it.b_prior = H.ctypes.data, b.ctypes.data
-        if w is not None and _get(w, "xyz") is not None:
+        if w is not None and window_field(w, "xyz") is not None:
             raise VioError(-5, "vio_marg_compute", "XYZ landmarks: the reference's Estimator never marginalises them")
         if w is not None:
             arrs = {}
             for k, shape in (("poses", (11, 7)), ("speed_bias", (11, 9)), ("ext", (7,))):
-                arrs[k] = _f64(_get(w, k), shape)
-            invd = _f64(_get(w, "inv_depth"))
-            lm = np.ascontiguousarray(_get(w, "lm"), dtype=np.int32)
-            host = np.ascontiguousarray(_get(w, "host"), dtype=np.int32)
-            target = np.ascontiguousarray(_get(w, "target"), dtype=np.int32)
+                arrs[k] = _f64(window_field(w, k), shape)
+            invd = _f64(window_field(w, "inv_depth"))
+            lm = np.ascontiguousarray(window_field(w, "lm"), dtype=np.int32)
+            host = np.ascontiguousarray(window_field(w, "host"), dtype=np.int32)
+            target = np.ascontiguousarray(window_field(w, "target"), dtype=np.int32)
             m = len(lm)
-            pi, pj = _f64(_get(w, "pts_i"), (m, 2)), _f64(_get(w, "pts_j"), (m, 2))
+            pi, pj = _f64(window_field(w, "pts_i"), (m, 2)), _f64(window_field(w, "pts_j"), (m, 2))
             keep += list(arrs.values()) + [invd, lm, host, target, pi, pj]
             it.poses, it.speed_bias, it.ext = arrs["poses"].ctypes.data, arrs["speed_bias"].ctypes.data, arrs["ext"].ctypes.data
             it.n, it.inv_depth = len(invd), (invd.ctypes.data if len(invd) else None)
@@ -135,10 +103,10 @@ class MargHandle:
             if m:
                 it.lm, it.host, it.target = lm.ctypes.data, host.ctypes.data, target.ctypes.data
                 it.pts_i, it.pts_j = pi.ctypes.data, pj.ctypes.data
-            pres = _get(w, "preint")
+            pres = window_field(w, "preint")
             p0 = pres[0] if pres is not None and len(pres) else None
             if p0 is not None:
-                p = p0 if isinstance(p0, VioPreint) else VioPreint.from_dict(p0)
+                p = VioPreint.from_dict(p0)
                 keep.append(p)
                 it.imu0 = C.addressof(p)
         return it, out
@@ -163,7 +131,7 @@ class MargHandle:
             e.window_status, e.results = self.window_status, res
             raise e
         if st not in (0, -3):
-            raise VioError(st, "vio_marg_compute_batch", self.last_error())
+            self._ck(st, "compute_batch")
         return res
 
     def compute(self, kind, window, prior=None, allow_nonfinite=False):
@@ -171,8 +139,8 @@ class MargHandle:
         keep = []
         it, out = self._item(kind, window, prior, keep)
         st = self.lib.fn["compute"](self.h, C.byref(it))
-        if not (st == -3 and allow_nonfinite) and st != 0:
-            raise VioError(st, "vio_marg_compute", self.last_error())
+        if not (st == -3 and allow_nonfinite):
+            self._ck(st, "compute")
         return out
 
     def timing(self):

@@ -9,12 +9,11 @@ flags of a window.
     [r, ...] = hip.batch_residuals(ctxs, windows)        # many windows, one launch per kernel
 """
 import ctypes as C
-import os
 
 import numpy as np
 
 from . import synth
-from .capi import NUM_FRAMES, WINDOW_SIZE, VioError, VioPreint, _dp, _f64, _ip
+from .capi import NUM_FRAMES, WINDOW_SIZE, CompanionHandle, VioError, _f64, open_lib, preint_pointers, window_field
 
 FLAG_REPROJ, FLAG_DEPTH, FLAG_STATE = 1, 2, 4
 FLAGS_ALL = FLAG_REPROJ | FLAG_DEPTH | FLAG_STATE
@@ -39,17 +38,8 @@ class ResLib:
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "compute", "compute_xyz", "compute_batch", "timing"]
 
     def __init__(self, path):
-        if not os.path.exists(path):
-            raise FileNotFoundError(
-                "%s not found — build it first (python -c 'import __graft_entry__ as g; g.build()')" % path)
         self.path = path
-        self.dll = C.CDLL(path, mode=getattr(os, "RTLD_LOCAL", 0) | getattr(os, "RTLD_NOW", 2))
-        self.fn = {s: getattr(self.dll, "vio_res_" + s) for s in self.SYMBOLS}
-        for s in self.SYMBOLS:
-            self.fn[s].restype = C.c_int
-        self.fn["destroy"].restype = None
-        self.fn["last_error"].restype = C.c_char_p
-        self.fn["version"].restype = C.c_int32
+        self.dll, self.fn = open_lib(path, "vio_res_", self.SYMBOLS)
         self.fn["compute"].argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
         self.fn["compute_xyz"].argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 3 + [C.c_int64, C.c_void_p, C.c_double, C.c_double] + [C.c_void_p] * 4
         self.fn["compute_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_double, C.c_double]
@@ -69,18 +59,18 @@ class ResLib:
             raise ValueError("%d contexts, %d windows" % (len(ctxs), len(windows)))
         B = len(ctxs)
         handles = [c.res_handle() for c in ctxs]
-        xyz0 = bool(B) and _is_xyz(windows[0])          # the batch's kind: the library refuses a context holding the other
+        xyz0 = bool(B) and window_field(windows[0], "xyz") is not None          # the batch's kind: the library refuses a context holding the other
         items = (VioResBatchItem * max(B, 1))()
         keep, res = [], []
         want = set(outputs)
         for i, (c, w) in enumerate(zip(ctxs, windows)):
-            g = _getter(w)
+            g = lambda k: window_field(w, k)
             n = c.n
             lm = np.ascontiguousarray(g("lm"), dtype=np.int32)
             m = lm.size
             if m != c.m:
                 raise VioError(-1, "vio_res_compute_batch", "(window %d has %d edges, its context %d)" % (i, m, c.m))
-            if _is_xyz(w):
+            if g("xyz") is not None:
                 arrs = [lm, None, np.ascontiguousarray(g("frame"), dtype=np.int32), None, _f64(g("pts"), (m, 2))]
             else:
                 arrs = [lm, np.ascontiguousarray(g("host"), dtype=np.int32), np.ascontiguousarray(g("target"), dtype=np.int32),
@@ -126,25 +116,17 @@ class VioResBatchItem(C.Structure):
                 ("lm_flags", C.c_void_p), ("summary", C.c_void_p)]
 
 
-def _getter(w):
-    return (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
-
-
-def _is_xyz(w):
-    return (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
-
-
 def _pre_array(pres):
     """The ten pointers of vio_set_imu_all (None: no edge) and the structs they point to (kept alive by the caller)."""
     pres = list(pres)
     if len(pres) != WINDOW_SIZE:
         raise ValueError("the window's %d IMU edges (None for a missing one), got %d" % (WINDOW_SIZE, len(pres)))
-    keep = [None if p is None else (p if isinstance(p, VioPreint) else VioPreint.from_dict(p)) for p in pres]
-    arr = (C.POINTER(VioPreint) * WINDOW_SIZE)(*[C.pointer(p) if p is not None else C.POINTER(VioPreint)() for p in keep])
-    return arr, keep
+    return preint_pointers(pres)
 
 
-class ResHandle:
+class ResHandle(CompanionHandle):
+    PREFIX = "vio_res_"
+
     def __init__(self, lib, ctx):
         self.lib = lib
         self.ctx = ctx
@@ -153,21 +135,6 @@ class ResHandle:
         if st != 0:
             raise VioError(st, "vio_res_create")
 
-    def close(self):
-        if self.h:
-            self.lib.fn["destroy"](self.h)
-            self.h = C.c_void_p()
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-    def _ck(self, st, where):
-        if st != 0:
-            msg = self.lib.fn["last_error"](self.h)
-            raise VioError(st, "vio_res_" + where, (msg or b"").decode(errors="replace"))
 
     def set_config(self, cfg):
         """vio_res_set_config: the configuration the context now runs with (after VioContext.set_config)."""
@@ -178,8 +145,8 @@ class ResHandle:
         library (default: the context's).  outputs: which outputs to ask for (the others are passed as NULL and come back None).
         out: optional dict of caller-owned arrays to fill ("obs" (m, 4), "lm" (n, 3), "flags" (n,) uint8); they are left untouched
         when the call fails.  imu=False passes pre = NULL (the IMU terms and chi2 come back NaN)."""
-        g = (lambda k: w[k]) if isinstance(w, dict) else (lambda k: getattr(w, k))
-        xyz = (w.get("xyz") if isinstance(w, dict) else getattr(w, "xyz", None)) is not None
+        g = lambda k: window_field(w, k)
+        xyz = g("xyz") is not None
         n = self.ctx.n if n is None else int(n)
         lm = np.ascontiguousarray(g("lm"), dtype=np.int32)
         m = lm.size
