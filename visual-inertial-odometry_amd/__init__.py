@@ -5,7 +5,7 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, imu, init, marg, residuals, sharded, stream, synth
+from . import batch_stream, capi, covariance, imu, init, marg, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
@@ -13,6 +13,7 @@ from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_
 from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
+from .sfm import SfmHandle, SfmLib, sfm_items_to_init_items
 from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
 PKG_DIR = os.path.dirname(os.path.abspath(__file__))
@@ -23,6 +24,7 @@ RES_LIB = os.path.join(PKG_DIR, "csrc", "libvio_res_hip.so")     # include/vio_r
 IMU_LIB = os.path.join(PKG_DIR, "csrc", "libvio_imu_hip.so")     # include/vio_imu.h, linked against libvio_hip.so
 MARG_LIB = os.path.join(PKG_DIR, "csrc", "libvio_marg_hip.so")   # include/vio_marg.h, linked against libvio_hip.so
 INIT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_init_hip.so")   # include/vio_init.h, linked against libvio_hip.so
+SFM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_sfm_hip.so")     # include/vio_sfm.h; calls nothing of libvio_hip.so (linked like the others)
 
 _hip = None
 
@@ -98,3 +100,8 @@ def load_marg():
 def load_init():
     """Load the visual-inertial alignment library (csrc/libvio_init_hip.so)."""
     return _load_companion("init", InitLib, INIT_LIB)
+
+
+def load_sfm():
+    """Load the structure-from-motion library (csrc/libvio_sfm_hip.so)."""
+    return _load_companion("sfm", SfmLib, SFM_LIB)

@@ -382,7 +382,11 @@ class StreamDriver:
         then multiplied by s.  On failure the oldest frame leaves without a prior (the INITIAL slideWindow) and the next frame comes
         in; max_tries failures raise.  self.init_tries, self.init_frame (the newest frame at success) and self.init_result record it.
         An `aligner` entry (a callable(items, intervals, tic, g_norm, noise) returning the dicts InitHandle.initialize_batch returns)
-        replaces the library (the CPU tests pass the numpy restatement).  None: the ground-truth start below."""
+        replaces the library (the CPU tests pass the numpy restatement).  An `sfm` entry makes the camera poses come from the
+        window's feature tracks instead of visual_trajectory (scale, rot_noise, pos_noise and seed are then unused): True runs
+        relativePose + GlobalSFM::construct through the SfM library (include/vio_sfm.h), a callable(items) returning the dicts
+        SfmHandle.sfm_batch returns replaces it; a window whose SfM fails counts as a failed try with status sfm.TRY_FAILED_SFM + |SfM status| and the
+        SfM status under `sfm_status` (self.init_sfm_status records every try's SfM status).  None: the ground-truth start below."""
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -436,17 +440,57 @@ class StreamDriver:
             cfg = dict(scale=1.0, rot_noise=0.0, pos_noise=0.0, max_tries=10, seed=0)
             cfg.update(self.initialize)
             self.initialize = cfg
-            self._init_h = self._init_imu = None
+            self._init_h = self._init_imu = self._sfm_h = None
+            self.init_sfm_status = []
 
     # ---- initialisation (initialize) ------------------------------------------------------------------
     def init_request(self):
         """The current window as an alignment item (visual_trajectory's R / T, the zero-bias records) and its raw intervals."""
         c = self.initialize
+        if c.get("sfm"):            # R / T are filled in by init_align's SfM call
+            from .sfm import item_from_tracks
+            return dict(sfm_item=item_from_tracks(self.tracks, self.frames)[0], owner=self, R=None, T=None, pre=list(self.preint),
+                        is_key=None), list(self.intervals)
         R, T = visual_trajectory(self.s, self.frames, 0, c["scale"], c["rot_noise"], c["pos_noise"], c["seed"] + self.init_tries)
         return dict(R=R, T=T, pre=list(self.preint), is_key=None), list(self.intervals)
 
+    def init_sfm(self, items):
+        """One SfM call for every item made with `sfm`: fills in R = Q RIC^T and T (estimator.cpp:316-318) where it succeeds.
+        Returns each item's SfM status."""
+        from .sfm import sfm_items_to_init_items
+        c = self.initialize
+        if callable(c["sfm"]):
+            res = c["sfm"]([it["sfm_item"] for it in items])
+        else:
+            if self._sfm_h is None:
+                from . import load_sfm
+                self._sfm_h = load_sfm().create(device=self.ctx.cfg.device)
+            res = self._sfm_h.sfm_batch([it["sfm_item"] for it in items])
+        for it, r in zip(items, res):
+            ric = synth.quat_to_rot(it["owner"].ext[3:7])
+            done = sfm_items_to_init_items([r], ric, [it["pre"]])[0]
+            if done is not None:
+                it["R"], it["T"] = done["R"], done["T"]
+        return [int(r["status"]) for r in res]
+
     def init_align(self, items, intervals):
         """The alignment of `items` on this driver's backend: the library (one handle pair per driver), or the `aligner` given."""
+        c = self.initialize
+        if c.get("sfm"):
+            from .sfm import TRY_FAILED_SFM
+            sts = self.init_sfm(items)
+            for it, st in zip(items, sts):
+                it["owner"].init_sfm_status.append(st)
+            ok = [i for i, st in enumerate(sts) if st == 0]
+            out = [dict(status=TRY_FAILED_SFM + abs(st), sfm_status=st) for st in sts]       # an SfM failure: a failed try
+            if ok:
+                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "owner")} for i in ok]
+                for i, r in zip(ok, self._init_align(plain, [intervals[i] for i in ok])):
+                    out[i] = r
+            return out
+        return self._init_align(items, intervals)
+
+    def _init_align(self, items, intervals):
         c = self.initialize
         if c.get("aligner") is not None:
             return c["aligner"](items, intervals, self.ext[0:3].copy(), self.g_norm, self.noise)
