@@ -47,7 +47,7 @@
             const double dep = pc_j[2];
             r[0] = pc_j[0] / dep - a.pts_j[2 * e];
             r[1] = pc_j[1] / dep - a.pts_j[2 * e + 1];
-            robust_info2(a.loss_type, a.loss_delta, s, r, W);
+            d_robust_info2(a.loss_type, a.loss_delta, s, r, W);
             const double red[6] = {1. / dep, 0, -pc_j[0] / (dep * dep), 0, 1. / dep, -pc_j[1] / (dep * dep)};
             double A[9], ARi[9], T[9], M[9], Ji[12], Jj[12], Je[12];
             double RjT[9];
@@ -64,37 +64,37 @@
             for (int r2 = 0; r2 < 2; ++r2)
                 Jl[r2] = (red[3 * r2] * v[0] + red[3 * r2 + 1] * v[1] + red[3 * r2 + 2] * v[2]) * -1.0 / (lam * lam);
             // J_pose_i = reduce [ric^T Rj^T | -ric^T Rj^T Ri hat(pb_i)]
-            reduce_mul(red, A, Ji, 0);
-            skew3(pb_i, M);
+            d_reduce_mul<6>(red, A, Ji, 0);
+            d_skew(pb_i, M);
             double Mm[9];
             d_m3_mul(ARi, M, Mm);
             for (int k = 0; k < 9; ++k) Mm[k] = -Mm[k];
-            reduce_mul(red, Mm, Ji, 3);
+            d_reduce_mul<6>(red, Mm, Ji, 3);
             // J_pose_j = reduce [-ric^T Rj^T | ric^T hat(pb_j)]
             for (int k = 0; k < 9; ++k) M[k] = -A[k];
-            reduce_mul(red, M, Jj, 0);
-            skew3(pb_j, M);
+            d_reduce_mul<6>(red, M, Jj, 0);
+            d_skew(pb_j, M);
             d_m3_mul(ricT, M, Mm);
-            reduce_mul(red, Mm, Jj, 3);
+            d_reduce_mul<6>(red, Mm, Jj, 3);
             // J_ext = reduce [ric^T (Rj^T Ri - I) | -T hat(pc_i) + hat(T pc_i) + hat(ric^T (Rj^T (Ri tic + Pi - Pj) - tic))]
             if (a.ext_free) {
                 d_m3_mul(RjT, Ri, M);
                 M[0] -= 1; M[4] -= 1; M[8] -= 1;
                 d_m3_mul(ricT, M, Mm);
-                reduce_mul(red, Mm, Je, 0);
+                d_reduce_mul<6>(red, Mm, Je, 0);
                 double S1[9], t1[9], v2[3], S2[9], u[3], ww[3], x[3], S3[9];
-                skew3(pc_i, S1);
+                d_skew(pc_i, S1);
                 d_m3_mul(T, S1, t1);
                 d_m3_vec(T, pc_i, v2);
-                skew3(v2, S2);
+                d_skew(v2, S2);
                 d_m3_vec(Ri, tic, u);
                 for (int k = 0; k < 3; ++k) u[k] = u[k] + Pi[k] - Pj[k];
                 d_m3_tvec(Rj, u, ww);
                 for (int k = 0; k < 3; ++k) ww[k] -= tic[k];
                 d_m3_tvec(ric, ww, x);
-                skew3(x, S3);
+                d_skew(x, S3);
                 for (int k = 0; k < 9; ++k) M[k] = -t1[k] + S2[k] + S3[k];
-                reduce_mul(red, M, Je, 3);
+                d_reduce_mul<6>(red, M, Je, 3);
             }
             // h_l += J_l^T W J_l;  w_l += (J_l^T W) [J_i | J_j | J_ext] on the host / target / extrinsic blocks
             const double t0 = Jl[0] * W[0] + Jl[1] * W[2], t1 = Jl[0] * W[1] + Jl[1] * W[3];
@@ -117,7 +117,7 @@
             const double dep = pc[2];
             r[0] = pc[0] / dep - a.pts_j[2 * e];
             r[1] = pc[1] / dep - a.pts_j[2 * e + 1];
-            robust_info2(a.loss_type, a.loss_delta, s, r, W);
+            d_robust_info2(a.loss_type, a.loss_delta, s, r, W);
             const double red[6] = {1. / dep, 0, -pc[0] / (dep * dep), 0, 1. / dep, -pc[1] / (dep * dep)};
             double RT[9], M[9], Mm[9], Jp[12], Jf[6];
 #pragma unroll
@@ -127,11 +127,11 @@
             // J_pose = reduce [ric^T (-Ri^T) | ric^T hat(pts_imu)],  J_feature = reduce ric^T Ri^T
             d_m3_mul(ricT, RT, Mm);
             for (int k = 0; k < 9; ++k) M[k] = -Mm[k];
-            reduce_mul(red, M, Jp, 0);
-            skew3(pim, M);
+            d_reduce_mul<6>(red, M, Jp, 0);
+            d_skew(pim, M);
             double Mh[9];
             d_m3_mul(ricT, M, Mh);
-            reduce_mul(red, Mh, Jp, 3);
+            d_reduce_mul<6>(red, Mh, Jp, 3);
             for (int r2 = 0; r2 < 2; ++r2)
                 for (int c = 0; c < 3; ++c)
                     Jf[3 * r2 + c] = red[3 * r2] * Mm[c] + red[3 * r2 + 1] * Mm[3 + c] + red[3 * r2 + 2] * Mm[6 + c];

@@ -5,8 +5,9 @@
 // (k_cov_pose_batch, k_cov_landmarks_batch: the same bodies, vio_cov_*_body.inc, one window per workgroup).
 //   k_cov_pose          one workgroup: the reduced H_pp_schur (fixed variables removed) as a packed lower triangle in LDS, inverted
 //                       in place by the symmetric sweep; Sigma written once as a full 171 x 171 and as the 72 x 72 camera block.
-//   k_cov_landmarks<D>  one lane per landmark: its observations' reprojection Jacobians and robust weights recomputed, h_l and w_l
-//                       accumulated in a fixed order, then the quadratic form against Sigma_cc staged in LDS.
+//   k_cov_landmarks<D>  one lane per landmark: its observations' reprojection Jacobians and robust weights (d_robust_info2 of
+//                       vio_device_math.h, which vio_marg.hip includes too) recomputed, h_l and w_l accumulated in a fixed order,
+//                       then the quadratic form against Sigma_cc staged in LDS.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -102,39 +103,6 @@ struct CovLmArgs {
 template <int D> struct LmNT;
 template <> struct LmNT<1> { static constexpr int v = 128; };     // LDS: Sigma_cc 41.5 KB + w 72 x 128 x 8 = 73.7 KB
 template <> struct LmNT<3> { static constexpr int v = 64; };      // LDS: Sigma_cc 41.5 KB + W 216 x 64 x 8 = 110.6 KB
-
-DEV void skew3(const double *v, double *S) {
-    S[0] = 0;     S[1] = -v[2]; S[2] = v[1];
-    S[3] = v[2];  S[4] = 0;     S[5] = -v[0];
-    S[6] = -v[1]; S[7] = v[0];  S[8] = 0;
-}
-
-// Edge::RobustInfo (edge.cc:48-74) for information s^2 I2: W row-major 2x2; type 0 = no loss object.  The same expression as
-// k_linearize's, so that the landmark terms carry the weights H_pp_schur was formed with.  (For Huber beyond delta the test
-// rho' + 2 rho'' e2 > 0 is exactly zero in exact arithmetic and its outcome is the rounding of the residual: DESIGN.md section 10.)
-DEV void robust_info2(int type, double delta, double s, const double *r, double *W) {
-    const double info = s * s;
-    if (type == 0) { W[0] = info; W[1] = 0; W[2] = 0; W[3] = info; return; }
-    const double e2 = r[0] * (info * r[0]) + r[1] * (info * r[1]);
-    double r0, r1, r2;
-    d_loss(type, delta, e2, r0, r1, r2);
-    const double w0 = s * r[0], w1 = s * r[1];
-    double ri[4] = {r1, 0, 0, r1};
-    if (r1 + 2 * r2 * e2 > 0.) {
-        const double c = 2 * r2;
-        ri[0] += c * w0 * w0; ri[1] += c * w0 * w1; ri[2] += c * w1 * w0; ri[3] += c * w1 * w1;
-    }
-    W[0] = ri[0] * info; W[1] = ri[1] * info; W[2] = ri[2] * info; W[3] = ri[3] * info;
-}
-
-// rows of reduce (2x3) times a 3x3 M: out 2x3, written into the 6 columns [c0, c0 + 3) of a 2 x 6 row-major J
-DEV void reduce_mul(const double *red, const double *M, double *J, int c0) {
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c)
-            J[6 * r + c0 + c] = red[3 * r] * M[c] + red[3 * r + 1] * M[3 + c] + red[3 * r + 2] * M[6 + c];
-}
 
 template <int D>
 __global__ void __launch_bounds__(LmNT<D>::v) k_cov_landmarks(CovLmArgs a) {

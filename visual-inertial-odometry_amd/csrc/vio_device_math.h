@@ -91,6 +91,12 @@ DEV void d_pose_plus(const double *p, const double *d, double *o) {
     o[3] = q.x; o[4] = q.y; o[5] = q.z; o[6] = q.w;
 }
 
+DEV void d_skew(const double *v, double *S) {
+    S[0] = 0;     S[1] = -v[2]; S[2] = v[1];
+    S[3] = v[2];  S[4] = 0;     S[5] = -v[0];
+    S[6] = -v[1]; S[7] = v[0];  S[8] = 0;
+}
+
 // EdgeReprojection::ComputeResidual (edge_reprojection.cc:18-37), the residual alone: Ri / Rj the rotations of the host and target
 // poses, ric / tic the extrinsic's, lam the inverse depth, p_i / p_j the normalised observations.  r (2); returns the point's depth in
 // the target camera.  (The same expressions as k_cov_landmarks's, which fuses them with the Jacobians.)
@@ -139,6 +145,36 @@ DEV void d_loss(int type, double delta, double e2, double &r0, double &r1, doubl
         if (e <= delta) { const double aux = e2 / d2, u = 1. - aux; r0 = d2 * (1. - u * u * u) / 3.; r1 = u * u; r2 = -2. * u / d2; }
         else { r0 = d2 / 3.; r1 = 0; r2 = 0; }
     } else { r0 = e2; r1 = 1; r2 = 0; }
+}
+
+// Edge::RobustInfo (edge.cc:48-74) for information s^2 I2: W row-major 2x2; type 0 = no loss object.  Returns rho'.  The expression
+// k_linearize evaluates, so that the landmark terms of the covariance and the marginalisation library carry the weights H_pp_schur
+// was formed with.  (For Huber beyond delta the test rho' + 2 rho'' e2 > 0 is exactly zero in exact arithmetic and its outcome is the
+// rounding of the residual: DESIGN.md section 10.)
+DEV double d_robust_info2(int type, double delta, double s, const double *r, double *W) {
+    const double info = s * s;
+    if (type == 0) { W[0] = info; W[1] = 0; W[2] = 0; W[3] = info; return 1.0; }
+    const double e2 = r[0] * (info * r[0]) + r[1] * (info * r[1]);
+    double r0, r1, r2;
+    d_loss(type, delta, e2, r0, r1, r2);
+    const double w0 = s * r[0], w1 = s * r[1];
+    double ri[4] = {r1, 0, 0, r1};
+    if (r1 + 2 * r2 * e2 > 0.) {
+        const double c = 2 * r2;
+        ri[0] += c * w0 * w0; ri[1] += c * w0 * w1; ri[2] += c * w1 * w0; ri[3] += c * w1 * w1;
+    }
+    W[0] = ri[0] * info; W[1] = ri[1] * info; W[2] = ri[2] * info; W[3] = ri[3] * info;
+    return r1;
+}
+
+// rows of reduce (2x3) times a 3x3 M: out 2x3, written into the columns [c0, c0 + 3) of a row-major J of leading dimension LD
+template <int LD>
+DEV void d_reduce_mul(const double *red, const double *M, double *J, int c0) {
+#pragma unroll
+    for (int r = 0; r < 2; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+            J[LD * r + c0 + c] = red[3 * r] * M[c] + red[3 * r + 1] * M[3 + c] + red[3 * r + 2] * M[6 + c];
 }
 
 // Wave-wide (64 lanes) sum of a double with DPP moves: quad swaps, half-row and row mirrors, then the two row

@@ -198,82 +198,6 @@ __global__ __launch_bounds__(128) void k_prepare(DeviceTables T) {
 }
 
 #include "vio_imu_math.h"
-#pragma clang fp contract(off)
-
-// One 3x3 block of the 15x30 Jacobian [J_pose_i | J_sb_i | J_pose_j | J_sb_j] (edge_imu.cc:74-153).
-// `blk` enumerates the 14 non-zero blocks; sJ is the 15x30 row-major LDS image (zero-initialised).
-// RiT = Qi.inverse().toRotationMatrix() (d_imu_rit)
-__device__ __forceinline__ void d_imu_rit(const ImuCommon &c, double *RiT) {
-    double qi[4] = {c.Qi_inv.x, c.Qi_inv.y, c.Qi_inv.z, c.Qi_inv.w};
-    nc_quat_to_R(qi, RiT);
-}
-__device__ void d_imu_jac_block(int blk, const double *pre, const double *G, const double *pi, const double *si,
-                                const double *pj, const double *sj, const ImuCommon &c, const double *RiT, double *sJ) {
-    const double *Jm = pre + PRE_JAC;
-    const double sum_dt = c.sum_dt;
-    double B[9];
-    int r0 = 0, c0 = 0;
-    switch (blk) {
-    case 0: r0 = O_P; c0 = 0 + O_P;       // jacobian_pose_i(O_P,O_P) = -Ri^T
-        for (int k = 0; k < 9; ++k) B[k] = -RiT[k];
-        break;
-    case 1: { r0 = O_P; c0 = 0 + O_R;     // skew(Qi^-1 (0.5 G dt^2 + Pj - Pi - Vi dt))
-        double t[3], u[3];
-        for (int k = 0; k < 3; ++k) t[k] = 0.5 * G[k] * sum_dt * sum_dt + pj[k] - pi[k] - si[k] * sum_dt;
-        nc_qrot(c.Qi_inv, t, u); d_skew(u, B);
-        break; }
-    case 2: { r0 = O_R; c0 = 0 + O_R;     // -(Qleft(Qj^-1 Qi) Qright(corrected_delta_q)).bottomRight
-        dquat a = nc_qmul(nc_qinv(c.Qj), c.Qi), b = c.cdq;
-        double La[9], Rb[9], P[9];
-        d_qleft_br(a, La); d_qright_br(b, Rb); nc_m3_mul(La, Rb, P);
-        const double va[3] = {a.x, a.y, a.z}, vb[3] = {b.x, b.y, b.z};
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -(va[i] * (-vb[j]) + P[3 * i + j]);
-        break; }
-    case 3: { r0 = O_V; c0 = 0 + O_R;     // skew(Qi^-1 (G dt + Vj - Vi))
-        double t[3], u[3];
-        for (int k = 0; k < 3; ++k) t[k] = G[k] * sum_dt + sj[k] - si[k];
-        nc_qrot(c.Qi_inv, t, u); d_skew(u, B);
-        break; }
-    case 4: r0 = O_P; c0 = 6 + 0;         // speedbias_i(O_P, V) = -Ri^T dt
-        for (int k = 0; k < 9; ++k) B[k] = -RiT[k] * sum_dt;
-        break;
-    case 5: r0 = O_P; c0 = 6 + 3;         // -dp_dba
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_P + i) + O_BA + j];
-        break;
-    case 6: r0 = O_P; c0 = 6 + 6;         // -dp_dbg
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_P + i) + O_BG + j];
-        break;
-    case 7: { r0 = O_R; c0 = 6 + 6;       // -Qleft(Qj^-1 Qi delta_q).bottomRight * dq_dbg  (delta_q, not corrected: edge_imu.cc:107-109)
-        double L[9], nL[9], D[9];
-        d_qleft_br(nc_qmul(nc_qmul(nc_qinv(c.Qj), c.Qi), c.dq), L);
-        for (int k = 0; k < 9; ++k) nL[k] = -L[k];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) D[3 * i + j] = Jm[15 * (O_R + i) + O_BG + j];
-        nc_m3_mul(nL, D, B);
-        break; }
-    case 8: r0 = O_V; c0 = 6 + 0;         // -Ri^T
-        for (int k = 0; k < 9; ++k) B[k] = -RiT[k];
-        break;
-    case 9: r0 = O_V; c0 = 6 + 3;         // -dv_dba
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_V + i) + O_BA + j];
-        break;
-    case 10: r0 = O_V; c0 = 6 + 6;        // -dv_dbg
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_V + i) + O_BG + j];
-        break;
-    case 11: r0 = O_P; c0 = 15 + O_P;     // pose_j(O_P,O_P) = Ri^T
-        for (int k = 0; k < 9; ++k) B[k] = RiT[k];
-        break;
-    case 12: { r0 = O_R; c0 = 15 + O_R;   // Qleft(corrected_dq^-1 Qi^-1 Qj).bottomRight
-        d_qleft_br(nc_qmul(nc_qmul(nc_qinv(c.cdq), c.Qi_inv), c.Qj), B);
-        break; }
-    case 13: r0 = O_V; c0 = 21 + 0;       // speedbias_j(O_V,V) = Ri^T
-        for (int k = 0; k < 9; ++k) B[k] = RiT[k];
-        break;
-    default: return;
-    }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) sJ[30 * (r0 + i) + c0 + j] = B[3 * i + j];
-}
-
-#pragma clang fp contract(fast)
 // T = J^T Info J (30x30), g = J^T Info r, chi = r^T Info r  for IMU edge k
 // (Round 6 tried the inputs staged in LDS and the sixteen tasks one per wave on uniform branches: bit-identical, the IMU workgroup 19-20 k ->
 //  16.4 k cycles — and k_linearize at 20 000 landmarks 13.5 -> 14.2 us, the GN iteration 45.7 -> 46.4 us (tools/ab.py, profiles/r06n_imu_item_ab.txt):

@@ -1,8 +1,9 @@
 // vio_marg.hip — libvio_marg_hip.so: Problem::Marginalize for many windows in one call (include/vio_marg.h).
 //
 //   k_marg_build  one workgroup per window: H_marg (171 x 171) and b_marg of the marginalisation graph (problem.cc:617-713)
-//                 phase 1  thread per landmark hosted in frame 0: its edges' residuals, Jacobians and robust weights (the
-//                          helpers k_cov_landmarks uses), h_l, b_l and the coupling row w_l; the IMU edge 0 -> 1 in LDS
+//                 phase 1  thread per landmark hosted in frame 0: its edges' residuals, Jacobians and robust weights
+//                          (d_robust_info2, k_cov_landmarks's), h_l, b_l and the coupling row w_l; the IMU edge 0 -> 1 in LDS
+//                          (d_imu_jac_block and d_imu_residual, the solver's)
 //                 phase 2  thread per entry of the lower triangle: the landmark sums in landmark order, then the IMU block and
 //                          the old prior; mirrored into the upper triangle
 //   k_marg_tail   one workgroup per window: the dense tail of problem.cc:717-779 — the 15 marginalised rows moved to the end,
@@ -10,8 +11,8 @@
 //                 by a parallel cyclic Jacobi solver (packed lower triangle in LDS, eigenvectors in HBM scratch), Jt_inv, err and
 //                 H = J^T J
 // No atomics: every sum has a fixed order, so repeated calls are bitwise identical and a window's result does not depend on its
-// batch.  The library calls no function of libvio_hip; it shares its device helpers (vio_device_math.h, vio_imu_math.h) and
-// host_dense.cpp's inverse15 at build time.
+// batch.  The library calls no function of libvio_hip; it includes its device code (vio_device_math.h: rotations, 3 x 3 products,
+// loss and robust weight; vio_imu_math.h: the IMU edge) and compiles host_dense.cpp's inverse15 a second time.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -60,105 +61,11 @@ constexpr int CD_W = VIO_CAM_DIM;      // 72
 // ---------------------------------------------------------------------------------------------------------
 // device helpers
 // ---------------------------------------------------------------------------------------------------------
-#include "vio_imu_math.h"
-#pragma clang fp contract(off)
-// The 14 non-zero 3 x 3 blocks of the IMU edge's 15 x 30 Jacobian [J_pose_i | J_sb_i | J_pose_j | J_sb_j] (edge_imu.cc:74-153), as
-// vio_kernels.hip's d_imu_jac_block forms them (same expressions, no contraction).
-static __device__ void mg_imu_jac_block(int blk, const double *pre, const double *G, const double *pi, const double *si, const double *pj,
-                                 const double *sj, const ImuCommon &c, const double *RiT, double *sJ) {
-    const double *Jm = pre + PRE_JAC;
-    const double sum_dt = c.sum_dt;
-    double B[9];
-    int r0 = 0, c0 = 0;
-    switch (blk) {
-    case 0: r0 = O_P; c0 = 0 + O_P;
-        for (int k = 0; k < 9; ++k) B[k] = -RiT[k];
-        break;
-    case 1: { r0 = O_P; c0 = 0 + O_R;
-        double t[3], u[3];
-        for (int k = 0; k < 3; ++k) t[k] = 0.5 * G[k] * sum_dt * sum_dt + pj[k] - pi[k] - si[k] * sum_dt;
-        nc_qrot(c.Qi_inv, t, u); d_skew(u, B);
-        break; }
-    case 2: { r0 = O_R; c0 = 0 + O_R;
-        dquat a = nc_qmul(nc_qinv(c.Qj), c.Qi), b = c.cdq;
-        double La[9], Rb[9], P[9];
-        d_qleft_br(a, La); d_qright_br(b, Rb); nc_m3_mul(La, Rb, P);
-        const double va[3] = {a.x, a.y, a.z}, vb[3] = {b.x, b.y, b.z};
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -(va[i] * (-vb[j]) + P[3 * i + j]);
-        break; }
-    case 3: { r0 = O_V; c0 = 0 + O_R;
-        double t[3], u[3];
-        for (int k = 0; k < 3; ++k) t[k] = G[k] * sum_dt + sj[k] - si[k];
-        nc_qrot(c.Qi_inv, t, u); d_skew(u, B);
-        break; }
-    case 4: r0 = O_P; c0 = 6 + 0;
-        for (int k = 0; k < 9; ++k) B[k] = -RiT[k] * sum_dt;
-        break;
-    case 5: r0 = O_P; c0 = 6 + 3;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_P + i) + O_BA + j];
-        break;
-    case 6: r0 = O_P; c0 = 6 + 6;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_P + i) + O_BG + j];
-        break;
-    case 7: { r0 = O_R; c0 = 6 + 6;
-        double L[9], nL[9], D[9];
-        d_qleft_br(nc_qmul(nc_qmul(nc_qinv(c.Qj), c.Qi), c.dq), L);
-        for (int k = 0; k < 9; ++k) nL[k] = -L[k];
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) D[3 * i + j] = Jm[15 * (O_R + i) + O_BG + j];
-        nc_m3_mul(nL, D, B);
-        break; }
-    case 8: r0 = O_V; c0 = 6 + 0;
-        for (int k = 0; k < 9; ++k) B[k] = -RiT[k];
-        break;
-    case 9: r0 = O_V; c0 = 6 + 3;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_V + i) + O_BA + j];
-        break;
-    case 10: r0 = O_V; c0 = 6 + 6;
-        for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) B[3 * i + j] = -Jm[15 * (O_V + i) + O_BG + j];
-        break;
-    case 11: r0 = O_P; c0 = 15 + O_P;
-        for (int k = 0; k < 9; ++k) B[k] = RiT[k];
-        break;
-    case 12: { r0 = O_R; c0 = 15 + O_R;
-        d_qleft_br(nc_qmul(nc_qmul(nc_qinv(c.cdq), c.Qi_inv), c.Qj), B);
-        break; }
-    case 13: r0 = O_V; c0 = 21 + 0;
-        for (int k = 0; k < 9; ++k) B[k] = RiT[k];
-        break;
-    default: return;
-    }
-    for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) sJ[30 * (r0 + i) + c0 + j] = B[3 * i + j];
-}
-#pragma clang fp contract(fast)
+#include "vio_imu_math.h"       // (here, not with the other headers: its no-contraction region ends where the code below begins)
 
 namespace {
 __device__ __forceinline__ int imu_vblock(int a) { return a < 6 ? 0 : (a < 15 ? 1 : (a < 21 ? 2 : 3)); }
 
-// Edge::RobustInfo with information s^2 I (edge.cc:48-74), as k_cov_landmarks forms it; rho1 (drho) is returned for b
-__device__ __forceinline__ double mg_robust_info2(int type, double delta, double s, const double *r, double *W) {
-    const double info = s * s;
-    if (type == 0) { W[0] = info; W[1] = 0; W[2] = 0; W[3] = info; return 1.0; }
-    const double e2 = r[0] * (info * r[0]) + r[1] * (info * r[1]);
-    double r0, r1, r2;
-    d_loss(type, delta, e2, r0, r1, r2);
-    const double w0 = s * r[0], w1 = s * r[1];
-    double ri[4] = {r1, 0, 0, r1};
-    if (r1 + 2 * r2 * e2 > 0.) {
-        const double c = 2 * r2;
-        ri[0] += c * w0 * w0; ri[1] += c * w0 * w1; ri[2] += c * w1 * w0; ri[3] += c * w1 * w1;
-    }
-    W[0] = ri[0] * info; W[1] = ri[1] * info; W[2] = ri[2] * info; W[3] = ri[3] * info;
-    return r1;
-}
-__device__ __forceinline__ void mg_reduce_mul(const double *red, const double *M, double *J, int c0) {     // 2 x 3 times 3 x 3 into J (2 x 18)
-#pragma unroll
-    for (int r = 0; r < 2; ++r)
-#pragma unroll
-        for (int c = 0; c < 3; ++c) J[18 * r + c0 + c] = red[3 * r] * M[c] + red[3 * r + 1] * M[3 + c] + red[3 * r + 2] * M[6 + c];
-}
-__device__ __forceinline__ void mg_skew(const double *v, double *S) {
-    S[0] = 0; S[1] = -v[2]; S[2] = v[1]; S[3] = v[2]; S[4] = 0; S[5] = -v[0]; S[6] = -v[1]; S[7] = v[0]; S[8] = 0;
-}
 // camera index (0 .. 71: ext, then 6 per pose) of a pose-ordering index, or -1 for a speed-bias variable
 __device__ __forceinline__ int mg_cam(int i) {
     if (i < 6) return i;
@@ -210,9 +117,8 @@ __global__ void __launch_bounds__(BUILD_NT) k_marg_build(const MargWin *__restri
                 ImuCommon c;
                 double RiT[9];
                 d_imu_common(pre, pi, si, pj, c);
-                double qi[4] = {c.Qi_inv.x, c.Qi_inv.y, c.Qi_inv.z, c.Qi_inv.w};
-                nc_quat_to_R(qi, RiT);
-                if (tid < 14) mg_imu_jac_block(tid, pre, cfg.gravity, pi, si, pj, sj, c, RiT, sJ);
+                d_imu_rit(c, RiT);
+                if (tid < 14) d_imu_jac_block(tid, pre, cfg.gravity, pi, si, pj, sj, c, RiT, sJ);
                 else if (tid == 14) {
                     double r[15];
                     d_imu_residual(pre, cfg.gravity, pi, si, pj, sj, c, r);
@@ -250,7 +156,9 @@ __global__ void __launch_bounds__(BUILD_NT) k_marg_build(const MargWin *__restri
             }
         }
 
-        // phase 1: thread per landmark; EdgeReprojection (edge_reprojection.cc:18-109) with the host in frame 0
+        // phase 1: thread per landmark; EdgeReprojection (edge_reprojection.cc:18-109) with the host in frame 0.  The statements are
+        // those of vio_cov_landmarks_body.inc, the blocks laid into one 2 x 18 record.  (Both kernels calling one inlined function
+        // was tried: the compiler then contracted fewer products in this kernel, DESIGN.md section 14, so each keeps its own text.)
         const int32_t *eoff = ints + W.i_eoff, *tgt = ints + W.i_tgt;
         const double *invd = dbl + W.o_invd, *ptsi = dbl + W.o_ptsi, *ptsj = dbl + W.o_ptsj;
         const double *ric = sR + 9 * NF, *tic = ext;
@@ -281,7 +189,7 @@ __global__ void __launch_bounds__(BUILD_NT) k_marg_build(const MargWin *__restri
                 double r[2], Wm[4];
                 r[0] = pc_j[0] / dep - ptsj[2 * e];
                 r[1] = pc_j[1] / dep - ptsj[2 * e + 1];
-                const double drho = mg_robust_info2(cfg.loss_type, cfg.loss_delta, s, r, Wm);
+                const double drho = d_robust_info2(cfg.loss_type, cfg.loss_delta, s, r, Wm);
                 const double red[6] = {1. / dep, 0, -pc_j[0] / (dep * dep), 0, 1. / dep, -pc_j[1] / (dep * dep)};
                 double A[9], ARi[9], T[9], M[9], Mm[9], J[36];
                 d_m3_mul(ricT, RjT, A);
@@ -292,36 +200,36 @@ __global__ void __launch_bounds__(BUILD_NT) k_marg_build(const MargWin *__restri
                 double Jl[2];
                 for (int r2 = 0; r2 < 2; ++r2) Jl[r2] = (red[3 * r2] * v[0] + red[3 * r2 + 1] * v[1] + red[3 * r2 + 2] * v[2]) * -1.0 / (lam * lam);
                 // host pose (columns 6..11): reduce [ric^T Rj^T | -ric^T Rj^T Ri hat(pb_i)]
-                mg_reduce_mul(red, A, J, 6);
-                mg_skew(pb_i, M);
+                d_reduce_mul<18>(red, A, J, 6);
+                d_skew(pb_i, M);
                 d_m3_mul(ARi, M, Mm);
                 for (int k = 0; k < 9; ++k) Mm[k] = -Mm[k];
-                mg_reduce_mul(red, Mm, J, 9);
+                d_reduce_mul<18>(red, Mm, J, 9);
                 // target pose (12..17): reduce [-ric^T Rj^T | ric^T hat(pb_j)]
                 for (int k = 0; k < 9; ++k) M[k] = -A[k];
-                mg_reduce_mul(red, M, J, 12);
-                mg_skew(pb_j, M);
+                d_reduce_mul<18>(red, M, J, 12);
+                d_skew(pb_j, M);
                 d_m3_mul(ricT, M, Mm);
-                mg_reduce_mul(red, Mm, J, 15);
+                d_reduce_mul<18>(red, Mm, J, 15);
                 // extrinsic (0..5), always a variable of Marginalize's graph
                 d_m3_mul(RjT, Ri, M);
                 M[0] -= 1; M[4] -= 1; M[8] -= 1;
                 d_m3_mul(ricT, M, Mm);
-                mg_reduce_mul(red, Mm, J, 0);
+                d_reduce_mul<18>(red, Mm, J, 0);
                 {
                     double S1[9], t1[9], v2[3], S2[9], u[3], ww[3], x[3], S3[9];
-                    mg_skew(pc_i, S1);
+                    d_skew(pc_i, S1);
                     d_m3_mul(T, S1, t1);
                     d_m3_vec(T, pc_i, v2);
-                    mg_skew(v2, S2);
+                    d_skew(v2, S2);
                     d_m3_vec(Ri, tic, u);
                     for (int k = 0; k < 3; ++k) u[k] = u[k] + Pi[k] - Pj[k];
                     d_m3_tvec(Rj, u, ww);
                     for (int k = 0; k < 3; ++k) ww[k] -= tic[k];
                     d_m3_tvec(ric, ww, x);
-                    mg_skew(x, S3);
+                    d_skew(x, S3);
                     for (int k = 0; k < 9; ++k) M[k] = -t1[k] + S2[k] + S3[k];
-                    mg_reduce_mul(red, M, J, 3);
+                    d_reduce_mul<18>(red, M, J, 3);
                 }
                 double *er = scr + W.s_edge + (size_t)e * EREC;
                 const double c0 = drho * (info * r[0]), c1 = drho * (info * r[1]);
