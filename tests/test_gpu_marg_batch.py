@@ -99,6 +99,68 @@ def test_no_prior_and_no_imu_edge(vio, hip_lib, oracle_lib, marg_lib):
     check_against(got, ref, *oracle_input(oracle_lib, vio.MARG_OLD, w, kw), 0)
 
 
+def empty_graph_window(vio, hip_lib):
+    """MargOldFrame's smallest graph: no landmark and no observation, IMU edge 0 and a prior (that of make_window(60, seed=21), whose
+    states the window keeps)."""
+    w = with_prior(vio, hip_lib, vio.synth.make_window(60, seed=21), {})
+    z = np.zeros(0, dtype=np.int32)
+    return vio.synth.Window(**dict(w.__dict__, inv_depth=np.zeros(0), lm=z, host=z, target=z, pts_i=np.zeros((0, 2)),
+                                   pts_j=np.zeros((0, 2)), n_landmarks=0, n_observations=0))
+
+
+def without_frame0_hosts(vio, w):
+    """w without the observations hosted in frame 0, and so without their landmarks (re-indexed as in without_huber_ambiguous):
+    MargOldFrame's graph keeps IMU edge 0 and has an empty Schur part."""
+    e = np.asarray(w.host) != 0
+    keep = np.unique(np.asarray(w.lm)[e])
+    new = -np.ones(len(w.inv_depth), dtype=np.int64)
+    new[keep] = np.arange(len(keep))
+    return vio.synth.Window(**dict(w.__dict__, inv_depth=np.asarray(w.inv_depth)[keep], lm=new[np.asarray(w.lm)[e]].astype(np.int32),
+                                   host=np.asarray(w.host)[e], target=np.asarray(w.target)[e], pts_i=np.asarray(w.pts_i)[e],
+                                   pts_j=np.asarray(w.pts_j)[e], n_landmarks=len(keep), n_observations=int(e.sum())))
+
+
+def empty_graph_cases(vio, hip_lib):
+    """Both windows carry the prior of make_window(60, seed=21) itself.  Without one MargOldFrame has nothing to compare: frame 0 then
+    hangs on IMU edge 0 alone, its 15 x 15 block is invertible, and the exact Schur complement is what the pseudo-inverse's cut
+    leaves, 0.44 at most, under an input of 4.0e15, whose rounding (2^-53 of it) is 0.44 as well.  Measured on the CPU for the
+    window without frame-0 hosts and without a prior: the oracle's own prior misses the 50-digit Schur complement by 2.6 and the
+    restatement's by 1.1, so check_against's eigenvalue comparison (2e-5) would compare two roundings.  With the prior the Schur
+    complement is 5.0e4 and the oracle's prior is within 1.2e-4 of it."""
+    w = with_prior(vio, hip_lib, vio.synth.make_window(60, seed=21), {})
+    assert (np.asarray(w.host) == 0).sum() > 0
+    no0 = without_frame0_hosts(vio, w)
+    assert 0 < no0.n_landmarks < 60 and not (np.asarray(no0.host) == 0).any() and no0.lm.max() == no0.n_landmarks - 1
+    return {"no_landmarks": empty_graph_window(vio, hip_lib), "no_frame0_hosts": no0}
+
+
+@pytest.mark.parametrize("case", ["no_landmarks", "no_frame0_hosts"])
+def test_marg_old_with_an_empty_schur_part(vio, hip_lib, oracle_lib, marg_lib, case):
+    """MARG_OLD of a window with n = 0, m = 0 (IMU edge 0 and a prior only) and of one in which no landmark is hosted in frame 0,
+    against vio_marginalize on a context loaded with the same arrays (or, should the context refuse a window without landmarks,
+    against the restatement's tail on the oracle's dense input), and bitwise the same inside a batch of ordinary windows."""
+    w = empty_graph_cases(vio, hip_lib)[case]
+    Hin, bin_ = oracle_input(oracle_lib, vio.MARG_OLD, w, {})
+    try:
+        ref = reference(hip_lib, vio.MARG_OLD, w, {})
+    except vio.VioError:
+        assert case == "no_landmarks"
+        ref = mr.tail(Hin, bin_, 0)[0]
+    mh = marg_lib.create()
+    got = mh.compute(vio.MARG_OLD, w, w.prior)
+    assert all(np.isfinite(got[k]).all() for k in ("H", "b", "err", "jt_inv"))
+    print(case, "live rows", mh.live_rows(0), int((np.abs(ref["H"]).sum(1) > 0).sum()))
+    assert mh.live_rows(0) == int((np.abs(ref["H"]).sum(1) > 0).sum())
+    check_against(got, ref, Hin, bin_, 0)
+    jobs = mixed_jobs(vio, hip_lib, 6)
+    jobs.insert(1, (vio.MARG_OLD, w, w.prior))
+    jobs.insert(5, (vio.MARG_OLD, w, w.prior))
+    res = mh.compute_batch(jobs)
+    assert same(res[1], got) and same(res[5], got)
+    for i in (0, 2, 4, 7):
+        assert same(res[i], mh.compute(*jobs[i])), i
+
+
 def test_reference_kat(vio, hip_lib, marg_lib):
     import test_marg_kat as kat
     w = vio.synth.make_window(8, seed=3)
