@@ -5,11 +5,12 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, imu, init, marg, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, covariance, exrot, imu, init, marg, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
+from .exrot import ExrotHandle, ExrotLib
 from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
@@ -25,6 +26,7 @@ IMU_LIB = os.path.join(PKG_DIR, "csrc", "libvio_imu_hip.so")     # include/vio_i
 MARG_LIB = os.path.join(PKG_DIR, "csrc", "libvio_marg_hip.so")   # include/vio_marg.h, linked against libvio_hip.so
 INIT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_init_hip.so")   # include/vio_init.h, linked against libvio_hip.so
 SFM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_sfm_hip.so")     # include/vio_sfm.h; calls nothing of libvio_hip.so (linked like the others)
+EXROT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_exrot_hip.so")     # include/vio_exrot.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -105,3 +107,8 @@ def load_init():
 def load_sfm():
     """Load the structure-from-motion library (csrc/libvio_sfm_hip.so)."""
     return _load_companion("sfm", SfmLib, SFM_LIB)
+
+
+def load_exrot():
+    """Load the extrinsic rotation calibration library (csrc/libvio_exrot_hip.so)."""
+    return _load_companion("exrot", ExrotLib, EXROT_LIB)

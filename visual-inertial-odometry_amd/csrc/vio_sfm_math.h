@@ -1,0 +1,172 @@
+// vio_sfm_math.h — the small dense device math libvio_sfm_hip (vio_sfm.hip) and libvio_exrot_hip (vio_exrot.hip) share: one copy of
+// the hash mixer, the fixed-sweep cyclic Jacobi, the SO(3) / quaternion helpers, the two-view triangulation and the normalised
+// 8-point model.  Device code only, one thread per call.  The including source sets `#pragma clang fp contract(off)` first: products
+// and sums round as the host restatement's (tests/sfm_reference.py) do.
+#pragma once
+
+#include <hip/hip_runtime.h>
+
+#include <cmath>
+#include <cstdint>
+
+#include "../../include/vio_sfm.h"
+
+__device__ __forceinline__ uint32_t mix32(uint32_t x) {
+    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
+    return x;
+}
+
+// cyclic Jacobi on the symmetric n x n matrix A (row-major, destroyed: its diagonal becomes the eigenvalues); V: the eigenvectors
+// in columns
+__device__ void jacobi(int n, double *A, double *V) {
+    for (int i = 0; i < n * n; ++i) V[i] = 0.0;
+    for (int i = 0; i < n; ++i) V[i * n + i] = 1.0;
+    for (int sw = 0; sw < VIO_SFM_JACOBI_SWEEPS; ++sw)
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A[p * n + q];
+                const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
+                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                if (apq == 0.0) t = 0.0;
+                if (!isfinite(t)) t = 0.0;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+                for (int k = 0; k < n; ++k) {
+                    const double rp = A[p * n + k], rq = A[q * n + k];
+                    A[p * n + k] = c * rp - s * rq;
+                    A[q * n + k] = s * rp + c * rq;
+                }
+                for (int k = 0; k < n; ++k) {
+                    const double cp = A[k * n + p], cq = A[k * n + q];
+                    A[k * n + p] = c * cp - s * cq;
+                    A[k * n + q] = s * cp + c * cq;
+                    const double vp = V[k * n + p], vq = V[k * n + q];
+                    V[k * n + p] = c * vp - s * vq;
+                    V[k * n + q] = s * vp + c * vq;
+                }
+            }
+}
+__device__ int argmin_diag(int n, const double *A) {
+    int k = 0;
+    for (int i = 1; i < n; ++i)
+        if (A[i * n + i] < A[k * n + k]) k = i;
+    return k;
+}
+
+__device__ void exp_so3(const double *w, double *R) {
+    const double th2 = w[0] * w[0] + w[1] * w[1] + w[2] * w[2];
+    const double th = sqrt(th2);
+    double a, b;
+    if (th < 1e-8) { a = 1.0 - th2 / 6.0; b = 0.5 - th2 / 24.0; }
+    else { a = sin(th) / th; b = (1.0 - cos(th)) / th2; }
+    const double K[9] = {0.0, -w[2], w[1], w[2], 0.0, -w[0], -w[1], w[0], 0.0};
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const double kk = K[3 * r] * K[c] + K[3 * r + 1] * K[3 + c] + K[3 * r + 2] * K[6 + c];
+            R[3 * r + c] = ((r == c ? 1.0 : 0.0) + a * K[3 * r + c]) + b * kk;
+        }
+}
+__device__ void rot_to_quat(const double *R, double *q) {     // (w, x, y, z): Eigen's Quaternion(Matrix3d)
+    double t = R[0] + R[4] + R[8];
+    if (t > 0) {
+        t = sqrt(t + 1.0);
+        q[0] = 0.5 * t;
+        t = 0.5 / t;
+        q[1] = (R[7] - R[5]) * t; q[2] = (R[2] - R[6]) * t; q[3] = (R[3] - R[1]) * t;
+    } else {
+        int i = 0;
+        if (R[4] > R[0]) i = 1;
+        if (R[8] > R[4 * i]) i = 2;
+        const int j = (i + 1) % 3, k = (i + 2) % 3;
+        t = sqrt(R[4 * i] - R[4 * j] - R[4 * k] + 1.0);
+        q[1 + i] = 0.5 * t;
+        t = 0.5 / t;
+        q[0] = (R[3 * k + j] - R[3 * j + k]) * t;
+        q[1 + j] = (R[3 * j + i] + R[3 * i + j]) * t;
+        q[1 + k] = (R[3 * k + i] + R[3 * i + k]) * t;
+    }
+}
+__device__ void quat_to_rot(const double *q, double *R) {
+    const double w = q[0], x = q[1], y = q[2], z = q[3];
+    R[0] = 1 - 2 * (y * y + z * z); R[1] = 2 * (x * y - w * z); R[2] = 2 * (x * z + w * y);
+    R[3] = 2 * (x * y + w * z); R[4] = 1 - 2 * (x * x + z * z); R[5] = 2 * (y * z - w * x);
+    R[6] = 2 * (x * z - w * y); R[7] = 2 * (y * z + w * x); R[8] = 1 - 2 * (x * x + y * y);
+}
+__device__ void mm3(const double *A, const double *B, double *C) {
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) C[3 * r + c] = A[3 * r] * B[c] + A[3 * r + 1] * B[3 + c] + A[3 * r + 2] * B[6 + c];
+}
+
+// GlobalSFM::triangulatePoint: cameras (R0, t0), (R1, t1) (rows of Pose = (R row, t)), points p0, p1
+__device__ void triangulate(const double *R0, const double *t0, const double *R1, const double *t1, const double *p0, const double *p1,
+                            double *X) {
+    double D[16], N[16], V[16];
+    for (int c = 0; c < 4; ++c) {
+        const double a2 = c < 3 ? R0[6 + c] : t0[2], a0 = c < 3 ? R0[c] : t0[0], a1 = c < 3 ? R0[3 + c] : t0[1];
+        const double b2 = c < 3 ? R1[6 + c] : t1[2], b0 = c < 3 ? R1[c] : t1[0], b1 = c < 3 ? R1[3 + c] : t1[1];
+        D[c] = p0[0] * a2 - a0;
+        D[4 + c] = p0[1] * a2 - a1;
+        D[8 + c] = p1[0] * b2 - b0;
+        D[12 + c] = p1[1] * b2 - b1;
+    }
+    for (int r = 0; r < 4; ++r)
+        for (int c = 0; c < 4; ++c) N[4 * r + c] = ((D[r] * D[c] + D[4 + r] * D[4 + c]) + D[8 + r] * D[8 + c]) + D[12 + r] * D[12 + c];
+    jacobi(4, N, V);
+    const int k = argmin_diag(4, N);
+    const double w = V[12 + k];
+    X[0] = V[k] / w; X[1] = V[4 + k] / w; X[2] = V[8 + k] / w;
+}
+
+// the normalised 8-point model over the correspondences corr[idx[0 .. n-1]] (x_a, y_a, x_b, y_b): x_b^T F x_a = 0
+__device__ void eight_point(const double *corr, const int *idx, int n, double *Fm) {
+    double ca[2] = {0, 0}, cb[2] = {0, 0};
+    for (int k = 0; k < n; ++k) {
+        const double *p = corr + 4 * idx[k];
+        ca[0] += p[0]; ca[1] += p[1]; cb[0] += p[2]; cb[1] += p[3];
+    }
+    for (int k = 0; k < 2; ++k) { ca[k] /= n; cb[k] /= n; }
+    double ma = 0, mb = 0;
+    for (int k = 0; k < n; ++k) {
+        const double *p = corr + 4 * idx[k];
+        const double ax = p[0] - ca[0], ay = p[1] - ca[1], bx = p[2] - cb[0], by = p[3] - cb[1];
+        ma += sqrt(ax * ax + ay * ay);
+        mb += sqrt(bx * bx + by * by);
+    }
+    const double sa = sqrt(2.0) / (ma / n), sb = sqrt(2.0) / (mb / n);
+    double N[81], V[81];
+    for (int i = 0; i < 81; ++i) N[i] = 0.0;
+    for (int k = 0; k < n; ++k) {
+        const double *p = corr + 4 * idx[k];
+        const double x1 = (p[0] - ca[0]) * sa, y1 = (p[1] - ca[1]) * sa, x2 = (p[2] - cb[0]) * sb, y2 = (p[3] - cb[1]) * sb;
+        const double r[9] = {x2 * x1, x2 * y1, x2, y2 * x1, y2 * y1, y2, x1, y1, 1.0};
+        for (int i = 0; i < 9; ++i)
+            for (int j = 0; j < 9; ++j) N[9 * i + j] += r[i] * r[j];
+    }
+    jacobi(9, N, V);
+    int m = argmin_diag(9, N);
+    double Fh[9];
+    for (int i = 0; i < 9; ++i) Fh[i] = V[9 * i + m];
+    double G[9], W[9];
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) G[3 * r + c] = Fh[r] * Fh[c] + Fh[3 + r] * Fh[3 + c] + Fh[6 + r] * Fh[6 + c];
+    jacobi(3, G, W);
+    m = argmin_diag(3, G);
+    const double v[3] = {W[m], W[3 + m], W[6 + m]};
+    for (int r = 0; r < 3; ++r) {
+        const double fv = Fh[3 * r] * v[0] + Fh[3 * r + 1] * v[1] + Fh[3 * r + 2] * v[2];
+        for (int c = 0; c < 3; ++c) Fh[3 * r + c] = Fh[3 * r + c] - fv * v[c];
+    }
+    const double T1[9] = {sa, 0, -sa * ca[0], 0, sa, -sa * ca[1], 0, 0, 1.0};
+    const double T2t[9] = {sb, 0, 0, 0, sb, 0, -sb * cb[0], -sb * cb[1], 1.0};
+    double tmp[9];
+    mm3(T2t, Fh, tmp);
+    mm3(tmp, T1, Fm);
+}
+
+__device__ __forceinline__ double epipolar_error(const double *F, const double *p) {
+    const double ax = p[0], ay = p[1], bx = p[2], by = p[3];
+    const double A = F[0] * ax + F[1] * ay + F[2], B = F[3] * ax + F[4] * ay + F[5], C = F[6] * ax + F[7] * ay + F[8];
+    const double d2 = bx * A + by * B + C, s2 = 1.0 / (A * A + B * B);
+    const double A1 = F[0] * bx + F[3] * by + F[6], B1 = F[1] * bx + F[4] * by + F[7], C1 = F[2] * bx + F[5] * by + F[8];
+    const double d1 = ax * A1 + ay * B1 + C1, s1 = 1.0 / (A1 * A1 + B1 * B1);
+    return fmax(d1 * d1 * s1, d2 * d2 * s2);
+}

@@ -386,7 +386,14 @@ class StreamDriver:
         window's feature tracks instead of visual_trajectory (scale, rot_noise, pos_noise and seed are then unused): True runs
         relativePose + GlobalSFM::construct through the SfM library (include/vio_sfm.h), a callable(items) returning the dicts
         SfmHandle.sfm_batch returns replaces it; a window whose SfM fails counts as a failed try with status sfm.TRY_FAILED_SFM + |SfM status| and the
-        SfM status under `sfm_status` (self.init_sfm_status records every try's SfM status).  None: the ground-truth start below."""
+        SfM status under `sfm_status` (self.init_sfm_status records every try's SfM status).  A `calibrate_ric` entry (with `sfm`)
+        starts from an unknown camera-IMU rotation: self.ext[3:7] is the identity and the stream's own rotation is not used.  Each
+        try first calibrates it on the window's tracks and the delta_q of its pre-integrations (include/vio_exrot.h,
+        InitialEXRotation::CalibrationExRotation); on success self.ext[3:7] is set before the SfM and the alignment, on failure the try
+        counts as failed with status exrot.TRY_FAILED_EXROT + |status| and the calibration's status under `exrot_status`
+        (self.init_exrot_status records every try's).  True: the library's defaults; a dict(min_sigma=, min_frames=, huber_deg=):
+        its gate; a callable(items) returning the dicts ExrotHandle.exrot_batch returns replaces the library.  None: the
+        ground-truth start below."""
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -411,6 +418,10 @@ class StreamDriver:
             self.poses[i, 3:7] = synth.quat_mul(st.Q[i], dq)
             self.sb[i, 0:3] = st.V[i]
         self.ext = st.ext.copy()
+        if initialize is not None and initialize.get("calibrate_ric"):
+            if not initialize.get("sfm"):
+                raise ValueError("StreamDriver: calibrate_ric needs sfm (the stand-in's poses are made with the true rotation)")
+            self.ext[3:7] = (0.0, 0.0, 0.0, 1.0)
         # tracks (FeaturePerId): landmark -> list of (global frame, normalised point), the first one is the host
         self.tracks = {}
         for f in self.frames:
@@ -440,8 +451,9 @@ class StreamDriver:
             cfg = dict(scale=1.0, rot_noise=0.0, pos_noise=0.0, max_tries=10, seed=0)
             cfg.update(self.initialize)
             self.initialize = cfg
-            self._init_h = self._init_imu = self._sfm_h = None
+            self._init_h = self._init_imu = self._sfm_h = self._exrot_h = None
             self.init_sfm_status = []
+            self.init_exrot_status = []
 
     # ---- initialisation (initialize) ------------------------------------------------------------------
     def init_request(self):
@@ -449,8 +461,12 @@ class StreamDriver:
         c = self.initialize
         if c.get("sfm"):            # R / T are filled in by init_align's SfM call
             from .sfm import item_from_tracks
-            return dict(sfm_item=item_from_tracks(self.tracks, self.frames)[0], owner=self, R=None, T=None, pre=list(self.preint),
-                        is_key=None), list(self.intervals)
+            item = dict(sfm_item=item_from_tracks(self.tracks, self.frames)[0], owner=self, R=None, T=None, pre=list(self.preint),
+                        is_key=None)
+            if c.get("calibrate_ric"):
+                from .exrot import delta_q_wxyz
+                item["exrot_item"] = dict(item["sfm_item"], delta_q=delta_q_wxyz(self.preint))
+            return item, list(self.intervals)
         R, T = visual_trajectory(self.s, self.frames, 0, c["scale"], c["rot_noise"], c["pos_noise"], c["seed"] + self.init_tries)
         return dict(R=R, T=T, pre=list(self.preint), is_key=None), list(self.intervals)
 
@@ -473,18 +489,51 @@ class StreamDriver:
                 it["R"], it["T"] = done["R"], done["T"]
         return [int(r["status"]) for r in res]
 
+    def init_exrot(self, items):
+        """One calibration call for every item made with `calibrate_ric`: sets the owner's ext[3:7] where it succeeds.  Returns each
+        item's calibration status."""
+        c = self.initialize
+        cal = c["calibrate_ric"]
+        if callable(cal):
+            res = cal([it["exrot_item"] for it in items])
+        else:
+            if self._exrot_h is None:
+                from . import load_exrot
+                self._exrot_h = load_exrot().create(device=self.ctx.cfg.device)
+                if isinstance(cal, dict):
+                    self._exrot_h.set_config(**cal)
+            res = self._exrot_h.exrot_batch([it["exrot_item"] for it in items])
+        for it, r in zip(items, res):
+            if r["status"] == 0:
+                w, x, y, z = r["q"]
+                it["owner"].ext[3:7] = (x, y, z, w)
+                it["owner"].init_exrot_result = r
+        return [int(r["status"]) for r in res]
+
     def init_align(self, items, intervals):
         """The alignment of `items` on this driver's backend: the library (one handle pair per driver), or the `aligner` given."""
         c = self.initialize
         if c.get("sfm"):
             from .sfm import TRY_FAILED_SFM
-            sts = self.init_sfm(items)
-            for it, st in zip(items, sts):
-                it["owner"].init_sfm_status.append(st)
-            ok = [i for i, st in enumerate(sts) if st == 0]
-            out = [dict(status=TRY_FAILED_SFM + abs(st), sfm_status=st) for st in sts]       # an SfM failure: a failed try
+            out = [None] * len(items)
+            live = list(range(len(items)))
+            if c.get("calibrate_ric"):
+                from .exrot import TRY_FAILED_EXROT
+                xs = self.init_exrot(items)
+                for i, st in enumerate(xs):
+                    items[i]["owner"].init_exrot_status.append(st)
+                    if st != 0:
+                        out[i] = dict(status=TRY_FAILED_EXROT + abs(st), exrot_status=st)     # a calibration failure: a failed try
+                live = [i for i in live if xs[i] == 0]
+            sts = self.init_sfm([items[i] for i in live]) if live else []
+            ok = []
+            for i, st in zip(live, sts):
+                items[i]["owner"].init_sfm_status.append(st)
+                out[i] = dict(status=TRY_FAILED_SFM + abs(st), sfm_status=st)               # an SfM failure: a failed try
+                if st == 0:
+                    ok.append(i)
             if ok:
-                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "owner")} for i in ok]
+                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "exrot_item", "owner")} for i in ok]
                 for i, r in zip(ok, self._init_align(plain, [intervals[i] for i in ok])):
                     out[i] = r
             return out
