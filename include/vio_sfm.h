@@ -8,7 +8,7 @@
  *   vio_sfm_construct_batch       GlobalSFM::construct (VM/src/initial/initial_sfm.cpp:121-313): the PnP / triangulation chains in
  *                                 its order, then the full bundle adjustment                               (k_sfm_construct)
  *   vio_sfm_batch                 both, without a host round trip in between
- * The PnP of the non-keyframes of all_image_frame (estimator.cpp:320-373) is not part of this library.  It works from host arrays
+ * The PnP of the non-keyframes of all_image_frame (estimator.cpp:320-373) is include/vio_pnp.h's, not this library's.  It works from host arrays
  * and needs nothing from libvio_hip but the vio_status type.  DESIGN.md section 16 has the math, the layout and the measurements.
  *
  * The reference does this part with OpenCV and Ceres.  What replaces them, so that the work is fixed and repeatable:

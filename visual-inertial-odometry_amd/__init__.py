@@ -5,7 +5,7 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, exrot, imu, init, marg, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, covariance, exrot, imu, init, marg, pnp, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
@@ -14,6 +14,7 @@ from .exrot import ExrotHandle, ExrotLib
 from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
+from .pnp import PnpHandle, PnpLib, all_frames_to_init_items, pnp_items_from_sfm
 from .sfm import SfmHandle, SfmLib, sfm_items_to_init_items
 from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
@@ -27,6 +28,7 @@ MARG_LIB = os.path.join(PKG_DIR, "csrc", "libvio_marg_hip.so")   # include/vio_m
 INIT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_init_hip.so")   # include/vio_init.h, linked against libvio_hip.so
 SFM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_sfm_hip.so")     # include/vio_sfm.h; calls nothing of libvio_hip.so (linked like the others)
 EXROT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_exrot_hip.so")     # include/vio_exrot.h; calls nothing of libvio_hip.so either
+PNP_LIB = os.path.join(PKG_DIR, "csrc", "libvio_pnp_hip.so")     # include/vio_pnp.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -112,3 +114,8 @@ def load_sfm():
 def load_exrot():
     """Load the extrinsic rotation calibration library (csrc/libvio_exrot_hip.so)."""
     return _load_companion("exrot", ExrotLib, EXROT_LIB)
+
+
+def load_pnp():
+    """Load the non-keyframe PnP library (csrc/libvio_pnp_hip.so)."""
+    return _load_companion("pnp", PnpLib, PNP_LIB)

@@ -42,7 +42,6 @@ constexpr int PC = 28;                  // per PnP point: upper triangle of Jc^T
 constexpr double FOCAL = 460.0;
 constexpr double RANSAC_THR = 0.3 / 460.0;
 constexpr double MAX_DEPTH = 50.0;
-constexpr double LM_RADIUS_MAX = 1e16, LM_RADIUS_MIN = 1e-32, LM_MIN_RHO = 1e-3, LM_DIAG_MIN = 1e-6, LM_DIAG_MAX = 1e32;
 constexpr double BA_COST_OK = 5e-3;
 
 struct SfmWin {
@@ -283,61 +282,6 @@ struct Lm {
     double cost, cost2, prev, radius, v, rho, lam, c0;      // cost: at the state; cost2: at the trial state; prev: before the step taken
     int it, ok, stop, converged, npts;
 };
-
-// normalised reprojection residual of point X in camera (R, t), the camera point and R X
-__device__ __forceinline__ void residual(const double *R, const double *t, const double *X, const double *p, double *r, double *Xc,
-                                         double *RX) {
-    for (int k = 0; k < 3; ++k) {
-        RX[k] = (R[3 * k] * X[0] + R[3 * k + 1] * X[1]) + R[3 * k + 2] * X[2];
-        Xc[k] = RX[k] + t[k];
-    }
-    r[0] = Xc[0] / Xc[2] - p[0];
-    r[1] = Xc[1] / Xc[2] - p[1];
-}
-// Jc (2 x 6, row-major) over (left rotation increment, translation)
-__device__ __forceinline__ void jac_cam(const double *Xc, const double *RX, double *Jc, double *Jpr) {
-    const double iz = 1.0 / Xc[2];
-    Jpr[0] = iz; Jpr[1] = 0.0; Jpr[2] = -Xc[0] * iz * iz;
-    Jpr[3] = 0.0; Jpr[4] = iz; Jpr[5] = -Xc[1] * iz * iz;
-    const double S[9] = {0.0, RX[2], -RX[1], -RX[2], 0.0, RX[0], RX[1], -RX[0], 0.0};
-    for (int r = 0; r < 2; ++r)
-        for (int c = 0; c < 3; ++c) {
-            Jc[6 * r + c] = (Jpr[3 * r] * S[c] + Jpr[3 * r + 1] * S[3 + c]) + Jpr[3 * r + 2] * S[6 + c];
-            Jc[6 * r + 3 + c] = Jpr[3 * r + c];
-        }
-}
-
-__device__ bool cholesky_solve6(double *A, const double *b, double *x) {     // lower Cholesky in place, one thread
-    for (int j = 0; j < 6; ++j) {
-        double d = 0.0;
-        for (int k = 0; k < j; ++k) d += A[6 * j + k] * A[6 * j + k];
-        d = A[6 * j + j] - d;
-        if (!(d > 0.0)) return false;
-        A[6 * j + j] = sqrt(d);
-        for (int i = j + 1; i < 6; ++i) {
-            double s = 0.0;
-            for (int k = 0; k < j; ++k) s += A[6 * i + k] * A[6 * j + k];
-            A[6 * i + j] = (A[6 * i + j] - s) / A[6 * j + j];
-        }
-    }
-    double y[6];
-    for (int i = 0; i < 6; ++i) {
-        double s = 0.0;
-        for (int k = 0; k < i; ++k) s += A[6 * i + k] * y[k];
-        y[i] = (b[i] - s) / A[6 * i + i];
-    }
-    for (int i = 5; i >= 0; --i) {
-        double s = 0.0;
-        for (int k = i + 1; k < 6; ++k) s += A[6 * k + i] * x[k];
-        x[i] = (y[i] - s) / A[6 * i + i];
-    }
-    return true;
-}
-
-__device__ __forceinline__ double lm_radius(double radius, double rho) {
-    const double x = 2.0 * rho - 1.0;
-    return fmin(radius / fmax(1.0 / 3.0, 1.0 - x * x * x), LM_RADIUS_MAX);
-}
 
 struct Ctx {
     int tid, F, nt, l;

@@ -1,6 +1,7 @@
-// vio_sfm_math.h — the small dense device math libvio_sfm_hip (vio_sfm.hip) and libvio_exrot_hip (vio_exrot.hip) share: one copy of
-// the hash mixer, the fixed-sweep cyclic Jacobi, the SO(3) / quaternion helpers, the two-view triangulation and the normalised
-// 8-point model.  Device code only, one thread per call.  The including source sets `#pragma clang fp contract(off)` first: products
+// vio_sfm_math.h — the small dense device math libvio_sfm_hip (vio_sfm.hip), libvio_exrot_hip (vio_exrot.hip) and libvio_pnp_hip
+// (vio_pnp.hip) share: one copy of the hash mixer, the fixed-sweep cyclic Jacobi, the SO(3) / quaternion helpers, the two-view
+// triangulation, the normalised 8-point model, and the reprojection residual, its camera Jacobian, the 6 x 6 Cholesky solve and the
+// trust-region radius rule of the PnP solves.  Device code only, one thread per call.  The including source sets `#pragma clang fp contract(off)` first: products
 // and sums round as the host restatement's (tests/sfm_reference.py) do.
 #pragma once
 
@@ -169,4 +170,62 @@ __device__ __forceinline__ double epipolar_error(const double *F, const double *
     const double A1 = F[0] * bx + F[3] * by + F[6], B1 = F[1] * bx + F[4] * by + F[7], C1 = F[2] * bx + F[5] * by + F[8];
     const double d1 = ax * A1 + ay * B1 + C1, s1 = 1.0 / (A1 * A1 + B1 * B1);
     return fmax(d1 * d1 * s1, d2 * d2 * s2);
+}
+
+// Ceres' trust-region rule of both Levenberg-Marquardt solves (include/vio_sfm.h) and of libvio_pnp_hip's (include/vio_pnp.h)
+constexpr double LM_RADIUS_MAX = 1e16, LM_RADIUS_MIN = 1e-32, LM_MIN_RHO = 1e-3, LM_DIAG_MIN = 1e-6, LM_DIAG_MAX = 1e32;
+
+// normalised reprojection residual of point X in camera (R, t), the camera point and R X
+__device__ __forceinline__ void residual(const double *R, const double *t, const double *X, const double *p, double *r, double *Xc,
+                                         double *RX) {
+    for (int k = 0; k < 3; ++k) {
+        RX[k] = (R[3 * k] * X[0] + R[3 * k + 1] * X[1]) + R[3 * k + 2] * X[2];
+        Xc[k] = RX[k] + t[k];
+    }
+    r[0] = Xc[0] / Xc[2] - p[0];
+    r[1] = Xc[1] / Xc[2] - p[1];
+}
+// Jc (2 x 6, row-major) over (left rotation increment, translation)
+__device__ __forceinline__ void jac_cam(const double *Xc, const double *RX, double *Jc, double *Jpr) {
+    const double iz = 1.0 / Xc[2];
+    Jpr[0] = iz; Jpr[1] = 0.0; Jpr[2] = -Xc[0] * iz * iz;
+    Jpr[3] = 0.0; Jpr[4] = iz; Jpr[5] = -Xc[1] * iz * iz;
+    const double S[9] = {0.0, RX[2], -RX[1], -RX[2], 0.0, RX[0], RX[1], -RX[0], 0.0};
+    for (int r = 0; r < 2; ++r)
+        for (int c = 0; c < 3; ++c) {
+            Jc[6 * r + c] = (Jpr[3 * r] * S[c] + Jpr[3 * r + 1] * S[3 + c]) + Jpr[3 * r + 2] * S[6 + c];
+            Jc[6 * r + 3 + c] = Jpr[3 * r + c];
+        }
+}
+
+__device__ bool cholesky_solve6(double *A, const double *b, double *x) {     // lower Cholesky in place, one thread
+    for (int j = 0; j < 6; ++j) {
+        double d = 0.0;
+        for (int k = 0; k < j; ++k) d += A[6 * j + k] * A[6 * j + k];
+        d = A[6 * j + j] - d;
+        if (!(d > 0.0)) return false;
+        A[6 * j + j] = sqrt(d);
+        for (int i = j + 1; i < 6; ++i) {
+            double s = 0.0;
+            for (int k = 0; k < j; ++k) s += A[6 * i + k] * A[6 * j + k];
+            A[6 * i + j] = (A[6 * i + j] - s) / A[6 * j + j];
+        }
+    }
+    double y[6];
+    for (int i = 0; i < 6; ++i) {
+        double s = 0.0;
+        for (int k = 0; k < i; ++k) s += A[6 * i + k] * y[k];
+        y[i] = (b[i] - s) / A[6 * i + i];
+    }
+    for (int i = 5; i >= 0; --i) {
+        double s = 0.0;
+        for (int k = i + 1; k < 6; ++k) s += A[6 * k + i] * x[k];
+        x[i] = (y[i] - s) / A[6 * i + i];
+    }
+    return true;
+}
+
+__device__ __forceinline__ double lm_radius(double radius, double rho) {
+    const double x = 2.0 * rho - 1.0;
+    return fmin(radius / fmax(1.0 / 3.0, 1.0 - x * x * x), LM_RADIUS_MAX);
 }
