@@ -5,12 +5,13 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, exrot, imu, init, marg, pnp, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, covariance, exrot, flow, imu, init, marg, pnp, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
 from .exrot import ExrotHandle, ExrotLib
+from .flow import FlowHandle, FlowLib
 from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
@@ -29,6 +30,7 @@ INIT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_init_hip.so")   # include/vio_i
 SFM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_sfm_hip.so")     # include/vio_sfm.h; calls nothing of libvio_hip.so (linked like the others)
 EXROT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_exrot_hip.so")     # include/vio_exrot.h; calls nothing of libvio_hip.so either
 PNP_LIB = os.path.join(PKG_DIR, "csrc", "libvio_pnp_hip.so")     # include/vio_pnp.h; calls nothing of libvio_hip.so either
+FLOW_LIB = os.path.join(PKG_DIR, "csrc", "libvio_flow_hip.so")   # include/vio_flow.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -119,3 +121,8 @@ def load_exrot():
 def load_pnp():
     """Load the non-keyframe PnP library (csrc/libvio_pnp_hip.so)."""
     return _load_companion("pnp", PnpLib, PNP_LIB)
+
+
+def load_flow():
+    """Load the feature tracking library (csrc/libvio_flow_hip.so)."""
+    return _load_companion("flow", FlowLib, FLOW_LIB)
