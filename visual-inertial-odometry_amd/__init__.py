@@ -5,13 +5,15 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, exrot, flow, imu, init, marg, pnp, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, covariance, detect, exrot, flow, frontend, imu, init, marg, pnp, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
+from .detect import DetectHandle, DetectLib
 from .exrot import ExrotHandle, ExrotLib
 from .flow import FlowHandle, FlowLib
+from .frontend import FeatureTracker
 from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
@@ -31,6 +33,7 @@ SFM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_sfm_hip.so")     # include/vio_s
 EXROT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_exrot_hip.so")     # include/vio_exrot.h; calls nothing of libvio_hip.so either
 PNP_LIB = os.path.join(PKG_DIR, "csrc", "libvio_pnp_hip.so")     # include/vio_pnp.h; calls nothing of libvio_hip.so either
 FLOW_LIB = os.path.join(PKG_DIR, "csrc", "libvio_flow_hip.so")   # include/vio_flow.h; calls nothing of libvio_hip.so either
+DETECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_detect_hip.so")   # include/vio_detect.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -126,3 +129,8 @@ def load_pnp():
 def load_flow():
     """Load the feature tracking library (csrc/libvio_flow_hip.so)."""
     return _load_companion("flow", FlowLib, FLOW_LIB)
+
+
+def load_detect():
+    """Load the corner detection library (csrc/libvio_detect_hip.so)."""
+    return _load_companion("detect", DetectLib, DETECT_LIB)

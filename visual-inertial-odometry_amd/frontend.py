@@ -1,0 +1,90 @@
+"""FeatureTracker: an image sequence in, ids with tracks out.  It composes the tracker (flow.FlowHandle) and the detector
+(detect.DetectHandle) the way FeatureTracker::readImage (VM/src/feature_tracker.cpp:97-164) and updateID (:204-214) do:
+
+    ft = FeatureTracker(vio.load_flow().create(), vio.load_detect().create())
+    for t, img in frames:
+        out = ft.read_image(img, t)            # dict(pts (n, 2) float32, ids (n,), track_cnt (n,)); ids are -1 for new points ...
+        ft.update_ids()                        # ... until this gives them the next free ids
+
+read_image tracks cur_pts into the new image, drops the points the tracker lost and those whose rounded position is outside `border`,
+adds one to every track_cnt, and on a published frame runs `reject` (if given), then setMask and the detection (which keeps at most
+max_cnt points min_dist apart, the long tracks first), then addPoints (id -1, count 1); last it rolls prev / cur.
+
+`tracker` and `detector` are any objects with .track(img_prev, img_next, pts) -> dict(next_pts, status) and
+.detect(img, tracked=, track_cnt=, mask=, max_total=) -> dict(keep_order, new_pts) of the handles' signatures; a detector with a
+set_config gets min_distance = min_dist (its other settings return to their defaults).  reject(cur_pts, forw_pts) -> a boolean array,
+True for the pairs to keep: the place of rejectWithF.
+
+Missing against the reference: rejectWithF (findFundamentalMat with RANSAC on the lifted points), undistortedPoints and the point
+velocities (the camera model), EQUALIZE (CLAHE).  One thing differs on purpose: prev_pts stays aligned with the points through setMask's
+reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
+"""
+import numpy as np
+
+
+class FeatureTracker:
+    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None):
+        self.tracker, self.detector = tracker, detector
+        self.max_cnt, self.min_dist, self.border, self.reject, self.mask = int(max_cnt), int(min_dist), int(border), reject, mask
+        if hasattr(detector, "set_config"):
+            detector.set_config(min_distance=self.min_dist)
+        self.prev_img = self.cur_img = None
+        self.prev_pts = np.zeros((0, 2), dtype=np.float32)
+        self.cur_pts = np.zeros((0, 2), dtype=np.float32)
+        self.ids = np.zeros(0, dtype=np.int64)
+        self.track_cnt = np.zeros(0, dtype=np.int32)
+        self.n_new = 0                          # the points the last read_image added
+        self.n_id = 0
+        self.cur_time = self.prev_time = None
+
+    def in_border(self, pts, shape):
+        """readImage's inBorder on the rounded positions (cvRound: ties to even) in an image of `shape`."""
+        h, w = shape
+        with np.errstate(invalid="ignore"):
+            r = np.rint(np.asarray(pts, dtype=np.float64).reshape(-1, 2))
+        b = self.border
+        return (b <= r[:, 0]) & (r[:, 0] < w - b) & (b <= r[:, 1]) & (r[:, 1] < h - b)
+
+    def _reduce(self, keep, *arrays):
+        return [a[keep] for a in arrays]
+
+    def read_image(self, img, t, publish=True):
+        img = np.asarray(img)
+        if img.dtype != np.uint8 or img.ndim != 2:
+            raise ValueError("an image must be a 2-d uint8 array")
+        self.prev_time, self.cur_time = self.cur_time, t
+        first = self.cur_img is None
+        if first:
+            self.prev_img = self.cur_img = img
+        cur, forw = self.cur_pts, np.zeros((0, 2), dtype=np.float32)
+        ids, cnt = self.ids, self.track_cnt
+        if len(cur) > 0:
+            out = self.tracker.track(self.cur_img, img, cur)
+            forw = np.asarray(out["next_pts"], dtype=np.float32).reshape(-1, 2)
+            ok = (np.asarray(out["status"]) == 0) & self.in_border(forw, img.shape)
+            cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
+        cnt = cnt + 1
+        self.n_new = 0
+        if publish:
+            if self.reject is not None and len(forw) > 0:
+                ok = np.asarray(self.reject(cur, forw), dtype=bool).reshape(-1)
+                cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
+            det = self.detector.detect(img, tracked=forw, track_cnt=cnt, mask=self.mask, max_total=self.max_cnt)
+            order = np.asarray(det["keep_order"], dtype=np.int64)
+            new = np.asarray(det["new_pts"], dtype=np.float32).reshape(-1, 2)
+            self.n_new = len(new)
+            cur = np.concatenate([cur[order], np.full((len(new), 2), np.nan, dtype=np.float32)])
+            forw = np.concatenate([forw[order], new])
+            ids = np.concatenate([ids[order], np.full(len(new), -1, dtype=np.int64)])
+            cnt = np.concatenate([cnt[order], np.ones(len(new), dtype=np.int32)]).astype(np.int32)
+        self.prev_img, self.cur_img = self.cur_img, img
+        self.prev_pts, self.cur_pts = cur, forw
+        self.ids, self.track_cnt = ids, cnt
+        return dict(pts=self.cur_pts.copy(), ids=self.ids.copy(), track_cnt=self.track_cnt.copy())
+
+    def update_ids(self):
+        """updateID over every point: a new point (id -1) gets the next free id.  Returns the ids."""
+        new = np.nonzero(self.ids == -1)[0]
+        self.ids[new] = self.n_id + np.arange(len(new))
+        self.n_id += len(new)
+        return self.ids.copy()
