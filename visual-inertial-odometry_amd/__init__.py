@@ -5,7 +5,7 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, detect, exrot, flow, frontend, imu, init, marg, pnp, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, covariance, detect, exrot, flow, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
@@ -18,6 +18,7 @@ from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib
 from .pnp import PnpHandle, PnpLib, all_frames_to_init_items, pnp_items_from_sfm
+from .reject import RejectHandle, RejectLib
 from .sfm import SfmHandle, SfmLib, sfm_items_to_init_items
 from .residuals import FLAG_DEPTH, FLAG_REPROJ, FLAG_STATE, FLAGS_ALL, ResLib
 
@@ -34,6 +35,8 @@ EXROT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_exrot_hip.so")     # include/v
 PNP_LIB = os.path.join(PKG_DIR, "csrc", "libvio_pnp_hip.so")     # include/vio_pnp.h; calls nothing of libvio_hip.so either
 FLOW_LIB = os.path.join(PKG_DIR, "csrc", "libvio_flow_hip.so")   # include/vio_flow.h; calls nothing of libvio_hip.so either
 DETECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_detect_hip.so")   # include/vio_detect.h; calls nothing of libvio_hip.so either
+
+REJECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_reject_hip.so")   # include/vio_reject.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -134,3 +137,8 @@ def load_flow():
 def load_detect():
     """Load the corner detection library (csrc/libvio_detect_hip.so)."""
     return _load_companion("detect", DetectLib, DETECT_LIB)
+
+
+def load_reject():
+    """Load the outlier rejection and undistortion library (csrc/libvio_reject_hip.so)."""
+    return _load_companion("reject", RejectLib, REJECT_LIB)

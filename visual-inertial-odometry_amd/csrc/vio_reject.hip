@@ -1,0 +1,635 @@
+// vio_reject.hip — libvio_reject_hip.so: rejectWithF and undistortedPoints for many streams in one call (include/vio_reject.h,
+// DESIGN.md section 21).
+//
+//   k_reject_lift     a thread per point, every item of the call in the grid (blockIdx.y).  Undistort: the lift, the normalised point
+//                     as float, then the id lookup: prev_ids goes through LDS in chunks of VIO_REJECT_ID_CHUNK, every thread scans the
+//                     chunk for its id and keeps the first match; the velocity from the matched previous point.  Bare lift: the two
+//                     doubles.
+//   k_reject_ransac   one 256-thread workgroup per pair.  Prologue: both point sets lifted (the same rej_lift: the bits are
+//                     k_reject_lift's), mapped to virtual pixels and rounded to float, into the pair's scratch slice as doubles.
+//                     Then rounds of VIO_REJECT_ROUND hypotheses: lane h of the first wavefront samples and fits hypothesis base + h
+//                     with its 9 x 9 normal matrix and eigenvectors in LDS (entry-major, lane-minor: no per-lane arrays, no bank
+//                     conflicts); all threads score (hypothesis, correspondence) pairs into integer LDS counters; thread 0 folds the
+//                     round into the running winner (count, lowest h).  The refit: the inlier flags thread per correspondence, the
+//                     centroids, the scales and the 45 entries of the normal matrix's upper triangle each summed by one thread in
+//                     correspondence order, the eigenproblem by thread 0 in the same LDS; the final mask thread per correspondence.
+// Contraction is off: products and sums round as the restatement's (tests/reject_reference.py) do.  No floating-point atomics; every
+// sum has a fixed order, so repeated calls are bitwise identical and a pair's result does not depend on its batch.
+#include <hip/hip_runtime.h>
+
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstdint>
+#include <cstring>
+#include <new>
+#include <vector>
+
+#include "../../include/vio_reject.h"
+#include "vio_companion.h"
+
+#pragma clang fp contract(off)
+
+#include "vio_reject_math.h"
+#include "vio_sfm_math.h"
+
+constexpr int NT = VIO_REJECT_THREADS;
+constexpr int ROUND = VIO_REJECT_ROUND;
+constexpr int CHUNK = VIO_REJECT_ID_CHUNK;
+constexpr int MAX_ITEMS = VIO_REJECT_MAX_ITEMS;
+constexpr int MINP = VIO_REJECT_MIN_POINTS;
+static_assert(ROUND == 64, "a round is one wavefront");
+static_assert(VIO_REJECT_MAX_HYPOTHESES == VIO_SFM_MAX_HYPOTHESES && VIO_REJECT_DEFAULT_HYPOTHESES == VIO_SFM_DEFAULT_HYPOTHESES, "the RANSAC is vio_sfm.h's");
+static_assert(162 * 8 * ROUND + 9 * 8 * ROUND <= 160 * 1024, "the round's matrices fit a CU's LDS");
+
+struct RejPair {
+    int32_t n, active;
+    uint32_t pair;
+    int32_t finite;     // no point of the pair is NaN or infinite
+    int64_t o_pts;      // staged floats: cur [n][2] | forw [n][2]
+    int64_t o_corr;     // double scratch: corr [n][4]
+    int64_t o_pt;       // the pair's first point in the flat per-point arrays (flags, mask)
+};
+
+struct RejRes {
+    int32_t status, hyp, n_inliers, pad;
+    double F[9];
+};
+
+struct RansacArgs {
+    const RejPair *pairs;
+    const float *pts;
+    double *corr;
+    int32_t *flag;      // [points of the call]: the winner's inliers
+    uint8_t *mask;      // [points of the call]
+    RejRes *res;
+    RejCam cam;
+    double focal, half_w, half_h, thr;
+    uint32_t seed;
+    int32_t hyps;
+};
+
+struct LiftItem {
+    int32_t n, m, active, pad;
+    int64_t o_pts;      // staged floats: pts [n][2]
+    int64_t o_prev;     // staged floats: prev_un_pts [m][2]
+    int64_t o_ids;      // staged int64: ids [n] | prev_ids [m]
+    int64_t o_out;      // the item's first point in the outputs
+    double dt;
+};
+
+struct LiftArgs {
+    const LiftItem *items;
+    const float *pts;
+    const long long *ids;
+    float *un;          // [points][2] un_pts | [points][2] velocity behind them (undistort)
+    float *vel;
+    double *lifted;     // [points][2] (bare lift)
+    RejCam cam;
+    int32_t bare, count;
+};
+
+// ---------------------------------------------------------------------------------------------------------
+// k_reject_lift
+// ---------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(NT) void k_reject_lift(LiftArgs a) {
+    __shared__ long long s_ids[CHUNK];
+    const int item = blockIdx.y;
+    if (item >= a.count) return;
+    const LiftItem &D = a.items[item];
+    if ((int)blockIdx.x * NT >= D.n) return;                 // (the whole workgroup: no barrier was reached)
+    const int i = blockIdx.x * NT + threadIdx.x;
+    const bool on = i < D.n;
+    double x = 0.0, y = 0.0;
+    if (on) {
+        const float *p = a.pts + D.o_pts + 2 * (int64_t)i;
+        rej_lift(a.cam, (double)p[0], (double)p[1], x, y);
+    }
+    if (a.bare) {
+        if (on) { a.lifted[2 * (D.o_out + i)] = x; a.lifted[2 * (D.o_out + i) + 1] = y; }
+        return;
+    }
+    const float ux = rej_unpoint(x), uy = rej_unpoint(y);
+    if (!D.active) {                                         // a point of the item is not finite
+        if (on) {
+            a.un[2 * (D.o_out + i)] = NAN; a.un[2 * (D.o_out + i) + 1] = NAN;
+            a.vel[2 * (D.o_out + i)] = NAN; a.vel[2 * (D.o_out + i) + 1] = NAN;
+        }
+        return;
+    }
+    const long long id = on ? a.ids[D.o_ids + i] : -1ll;
+    const long long *prev = a.ids + D.o_ids + D.n;
+    int found = -1;
+    for (int c0 = 0; c0 < D.m; c0 += CHUNK) {                // (D.m is the workgroup's: every thread meets every barrier)
+        const int len = D.m - c0 < CHUNK ? D.m - c0 : CHUNK;
+        __syncthreads();
+        for (int j = threadIdx.x; j < len; j += NT) s_ids[j] = prev[c0 + j];
+        __syncthreads();
+        if (id != -1ll && found < 0)
+            for (int j = 0; j < len; ++j)
+                if (s_ids[j] == id) { found = c0 + j; break; }
+    }
+    if (!on) return;
+    float vx = 0.f, vy = 0.f;
+    if (found >= 0) {
+        const float *q = a.pts + D.o_prev + 2 * (int64_t)found;
+        vx = rej_velocity(ux, q[0], D.dt); vy = rej_velocity(uy, q[1], D.dt);
+    }
+    a.un[2 * (D.o_out + i)] = ux; a.un[2 * (D.o_out + i) + 1] = uy;
+    a.vel[2 * (D.o_out + i)] = vx; a.vel[2 * (D.o_out + i) + 1] = vy;
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// k_reject_ransac
+// ---------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ uint32_t rej_hash4(uint32_t seed, uint32_t i, uint32_t h, uint32_t k) {
+    return mix32(mix32(mix32(mix32(seed + 0x9e3779b9u) + i) + h) + k);
+}
+
+// sample8 of vio_sfm.hip with every index a constant (the insertion is a chain of selects): taken and out stay in registers
+__device__ __forceinline__ void rej_sample8(uint32_t seed, uint32_t pair, uint32_t h, int n, int *out) {
+    int taken[8];
+#pragma unroll
+    for (int k = 0; k < 8; ++k) {
+        int idx = (int)(rej_hash4(seed, pair, h, (uint32_t)k) % (uint32_t)(n - k));
+        int pos = 0;
+#pragma unroll
+        for (int m = 0; m < k; ++m)                          // taken is ascending: the entries <= idx (as it grows) are a prefix
+            if (pos == m && idx >= taken[m]) { ++idx; ++pos; }
+#pragma unroll
+        for (int m = k; m > 0; --m)
+            if (m > pos) taken[m] = taken[m - 1];
+#pragma unroll
+        for (int m = 0; m <= k; ++m)
+            if (m == pos) taken[m] = idx;
+        out[k] = idx;
+    }
+}
+
+// entry t of the upper triangle of a 9 x 9 matrix, row by row: (i, j), i <= j
+__device__ __forceinline__ void tri_entry(int t, int &i, int &j) {
+    i = 0;
+    int len = 9;
+    while (t >= len) { t -= len; --len; ++i; }
+    j = i + t;
+}
+
+__device__ __forceinline__ double row_entry(const double *r, int i) {
+    double v = r[0];
+#pragma unroll
+    for (int k = 1; k < 9; ++k) v = i == k ? r[k] : v;
+    return v;
+}
+
+__global__ __launch_bounds__(NT) void k_reject_ransac(RansacArgs a) {
+    __shared__ double s_N[81 * ROUND], s_V[81 * ROUND];      // entry e of lane l at [e * ROUND + l]
+    __shared__ double s_F[ROUND][9];                         // the round's models
+    __shared__ double s_best[9], s_E[9];
+    __shared__ HartleyScale s_h;
+    __shared__ double s_sum[4];
+    __shared__ int s_cnt[ROUND];
+    __shared__ int s_i[4];                                   // best count, best h, ok, final inliers
+
+    const RejPair P = a.pairs[blockIdx.x];
+    if (!P.active) return;                                   // (n < 8 or a point that is not finite: the host writes the result)
+    const int tid = threadIdx.x, n = P.n;
+    double *corr = a.corr + P.o_corr;
+    int32_t *flag = a.flag + P.o_pt;
+    uint8_t *mask = a.mask + P.o_pt;
+    RejRes *o = a.res + blockIdx.x;
+
+    // prologue: the lift, the virtual pixels, the float rounding
+    {
+        const float *cur = a.pts + P.o_pts, *forw = cur + 2 * (int64_t)n;
+        for (int k = tid; k < n; k += NT) {
+            double x, y;
+            rej_lift(a.cam, (double)cur[2 * k], (double)cur[2 * k + 1], x, y);
+            corr[4 * k] = rej_virtual(a.focal, x, a.half_w); corr[4 * k + 1] = rej_virtual(a.focal, y, a.half_h);
+            rej_lift(a.cam, (double)forw[2 * k], (double)forw[2 * k + 1], x, y);
+            corr[4 * k + 2] = rej_virtual(a.focal, x, a.half_w); corr[4 * k + 3] = rej_virtual(a.focal, y, a.half_h);
+        }
+    }
+    if (tid == 0) { s_i[0] = -1; s_i[1] = -1; s_i[2] = 0; s_i[3] = 0; }
+    __syncthreads();
+
+    const double thr = a.thr;
+    for (int base = 0; base < a.hyps; base += ROUND) {
+        const int nh = a.hyps - base < ROUND ? a.hyps - base : ROUND;
+        if (tid < ROUND) s_cnt[tid] = 0;
+        if (tid < nh) {
+            int idx[8];
+            double Fm[9];
+            rej_sample8(a.seed, P.pair, (uint32_t)(base + tid), n, idx);
+            eight_point8_strided<ROUND>(corr, idx, s_N + tid, s_V + tid, Fm);
+#pragma unroll
+            for (int k = 0; k < 9; ++k) s_F[tid][k] = Fm[k];
+        }
+        __syncthreads();
+        for (int e = tid; e < nh * n; e += NT) {
+            const int h = e / n, k = e - h * n;
+            if (epipolar_error(s_F[h], corr + 4 * k) <= thr) atomicAdd(&s_cnt[h], 1);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int bc = s_i[0], bh = -1;
+            for (int h = 0; h < nh; ++h)
+                if (s_cnt[h] > bc) { bc = s_cnt[h]; bh = h; }        // (strictly more: ties stay with the lowest h)
+            if (bh >= 0) {
+                s_i[0] = bc; s_i[1] = base + bh;
+                for (int k = 0; k < 9; ++k) s_best[k] = s_F[bh][k];
+            }
+        }
+        __syncthreads();
+    }
+
+    const int best_c = s_i[0], hyp = s_i[1];
+    bool ok = best_c >= MINP;
+    if (ok) {
+        // the refit on the winner's inliers, every sum in correspondence order
+        for (int k = tid; k < n; k += NT) flag[k] = epipolar_error(s_best, corr + 4 * k) <= thr;
+        __syncthreads();
+        if (tid < 4) {
+            double s = 0.0;
+            for (int k = 0; k < n; ++k)
+                if (flag[k]) s += corr[4 * k + tid];
+            s_sum[tid] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            s_h.ca[0] = s_sum[0] / best_c; s_h.ca[1] = s_sum[1] / best_c;
+            s_h.cb[0] = s_sum[2] / best_c; s_h.cb[1] = s_sum[3] / best_c;
+        }
+        __syncthreads();
+        if (tid < 2) {
+            const double cx = tid ? s_h.cb[0] : s_h.ca[0], cy = tid ? s_h.cb[1] : s_h.ca[1];
+            double s = 0.0;
+            for (int k = 0; k < n; ++k)
+                if (flag[k]) {
+                    const double dx = corr[4 * k + 2 * tid] - cx, dy = corr[4 * k + 2 * tid + 1] - cy;
+                    s += sqrt(dx * dx + dy * dy);
+                }
+            s_sum[tid] = sqrt(2.0) / (s / best_c);
+        }
+        __syncthreads();
+        if (tid == 0) { s_h.sa = s_sum[0]; s_h.sb = s_sum[1]; }
+        __syncthreads();
+        if (tid < 45) {
+            int i, j;
+            tri_entry(tid, i, j);
+            const HartleyScale hs = s_h;
+            double s = 0.0;
+            for (int k = 0; k < n; ++k)
+                if (flag[k]) {
+                    double r[9];
+                    eight_point_row(corr + 4 * k, hs, r);
+                    s += row_entry(r, i) * row_entry(r, j);
+                }
+            s_N[(9 * i + j) * ROUND] = s;                    // lane 0's column
+            s_N[(9 * j + i) * ROUND] = s;
+        }
+        __syncthreads();
+        if (tid == 0) {
+            double Fm[9];
+            const HartleyScale hs = s_h;
+            eight_point_finish_strided<ROUND>(s_N, s_V, hs, Fm);
+            int fin = 1;
+            for (int k = 0; k < 9; ++k) { s_E[k] = Fm[k]; fin &= isfinite(Fm[k]) != 0; }
+            s_i[2] = fin;
+        }
+        __syncthreads();
+        ok = s_i[2] != 0;
+    }
+    if (ok) {
+        for (int k = tid; k < n; k += NT) {
+            const int in = epipolar_error(s_E, corr + 4 * k) <= thr;
+            mask[k] = (uint8_t)in;
+            if (in) atomicAdd(&s_i[3], 1);
+        }
+        __syncthreads();
+        if (tid == 0) { o->status = VIO_OK; o->hyp = hyp; o->n_inliers = s_i[3]; o->pad = 0; }
+        if (tid < 9) o->F[tid] = s_E[tid];
+    } else {
+        for (int k = tid; k < n; k += NT) mask[k] = 1;
+        if (tid == 0) { o->status = VIO_REJECT_FAIL_NO_MODEL; o->hyp = hyp; o->n_inliers = n; o->pad = 0; }
+        if (tid < 9) o->F[tid] = NAN;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// host side
+// ---------------------------------------------------------------------------------------------------------
+struct vio_reject {
+    int device = 0;
+    ErrText err = {0};
+    vio_reject_config cfg = {0u, VIO_REJECT_DEFAULT_HYPOTHESES, VIO_REJECT_DEFAULT_F_THRESHOLD, VIO_REJECT_DEFAULT_FOCAL_LENGTH};
+    vio_reject_camera camera = {};
+    RejCam cam = {};
+    bool have_camera = false;
+    Twin<char> tab;                                          // descriptors | staged floats | staged ids
+    Twin<char> out;                                          // results | masks, or un_pts | velocity, or the lifted doubles
+    DevBuf<char> scratch;                                    // corr | flags
+    StreamEvents<3> q;                                       // events: upload start, kernel start, kernel end
+    double timing[3] = {NAN, NAN, NAN};
+};
+
+namespace {
+
+vio_status fail_synced(vio_reject *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
+
+bool finite_pts(const float *p, int n) {
+    for (int k = 0; k < 2 * n; ++k)
+        if (!std::isfinite(p[k])) return false;
+    return true;
+}
+
+// the lift kernel over `count` items whose descriptors, floats and ids are staged in h->tab; the outputs come back in h->out
+vio_status run_lift(vio_reject *h, int count, int max_n, size_t b_tab, size_t o_flt, size_t o_ids, size_t n_pts, bool bare,
+                    std::chrono::steady_clock::time_point t0) {
+    const size_t b_out = bare ? sizeof(double) * 2 * n_pts : sizeof(float) * 4 * n_pts;
+    LiftArgs a;
+    std::memset(&a, 0, sizeof(a));
+    a.items = (const LiftItem *)h->tab.d;
+    a.pts = (const float *)(h->tab.d + o_flt);
+    a.ids = (const long long *)(h->tab.d + o_ids);
+    a.un = (float *)h->out.d; a.vel = a.un + 2 * n_pts;
+    a.lifted = (double *)h->out.d;
+    a.cam = h->cam; a.bare = bare; a.count = count;
+    const auto t1 = std::chrono::steady_clock::now();
+    hipStream_t q = h->q.stream;
+    (void)hipEventRecord(h->q.ev[0], q);
+    if (hipMemcpyAsync(h->tab.d, h->tab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
+    (void)hipEventRecord(h->q.ev[1], q);
+    hipLaunchKernelGGL(k_reject_lift, dim3((unsigned)((max_n + NT - 1) / NT), (unsigned)count), dim3(NT), 0, q, a);
+    (void)hipEventRecord(h->q.ev[2], q);
+    if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
+    if (hipMemcpyAsync(h->out.h, h->out.d, b_out, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+        return fail_synced(h, "kernel or read-back failed");
+    h->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count() + elapsed_ms(h->q.ev[0], h->q.ev[1]);
+    h->timing[1] = elapsed_ms(h->q.ev[1], h->q.ev[2]);
+    return VIO_OK;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t vio_reject_version(void) { return VIO_REJECT_VERSION; }
+
+const char *vio_reject_last_error(const vio_reject *h) { return h ? h->err : "NULL handle"; }
+
+vio_status vio_reject_create(int32_t device, void *stream, vio_reject **out) {
+    if (!out) return VIO_ERR_BAD_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
+    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
+    DeviceScope dev(device);
+    if (!dev.ok) return VIO_ERR_HIP;
+    vio_reject *h = new (std::nothrow) vio_reject();
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->device = device;
+    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
+    if (h->q.create_events() != hipSuccess) { vio_reject_destroy(h); return VIO_ERR_HIP; }
+    *out = h;
+    return VIO_OK;
+}
+
+void vio_reject_destroy(vio_reject *h) {
+    if (!h) return;
+    DeviceScope dev(h->device);
+    h->q.release();
+    delete h;                                                // (the buffers free themselves)
+}
+
+vio_status vio_reject_set_camera(vio_reject *h, const vio_reject_camera *cam) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (!cam) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: NULL camera");
+    if (cam->model != VIO_REJECT_MODEL_PINHOLE) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: model %d: only PINHOLE is built", cam->model);
+    const double v[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2};
+    for (double x : v)
+        if (!std::isfinite(x)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: a parameter is not finite");
+    if (cam->fx == 0.0 || cam->fy == 0.0 || cam->width < 1 || cam->height < 1)
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: fx, fy must not be 0, width and height at least 1");
+    h->camera = *cam;
+    h->camera.reserved = 0;
+    h->cam = rej_camera(cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2);
+    h->have_camera = true;
+    return VIO_OK;
+}
+
+vio_status vio_reject_set_config(vio_reject *h, const vio_reject_config *cfg) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (!cfg || cfg->ransac_hypotheses < 1 || cfg->ransac_hypotheses > VIO_REJECT_MAX_HYPOTHESES || !(cfg->f_threshold > 0.0) ||
+        !std::isfinite(cfg->f_threshold) || !(cfg->focal_length > 0.0) || !std::isfinite(cfg->focal_length))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_config: ransac_hypotheses in [1, %d], f_threshold and focal_length finite and > 0",
+                    VIO_REJECT_MAX_HYPOTHESES);
+    h->cfg = *cfg;
+    return VIO_OK;
+}
+
+vio_status vio_reject_timing(const vio_reject *h, double *out3) {
+    if (!h || !out3) return VIO_ERR_BAD_ARG;
+    std::memcpy(out3, h->timing, sizeof(h->timing));
+    return VIO_OK;
+}
+
+vio_status vio_reject_batch(vio_reject *h, int32_t count, const vio_reject_item *items, vio_reject_result *results, uint8_t *mask) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (count < 0 || count > MAX_ITEMS || (count > 0 && (!items || !results)))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
+    if (count == 0) return VIO_OK;
+    if (!h->have_camera) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_batch: no camera set");
+    const auto t0 = std::chrono::steady_clock::now();
+    // every argument of every item first: nothing is written or launched on an error
+    std::vector<RejPair> ps((size_t)count);
+    int64_t n_pts = 0, n_flt = 0, n_corr = 0;
+    bool any = false;
+    for (int i = 0; i < count; ++i) {
+        const vio_reject_item &it = items[i];
+        if (it.n < 0 || it.n > VIO_REJECT_MAX_POINTS) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: n must be in [0, %d]", i, VIO_REJECT_MAX_POINTS);
+        if (it.n > 0 && (!it.cur_pts || !it.forw_pts)) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: cur_pts and forw_pts are required", i);
+        n_pts += it.n;
+    }
+    if (n_pts > 0 && !mask) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_batch: NULL mask");
+    n_pts = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_reject_item &it = items[i];
+        RejPair &p = ps[(size_t)i];
+        std::memset(&p, 0, sizeof(p));
+        p.n = it.n; p.pair = it.pair;
+        p.finite = finite_pts(it.cur_pts, it.n) && finite_pts(it.forw_pts, it.n);
+        p.active = p.finite && it.n >= MINP;
+        p.o_pt = n_pts; n_pts += it.n;
+        if (!p.active) continue;                             // (nothing of it is staged)
+        p.o_pts = n_flt; n_flt += 4 * (int64_t)it.n;
+        p.o_corr = n_corr; n_corr += 4 * (int64_t)it.n;
+        any = true;
+    }
+    if (any) {
+        DeviceScope dev(h->device);
+        if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+        const size_t b_it = align256(sizeof(RejPair) * (size_t)count), b_tab = b_it + sizeof(float) * (size_t)n_flt;
+        const size_t b_res = align256(sizeof(RejRes) * (size_t)count), b_out = b_res + (size_t)n_pts;
+        const size_t b_corr = align256(sizeof(double) * (size_t)n_corr);
+        vio_status st;
+        if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->out.ensure(h->err, b_out)) != VIO_OK ||
+            (st = h->scratch.ensure(h->err, b_corr + sizeof(int32_t) * (size_t)n_pts)) != VIO_OK)
+            return st;
+        std::memcpy(h->tab.h, ps.data(), sizeof(RejPair) * (size_t)count);
+        float *hf = (float *)(h->tab.h + b_it);
+        for (int i = 0; i < count; ++i) {
+            const RejPair &p = ps[(size_t)i];
+            if (!p.active) continue;
+            std::memcpy(hf + p.o_pts, items[i].cur_pts, sizeof(float) * 2 * (size_t)p.n);
+            std::memcpy(hf + p.o_pts + 2 * (size_t)p.n, items[i].forw_pts, sizeof(float) * 2 * (size_t)p.n);
+        }
+        RansacArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.pairs = (const RejPair *)h->tab.d;
+        a.pts = (const float *)(h->tab.d + b_it);
+        a.corr = (double *)h->scratch.d;
+        a.flag = (int32_t *)(h->scratch.d + b_corr);
+        a.res = (RejRes *)h->out.d;
+        a.mask = (uint8_t *)(h->out.d + b_res);
+        a.cam = h->cam;
+        a.focal = h->cfg.focal_length; a.half_w = h->camera.width / 2.0; a.half_h = h->camera.height / 2.0;
+        a.thr = h->cfg.f_threshold * h->cfg.f_threshold;
+        a.seed = h->cfg.seed; a.hyps = h->cfg.ransac_hypotheses;
+        const auto t1 = std::chrono::steady_clock::now();
+        hipStream_t q = h->q.stream;
+        (void)hipEventRecord(h->q.ev[0], q);
+        if (hipMemcpyAsync(h->tab.d, h->tab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
+        (void)hipEventRecord(h->q.ev[1], q);
+        hipLaunchKernelGGL(k_reject_ransac, dim3((unsigned)count), dim3(NT), 0, q, a);
+        (void)hipEventRecord(h->q.ev[2], q);
+        if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
+        if (hipMemcpyAsync(h->out.h, h->out.d, b_out, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+            return fail_synced(h, "kernel or read-back failed");
+        h->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count() + elapsed_ms(h->q.ev[0], h->q.ev[1]);
+        h->timing[1] = elapsed_ms(h->q.ev[1], h->q.ev[2]);
+    }
+    vio_status ret = VIO_OK;
+    const RejRes *res = (const RejRes *)h->out.h;
+    const uint8_t *hm = any ? (const uint8_t *)(h->out.h + align256(sizeof(RejRes) * (size_t)count)) : nullptr;
+    for (int i = 0; i < count; ++i) {
+        const RejPair &p = ps[(size_t)i];
+        vio_reject_result &o = results[i];
+        o.reserved = 0;
+        for (int k = 0; k < 9; ++k) o.F[k] = NAN;
+        if (p.active) {
+            o.status = res[i].status; o.hyp = res[i].hyp;
+            o.n_inliers = std::min(std::max(res[i].n_inliers, 0), p.n);
+            std::memcpy(o.F, res[i].F, sizeof(o.F));
+            std::memcpy(mask + p.o_pt, hm + p.o_pt, (size_t)p.n);
+        } else if (p.finite) {                                  // the size gate
+            o.status = VIO_OK; o.hyp = -1; o.n_inliers = p.n;
+            if (p.n > 0) std::memset(mask + p.o_pt, 1, (size_t)p.n);
+        } else {
+            o.status = VIO_ERR_NOT_FINITE; o.hyp = -1; o.n_inliers = 0;
+            std::memset(mask + p.o_pt, 0, (size_t)p.n);
+            if (ret == VIO_OK) fail(h->err, VIO_ERR_NOT_FINITE, "item %d: a point is not finite", i);
+            ret = VIO_ERR_NOT_FINITE;
+        }
+    }
+    if (any) h->timing[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ret;
+}
+
+vio_status vio_reject_undistort_batch(vio_reject *h, int32_t count, const vio_reject_undistort_item *items, int32_t *status) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (count < 0 || count > MAX_ITEMS || (count > 0 && (!items || !status)))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_undistort_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
+    if (count == 0) return VIO_OK;
+    if (!h->have_camera) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_undistort_batch: no camera set");
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<LiftItem> its((size_t)count);
+    int64_t n_pts = 0, n_flt = 0, n_ids = 0;
+    int max_n = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_reject_undistort_item &it = items[i];
+        if (it.n < 0 || it.n > VIO_REJECT_MAX_POINTS || it.m < 0 || it.m > VIO_REJECT_MAX_POINTS)
+            return fail(h->err, VIO_ERR_BAD_ARG, "item %d: n and m must be in [0, %d]", i, VIO_REJECT_MAX_POINTS);
+        if ((it.n > 0 && (!it.pts || !it.ids || !it.un_pts || !it.velocity)) || (it.m > 0 && (!it.prev_ids || !it.prev_un_pts)))
+            return fail(h->err, VIO_ERR_BAD_ARG, "item %d: pts, ids, un_pts, velocity, prev_ids, prev_un_pts are required where they have rows", i);
+        if (it.m > 0 && !(std::isfinite(it.dt) && it.dt > 0.0)) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: dt must be finite and > 0", i);
+        LiftItem &d = its[(size_t)i];
+        std::memset(&d, 0, sizeof(d));
+        d.n = it.n; d.m = it.m; d.dt = it.m > 0 ? it.dt : 1.0;
+        d.active = finite_pts(it.pts, it.n);
+        d.o_pts = n_flt; n_flt += 2 * (int64_t)it.n;
+        d.o_prev = n_flt; n_flt += 2 * (int64_t)it.m;
+        d.o_ids = n_ids; n_ids += (int64_t)it.n + it.m;
+        d.o_out = n_pts; n_pts += it.n;
+        max_n = std::max(max_n, it.n);
+    }
+    vio_status ret = VIO_OK;
+    if (max_n > 0) {
+        DeviceScope dev(h->device);
+        if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+        const size_t b_it = align256(sizeof(LiftItem) * (size_t)count), b_flt = align256(sizeof(float) * (size_t)n_flt);
+        const size_t b_tab = b_it + b_flt + sizeof(int64_t) * (size_t)n_ids;
+        vio_status st;
+        if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->out.ensure(h->err, sizeof(float) * 4 * (size_t)n_pts)) != VIO_OK) return st;
+        std::memcpy(h->tab.h, its.data(), sizeof(LiftItem) * (size_t)count);
+        float *hf = (float *)(h->tab.h + b_it);
+        int64_t *hi = (int64_t *)(h->tab.h + b_it + b_flt);
+        for (int i = 0; i < count; ++i) {
+            const vio_reject_undistort_item &it = items[i];
+            const LiftItem &d = its[(size_t)i];
+            if (d.n > 0) { std::memcpy(hf + d.o_pts, it.pts, sizeof(float) * 2 * (size_t)d.n); std::memcpy(hi + d.o_ids, it.ids, sizeof(int64_t) * (size_t)d.n); }
+            if (d.m > 0) {
+                std::memcpy(hf + d.o_prev, it.prev_un_pts, sizeof(float) * 2 * (size_t)d.m);
+                std::memcpy(hi + d.o_ids + d.n, it.prev_ids, sizeof(int64_t) * (size_t)d.m);
+            }
+        }
+        st = run_lift(h, count, max_n, b_tab, b_it, b_it + b_flt, (size_t)n_pts, false, t0);
+        if (st != VIO_OK) return st;
+        const float *un = (const float *)h->out.h, *vel = un + 2 * (size_t)n_pts;
+        for (int i = 0; i < count; ++i) {
+            const LiftItem &d = its[(size_t)i];
+            if (d.n == 0) continue;
+            std::memcpy(items[i].un_pts, un + 2 * (size_t)d.o_out, sizeof(float) * 2 * (size_t)d.n);
+            std::memcpy(items[i].velocity, vel + 2 * (size_t)d.o_out, sizeof(float) * 2 * (size_t)d.n);
+        }
+    }
+    for (int i = 0; i < count; ++i) {
+        status[i] = its[(size_t)i].active ? VIO_OK : VIO_ERR_NOT_FINITE;
+        if (!its[(size_t)i].active) {
+            if (ret == VIO_OK) fail(h->err, VIO_ERR_NOT_FINITE, "item %d: a point is not finite", i);
+            ret = VIO_ERR_NOT_FINITE;
+        }
+    }
+    if (max_n > 0) h->timing[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ret;
+}
+
+vio_status vio_reject_lift(vio_reject *h, int32_t n, const float *pts, double *out) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (n < 0 || n > VIO_REJECT_MAX_POINTS || (n > 0 && (!pts || !out)))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_lift: n outside [0, %d] or a NULL array", VIO_REJECT_MAX_POINTS);
+    if (!h->have_camera) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_lift: no camera set");
+    if (n == 0) return VIO_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    LiftItem d;
+    std::memset(&d, 0, sizeof(d));
+    d.n = n; d.active = 1; d.dt = 1.0;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+    const size_t b_it = align256(sizeof(LiftItem)), b_tab = b_it + sizeof(float) * 2 * (size_t)n;
+    vio_status st;
+    if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->out.ensure(h->err, sizeof(double) * 2 * (size_t)n)) != VIO_OK) return st;
+    std::memcpy(h->tab.h, &d, sizeof(d));
+    std::memcpy(h->tab.h + b_it, pts, sizeof(float) * 2 * (size_t)n);
+    st = run_lift(h, 1, n, b_tab, b_it, b_it, (size_t)n, true, t0);
+    if (st != VIO_OK) return st;
+    std::memcpy(out, h->out.h, sizeof(double) * 2 * (size_t)n);
+    h->timing[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return VIO_OK;
+}
+
+}  // extern "C"

@@ -163,6 +163,162 @@ __device__ void eight_point(const double *corr, const int *idx, int n, double *F
     mm3(tmp, T1, Fm);
 }
 
+// ---- the same fit with the 9 x 9 matrices addressed through a stride (libvio_reject_hip: entry e of a lane's N and V at [e * S] of
+// its LDS column, include/vio_reject.h) and the 3 x 3 work unrolled into registers.  The operations and their order are jacobi's and
+// eight_point's above, so the bits are theirs.
+template <int S> __device__ __forceinline__ void jacobi9_strided(double *A, double *V) {
+    constexpr int n = 9;
+    for (int i = 0; i < n * n; ++i) V[i * S] = 0.0;
+    for (int i = 0; i < n; ++i) V[(i * n + i) * S] = 1.0;
+    for (int sw = 0; sw < VIO_SFM_JACOBI_SWEEPS; ++sw)
+        for (int p = 0; p < n - 1; ++p)
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A[(p * n + q) * S];
+                const double theta = (A[(q * n + q) * S] - A[(p * n + p) * S]) / (2.0 * apq);
+                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                if (apq == 0.0) t = 0.0;
+                if (!isfinite(t)) t = 0.0;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < n; ++k) {
+                    const double rp = A[(p * n + k) * S], rq = A[(q * n + k) * S];
+                    A[(p * n + k) * S] = c * rp - s * rq;
+                    A[(q * n + k) * S] = s * rp + c * rq;
+                }
+#pragma unroll
+                for (int k = 0; k < n; ++k) {
+                    const double cp = A[(k * n + p) * S], cq = A[(k * n + q) * S];
+                    A[(k * n + p) * S] = c * cp - s * cq;
+                    A[(k * n + q) * S] = s * cp + c * cq;
+                    const double vp = V[(k * n + p) * S], vq = V[(k * n + q) * S];
+                    V[(k * n + p) * S] = c * vp - s * vq;
+                    V[(k * n + q) * S] = s * vp + c * vq;
+                }
+            }
+}
+
+// jacobi(3, A, V) with every index a constant: A and V stay in registers
+__device__ __forceinline__ void jacobi3_unrolled(double *A, double *V) {
+    constexpr int n = 3;
+#pragma unroll
+    for (int i = 0; i < n * n; ++i) V[i] = 0.0;
+#pragma unroll
+    for (int i = 0; i < n; ++i) V[i * n + i] = 1.0;
+    for (int sw = 0; sw < VIO_SFM_JACOBI_SWEEPS; ++sw) {
+#pragma unroll
+        for (int p = 0; p < n - 1; ++p)
+#pragma unroll
+            for (int q = p + 1; q < n; ++q) {
+                const double apq = A[p * n + q];
+                const double theta = (A[q * n + q] - A[p * n + p]) / (2.0 * apq);
+                double t = (theta >= 0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(theta * theta + 1.0));
+                if (apq == 0.0) t = 0.0;
+                if (!isfinite(t)) t = 0.0;
+                const double c = 1.0 / sqrt(t * t + 1.0), s = t * c;
+#pragma unroll
+                for (int k = 0; k < n; ++k) {
+                    const double rp = A[p * n + k], rq = A[q * n + k];
+                    A[p * n + k] = c * rp - s * rq;
+                    A[q * n + k] = s * rp + c * rq;
+                }
+#pragma unroll
+                for (int k = 0; k < n; ++k) {
+                    const double cp = A[k * n + p], cq = A[k * n + q];
+                    A[k * n + p] = c * cp - s * cq;
+                    A[k * n + q] = s * cp + c * cq;
+                    const double vp = V[k * n + p], vq = V[k * n + q];
+                    V[k * n + p] = c * vp - s * vq;
+                    V[k * n + q] = s * vp + c * vq;
+                }
+            }
+    }
+}
+
+// Hartley's statistics of eight_point: the centroids and the scales of the correspondences corr[idx[0 .. n-1]]
+struct HartleyScale {
+    double ca[2], cb[2], sa, sb;
+};
+
+// row k of the 8-point design matrix of a correspondence p under the scaling
+__device__ __forceinline__ void eight_point_row(const double *p, const HartleyScale &h, double *r) {
+    const double x1 = (p[0] - h.ca[0]) * h.sa, y1 = (p[1] - h.ca[1]) * h.sa, x2 = (p[2] - h.cb[0]) * h.sb, y2 = (p[3] - h.cb[1]) * h.sb;
+    r[0] = x2 * x1; r[1] = x2 * y1; r[2] = x2; r[3] = y2 * x1; r[4] = y2 * y1; r[5] = y2; r[6] = x1; r[7] = y1; r[8] = 1.0;
+}
+
+// eight_point from the summed normal matrix on: N (destroyed) and V at stride S, the model to Fm
+template <int S> __device__ __forceinline__ void eight_point_finish_strided(double *N, double *V, const HartleyScale &h, double *Fm) {
+    jacobi9_strided<S>(N, V);
+    int m = 0;
+    for (int i = 1; i < 9; ++i)
+        if (N[(i * 9 + i) * S] < N[(m * 9 + m) * S]) m = i;
+    double Fh[9];
+#pragma unroll
+    for (int i = 0; i < 9; ++i) Fh[i] = V[(9 * i + m) * S];
+    double G[9], W[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) G[3 * r + c] = Fh[r] * Fh[c] + Fh[3 + r] * Fh[3 + c] + Fh[6 + r] * Fh[6 + c];
+    jacobi3_unrolled(G, W);
+    int m3 = 0;                                             // argmin_diag(3, G)
+    if (G[4] < G[0]) m3 = 1;
+    if (G[8] < (m3 == 1 ? G[4] : G[0])) m3 = 2;
+    double v[3];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) v[c] = m3 == 0 ? W[3 * c] : (m3 == 1 ? W[3 * c + 1] : W[3 * c + 2]);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+        const double fv = Fh[3 * r] * v[0] + Fh[3 * r + 1] * v[1] + Fh[3 * r + 2] * v[2];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Fh[3 * r + c] = Fh[3 * r + c] - fv * v[c];
+    }
+    const double T1[9] = {h.sa, 0, -h.sa * h.ca[0], 0, h.sa, -h.sa * h.ca[1], 0, 0, 1.0};
+    const double T2t[9] = {h.sb, 0, 0, 0, h.sb, 0, -h.sb * h.cb[0], -h.sb * h.cb[1], 1.0};
+    double tmp[9];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) tmp[3 * r + c] = T2t[3 * r] * Fh[c] + T2t[3 * r + 1] * Fh[3 + c] + T2t[3 * r + 2] * Fh[6 + c];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Fm[3 * r + c] = tmp[3 * r] * T1[c] + tmp[3 * r + 1] * T1[3 + c] + tmp[3 * r + 2] * T1[6 + c];
+}
+
+// eight_point(corr, idx, 8, Fm) of one thread with N and V at stride S
+template <int S> __device__ __forceinline__ void eight_point8_strided(const double *corr, const int *idx, double *N, double *V, double *Fm) {
+    constexpr int n = 8;
+    HartleyScale h;
+    h.ca[0] = 0; h.ca[1] = 0; h.cb[0] = 0; h.cb[1] = 0;
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+        const double *p = corr + 4 * idx[k];
+        h.ca[0] += p[0]; h.ca[1] += p[1]; h.cb[0] += p[2]; h.cb[1] += p[3];
+    }
+#pragma unroll
+    for (int k = 0; k < 2; ++k) { h.ca[k] /= n; h.cb[k] /= n; }
+    double ma = 0, mb = 0;
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+        const double *p = corr + 4 * idx[k];
+        const double ax = p[0] - h.ca[0], ay = p[1] - h.ca[1], bx = p[2] - h.cb[0], by = p[3] - h.cb[1];
+        ma += sqrt(ax * ax + ay * ay);
+        mb += sqrt(bx * bx + by * by);
+    }
+    h.sa = sqrt(2.0) / (ma / n); h.sb = sqrt(2.0) / (mb / n);
+    for (int i = 0; i < 81; ++i) N[i * S] = 0.0;
+#pragma unroll
+    for (int k = 0; k < n; ++k) {
+        double r[9];
+        eight_point_row(corr + 4 * idx[k], h, r);
+#pragma unroll
+        for (int i = 0; i < 9; ++i)
+#pragma unroll
+            for (int j = 0; j < 9; ++j) N[(9 * i + j) * S] += r[i] * r[j];
+    }
+    eight_point_finish_strided<S>(N, V, h, Fm);
+}
+
 __device__ __forceinline__ double epipolar_error(const double *F, const double *p) {
     const double ax = p[0], ay = p[1], bx = p[2], by = p[3];
     const double A = F[0] * ax + F[1] * ay + F[2], B = F[3] * ax + F[4] * ay + F[5], C = F[6] * ax + F[7] * ay + F[8];

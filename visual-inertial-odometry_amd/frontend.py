@@ -5,6 +5,7 @@
     for t, img in frames:
         out = ft.read_image(img, t)            # dict(pts (n, 2) float32, ids (n,), track_cnt (n,)); ids are -1 for new points ...
         ft.update_ids()                        # ... until this gives them the next free ids
+        ids, rows = ft.feature_frame()         # (with a rejecter) what the reference publishes to the estimator
 
 read_image tracks cur_pts into the new image, drops the points the tracker lost and those whose rounded position is outside `border`,
 adds one to every track_cnt, and on a published frame runs `reject` (if given), then setMask and the detection (which keeps at most
@@ -15,15 +16,22 @@ max_cnt points min_dist apart, the long tracks first), then addPoints (id -1, co
 set_config gets min_distance = min_dist (its other settings return to their defaults).  reject(cur_pts, forw_pts) -> a boolean array,
 True for the pairs to keep: the place of rejectWithF.
 
-Missing against the reference: rejectWithF (findFundamentalMat with RANSAC on the lifted points), undistortedPoints and the point
-velocities (the camera model), EQUALIZE (CLAHE).  One thing differs on purpose: prev_pts stays aligned with the points through setMask's
+`rejecter` is a reject.RejectHandle with its camera set, or any object with .reject(cur, forw, pair) -> a boolean array and
+.undistort(pts, ids, prev_ids, prev_un_pts, dt) -> (un_pts, velocity).  With one, read_image runs rejectWithF (feature_tracker.cpp:169-202)
+where the hook stands, with pair = the count of frames read, and after rolling prev / cur it runs undistortedPoints (:258-306): the
+dict gains un_pts (n, 2) float32, the normalised points, and velocity (n, 2) float32.  The previous frame's ids are kept as they were
+when its points were undistorted, before update_ids: a new point still carried -1 then, so its velocity is zero in its first two frames,
+as in the reference.  feature_frame() returns what the reference publishes.  With rejecter=None nothing of this happens.
+
+Missing against the reference: EQUALIZE (CLAHE), and the camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA).
+One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
 """
 import numpy as np
 
 
 class FeatureTracker:
-    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None):
+    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None):
         self.tracker, self.detector = tracker, detector
         self.max_cnt, self.min_dist, self.border, self.reject, self.mask = int(max_cnt), int(min_dist), int(border), reject, mask
         if hasattr(detector, "set_config"):
@@ -36,6 +44,12 @@ class FeatureTracker:
         self.n_new = 0                          # the points the last read_image added
         self.n_id = 0
         self.cur_time = self.prev_time = None
+        self.rejecter = rejecter
+        self.n_frames = 0                       # the frames read: rejectWithF's `pair`
+        self.cur_un_pts = np.zeros((0, 2), dtype=np.float32)
+        self.velocity = np.zeros((0, 2), dtype=np.float32)
+        self.prev_un_ids = np.zeros(0, dtype=np.int64)         # prev_un_pts_map: the ids and the normalised points of the frame before
+        self.prev_un_pts = np.zeros((0, 2), dtype=np.float32)
 
     def in_border(self, pts, shape):
         """readImage's inBorder on the rounded positions (cvRound: ties to even) in an image of `shape`."""
@@ -69,6 +83,9 @@ class FeatureTracker:
             if self.reject is not None and len(forw) > 0:
                 ok = np.asarray(self.reject(cur, forw), dtype=bool).reshape(-1)
                 cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
+            if self.rejecter is not None and len(forw) > 0:
+                ok = np.asarray(self.rejecter.reject(cur, forw, self.n_frames), dtype=bool).reshape(-1)
+                cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
             det = self.detector.detect(img, tracked=forw, track_cnt=cnt, mask=self.mask, max_total=self.max_cnt)
             order = np.asarray(det["keep_order"], dtype=np.int64)
             new = np.asarray(det["new_pts"], dtype=np.float32).reshape(-1, 2)
@@ -80,7 +97,30 @@ class FeatureTracker:
         self.prev_img, self.cur_img = self.cur_img, img
         self.prev_pts, self.cur_pts = cur, forw
         self.ids, self.track_cnt = ids, cnt
-        return dict(pts=self.cur_pts.copy(), ids=self.ids.copy(), track_cnt=self.track_cnt.copy())
+        self.n_frames += 1
+        out = dict(pts=self.cur_pts.copy(), ids=self.ids.copy(), track_cnt=self.track_cnt.copy())
+        if self.rejecter is not None:
+            dt = None if self.prev_time is None else self.cur_time - self.prev_time
+            un, vel = self.rejecter.undistort(self.cur_pts, self.ids, self.prev_un_ids, self.prev_un_pts, dt)
+            self.cur_un_pts = np.asarray(un, dtype=np.float32).reshape(-1, 2)
+            self.velocity = np.asarray(vel, dtype=np.float32).reshape(-1, 2)
+            self.prev_un_ids, self.prev_un_pts = self.ids.copy(), self.cur_un_pts.copy()       # (before update_ids: the quirk above)
+            out.update(un_pts=self.cur_un_pts.copy(), velocity=self.velocity.copy())
+        return out
+
+    def feature_frame(self):
+        """What the reference publishes of the frame (System::PubImageData, VM/src/System.cpp:228-250): the points with track_cnt > 1,
+        as (ids (n,) int64, rows (n, 7) float64 of x, y, 1, u, v, vx, vy), the per-frame input of FeatureManager and processImage.  Call
+        it after update_ids; it needs a rejecter."""
+        if self.rejecter is None:
+            raise RuntimeError("feature_frame needs a rejecter: the normalised points and the velocities are its")
+        k = np.nonzero(self.track_cnt > 1)[0]
+        rows = np.zeros((len(k), 7), dtype=np.float64)
+        rows[:, 0:2] = self.cur_un_pts[k]
+        rows[:, 2] = 1.0
+        rows[:, 3:5] = self.cur_pts[k]
+        rows[:, 5:7] = self.velocity[k]
+        return self.ids[k].copy(), rows
 
     def update_ids(self):
         """updateID over every point: a new point (id -1) gets the next free id.  Returns the ids."""
