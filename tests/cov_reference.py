@@ -1,7 +1,10 @@
 """numpy reference of the marginal covariances (include/vio_covariance.h), built from the oracle's own pieces:
 vioo_reproj_edge / vioo_reproj_xyz_edge for the Jacobians, vioo_robust_info2 for the robust weights, vioo_get_pose_hessian for the
-pose block of the Hessian.  Shared by test_covariance_reference.py (CPU) and test_gpu_covariance.py."""
+pose block of the Hessian.  Shared by test_covariance_reference.py (CPU), test_gpu_covariance.py and the limits modules
+(test_gpu_covariance_limits.py, test_gpu_residuals_limits.py), with the comparison the GPU modules hold the library to."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 
@@ -215,3 +218,57 @@ def make_case(vio, oracle_lib, case):
 def tolerance(S, keep):
     """What fp64 allows for an inverse of S[keep, keep] in the scaled metric: 100 eps kappa, and no less than 1e-10."""
     return max(1e-10, 100 * np.finfo(np.float64).eps * cond_scaled(S, keep))
+
+
+# ---- the comparison of a query's outputs with the reference (the GPU modules' tolerances) ------------------------------------------
+def reference_at(oracle_lib, ctx, w, gauge, xyz, landmarks=None):
+    """(pose_cov, lm, S, keep, h) of the numpy reference at the HIP context's state and from its own H_pp_schur."""
+    S, _ = ctx.get_schur_system()
+    poses, _, ext = ctx.get_window()
+    vals = ctx.get_landmarks_xyz() if xyz else ctx.get_landmarks()
+    keep = keep_index(ctx.cfg.ext_fixed, gauge, xyz)
+    P = pose_cov_from_schur(S, keep)
+    h, Wl = landmark_terms(oracle_lib, ctx.cfg, w, poses, ext, vals, landmarks)
+    return P, landmark_cov(P, h, Wl), S, keep, h
+
+
+def lm_err(got, want):
+    n = want.shape[0]
+    D = 1 if want.ndim == 1 else 3
+    g, v = got.reshape(n, D, D), want.reshape(n, D, D)
+    s = np.sqrt(np.abs(np.einsum("nii->ni", v)))
+    return float((np.abs(g - v) / (s[:, :, None] * s[:, None, :])).max())
+
+
+def check_cov(oracle_lib, ctx, w, P, L, xyz, gauge=1):
+    """(P, L) of a covariance query of a Cauchy or loss-free window against the reference at ctx's state, to tolerance(S, keep): the
+    assertions of test_gpu_covariance.py's parametrised test, with the landmark information the handle keeps against the solver's
+    (vio_get_landmark_system) and the reference's."""
+    assert ctx.cfg.loss_type != 1                                  # (Huber has landmarks to leave out: huber_ambiguous)
+    Pr, Lr, S, keep, h = reference_at(oracle_lib, ctx, w, gauge, xyz)
+    tol = tolerance(S, keep)
+    assert tol < 1e-6, tol
+    assert scaled_err(P, Pr) <= tol
+    assert np.array_equal(P, P.T)                                  # both triangles written from the one packed entry
+    fixed = np.setdiff1d(np.arange(PD), keep)
+    assert np.all(P[fixed] == 0.0) and np.all(P[:, fixed] == 0.0)
+    n = Lr.shape[0]
+    assert L.shape == Lr.shape
+    if n == 0:
+        return tol
+    assert lm_err(L, Lr) <= tol
+    hk = ctx._cov.landmark_information(xyz)
+    hll, _ = ctx.get_landmark_system()
+    assert np.abs(hk - hll).max() <= 1e-12 * np.abs(hll).max()
+    assert np.abs(hk - h.reshape(hk.shape)).max() <= 1e-12 * np.abs(h).max()
+    return tol
+
+
+COV_SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "visual-inertial-odometry_amd", "csrc",
+                          "vio_covariance.hip")
+
+
+def lm_tile(D, path=COV_SOURCE):
+    """LmNT<D>::v, the landmarks a workgroup of k_cov_landmarks<D> takes, as vio_covariance.hip defines it."""
+    src = open(path).read()
+    return int(re.search(r"template <> struct LmNT<%d> \{ static constexpr int v = (\d+); \};" % D, src).group(1))

@@ -1,7 +1,10 @@
 """numpy reference of the residual query (include/vio_residuals.h), built from the oracle's own pieces:
 vioo_reproj_edge / vioo_reproj_xyz_edge for the residuals, vioo_loss for rho0, vioo_imu_edge and vioo_inverse15 for the IMU chi2.
-Shared by test_residuals_reference.py (CPU) and test_gpu_residuals.py."""
+Shared by test_residuals_reference.py (CPU), test_gpu_residuals.py and test_gpu_residuals_limits.py, with the comparison the GPU
+modules hold the library to (check) and the window surgery of the limits module (edges dropped, truncated, permuted)."""
 import ctypes as C
+import os
+import re
 
 import numpy as np
 
@@ -76,7 +79,8 @@ def reference(oracle_lib, vio, cfg, w, poses, sb, ext, vals, err_prior, focal=FO
     for e in range(m):                                              # (a landmark's edges in the caller's order)
         l = lm[e]
         lmo[l, 0] += px[e]
-        lmo[l, 1] = px[e] if np.isnan(px[e]) or np.isnan(lmo[l, 1]) else max(lmo[l, 1], px[e])
+        if not np.isnan(lmo[l, 1]):                                 # (a NaN sticks: no later finite edge replaces it)
+            lmo[l, 1] = px[e] if np.isnan(px[e]) else max(lmo[l, 1], px[e])
         lmo[l, 2] += obs[e, 3]
         if dneg[e]:
             flags[l] |= 2
@@ -84,7 +88,7 @@ def reference(oracle_lib, vio, cfg, w, poses, sb, ext, vals, err_prior, focal=FO
     lmo[has, 0] /= cnt[has]
     flags[has & ~(lmo[:, 0] <= outlier_px)] |= 1
     vals = np.asarray(vals, dtype=np.float64)
-    bad_state = ~np.all(np.isfinite(vals.reshape(n, -1)), axis=1) if xyz else ~((vals > 0) & np.isfinite(vals))
+    bad_state = ~np.all(np.isfinite(vals.reshape(n, 3)), axis=1) if xyz else ~((vals > 0) & np.isfinite(vals))
     flags[bad_state] |= 4
 
     imu_edge = np.full(NW, np.nan)
@@ -186,3 +190,129 @@ def outlier_window(vio):
     w = vio.synth.make_window(2000, seed=OUTLIER_SEED)
     truth = corrupt(vio, w)
     return w, truth
+
+
+# ---- the comparison of a query's outputs with the reference (the GPU modules' tolerances) ------------------------------------------
+def rel_err(got, want):
+    """max |got - want| / |want|, with |want| floored at 1e-6 of the largest |want| (entries that are ~0 are held to that scale)."""
+    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
+    if want.size == 0:
+        return 0.0
+    scale = np.maximum(np.abs(want), 1e-6 * max(np.abs(want).max(), 1e-300))
+    return float((np.abs(got - want) / scale).max())
+
+
+def compare(got, ref, outlier_px=3.0, chi=None):
+    """A query's outputs against (obs, lm, flags, summary) of reference(): residual entries to 1e-12, e2, rho0 and every sum to 1e-10
+    relative, the flags exactly (but for a mean within rounding of the threshold).  chi: the context's vio_chi2, where it can give
+    one."""
+    obs, lmo, flags, s = ref
+    assert np.abs(got["obs"][:, :2] - obs[:, :2]).max(initial=0.0) <= 1e-12
+    assert rel_err(got["obs"][:, 2], obs[:, 2]) <= 1e-10
+    assert rel_err(got["obs"][:, 3], obs[:, 3]) <= 1e-10
+    for k in range(3):
+        assert rel_err(got["lm"][:, k], lmo[:, k]) <= 1e-10, k
+    near = np.abs(lmo[:, 0] - outlier_px) <= 1e-9 * outlier_px
+    assert np.array_equal(got["flags"][~near], flags[~near])
+    g = got["summary"]
+    if chi is not None:
+        assert abs(g["chi2"] - chi) <= 1e-10 * abs(chi), (g["chi2"], chi)
+    assert abs(g["chi2"] - s["chi2"]) <= 1e-10 * abs(s["chi2"])
+    for k in range(NW):
+        assert abs(g["imu_edge"][k] - s["imu_edge"][k]) <= 1e-10 * abs(s["imu_edge"][k]), k
+    for key in ("visual_robust", "visual_plain", "imu", "prior"):
+        assert abs(g[key] - s[key]) <= 1e-10 * abs(s[key]), key
+    assert rel_err(g["frame_robust"], s["frame_robust"]) <= 1e-10
+    assert np.array_equal(g["frame_edges"], s["frame_edges"])
+    assert np.array_equal(g["n_flagged"], [np.count_nonzero(got["flags"] & b) for b in (1, 2, 4)])
+
+
+def check(vio, oracle_lib, c, w, got, outlier_px=3.0):
+    """compare() with the reference at the state the context c holds, and with c's vio_chi2."""
+    ref = reference_of(oracle_lib, vio, c, w, outlier_px=outlier_px)
+    compare(got, ref, outlier_px, chi=c.chi2())
+    return ref
+
+
+# ---- the limits module's shapes and windows --------------------------------------------------------------------------------------
+RES_SOURCE = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "visual-inertial-odometry_amd", "csrc",
+                          "vio_residuals.hip")
+
+
+def tile_constants(path=RES_SOURCE):
+    """OBS_NT, LM_NT and TAIL_NT as vio_residuals.hip defines them: the shapes of test_gpu_residuals_limits.py follow the source."""
+    src = open(path).read()
+    return {k: int(re.search(r"^#define %s (\d+)\s*$" % k, src, re.M).group(1)) for k in ("OBS_NT", "LM_NT", "TAIL_NT")}
+
+
+EDGE_FIELDS = ("lm", "host", "target", "pts_i", "pts_j")
+EDGE_FIELDS_XYZ = ("lm", "frame", "pts")
+
+
+def take_edges(w, index):
+    """A copy of the window w with the edges `index` selects (a bool mask, a slice, or an index array: a permutation reorders the
+    caller's list), its landmarks and states as they are."""
+    out = w.copy()
+    for k in (EDGE_FIELDS_XYZ if getattr(w, "xyz", None) is not None else EDGE_FIELDS):
+        setattr(out, k, np.ascontiguousarray(getattr(w, k)[index]))
+    out.n_observations = int(out.lm.size)
+    return out
+
+
+def with_state(w, ctx):
+    """A copy of w that carries the state the context ctx holds (poses, speed and biases, extrinsic, landmarks): loaded into another
+    context it is queried at exactly that state, without a solve."""
+    out = w.copy()
+    out.poses, out.speed_bias, out.ext = ctx.get_window()
+    if getattr(w, "xyz", None) is not None:
+        out.xyz = np.array(ctx.get_landmarks_xyz())
+    else:
+        out.inv_depth = np.array(ctx.get_landmarks())
+    return out
+
+
+LIMITS_PIXEL_NOISE = 20.0          # px; see limits_window()
+
+
+def limits_window(vio, n, xyz=False, **kw):
+    """The windows test_gpu_residuals_limits.py queries: synth.make_window(_xyz) with 20 px of observation noise, and outliers of 40
+    to 60 px on 5 % of the landmarks (add_outliers).  Bit 0 and the flag counts are then not all zero, so their partial sums are
+    tested at the tile edges too; and check()'s relative bound on e2 and rho0 can be decided for (nearly) every edge, which on a clean
+    window at 1 px it cannot:
+    an edge's e2 = s^2 |r|^2 carries the relative error 2 dr / |r|, where dr -- 1 to 3 e-15, measured as the difference between the
+    library's and the oracle's residual -- is the rounding of world coordinates of tens of metres (eps x 25 m = 5.5e-15), in the
+    library and in the reference alike: neither is nearer the exact value.  1e-10 therefore needs |r| >= 2 dr / 1e-10 = 2 to 6 e-5
+    (0.01 to 0.03 px), or an entry under rel_err()'s floor of 1e-6 of the column's largest.  For e2 the floor is |r| < 1e-3 max |r|,
+    which the outliers lift to about 1e-4; for Cauchy's rho0 = log(1 + e2) the largest entry is about 7 whatever the window holds, the
+    floor stays at |r| < 9e-6, and an edge with 9e-6 < |r| < 6e-5 can miss the bound by a factor of up to 6.  At 1 px of noise
+    (sigma_r = 2.2e-3) one edge in 30 000 lies there: measured on clean windows after a short solve, rho0 differed by 2.6e-10
+    (16385 landmarks, seed 13), 1.4e-10 (600 ragged landmarks, seed 15), 1.3e-10 (515 landmarks, seed 5), and by 1.2e-10 on a
+    20000-landmark window without a prior after solve(10).  At 20 px such an edge is 400 times rarer."""
+    make = vio.synth.make_window_xyz if xyz else vio.synth.make_window
+    kw.setdefault("pixel_noise", LIMITS_PIXEL_NOISE / vio.synth.FOCAL)
+    return add_outliers(vio, make(n, **kw))
+
+
+def add_outliers(vio, w, fraction=0.05, seed=11, lo_px=40.0, hi_px=60.0):
+    """corrupt() for either kind of window and any size: every observation of a seeded `fraction` of the landmarks (at least one) is
+    shifted by lo_px .. hi_px pixels; returns the window."""
+    rng = np.random.RandomState(seed)
+    n = w.n_landmarks
+    bad = np.zeros(n, dtype=bool)
+    bad[rng.choice(n, max(1, int(round(fraction * n))), replace=False)] = True
+    key = "pts" if getattr(w, "xyz", None) is not None else "pts_j"
+    pts = np.array(getattr(w, key), dtype=np.float64)
+    for e in np.nonzero(bad[np.asarray(w.lm)])[0]:
+        a = rng.uniform(0, 2 * np.pi)
+        pts[e] += rng.uniform(lo_px, hi_px) / vio.synth.FOCAL * np.array([np.cos(a), np.sin(a)])
+    setattr(w, key, pts)
+    return w
+
+
+def behind_every_camera(w, l):
+    """World point l of an XYZ window mirrored through the camera that observes it first: at negative depth there, and (the window's
+    cameras move a fraction of the point's distance and barely turn) in every other frame that observes it."""
+    e = int(np.nonzero(np.asarray(w.lm) == l)[0][0])
+    f = int(w.frame[e])
+    cam = _rot(w.poses[f, 3:7]) @ w.ext[0:3] + w.poses[f, 0:3]
+    return 2.0 * cam - w.xyz[l]

@@ -65,3 +65,36 @@ def test_pose_block_helper(vio):
     assert np.array_equal(vio.speed_bias_block(P, 0), P[12:21, 12:21])
     with pytest.raises(IndexError):
         vio.pose_block(P, 11)
+
+
+def test_a_landmark_without_an_edge_has_no_information(vio, oracle_lib):
+    """What test_gpu_covariance_limits.py asks the device to refuse: with every edge of a landmark taken out of the list its h_l and
+    its coupling are exactly 0 (so 1 / h_l is no variance), and the other landmarks' terms do not change by a bit."""
+    import res_reference as rr
+    n = cr.lm_tile(1) + 1
+    w = vio.synth.make_window(n, seed=18)
+    c = oracle_lib.context(loss_type=vio.LOSS_CAUCHY)
+    c.load(w)
+    c.solve(3)
+    poses, _, ext = c.get_window()
+    vals = c.get_landmarks()
+    h, Wl = cr.landmark_terms(oracle_lib, c.cfg, w, poses, ext, vals)
+    assert np.all(h > 0)
+    for gone in ([0], [n - 1], [5, n - 1]):
+        bare = rr.take_edges(w, ~np.isin(w.lm, gone))
+        hb, Wb = cr.landmark_terms(oracle_lib, c.cfg, bare, poses, ext, vals)
+        assert np.all(hb[gone] == 0.0) and not Wb[gone].any()
+        rest = np.delete(np.arange(n), gone)
+        assert np.array_equal(hb[rest], h[rest]) and np.array_equal(Wb[rest], Wl[rest])
+        assert int(np.nonzero(~(hb > 0))[0].min()) == min(gone)           # the landmark the library names
+    # XYZ: H_ll = 0 fails Sylvester's criterion at its first minor
+    wx = vio.synth.make_window_xyz(cr.lm_tile(3) + 1, seed=18)
+    cx = oracle_lib.context(loss_type=vio.LOSS_CAUCHY)
+    cx.load(wx)
+    posx, _, extx = cx.get_window()
+    Hb, Wx = cr.landmark_terms(oracle_lib, cx.cfg, rr.take_edges(wx, wx.lm != 64), posx, extx, cx.get_landmarks_xyz())
+    assert not Hb[64].any() and not Wx[64].any() and np.all(np.linalg.det(Hb[:64]) > 0)
+
+
+def test_the_limits_module_reads_its_tiles_from_the_source():
+    assert (cr.lm_tile(1), cr.lm_tile(3)) == (128, 64)

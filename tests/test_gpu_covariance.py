@@ -12,23 +12,7 @@ import cov_reference as cr  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def reference(oracle_lib, ctx, w, gauge, xyz, landmarks=None):
-    """(pose_cov, lm, S, keep, h) of the numpy reference at the HIP context's state and from its own H_pp_schur."""
-    S, _ = ctx.get_schur_system()
-    poses, _, ext = ctx.get_window()
-    vals = ctx.get_landmarks_xyz() if xyz else ctx.get_landmarks()
-    keep = cr.keep_index(ctx.cfg.ext_fixed, gauge, xyz)
-    P = cr.pose_cov_from_schur(S, keep)
-    h, Wl = cr.landmark_terms(oracle_lib, ctx.cfg, w, poses, ext, vals, landmarks)
-    return P, cr.landmark_cov(P, h, Wl), S, keep, h
-
-
-def lm_err(got, want):
-    n = want.shape[0]
-    D = 1 if want.ndim == 1 else 3
-    g, v = got.reshape(n, D, D), want.reshape(n, D, D)
-    s = np.sqrt(np.abs(np.einsum("nii->ni", v)))
-    return float((np.abs(g - v) / (s[:, :, None] * s[:, None, :])).max())
+reference, lm_err = cr.reference_at, cr.lm_err         # (shared with the limits modules)
 
 
 @pytest.mark.parametrize("case", cr.CASES, ids=[c[0] for c in cr.CASES])

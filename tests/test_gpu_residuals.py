@@ -13,36 +13,7 @@ import res_reference as rr  # noqa: E402
 pytestmark = pytest.mark.gpu
 
 
-def rel_err(got, want):
-    """max |got - want| / |want|, with |want| floored at 1e-6 of the largest |want| (entries that are ~0 are held to that scale)."""
-    got, want = np.asarray(got, dtype=np.float64), np.asarray(want, dtype=np.float64)
-    if want.size == 0:
-        return 0.0
-    scale = np.maximum(np.abs(want), 1e-6 * max(np.abs(want).max(), 1e-300))
-    return float((np.abs(got - want) / scale).max())
-
-
-def check(vio, oracle_lib, c, w, got, outlier_px=3.0):
-    obs, lmo, flags, s = rr.reference_of(oracle_lib, vio, c, w, outlier_px=outlier_px)
-    assert np.abs(got["obs"][:, :2] - obs[:, :2]).max(initial=0.0) <= 1e-12
-    assert rel_err(got["obs"][:, 2], obs[:, 2]) <= 1e-10
-    assert rel_err(got["obs"][:, 3], obs[:, 3]) <= 1e-10
-    for k in range(3):
-        assert rel_err(got["lm"][:, k], lmo[:, k]) <= 1e-10, k
-    near = np.abs(lmo[:, 0] - outlier_px) <= 1e-9 * outlier_px
-    assert np.array_equal(got["flags"][~near], flags[~near])
-    g = got["summary"]
-    chi = c.chi2()
-    assert abs(g["chi2"] - chi) <= 1e-10 * abs(chi), (g["chi2"], chi)
-    assert abs(g["chi2"] - s["chi2"]) <= 1e-10 * abs(s["chi2"])
-    for k in range(rr.NW):
-        assert abs(g["imu_edge"][k] - s["imu_edge"][k]) <= 1e-10 * abs(s["imu_edge"][k]), k
-    for key in ("visual_robust", "visual_plain", "imu", "prior"):
-        assert abs(g[key] - s[key]) <= 1e-10 * abs(s[key]), key
-    assert rel_err(g["frame_robust"], s["frame_robust"]) <= 1e-10
-    assert np.array_equal(g["frame_edges"], s["frame_edges"])
-    assert np.array_equal(g["n_flagged"], [np.count_nonzero(got["flags"] & b) for b in (1, 2, 4)])
-    return obs, lmo, flags, s
+check, rel_err = rr.check, rr.rel_err         # (shared with test_gpu_residuals_limits.py)
 
 
 @pytest.mark.parametrize("case", rr.CASES, ids=[c[0] for c in rr.CASES])

@@ -62,3 +62,38 @@ def test_the_default_driver_never_loads_the_imu_library(vio, oracle_lib, monkeyp
         runs.append(drv.run())
         assert drv.repropagated == []
     assert np.array_equal(runs[0], runs[1])
+
+
+# ---- what test_gpu_imu_limits.py rests on, without a GPU: the host routine (vio_preintegrate, no kernel) and the numpy restatement --
+def test_host_routine_against_the_numpy_restatement(vio):
+    """The measurement behind test_gpu_imu_limits.py's bound: the largest per-block relative difference between vio_preintegrate and
+    vio.synth.preintegrate over imu_reference.limits_inputs().  Both run on the CPU and differ by rounding order alone; the value
+    measured when the bound was set is imu_reference.HOST_VS_NUMPY, and the host routine, like the device, stays within
+    NUMPY_FACTOR times it."""
+    import imu_reference as ir
+    hip = vio.load_hip()
+    worst = (0.0, None)
+    for name, ivs, ba, bg, noise in ir.limits_inputs(vio):
+        if name == "ragged":
+            assert sorted({len(iv["dt"]) for iv in ivs}) == list(ir.LIMIT_SIZES)
+        for k, iv in enumerate(ivs):
+            h, r = ir.host_record(hip, iv, ba[k], bg[k], noise), ir.numpy_record(vio, iv, ba[k], bg[k], noise)
+            assert np.array_equal(ir.vec(h)[11:17], ir.vec(r)[11:17])
+            d, blk = ir.worst_block(h, r)
+            if d > worst[0]:
+                worst = (d, (name, k, len(iv["dt"])) + blk)
+    print("\nhost against numpy: largest block difference %.4e at %s (recorded: %.3e)" % (worst[0], worst[1], ir.HOST_VS_NUMPY))
+    assert 0.0 < worst[0] <= ir.NUMPY_FACTOR * ir.HOST_VS_NUMPY, worst
+
+
+def test_zero_dt_samples_on_the_host_and_in_numpy(vio):
+    """The rule test_gpu_imu_limits.py asks of the device: the acc and gyr of a dt == 0 sample that no dt != 0 sample reads as a0 / g0
+    change nothing, those of one that is read do."""
+    import imu_reference as ir
+    hip = vio.load_hip()
+    ivs = ir.zero_dt_intervals()
+    ba, bg = np.full(3, 0.05), np.full(3, -0.01)
+    for record in (lambda iv: ir.host_record(hip, iv, ba, bg, ir.RAGGED_NOISE), lambda iv: ir.numpy_record(vio, iv, ba, bg, ir.RAGGED_NOISE)):
+        base, same, other = [ir.vec(record(iv)).copy() for iv in ivs]
+        assert np.array_equal(base, same)
+        assert not np.array_equal(base[1:11], other[1:11]) and not np.array_equal(base[242:467], other[242:467])

@@ -2,6 +2,7 @@
 breakdown adds up to the oracle context's vio_chi2 under every loss, with the extrinsic fixed and free, for XYZ landmarks, with a
 marginalisation prior and with an IMU edge missing; and on the seeded outlier window its flags meet the recall and precision the GPU
 tests hold the library to."""
+import math
 import os
 import sys
 
@@ -73,3 +74,133 @@ def test_flag_rules_on_a_broken_state(vio, oracle_lib):
     assert np.isnan(lmo[7, 0]) and np.isnan(lmo[7, 1])
     assert not np.delete(flags, [3, 7]).any()
     assert list(s["n_flagged"]) == [int(flags[3] & 1) + 1, 1, 2]
+
+
+# ---- the rules test_gpu_residuals_limits.py asks the device for, established here first ------------------------------------------
+def _state(c):
+    poses, sb, ext = c.get_window()
+    _, err = c.get_prior()
+    return poses, sb, ext, err
+
+
+def test_landmarks_and_frames_without_edges(vio, oracle_lib):
+    """A landmark without an edge reports zeros and no REPROJ bit, a frame without an edge 0 edges and 0.0; everything else is what
+    the full window's reference gives for the edges that are left."""
+    n = 300
+    w = vio.synth.make_window(n, seed=12)
+    gone, frame = [0, 255, 256, n - 1], 5
+    keep = ~np.isin(w.lm, gone) & (w.target != frame)
+    wd = rr.take_edges(w, keep)
+    assert 0 < wd.lm.size < w.lm.size and np.all(np.bincount(wd.lm, minlength=n)[gone] == 0)
+    c = oracle_lib.context(loss_type=vio.LOSS_CAUCHY)
+    c.load(w)
+    poses, sb, ext, err = _state(c)
+    vals = np.array(c.get_landmarks())
+    obs, lmo, flags, s = rr.reference(oracle_lib, vio, c.cfg, w, poses, sb, ext, vals, err, outlier_px=1e4)
+    obd, lmd, fld, sd = rr.reference(oracle_lib, vio, c.cfg, wd, poses, sb, ext, vals, err, outlier_px=1e4)
+    assert np.array_equal(obd, obs[keep])                          # an edge's row depends on that edge alone
+    assert np.all(lmd[gone] == 0.0) and not fld[gone].any()
+    whole = np.bincount(wd.lm, minlength=n) == np.bincount(w.lm, minlength=n)
+    assert whole.sum() > n // 3 and np.array_equal(lmd[whole], lmo[whole]) and np.array_equal(fld[whole], flags[whole])
+    assert sd["frame_edges"][frame] == 0 and sd["frame_robust"][frame] == 0.0
+    assert np.array_equal(sd["frame_edges"], np.bincount(w.target[keep], minlength=rr.NF))
+    assert sd["frame_edges"].sum() == wd.lm.size
+    assert abs(sd["visual_robust"] - math.fsum(obs[keep, 3])) <= 1e-13 * sd["visual_robust"]
+    assert abs(sd["visual_plain"] - math.fsum(obs[keep, 2])) <= 1e-13 * sd["visual_plain"]
+    assert np.array_equal(sd["imu_edge"], s["imu_edge"]) and sd["prior"] == s["prior"]
+    assert list(sd["n_flagged"]) == [0, 0, 0]
+
+
+def test_xyz_point_behind_the_cameras_and_nan_coordinate(vio, oracle_lib):
+    """XYZ: a finite point behind every camera that observes it has bit 1 alone and a finite mean; a NaN coordinate has bits 0 and 2,
+    NaN mean and maximum, and no bit 1 (a NaN depth is not <= 0)."""
+    w = vio.synth.make_window_xyz(40, seed=5)
+    w.xyz = np.array(w.xyz)
+    behind, nan = [3, 17], [7, 39]
+    for l in behind:
+        w.xyz[l] = rr.behind_every_camera(w, l)
+    for k, l in enumerate(nan):
+        w.xyz[l, k] = np.nan
+    c = oracle_lib.context()
+    c.load(w)
+    poses, sb, ext, err = _state(c)
+    obs, lmo, flags, s = rr.reference(oracle_lib, vio, c.cfg, w, poses, sb, ext, w.xyz, err, outlier_px=1e4)
+    for l in behind:
+        edges = np.nonzero(w.lm == l)[0]
+        assert all(rr._depth(poses, ext, w, e, w.xyz, True) < 0.0 for e in edges)     # every observing camera, not just the first
+        assert flags[l] == 2 and np.all(np.isfinite(lmo[l])) and np.all(np.isfinite(obs[edges]))
+    for l in nan:
+        assert flags[l] == 5 and np.isnan(lmo[l, 0]) and np.isnan(lmo[l, 1]) and np.isnan(lmo[l, 2])
+    others = np.delete(np.arange(40), behind + nan)
+    assert not flags[others].any() and np.all(np.isfinite(lmo[others]))
+    assert list(s["n_flagged"]) == [2, 2, 2]
+    assert np.isnan(s["visual_robust"]) and np.isnan(s["chi2"])
+    nan_frames = np.unique(w.frame[np.isin(w.lm, nan)])
+    assert np.array_equal(np.nonzero(np.isnan(s["frame_robust"]))[0], nan_frames)
+
+
+def test_a_nan_maximum_sticks(vio, oracle_lib):
+    """One NaN observation among a landmark's edges: the mean and the maximum are NaN whatever the edge's place in the list (the
+    first edge's NaN is not replaced by the finite ones after it), bit 0 is set and nothing else."""
+    w = vio.synth.make_window(20, seed=5)
+    c = oracle_lib.context()
+    c.load(w)
+    poses, sb, ext, err = _state(c)
+    vals = np.array(c.get_landmarks())
+    for l, which in ((4, 0), (9, 2), (15, -1)):
+        wn = w.copy()
+        wn.pts_j[np.nonzero(w.lm == l)[0][which], 1] = np.nan
+        _, lmo, flags, s = rr.reference(oracle_lib, vio, c.cfg, wn, poses, sb, ext, vals, err, outlier_px=1e4)
+        assert np.isnan(lmo[l, 0]) and np.isnan(lmo[l, 1]) and np.isnan(lmo[l, 2]) and flags[l] == 1
+        assert not np.delete(flags, l).any() and np.all(np.isfinite(np.delete(lmo, l, axis=0)))
+
+
+def test_edges_in_any_order(vio, oracle_lib):
+    """The caller's order is kept: a permuted list gives the permuted rows bit for bit, the same flags and frame counts, and the
+    per-landmark and per-frame sums to the rounding of another summation order."""
+    w = vio.synth.make_window(60, seed=8, ragged=True)
+    c = oracle_lib.context(loss_type=vio.LOSS_CAUCHY)
+    c.load(w)
+    c.solve(3)
+    perm = np.random.RandomState(4).permutation(w.lm.size)
+    wp = rr.take_edges(w, perm)
+    assert not np.array_equal(wp.lm, w.lm) and np.array_equal(np.sort(wp.lm), w.lm)
+    obs, lmo, flags, s = rr.reference_of(oracle_lib, vio, c, w)
+    obp, lmp, flp, sp = rr.reference_of(oracle_lib, vio, c, wp)
+    assert np.array_equal(obp, obs[perm])
+    assert np.array_equal(lmp[:, 1], lmo[:, 1]) and np.allclose(lmp, lmo, rtol=1e-13, atol=0.0)
+    assert np.array_equal(flp, flags) and np.array_equal(sp["frame_edges"], s["frame_edges"])
+    assert np.allclose(sp["frame_robust"], s["frame_robust"], rtol=1e-13, atol=0.0)
+    for k in ("visual_robust", "visual_plain", "chi2"):
+        assert abs(sp[k] - s[k]) <= 1e-13 * abs(s[k]), k
+
+
+def test_empty_windows(vio, oracle_lib):
+    """No landmarks and no edges: empty outputs, the visual terms exactly 0, and chi2 still the oracle's (IMU alone).  Landmarks
+    without any edge: rows of zeros and no flag."""
+    w = vio.synth.make_window(0, seed=5)
+    assert w.lm.size == 0 and w.n_landmarks == 0
+    c = oracle_lib.context(loss_type=vio.LOSS_CAUCHY)
+    c.load(w)
+    c.solve(3)
+    obs, lmo, flags, s = rr.reference_of(oracle_lib, vio, c, w)
+    assert obs.shape == (0, 4) and lmo.shape == (0, 3) and flags.shape == (0,)
+    assert s["visual_robust"] == 0.0 and s["visual_plain"] == 0.0 and not s["frame_robust"].any() and not s["frame_edges"].any()
+    chi = c.chi2()
+    assert s["imu"] > 0.0 and abs(s["chi2"] - chi) <= 1e-12 * abs(chi) and list(s["n_flagged"]) == [0, 0, 0]
+    wx = vio.synth.make_window_xyz(0, seed=5)                     # ... the same for an XYZ window
+    cx = oracle_lib.context(loss_type=vio.LOSS_CAUCHY)
+    cx.load(wx)
+    ox, lx, fx, sx = rr.reference_of(oracle_lib, vio, cx, wx)
+    assert ox.shape == (0, 4) and lx.shape == (0, 3) and fx.shape == (0,) and sx["visual_robust"] == 0.0 and sx["imu"] > 0.0
+    w = rr.take_edges(vio.synth.make_window(5, seed=5), np.zeros(20, dtype=bool))
+    c.load(w)
+    poses, sb, ext, err = _state(c)
+    obs, lmo, flags, s2 = rr.reference(oracle_lib, vio, c.cfg, w, poses, sb, ext, np.array(c.get_landmarks()), err)
+    assert obs.shape == (0, 4) and lmo.shape == (5, 3) and not lmo.any() and not flags.any()
+    assert s2["visual_robust"] == 0.0 and not s2["frame_edges"].any() and s2["chi2"] == 0.5 * (s2["imu"] + s2["prior"])
+
+
+def test_the_limits_module_reads_its_tiles_from_the_source():
+    t = rr.tile_constants()
+    assert t == {"OBS_NT": 256, "LM_NT": 256, "TAIL_NT": 256}, t
