@@ -31,5 +31,5 @@ keys = ["VGPRs", "AGPRs", "VGPRs Spill", "ScratchSize [bytes/lane]", "TotalSGPRs
 print("%-34s %6s %6s %6s %8s %6s %5s %8s" % ("kernel", "VGPR", "AGPR", "spill", "scratch", "SGPR", "occ", "LDS(st)"))
 for r in rows:
     name = re.sub(r"^_Z\d+", "", r["name"])
-    name = re.sub(r"(12DeviceTables|9BatchArgs|13ReduceTables|9TriTables|7SfmArgs|7PnpArgs|7DetArgs|10RansacArgs|8LiftArgs).*$", "", name)
+    name = re.sub(r"(12DeviceTables|9BatchArgs|13ReduceTables|9TriTables|7SfmArgs|7PnpArgs|7DetArgs|10RansacArgs|8LiftArgs|9ClaheArgs).*$", "", name)
     print("%-34s %6s %6s %6s %8s %6s %5s %8s" % tuple([name[:34]] + [r.get(k, "-") for k in keys]))

@@ -5,10 +5,11 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, covariance, detect, exrot, flow, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, clahe, covariance, detect, exrot, flow, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
+from .clahe import ClaheHandle, ClaheLib
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
 from .detect import DetectHandle, DetectLib
 from .exrot import ExrotHandle, ExrotLib
@@ -37,6 +38,7 @@ FLOW_LIB = os.path.join(PKG_DIR, "csrc", "libvio_flow_hip.so")   # include/vio_f
 DETECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_detect_hip.so")   # include/vio_detect.h; calls nothing of libvio_hip.so either
 
 REJECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_reject_hip.so")   # include/vio_reject.h; calls nothing of libvio_hip.so either
+CLAHE_LIB = os.path.join(PKG_DIR, "csrc", "libvio_clahe_hip.so")     # include/vio_clahe.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -142,3 +144,8 @@ def load_detect():
 def load_reject():
     """Load the outlier rejection and undistortion library (csrc/libvio_reject_hip.so)."""
     return _load_companion("reject", RejectLib, REJECT_LIB)
+
+
+def load_clahe():
+    """Load the CLAHE equalisation library (csrc/libvio_clahe_hip.so)."""
+    return _load_companion("clahe", ClaheLib, CLAHE_LIB)

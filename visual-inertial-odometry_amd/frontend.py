@@ -23,7 +23,11 @@ dict gains un_pts (n, 2) float32, the normalised points, and velocity (n, 2) flo
 when its points were undistorted, before update_ids: a new point still carried -1 then, so its velocity is zero in its first two frames,
 as in the reference.  feature_frame() returns what the reference publishes.  With rejecter=None nothing of this happens.
 
-Missing against the reference: EQUALIZE (CLAHE), and the camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA).
+`equalizer` is a clahe.ClaheHandle, or any object with .apply(img) -> a uint8 image of the same shape: the reference's EQUALIZE
+(feature_tracker.cpp:87-95).  With one, read_image equalises the image first, so the tracker, the detector and cur_img / prev_img see
+equalised images only, as in the reference.  With equalizer=None nothing of this happens.
+
+Missing against the reference: the camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA).
 One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
 """
@@ -31,7 +35,7 @@ import numpy as np
 
 
 class FeatureTracker:
-    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None):
+    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None, equalizer=None):
         self.tracker, self.detector = tracker, detector
         self.max_cnt, self.min_dist, self.border, self.reject, self.mask = int(max_cnt), int(min_dist), int(border), reject, mask
         if hasattr(detector, "set_config"):
@@ -45,6 +49,7 @@ class FeatureTracker:
         self.n_id = 0
         self.cur_time = self.prev_time = None
         self.rejecter = rejecter
+        self.equalizer = equalizer
         self.n_frames = 0                       # the frames read: rejectWithF's `pair`
         self.cur_un_pts = np.zeros((0, 2), dtype=np.float32)
         self.velocity = np.zeros((0, 2), dtype=np.float32)
@@ -66,6 +71,10 @@ class FeatureTracker:
         img = np.asarray(img)
         if img.dtype != np.uint8 or img.ndim != 2:
             raise ValueError("an image must be a 2-d uint8 array")
+        if self.equalizer is not None:
+            img = np.asarray(self.equalizer.apply(img))
+            if img.dtype != np.uint8 or img.ndim != 2:
+                raise ValueError("the equalizer must return a 2-d uint8 array")
         self.prev_time, self.cur_time = self.cur_time, t
         first = self.cur_img is None
         if first:
