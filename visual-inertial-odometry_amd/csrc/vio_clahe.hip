@@ -13,6 +13,7 @@
 //                    global memory instead was measured and is slower.
 // No floating-point atomics, no spin-waits, nothing between workgroups.  Contraction is off as in vio_flow.hip and vio_detect.hip: here
 // it matters, a fused multiply-add in the blend changes output bytes (vio_clahe_math.h).
+// The kernels themselves are in vio_clahe_body.inc, which libvio_frame_hip compiles too; the host side is here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,139 +31,9 @@
 
 #include "vio_clahe_math.h"
 
-constexpr int WAVE = 64;
-constexpr int BINS = VIO_CLAHE_BINS;
-constexpr int NT = 256;                 // threads of both kernels
-constexpr int NW = NT / WAVE;
-constexpr int TX = VIO_CLAHE_TILE_X, TY = VIO_CLAHE_TILE_Y;
-constexpr int PX = 4;                   // pixels of a thread per pass
-constexpr int ROWS = NT / (TX / PX);    // rows of a pass
+#include "vio_clahe_body.inc"
+
 constexpr int MAX_ITEMS = 4096;
-static_assert(NT == BINS, "k_clahe_lut: thread b owns bin b");
-static_assert(TX % PX == 0 && NT % (TX / PX) == 0 && TY % ROWS == 0, "k_clahe_apply: whole passes over the block of pixels");
-
-struct ClaheItemD {
-    int32_t w, h, pitch, ext;
-    int32_t tile_w, tile_h, area, clip;
-    int32_t ptiles_x, ptiles;           // the blocks of pixels of k_clahe_apply: across, and in all
-    float lut_scale, inv_tile_w, inv_tile_h;
-    int32_t pad;
-    int64_t img;                        // the byte offset of the source in the input buffer and of the result in the output buffer
-};
-
-struct ClaheArgs {
-    const ClaheItemD *items;
-    const uint8_t *src;
-    uint8_t *dst;
-    uint8_t *luts;                      // [count][tiles_y][tiles_x][256]
-    int32_t tiles_x, tiles_y, count;
-};
-
-// ---------------------------------------------------------------------------------------------------------
-// kernels
-// ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT) void k_clahe_lut(ClaheArgs a) {
-    __shared__ int32_t hist[NW][BINS];
-    __shared__ int32_t slot[2][NW];
-    const int item = blockIdx.z, tile = blockIdx.x;
-    if (item >= a.count || tile >= a.tiles_x * a.tiles_y) return;      // (the whole workgroup: no barrier was reached)
-    const ClaheItemD &D = a.items[item];
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) hist[k][tid] = 0;
-    __syncthreads();
-    const int w = D.w, h = D.h, tile_w = D.tile_w, area = D.area;
-    const int x0 = (tile % a.tiles_x) * tile_w, y0 = (tile / a.tiles_x) * D.tile_h;
-    const uint8_t *img = a.src + D.img;
-    // pixel i of the tile, row by row, belongs to thread i mod NT; (tx, ty) follows i without a division per pixel
-    int tx = tid % tile_w, ty = tid / tile_w;
-    const int step_x = NT % tile_w, step_y = NT / tile_w;
-    for (int i = tid; i < area; i += NT) {
-        int x = x0 + tx, y = y0 + ty;
-        if (D.ext) {                                                    // (positions past the image exist only in the extended one)
-            if (x >= w) x = clahe_refl(x, w);
-            if (y >= h) y = clahe_refl(y, h);
-        }
-        atomicAdd(&hist[wv][img[(int64_t)y * D.pitch + x]], 1);
-        tx += step_x; ty += step_y;
-        if (tx >= tile_w) { tx -= tile_w; ty += 1; }
-    }
-    __syncthreads();
-    int32_t v = 0;
-#pragma unroll
-    for (int k = 0; k < NW; ++k) v += hist[k][tid];
-    if (D.clip > 0) {                                                   // (the same in every thread)
-        int32_t excess = v > D.clip ? v - D.clip : 0;
-#pragma unroll
-        for (int s = 1; s < WAVE; s <<= 1) excess += __shfl_xor(excess, s, WAVE);
-        if (lane == 0) slot[0][wv] = excess;
-        __syncthreads();
-        excess = 0;
-#pragma unroll
-        for (int k = 0; k < NW; ++k) excess += slot[0][k];
-        v = clahe_redistribute(v, tid, D.clip, excess);
-    }
-    int32_t sum = v;
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const int32_t o = __shfl_up(sum, s, WAVE);
-        if (lane >= s) sum += o;
-    }
-    if (lane == WAVE - 1) slot[1][wv] = sum;
-    __syncthreads();
-    for (int k = 0; k < wv; ++k) sum += slot[1][k];
-    a.luts[((int64_t)item * (a.tiles_x * a.tiles_y) + tile) * BINS + tid] = clahe_lut_value(sum, D.lut_scale);
-}
-
-__global__ __launch_bounds__(NT) void k_clahe_apply(ClaheArgs a) {
-    extern __shared__ __align__(16) uint8_t lds[];                      // tiles_y * tiles_x * 256 bytes: room for every LUT of an image
-    const int item = blockIdx.z;
-    if (item >= a.count) return;
-    const ClaheItemD &D = a.items[item];
-    if ((int)blockIdx.x >= D.ptiles) return;                            // (the whole workgroup: no barrier was reached)
-    const int w = D.w, h = D.h, tid = threadIdx.x;
-    const int px0 = ((int)blockIdx.x % D.ptiles_x) * TX, py0 = ((int)blockIdx.x / D.ptiles_x) * TY;
-    const uint8_t *glut = a.luts + (int64_t)item * (a.tiles_x * a.tiles_y) * BINS;
-    // the tiles of the block's first and last pixel bound those of every pixel between them
-    int tx_lo, ty_lo, tx_hi, ty_hi, t1, t2;
-    float f0, f1;
-    clahe_axis(px0, D.inv_tile_w, a.tiles_x, tx_lo, t2, f0, f1);
-    clahe_axis((px0 + TX < w ? px0 + TX : w) - 1, D.inv_tile_w, a.tiles_x, t1, tx_hi, f0, f1);
-    clahe_axis(py0, D.inv_tile_h, a.tiles_y, ty_lo, t2, f0, f1);
-    clahe_axis((py0 + TY < h ? py0 + TY : h) - 1, D.inv_tile_h, a.tiles_y, t1, ty_hi, f0, f1);
-    const int nx = tx_hi - tx_lo + 1, ny = ty_hi - ty_lo + 1;
-    const int per = nx * (BINS / 16);                                   // a row of tiles is nx * 256 contiguous bytes: 16-byte pieces
-    for (int id = tid; id < ny * per; id += NT) {
-        const int j = id / per, k = id - j * per;
-        ((uint4 *)lds)[id] = ((const uint4 *)(glut + (int64_t)((ty_lo + j) * a.tiles_x + tx_lo) * BINS))[k];
-    }
-    __syncthreads();
-    // entry v of tile (ty, tx) in the staged range
-    auto lut = [&](int ty, int tx, int v) -> uint8_t { return lds[((ty - ty_lo) * nx + (tx - tx_lo)) * BINS + v]; };
-    const int gx = tid % (TX / PX), gy = tid / (TX / PX);
-#pragma unroll
-    for (int pass = 0; pass < TY / ROWS; ++pass) {
-        const int x = px0 + gx * PX, y = py0 + pass * ROWS + gy;
-        if (x >= w || y >= h) continue;
-        int ty1, ty2;
-        float ya, ya1;
-        clahe_axis(y, D.inv_tile_h, a.tiles_y, ty1, ty2, ya, ya1);
-        const int64_t at = D.img + (int64_t)y * D.pitch + x;            // (a multiple of 4)
-        const uint32_t in4 = *(const uint32_t *)(a.src + at);
-        uint32_t out4 = 0;
-#pragma unroll
-        for (int k = 0; k < PX; ++k) {
-            if (x + k >= w) continue;                                   // (the row's padding stays 0)
-            int tx1, tx2;
-            float xa, xa1;
-            clahe_axis(x + k, D.inv_tile_w, a.tiles_x, tx1, tx2, xa, xa1);
-            const int v = (int)((in4 >> (8 * k)) & 255u);
-            const uint8_t o = clahe_blend(lut(ty1, tx1, v), lut(ty1, tx2, v), lut(ty2, tx1, v), lut(ty2, tx2, v), xa, xa1, ya, ya1);
-            out4 |= (uint32_t)o << (8 * k);
-        }
-        *(uint32_t *)(a.dst + at) = out4;
-    }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // host side
@@ -246,6 +117,7 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
     // every argument of every item first: nothing is written or launched on an error
     const int tiles_x = h->cfg.tiles_x, tiles_y = h->cfg.tiles_y, tiles = tiles_x * tiles_y;
     std::vector<ClaheItemD> its((size_t)count);
+    std::vector<int64_t> at((size_t)count, 0);           // an item's byte offset in the input buffer and, past the LUTs, in the output buffer
     int64_t b_img = 0;
     int max_ptiles = 0;
     bool want_luts = false;
@@ -266,7 +138,7 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
         d.ptiles_x = (it.width + TX - 1) / TX;
         d.ptiles = d.ptiles_x * ((it.height + TY - 1) / TY);
         d.lut_scale = g.lut_scale; d.inv_tile_w = g.inv_tile_w; d.inv_tile_h = g.inv_tile_h;
-        d.img = b_img;
+        at[(size_t)i] = b_img;
         b_img += (int64_t)align256((size_t)d.pitch * (size_t)d.h);
         max_ptiles = std::max(max_ptiles, d.ptiles);
         want_luts = want_luts || it.luts != nullptr;
@@ -278,21 +150,23 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
     if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->img.ensure(h->err, (size_t)b_img)) != VIO_OK ||
         (st = h->out.ensure(h->err, b_lut + (size_t)b_img)) != VIO_OK)
         return st;
+    for (int i = 0; i < count; ++i) {                    // (the buffers are where they stay now)
+        its[(size_t)i].src = h->img.d + at[(size_t)i];
+        its[(size_t)i].dst = h->out.d + b_lut + at[(size_t)i];
+    }
     std::memcpy(h->tab.h, its.data(), b_tab);
     for (int i = 0; i < count; ++i) {
         const vio_clahe_item &it = items[i];
         const ClaheItemD &d = its[(size_t)i];
         for (int y = 0; y < d.h; ++y) {
-            uint8_t *row = h->img.h + d.img + (size_t)y * (size_t)d.pitch;
+            uint8_t *row = h->img.h + at[(size_t)i] + (size_t)y * (size_t)d.pitch;
             std::memcpy(row, it.src + (size_t)y * (size_t)it.src_stride, (size_t)d.w);
             std::memset(row + d.w, 0, (size_t)(d.pitch - d.w));
         }
     }
     ClaheArgs a;
     a.items = (const ClaheItemD *)h->tab.d;
-    a.src = h->img.d;
     a.luts = h->out.d;
-    a.dst = h->out.d + b_lut;
     a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.count = count;
     const auto t1 = std::chrono::steady_clock::now();
     hipStream_t q = h->q.stream;
@@ -316,7 +190,7 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
         vio_clahe_result &o = results[i];
         o.status = VIO_OK; o.clip = d.clip; o.tile_w = d.tile_w; o.tile_h = d.tile_h;
         for (int y = 0; y < d.h; ++y)
-            std::memcpy(it.dst + (size_t)y * (size_t)it.dst_stride, h->out.h + b_lut + d.img + (size_t)y * (size_t)d.pitch, (size_t)d.w);
+            std::memcpy(it.dst + (size_t)y * (size_t)it.dst_stride, h->out.h + b_lut + at[(size_t)i] + (size_t)y * (size_t)d.pitch, (size_t)d.w);
         if (it.luts) std::memcpy(it.luts, h->out.h + (size_t)i * (size_t)tiles * BINS, (size_t)tiles * BINS);
     }
     const auto t2 = std::chrono::steady_clock::now();

@@ -15,6 +15,7 @@
 // the maximum), one reduction and one barrier; the rounds are bounded by a count known at launch.  No sort, no spin-waits, no
 // synchronisation between workgroups; a thread only ever strikes the entries it reads itself.
 // Contraction is off as in vio_flow.hip; with this arithmetic it cannot change a bit (vio_detect_math.h).  No floating-point atomics.
+// The kernels themselves are in vio_detect_body.inc, which libvio_frame_hip compiles too; the host side is here.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -32,267 +33,9 @@
 
 #include "vio_detect_math.h"
 
-constexpr int WAVE = 64;
-constexpr int TX = VIO_DETECT_TILE_X, TY = VIO_DETECT_TILE_Y;
-constexpr int NT = TX * TY;             // threads of a tile
-constexpr int NT_MASK = 256;            // threads of k_detect_setmask
-constexpr int NT_SEL = 1024;            // threads of k_detect_select
+#include "vio_detect_body.inc"
+
 constexpr int MAX_ITEMS = 4096;
-constexpr uint32_t DEAD = 0x80000000u;  // a struck candidate (pixel indices are below 2^28)
-static_assert(NT % WAVE == 0 && NT <= 1024, "a tile is whole wavefronts");
-
-struct DetItemD {
-    int32_t w, h, n_tracked, max_total;
-    int32_t active, has_mask, tiles_x, tiles;
-    int64_t img, mask;                  // byte offsets in the image buffer (rows tightly packed)
-    int64_t r;                          // the response map's offset, in doubles
-    int64_t cand;                       // the candidate list's offset, in entries
-    int32_t trk;                        // the first tracked point, in the tables of the call
-    int32_t newp;                       // the first row of new_pts, in the call's
-};
-
-struct DetTrk {
-    int32_t cx, cy, cnt, pad;
-};
-
-struct DetRes {
-    int32_t n_kept, n_new, n_cand, pad;
-    unsigned long long maxbits;         // the bits of maxR
-};
-
-struct DetArgs {
-    const DetItemD *items;
-    const DetTrk *trk;
-    const uint8_t *img;
-    double *r;
-    uint32_t *cand;
-    unsigned long long *tkey;           // [tracked points of the call]: the keys of the setMask loop, 0 once struck
-    int32_t *kept_xy;                   // [tracked points of the call][2]: the kept centres in output order
-    DetRes *res;
-    int32_t *keep_order;
-    float *new_pts;
-    double quality;
-    int32_t d2, count;
-};
-
-// ---------------------------------------------------------------------------------------------------------
-// the greedy loop
-// ---------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ DetKey key_shfl_xor(const DetKey &a, int s) {
-    DetKey o;
-    o.k = __shfl_xor(a.k, s, WAVE);
-    o.x = __shfl_xor(a.x, s, WAVE);
-    o.y = __shfl_xor(a.y, s, WAVE);
-    return o;
-}
-
-// Src: load(i) -> DetKey (k == 0: struck) and kill(i); emit(position, winner) runs on thread 0.  slots: [2][NTH / 64] in LDS.  Every
-// thread returns the number of entries taken.
-template <int NTH, bool STRICT, class Src, class Emit>
-__device__ __forceinline__ int greedy(Src &src, int n, int rounds, int32_t d2, Emit &emit, DetKey *slots) {
-    constexpr int NW = NTH / WAVE;
-    const int tid = threadIdx.x, lane = tid & (WAVE - 1), wv = tid / WAVE;
-    DetKey last = {0ull, 0, 0};
-    int taken = 0;
-    for (int r = 0; r < rounds; ++r) {
-        DetKey best = {0ull, 0, 0};
-        for (int i = tid; i < n; i += NTH) {
-            const DetKey e = src.load(i);
-            if (e.k == 0ull) continue;
-            if (r > 0 && det_struck<STRICT>(e.x, e.y, last.x, last.y, d2)) {
-                src.kill(i);
-                continue;
-            }
-            if (det_key_before(e, best)) best = e;
-        }
-#pragma unroll
-        for (int s = 1; s < WAVE; s <<= 1) {
-            const DetKey o = key_shfl_xor(best, s);
-            if (det_key_before(o, best)) best = o;
-        }
-        DetKey *slot = slots + (r & 1) * NW;            // (two sets: a round's slots are read while the next round's are written)
-        if (lane == 0) slot[wv] = best;
-        __syncthreads();
-        best = slot[0];
-#pragma unroll
-        for (int w = 1; w < NW; ++w) {
-            const DetKey o = slot[w];
-            if (det_key_before(o, best)) best = o;
-        }
-        if (best.k == 0ull) break;                      // (the same in every thread: nothing is left)
-        if (tid == 0) emit(taken, best);
-        last = best;
-        taken += 1;
-    }
-    return taken;
-}
-
-struct TrackedSrc {
-    const DetTrk *trk;
-    unsigned long long *key;
-    __device__ __forceinline__ DetKey load(int i) const {
-        DetKey e;
-        e.k = key[i]; e.x = trk[i].cx; e.y = trk[i].cy;
-        return e;
-    }
-    __device__ __forceinline__ void kill(int i) const { key[i] = 0ull; }
-};
-
-struct TrackedEmit {
-    int32_t *keep_order, *kept_xy;
-    __device__ __forceinline__ void operator()(int pos, const DetKey &e) const {
-        keep_order[pos] = (int32_t)(0xFFFFFFFFu - (uint32_t)(e.k & 0xFFFFFFFFull));
-        kept_xy[2 * pos] = e.x; kept_xy[2 * pos + 1] = e.y;
-    }
-};
-
-struct CandSrc {
-    uint32_t *cand;
-    const double *r;
-    int32_t w;
-    __device__ __forceinline__ DetKey load(int i) const {
-        DetKey e = {0ull, 0, 0};
-        const uint32_t p = cand[i];
-        if (p & DEAD) return e;
-        e.k = (unsigned long long)__double_as_longlong(r[p]);
-        e.x = (int32_t)(p % (uint32_t)w); e.y = (int32_t)(p / (uint32_t)w);
-        return e;
-    }
-    __device__ __forceinline__ void kill(int i) const { cand[i] |= DEAD; }
-};
-
-struct CandEmit {
-    float *new_pts;
-    __device__ __forceinline__ void operator()(int pos, const DetKey &e) const {
-        new_pts[2 * pos] = (float)e.x; new_pts[2 * pos + 1] = (float)e.y;
-    }
-};
-
-// ---------------------------------------------------------------------------------------------------------
-// kernels
-// ---------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(NT_MASK) void k_detect_setmask(DetArgs a) {
-    __shared__ DetKey slots[2 * (NT_MASK / WAVE)];
-    const int item = blockIdx.x;
-    if (item >= a.count) return;
-    const DetItemD &D = a.items[item];
-    if (!D.active || D.n_tracked == 0) return;           // (n_kept stays 0)
-    const DetTrk *trk = a.trk + D.trk;
-    unsigned long long *key = a.tkey + D.trk;
-    const uint8_t *mask = a.img + D.mask;
-    // the keys; a point on a zero mask pixel is struck from the start.  Entry i belongs to thread i mod NT_MASK from here on.
-    for (int i = threadIdx.x; i < D.n_tracked; i += NT_MASK) {
-        const DetTrk t = trk[i];
-        const bool on = !D.has_mask || mask[(int64_t)t.cy * D.w + t.cx] != 0;
-        key[i] = on ? det_track_key(t.cnt, i) : 0ull;
-    }
-    TrackedSrc src = {trk, key};
-    TrackedEmit emit = {a.keep_order + D.trk, a.kept_xy + 2 * (int64_t)D.trk};
-    const int n_kept = greedy<NT_MASK, false>(src, D.n_tracked, D.n_tracked, a.d2, emit, slots);
-    if (threadIdx.x == 0) a.res[item].n_kept = n_kept;
-}
-
-// allowed(p) of the contract
-__device__ __forceinline__ bool allowed(const DetArgs &a, const DetItemD &D, int n_kept, int x, int y) {
-    if (D.has_mask && a.img[D.mask + (int64_t)y * D.w + x] == 0) return false;
-    const int32_t *kx = a.kept_xy + 2 * (int64_t)D.trk;
-    for (int k = 0; k < n_kept; ++k)
-        if (det_struck<false>(x, y, kx[2 * k], kx[2 * k + 1], a.d2)) return false;
-    return true;
-}
-
-__global__ __launch_bounds__(NT) void k_detect_response(DetArgs a) {
-    __shared__ int tile[TY + 4][TX + 4];
-    __shared__ int pxx[TY + 2][TX + 2], pxy[TY + 2][TX + 2], pyy[TY + 2][TX + 2];
-    const int item = blockIdx.z;
-    if (item >= a.count) return;
-    const DetItemD &D = a.items[item];
-    if (!D.active || (int)blockIdx.x >= D.tiles) return;            // (the whole workgroup: no barrier was reached)
-    const int w = D.w, h = D.h;
-    const int x0 = ((int)blockIdx.x % D.tiles_x) * TX, y0 = ((int)blockIdx.x / D.tiles_x) * TY;
-    const uint8_t *img = a.img + D.img;
-    // the tile with a halo of 2, position (x0 - 2 + i, y0 - 2 + j) reflected into the image
-    for (int id = threadIdx.x; id < (TX + 4) * (TY + 4); id += NT) {
-        const int i = id % (TX + 4), j = id / (TX + 4);
-        tile[j][i] = img[(int64_t)det_refl(y0 - 2 + j, h) * w + det_refl(x0 - 2 + i, w)];
-    }
-    __syncthreads();
-    // the products at a halo of 1: position p outside the image is the product map's reflection, the gradient at q = refl(p), whose
-    // own neighbourhood q - 1 .. q + 1 lies in the tile for every p in [-1, W]; positions past that are never summed
-    for (int id = threadIdx.x; id < (TX + 2) * (TY + 2); id += NT) {
-        const int i = id % (TX + 2), j = id / (TX + 2);
-        const int px = x0 - 1 + i, py = y0 - 1 + j;
-        int gx = 0, gy = 0;
-        if (px <= w && py <= h) {
-            const int c = det_refl(px, w) - (x0 - 2), r = det_refl(py, h) - (y0 - 2);
-            int v[3][3];
-#pragma unroll
-            for (int dj = 0; dj < 3; ++dj)
-#pragma unroll
-                for (int di = 0; di < 3; ++di) v[dj][di] = tile[r - 1 + dj][c - 1 + di];
-            det_sobel(v, gx, gy);
-        }
-        pxx[j][i] = gx * gx; pxy[j][i] = gx * gy; pyy[j][i] = gy * gy;
-    }
-    __syncthreads();
-    const int tx = threadIdx.x % TX, ty = threadIdx.x / TX;
-    const int x = x0 + tx, y = y0 + ty;
-    unsigned long long bits = 0ull;
-    if (x < w && y < h) {
-        int32_t sa = 0, sb = 0, sc = 0;
-#pragma unroll
-        for (int dj = 0; dj < 3; ++dj)
-#pragma unroll
-            for (int di = 0; di < 3; ++di) { sa += pxx[ty + dj][tx + di]; sb += pxy[ty + dj][tx + di]; sc += pyy[ty + dj][tx + di]; }
-        const double R = det_response(sa, sb, sc);
-        a.r[D.r + (int64_t)y * w + x] = R;
-        if (allowed(a, D, a.res[item].n_kept, x, y)) bits = (unsigned long long)__double_as_longlong(R);
-    }
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-        const unsigned long long o = __shfl_xor(bits, s, WAVE);
-        bits = o > bits ? o : bits;
-    }
-    if ((threadIdx.x & (WAVE - 1)) == 0 && bits != 0ull) atomicMax(&a.res[item].maxbits, bits);
-}
-
-__global__ __launch_bounds__(NT) void k_detect_candidates(DetArgs a) {
-    const int item = blockIdx.z;
-    if (item >= a.count) return;
-    const DetItemD &D = a.items[item];
-    if (!D.active || (int)blockIdx.x >= D.tiles) return;
-    const int w = D.w, h = D.h;
-    const int x = ((int)blockIdx.x % D.tiles_x) * TX + (int)threadIdx.x % TX, y = ((int)blockIdx.x / D.tiles_x) * TY + (int)threadIdx.x / TX;
-    if (x < 1 || y < 1 || x > w - 2 || y > h - 2) return;
-    const double *R = a.r + D.r;
-    const double t = __longlong_as_double((long long)a.res[item].maxbits) * a.quality;
-    const int64_t p = (int64_t)y * w + x;
-    const double v = R[p];
-    if (!(v > t && v > 0.0)) return;
-    bool top = true;
-#pragma unroll
-    for (int dj = -1; dj <= 1; ++dj)
-#pragma unroll
-        for (int di = -1; di <= 1; ++di) top = top && v >= R[p + (int64_t)dj * w + di];
-    if (!top || !allowed(a, D, a.res[item].n_kept, x, y)) return;
-    const int slot = atomicAdd(&a.res[item].n_cand, 1);           // (below (w - 2) (h - 2), the list's size: a pixel arrives once)
-    a.cand[D.cand + slot] = (uint32_t)p;
-}
-
-__global__ __launch_bounds__(NT_SEL) void k_detect_select(DetArgs a) {
-    __shared__ DetKey slots[2 * (NT_SEL / WAVE)];
-    const int item = blockIdx.x;
-    if (item >= a.count) return;
-    const DetItemD &D = a.items[item];
-    if (!D.active) return;
-    const int n = a.res[item].n_cand, n_want = D.max_total - a.res[item].n_kept;
-    const int rounds = n_want < n ? n_want : n;
-    if (rounds <= 0) return;                                        // (n_new stays 0)
-    CandSrc src = {a.cand + D.cand, a.r + D.r, D.w};
-    CandEmit emit = {a.new_pts + 2 * (int64_t)D.newp};
-    const int n_new = greedy<NT_SEL, true>(src, n, rounds, a.d2, emit, slots);
-    if (threadIdx.x == 0) a.res[item].n_new = n_new;
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // host side
@@ -326,7 +69,7 @@ void copy_rows(uint8_t *dst, const uint8_t *src, int width, int height, int stri
 }
 
 void set_geometry(DetItemD &d, int width, int height) {
-    d.w = width; d.h = height;
+    d.w = width; d.h = height; d.pitch = width;          // (rows tightly packed)
     d.tiles_x = (width + TX - 1) / TX;
     d.tiles = d.tiles_x * ((height + TY - 1) / TY);
 }
@@ -388,6 +131,7 @@ vio_status vio_detect_batch(vio_detect *h, int32_t count, const vio_detect_item 
     const auto t0 = std::chrono::steady_clock::now();
     // every argument of every item first: nothing is written or launched on an error
     std::vector<DetItemD> its((size_t)count);
+    std::vector<int64_t> at((size_t)count * 2, 0);       // the byte offsets of an item's image and mask in the image buffer
     int64_t b_img = 0, n_r = 0, n_cand = 0, n_trk = 0, n_new = 0;
     int max_tiles = 0;
     for (int i = 0; i < count; ++i) {
@@ -416,8 +160,8 @@ vio_status vio_detect_batch(vio_detect *h, int32_t count, const vio_detect_item 
         n_trk += it.n_tracked; n_new += it.max_total;
         if (!d.active) continue;                         // (nothing of it is staged)
         const int64_t px = (int64_t)it.width * it.height;
-        d.img = b_img; b_img += px;
-        if (d.has_mask) { d.mask = b_img; b_img += px; }
+        at[2 * (size_t)i] = b_img; b_img += px;
+        if (d.has_mask) { at[2 * (size_t)i + 1] = b_img; b_img += px; }
         d.r = n_r; n_r += px;
         d.cand = n_cand; n_cand += (int64_t)std::max(it.width - 2, 0) * std::max(it.height - 2, 0);
         max_tiles = std::max(max_tiles, d.tiles);
@@ -434,6 +178,12 @@ vio_status vio_detect_batch(vio_detect *h, int32_t count, const vio_detect_item 
         (st = h->cand.ensure(h->err, sizeof(uint32_t) * (size_t)n_cand)) != VIO_OK ||
         (st = h->scratch.ensure(h->err, b_key + sizeof(int32_t) * 2 * (size_t)n_trk)) != VIO_OK)
         return st;
+    for (int i = 0; i < count; ++i) {                    // (the image buffer is where it stays now)
+        DetItemD &d = its[(size_t)i];
+        if (!d.active) continue;
+        d.img = h->img.d + at[2 * (size_t)i];
+        if (d.has_mask) d.mask = h->img.d + at[2 * (size_t)i + 1];
+    }
     std::memcpy(h->tab.h, its.data(), sizeof(DetItemD) * (size_t)count);
     DetTrk *ht = (DetTrk *)(h->tab.h + b_it);
     for (int i = 0; i < count; ++i) {
@@ -447,13 +197,13 @@ vio_status vio_detect_batch(vio_detect *h, int32_t count, const vio_detect_item 
             t.cnt = it.track_cnt[k];
         }
         if (!d.active) continue;
-        copy_rows(h->img.h + d.img, it.img, it.width, it.height, it.stride);
-        if (d.has_mask) copy_rows(h->img.h + d.mask, it.mask, it.width, it.height, it.stride);
+        copy_rows(h->img.h + at[2 * (size_t)i], it.img, it.width, it.height, it.stride);
+        if (d.has_mask) copy_rows(h->img.h + at[2 * (size_t)i + 1], it.mask, it.width, it.height, it.stride);
     }
     DetArgs a;
     a.items = (const DetItemD *)h->tab.d;
     a.trk = (const DetTrk *)(h->tab.d + b_it);
-    a.img = h->img.d; a.r = h->r.d; a.cand = h->cand.d;
+    a.r = h->r.d; a.cand = h->cand.d;
     a.tkey = (unsigned long long *)h->scratch.d;
     a.kept_xy = (int32_t *)(h->scratch.d + b_key);
     a.res = (DetRes *)h->out.d;
@@ -526,12 +276,13 @@ vio_status vio_detect_response(vio_detect *h, const uint8_t *img, int32_t width,
     if ((st = h->tab.ensure(h->err, sizeof(DetItemD))) != VIO_OK || (st = h->img.ensure(h->err, px)) != VIO_OK ||
         (st = h->out.ensure(h->err, b_res + sizeof(double) * px)) != VIO_OK || (st = h->r.ensure(h->err, sizeof(double) * px)) != VIO_OK)
         return st;
+    d.img = h->img.d;
     std::memcpy(h->tab.h, &d, sizeof(d));
     copy_rows(h->img.h, img, width, height, stride);
     DetArgs a;
     std::memset(&a, 0, sizeof(a));
     a.items = (const DetItemD *)h->tab.d;
-    a.img = h->img.d; a.r = h->r.d;
+    a.r = h->r.d;
     a.res = (DetRes *)h->out.d;                          // (n_kept = 0 and no mask: every pixel is allowed, nothing else is read)
     a.quality = h->cfg.quality; a.d2 = det_d2(h->cfg.min_distance); a.count = 1;
     hipStream_t q = h->q.stream;

@@ -13,6 +13,7 @@
 // Keypoints of one workgroup end after different iteration counts, so k_flow_track has no workgroup barrier: shuffles only.  Every
 // lane of a wavefront holds the same loop state, so the trip counts are uniform within the wavefront.
 // Contraction is off: products and sums round as the host restatement's (tests/flow_reference.py) do.  No floating-point atomics.
+// The kernels themselves are in vio_flow_body.inc, which libvio_frame_hip compiles too; the host side is here.
 #include <hip/hip_runtime.h>
 
 #include <chrono>
@@ -29,174 +30,9 @@
 
 #include "vio_flow_math.h"
 
-constexpr int WAVE = 64;
-constexpr int WAVES = 4;                // keypoints per workgroup
-constexpr int NT = WAVE * WAVES;
-constexpr int MAXL = VIO_FLOW_MAX_LEVELS;
-constexpr int PPL = (4 * VIO_FLOW_MAX_HALF_PATCH * VIO_FLOW_MAX_HALF_PATCH) / WAVE;     // patch pixels per lane at the largest patch
+#include "vio_flow_body.inc"
+
 constexpr int MAX_ITEMS = 16384;
-
-struct FlowItemD {
-    int32_t w[MAXL], h[MAXL];
-    int64_t prev[MAXL], next[MAXL];     // the levels' offsets in the pyramid buffer (rows tightly packed)
-    int32_t active, pad;                // 0: an item without keypoints, nothing of it is staged
-};
-
-struct FlowPt {
-    int32_t item, has_guess;
-    float px, py, gx, gy;
-};
-
-struct FlowOut {
-    float x, y;
-    int32_t status, iterations;
-    double cost;
-};
-
-struct PyrArgs {
-    const FlowItemD *items;
-    uint8_t *pyr;
-    int32_t level;                      // the source level
-    int32_t nimg;
-};
-
-struct FlowArgs {
-    const FlowItemD *items;
-    const FlowPt *pts;
-    const uint8_t *pyr;
-    FlowOut *out;
-    int32_t npts, levels, half_patch, max_iter, border, early_stop;
-};
-
-__global__ __launch_bounds__(NT) void k_flow_pyr_down(PyrArgs a) {
-    const int img = blockIdx.y;
-    if (img >= a.nimg) return;
-    const FlowItemD &D = a.items[img >> 1];
-    if (!D.active) return;
-    const int k = a.level;
-    const int w = D.w[k], h = D.h[k], ow = D.w[k + 1], oh = D.h[k + 1];
-    const int id = blockIdx.x * NT + threadIdx.x;
-    if (id >= ow * oh) return;
-    const int ox = id % ow, oy = id / ow;
-    const uint8_t *src = a.pyr + ((img & 1) ? D.next[k] : D.prev[k]);
-    uint8_t *dst = a.pyr + ((img & 1) ? D.next[k + 1] : D.prev[k + 1]);
-    const int kw[5] = {1, 4, 6, 4, 1};
-    int cols[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) cols[i] = refl(2 * ox - 2 + i, w);
-    int sum = 0;
-#pragma unroll
-    for (int j = 0; j < 5; ++j) {
-        const uint8_t *row = src + (int64_t)refl(2 * oy - 2 + j, h) * w;
-        int r = 0;
-#pragma unroll
-        for (int i = 0; i < 5; ++i) r += kw[i] * (int)row[cols[i]];
-        sum += kw[j] * r;
-    }
-    dst[(int64_t)oy * ow + ox] = (uint8_t)((sum + 128) >> 8);
-}
-
-template <int N> __device__ __forceinline__ void butterfly(double *v) {
-#pragma unroll
-    for (int s = 1; s < WAVE; s <<= 1) {
-#pragma unroll
-        for (int e = 0; e < N; ++e) v[e] = v[e] + __shfl_xor(v[e], s, WAVE);
-    }
-}
-
-template <bool INV> __global__ __launch_bounds__(NT) void k_flow_track(FlowArgs a) {
-    const int lane = threadIdx.x & (WAVE - 1);
-    const int k = blockIdx.x * WAVES + (threadIdx.x >> 6);
-    if (k >= a.npts) return;                        // (whole wavefronts: no barrier follows)
-    const FlowPt P = a.pts[k];
-    const FlowItemD &D = a.items[P.item];
-    FlowOut *o = a.out + k;
-    bool bad = !isfinite(P.px) || !isfinite(P.py);
-    if (P.has_guess) bad = bad || !isfinite(P.gx) || !isfinite(P.gy);
-    if (bad) {
-        if (lane == 0) { o->x = NAN; o->y = NAN; o->status = VIO_ERR_NOT_FINITE; o->iterations = 0; o->cost = NAN; }
-        return;
-    }
-    const int hp = a.half_patch, side = 2 * hp, npix = side * side;
-    // this lane's patch pixels: (du, dv) of m = lane, lane + 64, ...
-    int pdu[PPL], pdv[PPL];
-#pragma unroll
-    for (int j = 0; j < PPL; ++j) {
-        const int m = j * WAVE + lane;
-        pdu[j] = m / side - hp; pdv[j] = m % side - hp;
-    }
-    float sx = 0.f, sy = 0.f;
-    bool ok = false;
-    int its = 0;
-    double cost_last = NAN;
-    for (int l = a.levels - 1; l >= 0; --l) {
-        const double scale = ldexp(1.0, -l);
-        const float tx = (float)((double)P.px * scale), ty = (float)((double)P.py * scale);
-        if (l == a.levels - 1) {
-            sx = P.has_guess ? (float)((double)P.gx * scale) : tx;
-            sy = P.has_guess ? (float)((double)P.gy * scale) : ty;
-        }
-        const double x0 = tx, y0 = ty;
-        double dx = (double)sx - x0, dy = (double)sy - y0;
-        const int w = D.w[l], h = D.h[l];
-        const uint8_t *T = a.pyr + D.prev[l], *I = a.pyr + D.next[l];
-        ok = false; its = 0; cost_last = NAN;
-        if (valid_patch(x0, y0, w, h, hp)) {
-            double tv[PPL], tjx[INV ? PPL : 1], tjy[INV ? PPL : 1], Hs[3] = {0.0, 0.0, 0.0};
-#pragma unroll
-            for (int j = 0; j < PPL; ++j) {
-                tv[j] = 0.0;
-                if constexpr (INV) { tjx[j] = 0.0; tjy[j] = 0.0; }
-                if (j * WAVE < npix && j * WAVE + lane < npix) {
-                    double g0 = 0.0, g1 = 0.0;
-                    sample<INV>(T, w, h, x0 + (double)pdu[j], y0 + (double)pdv[j], tv[j], g0, g1);
-                    if constexpr (INV) {
-                        tjx[j] = g0; tjy[j] = g1;
-                        Hs[0] = Hs[0] + g0 * g0; Hs[1] = Hs[1] + g0 * g1; Hs[2] = Hs[2] + g1 * g1;
-                    }
-                }
-            }
-            if (INV) butterfly<3>(Hs);
-            double cost_prev = DBL_MAX;
-            for (int it = 0; it < a.max_iter; ++it) {
-                const double x = x0 + dx, y = y0 + dy;
-                if (!valid_patch(x, y, w, h, hp)) { ok = false; break; }
-                double v[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
-#pragma unroll
-                for (int j = 0; j < PPL; ++j) {
-                    if (j * WAVE < npix && j * WAVE + lane < npix) {
-                        double iv, jx = 0.0, jy = 0.0;
-                        sample<!INV>(I, w, h, x + (double)pdu[j], y + (double)pdv[j], iv, jx, jy);
-                        const double err = tv[j] - iv;
-                        if constexpr (INV) { jx = tjx[j]; jy = tjy[j]; }
-                        else { v[0] = v[0] + jx * jx; v[1] = v[1] + jx * jy; v[2] = v[2] + jy * jy; }
-                        v[3] = v[3] + err * jx; v[4] = v[4] + err * jy; v[5] = v[5] + (0.5 * err) * err;
-                    }
-                }
-                if (INV) { butterfly<3>(v + 3); v[0] = Hs[0]; v[1] = Hs[1]; v[2] = Hs[2]; }
-                else butterfly<6>(v);
-                double dp0, dp1;
-                solve2(v[0], v[1], v[2], v[3], v[4], dp0, dp1);
-                its += 1;
-                cost_last = v[5];
-                if (isnan(dp0) || isnan(dp1)) { ok = false; break; }
-                if (cost_prev <= v[5]) break;
-                if (a.early_stop) cost_prev = v[5];
-                dx = dx + dp0; dy = dy + dp1;
-                ok = true;
-            }
-        }
-        sx = tx + (float)dx; sy = ty + (float)dy;
-        if (l > 0) { sx = (float)((double)sx / 0.5); sy = (float)((double)sy / 0.5); }
-    }
-    int status = VIO_FLOW_FAIL_LOST;
-    if (ok) {
-        const double rx = rint((double)sx), ry = rint((double)sy), b = (double)a.border;
-        const bool inside = b <= rx && rx < (double)D.w[0] - b && b <= ry && ry < (double)D.h[0] - b;
-        status = inside ? VIO_OK : VIO_FLOW_FAIL_BORDER;
-    }
-    if (lane == 0) { o->x = sx; o->y = sy; o->status = status; o->iterations = its; o->cost = cost_last; }
-}
 
 // ---------------------------------------------------------------------------------------------------------
 // host side
@@ -243,7 +79,7 @@ void copy_rows(uint8_t *dst, const uint8_t *src, int width, int height, int stri
 void launch_pyramids(vio_flow *h, const FlowItemD *items_d, int nimg, const int64_t *max_px) {
     for (int l = 0; l + 1 < h->cfg.levels; ++l) {
         PyrArgs pa;
-        pa.items = items_d; pa.pyr = h->pyr.d; pa.level = l; pa.nimg = nimg;
+        pa.items = items_d; pa.level = l; pa.nimg = nimg; pa.both = 1; pa.pad = 0;
         hipLaunchKernelGGL(k_flow_pyr_down, dim3((unsigned)((max_px[l + 1] + NT - 1) / NT), (unsigned)nimg), dim3(NT), 0, h->q.stream, pa);
     }
 }
@@ -320,25 +156,29 @@ vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item 
     if (total == 0) return VIO_OK;
     // the pyramid buffer: level 0 of every image of an item with keypoints, then the levels above; the descriptor tables
     std::vector<FlowItemD> its((size_t)count);
+    std::vector<int64_t> at((size_t)count * 2 * MAXL, 0);       // the levels' offsets in the pyramid buffer: [item][prev, next][level]
     int64_t off = 0, max_px[MAXL] = {0};
     for (int i = 0; i < count; ++i) {
         FlowItemD &d = its[(size_t)i];
+        int64_t *prev = &at[(size_t)i * 2 * MAXL], *next = prev + MAXL;
         std::memset(&d, 0, sizeof(d));
         if (items[i].n_pts == 0) continue;
         d.active = 1;
         level_dims(items[i].width, items[i].height, L, d.w, d.h);
-        d.prev[0] = off; off += (int64_t)d.w[0] * d.h[0];
-        d.next[0] = off; off += (int64_t)d.w[0] * d.h[0];
+        for (int l = 0; l < L; ++l) d.pitch[l] = d.w[l];        // (rows tightly packed)
+        prev[0] = off; off += (int64_t)d.w[0] * d.h[0];
+        next[0] = off; off += (int64_t)d.w[0] * d.h[0];
         for (int l = 0; l < L; ++l) max_px[l] = std::max(max_px[l], (int64_t)d.w[l] * d.h[l]);
     }
     const size_t b_l0 = (size_t)off;
     off = (int64_t)align256(b_l0);
     for (int i = 0; i < count; ++i) {
-        FlowItemD &d = its[(size_t)i];
+        const FlowItemD &d = its[(size_t)i];
+        int64_t *prev = &at[(size_t)i * 2 * MAXL], *next = prev + MAXL;
         if (!d.active) continue;
         for (int l = 1; l < L; ++l) {
-            d.prev[l] = off; off += (int64_t)d.w[l] * d.h[l];
-            d.next[l] = off; off += (int64_t)d.w[l] * d.h[l];
+            prev[l] = off; off += (int64_t)d.w[l] * d.h[l];
+            next[l] = off; off += (int64_t)d.w[l] * d.h[l];
         }
     }
     DeviceScope dev(h->device);
@@ -348,6 +188,11 @@ vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item 
     if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->pyr.ensure(h->err, (size_t)off)) != VIO_OK ||
         (st = h->out.ensure(h->err, sizeof(FlowOut) * total)) != VIO_OK)
         return st;
+    for (int i = 0; i < count; ++i) {                    // (the pyramid buffer is where it stays now)
+        FlowItemD &d = its[(size_t)i];
+        const int64_t *prev = &at[(size_t)i * 2 * MAXL], *next = prev + MAXL;
+        for (int l = 0; d.active && l < L; ++l) { d.prev[l] = h->pyr.d + prev[l]; d.next[l] = h->pyr.d + next[l]; }
+    }
     std::memcpy(h->tab.h, its.data(), sizeof(FlowItemD) * (size_t)count);
     FlowPt *hp = (FlowPt *)(h->tab.h + b_it);
     size_t row = 0;
@@ -355,8 +200,8 @@ vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item 
         const vio_flow_item &it = items[i];
         const FlowItemD &d = its[(size_t)i];
         if (!d.active) continue;
-        copy_rows(h->pyr.h + d.prev[0], it.img_prev, it.width, it.height, it.stride);
-        copy_rows(h->pyr.h + d.next[0], it.img_next, it.width, it.height, it.stride);
+        copy_rows(h->pyr.h + at[(size_t)i * 2 * MAXL], it.img_prev, it.width, it.height, it.stride);
+        copy_rows(h->pyr.h + at[(size_t)i * 2 * MAXL + MAXL], it.img_next, it.width, it.height, it.stride);
         for (int k = 0; k < it.n_pts; ++k) {
             FlowPt &p = hp[row + (size_t)k];
             p.item = i; p.has_guess = it.guess != nullptr;
@@ -368,7 +213,7 @@ vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item 
     FlowArgs a;
     a.items = (const FlowItemD *)h->tab.d;
     a.pts = (const FlowPt *)(h->tab.d + b_it);
-    a.pyr = h->pyr.d; a.out = h->out.d;
+    a.out = h->out.d;
     a.npts = (int32_t)total; a.levels = L; a.half_patch = h->cfg.half_patch; a.max_iter = h->cfg.max_iter;
     a.border = h->cfg.border; a.early_stop = h->cfg.early_stop;
     const auto t1 = std::chrono::steady_clock::now();
@@ -425,14 +270,16 @@ vio_status vio_flow_pyramid(vio_flow *h, const uint8_t *img, int32_t width, int3
     d.active = 1;
     level_dims(width, height, L, d.w, d.h);
     int64_t off = 0, max_px[MAXL] = {0};
+    int64_t at[MAXL] = {0};
     for (int l = 0; l < L; ++l) {
-        d.prev[l] = off; d.next[l] = off;
+        at[l] = off; d.pitch[l] = d.w[l];
         max_px[l] = (int64_t)d.w[l] * d.h[l];
         off += max_px[l];
     }
     DeviceScope dev(h->device);
     if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     if ((st = h->tab.ensure(h->err, sizeof(FlowItemD))) != VIO_OK || (st = h->pyr.ensure(h->err, (size_t)off)) != VIO_OK) return st;
+    for (int l = 0; l < L; ++l) d.prev[l] = d.next[l] = h->pyr.d + at[l];
     std::memcpy(h->tab.h, &d, sizeof(d));
     copy_rows(h->pyr.h, img, width, height, stride);
     hipStream_t q = h->q.stream;

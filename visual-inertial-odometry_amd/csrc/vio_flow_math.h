@@ -26,14 +26,15 @@ __device__ __forceinline__ bool valid_patch(double x, double y, int w, int h, in
 
 // The bilinear value at (x, y) of the level p (w x h), and with GRAD its Scharr gradient over VIO_FLOW_GRADIENT_DIVISOR.  (x, y) is
 // inside a valid patch, so int(x), int(y) are pixels of the image; the clamps keep every load inside it whatever comes.
-template <bool GRAD> __device__ __forceinline__ void sample(const uint8_t *p, int w, int h, double x, double y, double &val, double &jx,
-                                                            double &jy) {
+// pitch: the bytes between the level's rows (>= w).
+template <bool GRAD> __device__ __forceinline__ void sample_pitched(const uint8_t *p, int pitch, int w, int h, double x, double y, double &val,
+                                                                    double &jx, double &jy) {
     const int c0 = flow_min(flow_max((int)x, 0), w - 1), r0 = flow_min(flow_max((int)y, 0), h - 1);
     const int c1 = flow_min(c0 + 1, w - 1), r1 = flow_min(r0 + 1, h - 1);
     const double xx = x - (double)c0, yy = y - (double)r0;
     const double w00 = (1.0 - xx) * (1.0 - yy), w01 = xx * (1.0 - yy), w10 = (1.0 - xx) * yy, w11 = xx * yy;
     if (!GRAD) {
-        const uint8_t *ra = p + (int64_t)r0 * w, *rb = p + (int64_t)r1 * w;
+        const uint8_t *ra = p + (int64_t)r0 * pitch, *rb = p + (int64_t)r1 * pitch;
         val = ((w00 * (double)ra[c0] + w01 * (double)ra[c1]) + w10 * (double)rb[c0]) + w11 * (double)rb[c1];
         return;
     }
@@ -43,7 +44,7 @@ template <bool GRAD> __device__ __forceinline__ void sample(const uint8_t *p, in
     int dxr[4][2], smr[4][2], v12[2][2];
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-        const uint8_t *row = p + (int64_t)R[i] * w;
+        const uint8_t *row = p + (int64_t)R[i] * pitch;
         const int v0 = row[C[0]], v1 = row[C[1]], v2 = row[C[2]], v3 = row[C[3]];
         const int L0 = v0, C0 = v1, R0 = cx ? v0 : v2, L1 = cx ? v0 : v1, C1 = v2, R1 = v3;
         dxr[i][0] = R0 - L0; dxr[i][1] = R1 - L1;
@@ -62,6 +63,12 @@ template <bool GRAD> __device__ __forceinline__ void sample(const uint8_t *p, in
     }
     jx = (((w00 * (double)gx[0][0] + w01 * (double)gx[0][1]) + w10 * (double)gx[1][0]) + w11 * (double)gx[1][1]) / VIO_FLOW_GRADIENT_DIVISOR;
     jy = (((w00 * (double)gy[0][0] + w01 * (double)gy[0][1]) + w10 * (double)gy[1][0]) + w11 * (double)gy[1][1]) / VIO_FLOW_GRADIENT_DIVISOR;
+}
+
+// the same for a level whose rows are tightly packed
+template <bool GRAD> __device__ __forceinline__ void sample(const uint8_t *p, int w, int h, double x, double y, double &val, double &jx,
+                                                            double &jy) {
+    sample_pitched<GRAD>(p, w, w, h, x, y, val, jx, jy);
 }
 
 // H.fullPivHouseholderQr().solve(b) of Eigen 3.3 for the symmetric 2 x 2 H = [h00 h01; h01 h11] (include/vio_flow.h)

@@ -1,0 +1,227 @@
+"""ctypes binding of include/vio_frame.h (csrc/libvio_frame_hip.so): frames that stay on the GPU across CLAHE, tracking and detection,
+the image steps of FeatureTracker::readImage (feature_tracker.cpp:87-149) for many image streams without the four uploads per frame.
+
+    fr = vio.load_frame().create()                                   # (device 0, its own stream)
+    fr.set_config(equalize=True, clahe=dict(clip_limit=3.0, tiles=(8, 8)), flow=dict(levels=4), detect=dict(min_distance=30))
+    fr.push(img)                                                     # slot 0: upload once, equalise, build the pyramid; does not wait
+    fr.push(img2)                                                    # the former frame is `prev` now
+    out = fr.track(prev_pts)                                         # FlowHandle.track's dict, from prev into next
+    out = fr.detect(tracked=pts, track_cnt=cnt, max_total=150)       # DetectHandle.detect's dict, on next
+    fr.set_mask(mask, slot=0); fr.download(slot=0, which=NEXT, level=0); fr.counters(); fr.reset(slot=0)
+    fr.push_batch([dict(slot=s, img=a), ...]); fr.track_batch([dict(slot=s, prev_pts=p, guess=None), ...])
+    fr.detect_batch([dict(slot=s, tracked=p, track_cnt=c, max_total=150), ...])
+
+A handle is what frontend.FeatureTracker takes as `frames`.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .capi import CompanionHandle, VioError, open_lib
+from .clahe import DEFAULT_CLIP_LIMIT, DEFAULT_TILES, VioClaheConfig
+from .detect import DEFAULT_MAX_TOTAL, DEFAULT_MIN_DISTANCE, DEFAULT_QUALITY, VioDetectConfig, VioDetectResult
+from .flow import DEFAULT_BORDER, DEFAULT_HALF_PATCH, DEFAULT_LEVELS, DEFAULT_MAX_ITER, VioFlowConfig, VioFlowPtInfo, _image
+
+MAX_SLOTS, MAX_DIM = 256, 16384
+PREV, NEXT = 0, 1
+OK, NOT_FINITE = 0, -3
+
+
+class VioFramePushItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("img", C.c_void_p)]
+
+
+class VioFrameTrackItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n_pts", C.c_int32), ("prev_pts", C.c_void_p), ("guess", C.c_void_p)]
+
+
+class VioFrameDetectItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n_tracked", C.c_int32), ("max_total", C.c_int32), ("reserved", C.c_int32), ("tracked", C.c_void_p),
+                ("track_cnt", C.c_void_p), ("keep_order", C.c_void_p), ("new_pts", C.c_void_p)]
+
+
+class FrameLib:
+    """libvio_frame_hip.so: vio_frame_*."""
+
+    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "push_batch", "track_batch", "set_mask", "detect_batch",
+               "download", "reset", "counters", "timing"]
+
+    def __init__(self, path):
+        self.path = path
+        self.dll, self.fn = open_lib(path, "vio_frame_", self.SYMBOLS)
+        self.fn["create"].argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
+        self.fn["set_config"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.fn["push_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        self.fn["track_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.fn["set_mask"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_int32, C.c_int32]
+        self.fn["detect_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        self.fn["download"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
+        self.fn["reset"].argtypes = [C.c_void_p, C.c_int32]
+        self.fn["counters"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
+
+    def create(self, device=0, stream=None):
+        """A vio_frame handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
+        return FrameHandle(self, device, stream)
+
+
+class FrameHandle(CompanionHandle):
+    PREFIX = "vio_frame_"
+
+    def __init__(self, lib, device=0, stream=None):
+        self.lib = lib
+        self.h = C.c_void_p()
+        self.levels = DEFAULT_LEVELS
+        self.shapes = {}                    # slot -> (height, width) of its resident frames
+        self._cfg = dict(equalize=False, clahe={}, flow={}, detect={})
+        st = lib.fn["create"](C.c_int32(device), C.c_void_p(stream) if stream else None, C.byref(self.h))
+        if st != 0:
+            raise VioError(st, "vio_frame_create")
+
+    def _ck(self, st, where, allow_not_finite=False):
+        if not (allow_not_finite and st == NOT_FINITE):
+            super()._ck(st, where)
+
+    def set_config(self, equalize=None, clahe=None, flow=None, detect=None):
+        """equalize: bool; clahe: dict(clip_limit, tiles=(tiles_x, tiles_y)); flow: dict of FlowHandle.set_config's arguments; detect:
+        dict(quality, min_distance).  An argument left None keeps what the handle has; a dict replaces that library's settings (what
+        it does not name returns to the default).  A change of flow's levels drops every resident frame."""
+        new = dict(self._cfg)
+        for k, v in (("equalize", equalize), ("clahe", clahe), ("flow", flow), ("detect", detect)):
+            if v is not None:
+                new[k] = bool(v) if k == "equalize" else dict(v)
+        c, f, d = new["clahe"], new["flow"], new["detect"]
+        tiles = c.get("tiles", (DEFAULT_TILES, DEFAULT_TILES))
+        cc = VioClaheConfig(float(c.get("clip_limit", DEFAULT_CLIP_LIMIT)), int(tiles[0]), int(tiles[1]))
+        fc = VioFlowConfig(int(f.get("levels", DEFAULT_LEVELS)), int(f.get("half_patch", DEFAULT_HALF_PATCH)), int(f.get("max_iter", DEFAULT_MAX_ITER)),
+                           int(f.get("inverse", 0)), int(f.get("border", DEFAULT_BORDER)), int(f.get("early_stop", 0)))
+        dc = VioDetectConfig(float(d.get("quality", DEFAULT_QUALITY)), int(d.get("min_distance", DEFAULT_MIN_DISTANCE)), 0)
+        self._ck(self.lib.fn["set_config"](self.h, C.c_int32(1 if new["equalize"] else 0), C.byref(cc), C.byref(fc), C.byref(dc)), "set_config")
+        self._cfg = new
+        if fc.levels != self.levels:
+            self.shapes = {}
+        self.levels = fc.levels
+
+    # ---- frames ---------------------------------------------------------------------------
+    def push_batch(self, items):
+        """items: dicts of slot and img ((height, width) uint8, rows may be strided).  Each becomes its slot's `next`.  Does not wait."""
+        B = len(items)
+        arr = (VioFramePushItem * max(B, 1))()
+        keep = []
+        for i, it in enumerate(items):
+            a = _image(it["img"])
+            keep.append(a)
+            arr[i] = VioFramePushItem(int(it.get("slot", 0)), a.shape[1], a.shape[0], a.strides[0], a.ctypes.data)
+        self._ck(self.lib.fn["push_batch"](self.h, C.c_int32(B), C.addressof(arr)), "push_batch")
+        for i, it in enumerate(items):
+            self.shapes[int(it.get("slot", 0))] = keep[i].shape
+
+    def push(self, img, slot=0):
+        self.push_batch([dict(slot=slot, img=img)])
+
+    def reset(self, slot=0):
+        """Drop the slot's frames (its mask stays): the next push may bring another geometry."""
+        self._ck(self.lib.fn["reset"](self.h, C.c_int32(slot)), "reset")
+        self.shapes.pop(int(slot), None)
+
+    def set_mask(self, mask, slot=0):
+        """The slot's mask, like its images, zero where nothing may be detected; None clears it."""
+        if mask is None:
+            self._ck(self.lib.fn["set_mask"](self.h, C.c_int32(slot), None, 0, 0, 0), "set_mask")
+            return
+        m = _image(mask)
+        self._ck(self.lib.fn["set_mask"](self.h, C.c_int32(slot), m.ctypes.data, C.c_int32(m.shape[1]), C.c_int32(m.shape[0]),
+                                         C.c_int32(m.strides[0])), "set_mask")
+
+    def download(self, slot=0, which=NEXT, level=0):
+        """Level `level` of the slot's prev (PREV) or next (NEXT): a uint8 array.  It waits for the device."""
+        shape = self.shapes.get(int(slot))
+        if shape is None or not 0 <= int(level) < self.levels:
+            out = np.zeros(1, dtype=np.uint8)           # (the library says what is wrong)
+            self._ck(self.lib.fn["download"](self.h, C.c_int32(slot), C.c_int32(which), C.c_int32(level), out.ctypes.data), "download")
+            raise VioError(-1, "vio_frame_download", "the binding does not know the slot's geometry")
+        h, w = shape[0] >> int(level), shape[1] >> int(level)
+        out = np.zeros((h, w), dtype=np.uint8)
+        self._ck(self.lib.fn["download"](self.h, C.c_int32(slot), C.c_int32(which), C.c_int32(level), out.ctypes.data), "download")
+        return out
+
+    # ---- tracking -------------------------------------------------------------------------
+    def track_batch(self, items):
+        """items: dicts of slot, prev_pts (n, 2) float32, guess (n, 2) or None.  FlowHandle.track_batch's list of dicts."""
+        B = len(items)
+        arr = (VioFrameTrackItem * max(B, 1))()
+        keep, n = [], []
+        for i, it in enumerate(items):
+            pts = np.ascontiguousarray(it["prev_pts"], dtype=np.float32).reshape(-1, 2)
+            g = None if it.get("guess") is None else np.ascontiguousarray(it["guess"], dtype=np.float32).reshape(-1, 2)
+            if g is not None and len(g) != len(pts):
+                raise ValueError("item %d: guess needs one row per keypoint" % i)
+            k = int(it.get("n_pts", len(pts)))
+            keep += [pts, g]
+            n.append(max(k, 0))
+            arr[i] = VioFrameTrackItem(int(it.get("slot", 0)), k, pts.ctypes.data, None if g is None else g.ctypes.data)
+        total = sum(n)
+        base = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
+        nxt = np.full((max(total, 1), 2), np.nan, dtype=np.float32)
+        info = (VioFlowPtInfo * max(total, 1))()
+        st = self.lib.fn["track_batch"](self.h, C.c_int32(B), C.addressof(arr), nxt.ctypes.data, C.addressof(info))
+        self._ck(st, "track_batch", allow_not_finite=True)
+        rec = np.frombuffer(info, dtype=np.dtype([("status", np.int32), ("iterations", np.int32), ("cost", np.float64)]), count=max(total, 1))
+        out = []
+        for i in range(B):
+            lo, hi = int(base[i]), int(base[i + 1])
+            out.append(dict(next_pts=nxt[lo:hi].copy(), status=rec["status"][lo:hi].copy(), iterations=rec["iterations"][lo:hi].copy(),
+                            cost=rec["cost"][lo:hi].copy()))
+        return out
+
+    def track(self, prev_pts, guess=None, slot=0):
+        return self.track_batch([dict(slot=slot, prev_pts=prev_pts, guess=guess)])[0]
+
+    # ---- detection ------------------------------------------------------------------------
+    def detect_batch(self, items):
+        """items: dicts of slot, tracked (n, 2) float32 or None, track_cnt (n,) int32, max_total.  DetectHandle.detect_batch's list of
+        dicts.  The mask is the slot's (set_mask)."""
+        B = len(items)
+        arr = (VioFrameDetectItem * max(B, 1))()
+        res = (VioDetectResult * max(B, 1))()
+        keep, kos, npts = [], [], []
+        for i, it in enumerate(items):
+            trk = it.get("tracked")
+            pts = np.zeros((0, 2), dtype=np.float32) if trk is None else np.ascontiguousarray(trk, dtype=np.float32).reshape(-1, 2)
+            cnt = it.get("track_cnt")
+            cnt = np.ones(len(pts), dtype=np.int32) if cnt is None else np.ascontiguousarray(cnt, dtype=np.int32).reshape(-1)
+            if len(cnt) != len(pts):
+                raise ValueError("item %d: track_cnt needs one entry per tracked point" % i)
+            max_total = int(it.get("max_total", DEFAULT_MAX_TOTAL))
+            ko = np.full(max(len(pts), 1), -1, dtype=np.int32)
+            npt = np.full((max(max_total, 1), 2), np.nan, dtype=np.float32)
+            keep += [pts, cnt]
+            kos.append(ko)
+            npts.append(npt)
+            arr[i] = VioFrameDetectItem(int(it.get("slot", 0)), len(pts), max_total, 0, pts.ctypes.data, cnt.ctypes.data, ko.ctypes.data,
+                                        npt.ctypes.data)
+        st = self.lib.fn["detect_batch"](self.h, C.c_int32(B), C.addressof(arr), C.addressof(res))
+        self._ck(st, "detect_batch", allow_not_finite=True)
+        out = []
+        for i in range(B):
+            r = res[i]
+            out.append(dict(status=int(r.status), n_kept=int(r.n_kept), n_new=int(r.n_new), n_candidates=int(r.n_candidates),
+                            max_response=float(r.max_response), keep_order=kos[i][:r.n_kept].copy(), new_pts=npts[i][:r.n_new].copy()))
+        return out
+
+    def detect(self, tracked=None, track_cnt=None, max_total=DEFAULT_MAX_TOTAL, slot=0):
+        return self.detect_batch([dict(slot=slot, tracked=tracked, track_cnt=track_cnt, max_total=max_total)])[0]
+
+    # ---- accounting -----------------------------------------------------------------------
+    def counters(self):
+        """Bytes moved since creation (include/vio_frame.h)."""
+        c = (C.c_uint64 * 4)()
+        self._ck(self.lib.fn["counters"](self.h, c), "counters")
+        return {"image_up": int(c[0]), "image_down": int(c[1]), "other_up": int(c[2]), "other_down": int(c[3])}
+
+    def timing(self):
+        """ms of the last push, track and detect (include/vio_frame.h); waits for the last push."""
+        t = (C.c_double * 8)()
+        self._ck(self.lib.fn["timing"](self.h, t), "timing")
+        return {"push_host_ms": t[0], "push_upload_ms": t[1], "push_clahe_ms": t[2], "push_pyramid_ms": t[3], "track_ms": t[4],
+                "track_total_ms": t[5], "detect_ms": t[6], "detect_total_ms": t[7]}

@@ -27,6 +27,12 @@ as in the reference.  feature_frame() returns what the reference publishes.  Wit
 (feature_tracker.cpp:87-95).  With one, read_image equalises the image first, so the tracker, the detector and cur_img / prev_img see
 equalised images only, as in the reference.  With equalizer=None nothing of this happens.
 
+`frames` is a frame.FrameHandle, or any object with .push(img, slot=), .track(prev_pts, slot=) and .detect(tracked=, track_cnt=,
+max_total=, slot=) of the handle's signatures (and .set_mask(mask, slot=) if a mask is given, .set_config(detect=) if it has one).  With
+one, read_image pushes the raw image into `slot` and tracks and detects through it: the image is uploaded once, and equalising is the
+handle's business (its equalize setting), so tracker, detector and equalizer may be None and are not used.  prev_img / cur_img stay
+None; frames.download(slot, PREV or NEXT) gives them.  With frames=None nothing of this happens.
+
 Missing against the reference: the camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA).
 One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
@@ -35,10 +41,17 @@ import numpy as np
 
 
 class FeatureTracker:
-    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None, equalizer=None):
+    def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None, equalizer=None, frames=None,
+                 slot=0):
         self.tracker, self.detector = tracker, detector
+        self.frames, self.slot = frames, int(slot)
         self.max_cnt, self.min_dist, self.border, self.reject, self.mask = int(max_cnt), int(min_dist), int(border), reject, mask
-        if hasattr(detector, "set_config"):
+        if frames is not None:
+            if hasattr(frames, "set_config"):
+                frames.set_config(detect=dict(min_distance=self.min_dist))
+            if mask is not None:
+                frames.set_mask(mask, slot=self.slot)
+        elif hasattr(detector, "set_config"):
             detector.set_config(min_distance=self.min_dist)
         self.prev_img = self.cur_img = None
         self.prev_pts = np.zeros((0, 2), dtype=np.float32)
@@ -71,18 +84,19 @@ class FeatureTracker:
         img = np.asarray(img)
         if img.dtype != np.uint8 or img.ndim != 2:
             raise ValueError("an image must be a 2-d uint8 array")
-        if self.equalizer is not None:
+        if self.frames is not None:
+            self.frames.push(img, slot=self.slot)
+        elif self.equalizer is not None:
             img = np.asarray(self.equalizer.apply(img))
             if img.dtype != np.uint8 or img.ndim != 2:
                 raise ValueError("the equalizer must return a 2-d uint8 array")
         self.prev_time, self.cur_time = self.cur_time, t
-        first = self.cur_img is None
-        if first:
+        if self.frames is None and self.cur_img is None:
             self.prev_img = self.cur_img = img
         cur, forw = self.cur_pts, np.zeros((0, 2), dtype=np.float32)
         ids, cnt = self.ids, self.track_cnt
         if len(cur) > 0:
-            out = self.tracker.track(self.cur_img, img, cur)
+            out = self.frames.track(cur, slot=self.slot) if self.frames is not None else self.tracker.track(self.cur_img, img, cur)
             forw = np.asarray(out["next_pts"], dtype=np.float32).reshape(-1, 2)
             ok = (np.asarray(out["status"]) == 0) & self.in_border(forw, img.shape)
             cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
@@ -95,7 +109,10 @@ class FeatureTracker:
             if self.rejecter is not None and len(forw) > 0:
                 ok = np.asarray(self.rejecter.reject(cur, forw, self.n_frames), dtype=bool).reshape(-1)
                 cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
-            det = self.detector.detect(img, tracked=forw, track_cnt=cnt, mask=self.mask, max_total=self.max_cnt)
+            if self.frames is not None:
+                det = self.frames.detect(tracked=forw, track_cnt=cnt, max_total=self.max_cnt, slot=self.slot)
+            else:
+                det = self.detector.detect(img, tracked=forw, track_cnt=cnt, mask=self.mask, max_total=self.max_cnt)
             order = np.asarray(det["keep_order"], dtype=np.int64)
             new = np.asarray(det["new_pts"], dtype=np.float32).reshape(-1, 2)
             self.n_new = len(new)
@@ -103,7 +120,8 @@ class FeatureTracker:
             forw = np.concatenate([forw[order], new])
             ids = np.concatenate([ids[order], np.full(len(new), -1, dtype=np.int64)])
             cnt = np.concatenate([cnt[order], np.ones(len(new), dtype=np.int32)]).astype(np.int32)
-        self.prev_img, self.cur_img = self.cur_img, img
+        if self.frames is None:
+            self.prev_img, self.cur_img = self.cur_img, img
         self.prev_pts, self.cur_pts = cur, forw
         self.ids, self.track_cnt = ids, cnt
         self.n_frames += 1
