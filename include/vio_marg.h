@@ -16,6 +16,10 @@
  *   - inverse-depth windows only (the reference never marginalises XYZ landmarks);
  *   - a landmark block without an inverse gives that window H = 0 and b, err, jt_inv NaN, and window_status VIO_ERR_NOT_FINITE;
  *     the other windows are computed, and the call returns VIO_ERR_NOT_FINITE;
+ *     any non-finite entry of H_marg or b_marg gives this outcome, whatever its source (a zero or non-finite inverse depth, a non-finite
+ *     observation of an edge of the graph, a non-finite entry of b_prior or of the lower triangle of H_prior, which is the one read:
+ *     H_prior is taken as symmetric); what lies outside the graph (landmarks hosted in other frames, landmarks without observations)
+ *     is not read;
  *   - argument errors (bad kind, null array, index out of range, host == target, a landmark with two hosts) write nothing and
  *     launch nothing: VIO_ERR_BAD_ARG, vio_marg_last_error names the window.  count == 0 does nothing and returns VIO_OK;
  *   - repeated calls are bitwise identical, and a window's result does not depend on the batch it is in (no atomics, fixed
