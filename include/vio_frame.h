@@ -12,7 +12,10 @@
  * (equalised if the handle is configured so), and the pyramid levels 1 .. levels - 1 of include/vio_flow.h above it.
  *   vio_frame_push_batch      uploads each raw image once, equalises it on the device into level 0 (k_clahe_lut, k_clahe_apply) or
  *                             takes it as level 0, builds the pyramid once (k_flow_pyr_down), and makes the result the slot's next:
- *                             the former next becomes prev, the former prev is dropped.  It does not wait for the device.
+ *                             the former next becomes prev, the former prev is dropped.  It does not wait for the device: not for
+ *                             its own work.  It does wait for the push before it (whose timing events it reads), and a buffer
+ *                             that a later, larger call regrows is released by hipFree, which waits: calls back to back are safe
+ *                             through those two waits, not through the stream's order alone.
  *   vio_frame_track_batch     vio_flow_track_batch's contract word for word, from the slot's prev into its next     (k_flow_track)
  *   vio_frame_set_mask        the slot's mask (the reference's fisheye mask): uploaded once, resident until replaced or cleared
  *   vio_frame_detect_batch    vio_detect_batch's contract word for word, on level 0 of the slot's next with the slot's mask

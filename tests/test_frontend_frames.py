@@ -9,7 +9,9 @@ import numpy as np
 import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import clahe_reference as cr  # noqa: E402
 import detect_reference as dr  # noqa: E402
+import flow_reference as fr  # noqa: E402
 from test_frontend_equalize import CachedEqualizer  # noqa: E402
 from test_frontend_reference import MAX_CNT, MIN_DIST, Tracker, check_frames, fixture_frames  # noqa: E402
 
@@ -42,6 +44,67 @@ class StandInFrames:
     def detect(self, tracked=None, track_cnt=None, max_total=150, slot=0):
         self.calls.append(("detect", slot, 0 if tracked is None else len(tracked)))
         return self.de.detect(self.slots[slot][1], tracked=tracked, track_cnt=track_cnt, mask=self.masks.get(slot), max_total=max_total)
+
+
+class StandInSequenceFrames(StandInFrames):
+    """StandInFrames with the rest of FrameHandle's methods and settings (push_batch, reset, download, track_batch, detect_batch;
+    equalize, the CLAHE settings, levels), for tests/frame_sequences.py: the roll, the reset and the change of levels in a few lines."""
+
+    def __init__(self):
+        StandInFrames.__init__(self)
+        self.levels, self.equalize, self.clahe, self.flow, self.detect_kw = 4, False, {}, {}, {}
+
+    def set_config(self, equalize=None, clahe=None, flow=None, detect=None):
+        if equalize is not None:
+            self.equalize = bool(equalize)
+        if clahe is not None:
+            self.clahe = dict(clahe)
+        if detect is not None:
+            self.detect_kw = dict(detect)
+        if flow is not None:
+            if flow.get("levels", 4) != self.levels:
+                self.slots = {}                              # (the masks stay)
+            self.flow, self.levels = dict(flow), flow.get("levels", 4)
+
+    def set_mask(self, mask, slot=0):
+        self.masks.pop(slot, None)
+        if mask is not None:
+            self.masks[slot] = np.ascontiguousarray(mask)
+
+    def push_batch(self, items):
+        for it in items:
+            img = np.ascontiguousarray(it["img"])
+            slot = it.get("slot", 0)
+            self.slots[slot] = (self.slots.get(slot, (None, None))[1], cr.apply(img, **self.clahe) if self.equalize else img)
+
+    def push(self, img, slot=0):
+        self.push_batch([dict(slot=slot, img=img)])
+
+    def reset(self, slot=0):
+        self.slots.pop(slot, None)
+
+    def download(self, slot=0, which=1, level=0):
+        assert self.slots[slot][which] is not None and 0 <= level < self.levels
+        return fr.pyramid(self.slots[slot][which], self.levels)[level]
+
+    def track_batch(self, items):
+        out = []
+        for it in items:
+            prev, nxt = self.slots[it["slot"]]
+            assert prev is not None, "tracking needs two frames"
+            res = fr.multi_level(prev, nxt, it["prev_pts"], it.get("guess"), order="wave64", **self.flow)
+            out.append(dict(zip(("next_pts", "status", "iterations", "cost"), res)))
+        return out
+
+    def detect_batch(self, items):
+        return [dr.detect(self.slots[it["slot"]][1], it.get("tracked"), it.get("track_cnt"), self.masks.get(it["slot"]), it["max_total"],
+                          **self.detect_kw) for it in items]
+
+    def track(self, prev_pts, guess=None, slot=0):
+        return self.track_batch([dict(slot=slot, prev_pts=prev_pts, guess=guess)])[0]
+
+    def detect(self, tracked=None, track_cnt=None, max_total=150, slot=0):
+        return self.detect_batch([dict(slot=slot, tracked=tracked, track_cnt=track_cnt, max_total=max_total)])[0]
 
 
 @pytest.fixture(scope="module")
