@@ -181,3 +181,36 @@ def test_statuses():
     r = pr.frames(flat)
     assert (r["status"], r["fail_frame"], r["iterations"][0]) == (pr.FAIL_NO_POSE, 0, 0) and np.all(np.isnan(r["T"]))
     assert pr.frames(pr.synthetic_frame(8, 1))["status"] == pr.OK
+
+
+def test_limit_cases_take_their_branches():
+    """What tests/test_gpu_pnp_limits.py sends to the device, on the restatement alone: every case takes the branches it is there
+    for (pnp_reference.LIMIT_CASES), no frame of any case or window changes its iteration count under one ulp, so the device
+    comparison skips none, and together the cases reach every way out of the loop.  A changed seed or constant fails here first."""
+    seen, shapes, skipped = set(), {}, 0
+    for name, c in pr.LIMIT_CASES.items():
+        item, cfg, ref, trace = pr.check_limit_case(name)
+        seen |= set(trace)
+        shapes[name] = pr.shape(trace)
+        if c["quat"] is not None:
+            seen.add("quat%d" % c["quat"])
+        skipped += pr.undecidable(item, cfg)
+    windows = pr.limit_windows()
+    skipped += sum(pr.undecidable(w) for w in windows.values())
+    print("undecidable frames:", skipped)
+    assert skipped == 0
+    assert seen >= set(pr.EVENTS) - {"c2_not_finite", "model_not_positive"} | {"quat0", "quat1", "quat2"}, seen
+    # consecutive rejects, then a reject behind a later accept (vv was reset); a converged run with at least four rejects; the
+    # radius floor with and without an accepted step, by failed factorisations and by rejected steps
+    assert any("RRA" in s and "AR" in s for s in shapes.values())
+    assert any(s.count("R") >= 4 and pr.limit_case(n)[3][-1] == "steptol" for n, s in shapes.items())
+    floor = [s for n, s in shapes.items() if pr.limit_case(n)[3][-1] == "radmin"]
+    assert any("A" in s and len(s) < 20 for s in floor) and any(set(s) == {"C"} for s in floor) and any(set(s) == {"R"} for s in floor)
+    # one workgroup, four fates: 0 iterations, an easy solve, the cap, the radius floor
+    its = [int(pr.limit_case(n)[2]["iterations"][0]) for n in pr.FOUR_FATES]
+    assert its[0] == 0 and 3 <= its[1] <= 4 and its[2] == 20 and its[3] < 20 and pr.limit_case(pr.FOUR_FATES[3])[3][-1] == "radmin", its
+    ref = pr.frames(windows["four_fates_straddling"])
+    assert list(ref["iterations"][3:]) == its and ref["status"] == pr.OK
+    ref = pr.frames(windows["empty_between"])
+    assert (ref["status"], ref["fail_frame"], ref["n_used"][1]) == (pr.FAIL_FEW_POINTS, 1, 0) and list(ref["iterations"][[0, 2]]) == its[1:3]
+    assert len(windows["full_window"]["guess_key"]) == pr.MAX_FRAMES
