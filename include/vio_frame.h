@@ -22,6 +22,7 @@
  *                             (k_detect_setmask, k_detect_response, k_detect_candidates, k_detect_select)
  *   vio_frame_download        one level of prev or next, tightly packed
  *   vio_frame_reset           drops the slot's frames (its mask stays), after which a push may bring another geometry
+ *   vio_frame_read_batch      all of readImage for one new image per slot, the points kept on the device (vio_frame_read.h)
  * All work of a handle is enqueued on its one stream, in call order; that order is what keeps a frame from being overwritten while an
  * earlier call still reads it.  The handle owns the pinned memory uploads are staged in, and does not touch it again before the copy
  * that reads it has finished (an event).  Device storage grows by whole blocks and never moves or frees a frame.
@@ -36,6 +37,9 @@
  *     keypoint or the item, the others are computed as if it were not there;
  *   - repeated calls are bitwise identical, and an item's result depends neither on the batch nor on the slot it is in;
  *   - the calling thread's current HIP device is restored; one handle is used by one caller thread at a time.
+ *
+ * Resident points (VIO_FRAME_HAS_READ): include/vio_frame_read.h, which this header includes, declares vio_frame_read_batch and what
+ * goes with it: all of readImage for one new image per slot, the points kept on the device.
  */
 #ifndef VIO_FRAME_H
 #define VIO_FRAME_H
@@ -58,6 +62,7 @@ extern "C" {
 #define VIO_FRAME_MAX_DIM 16384                     /* width and height, as VIO_FLOW_MAX_DIM */
 #define VIO_FRAME_PREV 0                            /* `which` of vio_frame_download */
 #define VIO_FRAME_NEXT 1
+#define VIO_FRAME_HAS_READ 1                        /* include/vio_frame_read.h is there */
 
 typedef struct vio_frame vio_frame;
 
@@ -126,4 +131,7 @@ vio_status vio_frame_timing(vio_frame *h, double *out8);
 #ifdef __cplusplus
 }
 #endif
+
+#include "vio_frame_read.h"
+
 #endif

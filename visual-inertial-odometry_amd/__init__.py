@@ -15,7 +15,7 @@ from .detect import DetectHandle, DetectLib
 from .exrot import ExrotHandle, ExrotLib
 from .flow import FlowHandle, FlowLib
 from .frame import FrameHandle, FrameLib
-from .frontend import FeatureTracker
+from .frontend import BatchFeatureTracker, FeatureTracker
 from .imu import ImuHandle, ImuLib
 from .init import InitHandle, InitLib
 from .marg import MargHandle, MargLib

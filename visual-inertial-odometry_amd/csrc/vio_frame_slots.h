@@ -2,12 +2,16 @@
 // layout of a frame's levels, the pool of device blocks frames and masks live in, and the slot table with its roll, its geometry
 // check and its invalidation.  vio_frame.hip gives the pool an allocator that calls hipMalloc; tests/cpp/frame_slots_main.cpp gives it
 // one that calls malloc and runs a scripted sequence under ASan and UBSan (tests/test_frame_host_units.py).
+// A slot also mirrors what the host knows of its resident points: the rows of its point table and of its
+// prev_un table, which it learns from each read's read-back, the id counter, the frames read and the last time stamp.  The tables
+// themselves are on the device; tests/cpp/front_math_main.cpp runs this part (tests/test_front_cpu.py).
 //
 // The pool never moves and never frees a block before it is destroyed: growing is adding a block.  A block is IN USE while the table
 // refers to it and FREE otherwise; a free block is handed out again to a request it fits.  That is safe without waiting because every
 // reader and the next writer of a block are enqueued on the handle's one stream, in call order.
 #pragma once
 
+#include <cmath>
 #include <cstddef>
 #include <cstdint>
 #include <vector>
@@ -16,9 +20,11 @@ constexpr int FRAME_MAX_SLOTS = 256;            // VIO_FRAME_MAX_SLOTS
 constexpr int FRAME_MAX_LEVELS = 8;             // VIO_FLOW_MAX_LEVELS
 constexpr int FRAME_MAX_DIM = 16384;            // VIO_FRAME_MAX_DIM
 constexpr int FRAME_ALIGN = 256;                // of a block and of every level in it
+constexpr int FRAME_MAX_TRACK_POINTS = 1024;    // VIO_FRAME_MAX_TRACK_POINTS
 
 // outcomes of the checks, in the order they are made
-enum FrameCheck { FRAME_OK = 0, FRAME_BAD_SLOT, FRAME_TWICE, FRAME_BAD_DIMS, FRAME_SMALL_LEVEL, FRAME_GEOMETRY, FRAME_TOO_FEW, FRAME_MASK_GEOMETRY };
+enum FrameCheck { FRAME_OK = 0, FRAME_BAD_SLOT, FRAME_TWICE, FRAME_BAD_DIMS, FRAME_SMALL_LEVEL, FRAME_GEOMETRY, FRAME_TOO_FEW, FRAME_MASK_GEOMETRY,
+                  FRAME_BAD_TIME, FRAME_BAD_POINTS };
 
 inline int64_t frame_align(int64_t x) { return (x + FRAME_ALIGN - 1) / FRAME_ALIGN * FRAME_ALIGN; }
 
@@ -118,6 +124,12 @@ struct FrameSlot {
     int prev = -1, next = -1;           // blocks
     int mask = -1;
     int32_t mask_w = 0, mask_h = 0;
+    // the resident points (vio_frame_read_batch): rows of the slot's point table, which belong to its next frame, and of its prev_un
+    // table; the next free id; the frames read (rejectWithF's `pair`); the time of the last one
+    int32_t n_pts = 0, n_prev_un = 0;
+    int64_t next_id = 0;
+    uint32_t n_read = 0;
+    double time = 0.0;
 };
 
 struct FrameTable {
@@ -157,6 +169,7 @@ struct FrameTable {
         pool.release(s.prev);
         s.prev = s.next;
         s.next = blk;
+        s.n_pts = 0;                    // (the points were the rolled frame's; a read puts its own back: points_after_read)
         s.n_frames = s.n_frames < 2 ? s.n_frames + 1 : 2;
         s.width = width; s.height = height;
         return blk;
@@ -169,6 +182,8 @@ struct FrameTable {
         pool.release(s.next);
         s.prev = s.next = -1;
         s.n_frames = 0; s.width = s.height = 0;
+        s.n_pts = s.n_prev_un = 0;      // (the id counter stays: ids are never handed out twice)
+        s.n_read = 0; s.time = 0.0;
     }
 
     // a change of the levels drops every frame: its layout is another
@@ -212,6 +227,40 @@ struct FrameTable {
         if (!slot_ok(slot)) return FRAME_BAD_SLOT;
         if ((which != 0 && which != 1) || level < 0 || level >= levels) return FRAME_BAD_DIMS;
         return slots[slot].n_frames < (which == 0 ? 2 : 1) ? FRAME_TOO_FEW : FRAME_OK;
+    }
+
+    // The checks of a read of `count` items besides check_push's, none of which changes anything: a time that is finite and, while the
+    // slot's prev_un holds rows, after the slot's last; with `publish`, a mask of the frame's geometry.
+    FrameCheck check_read(int32_t count, const int32_t *slot, const int32_t *width, const int32_t *height, const double *time, bool publish,
+                          int32_t *bad) const {
+        const FrameCheck ck = check_push(count, slot, width, height, bad);
+        if (ck != FRAME_OK) return ck;
+        for (int32_t i = 0; i < count; ++i) {
+            *bad = i;
+            const FrameSlot &s = slots[slot[i]];
+            if (!std::isfinite(time[i]) || (s.n_prev_un > 0 && !(time[i] > s.time))) return FRAME_BAD_TIME;
+            if (publish && s.mask >= 0 && (s.mask_w != width[i] || s.mask_h != height[i])) return FRAME_MASK_GEOMETRY;
+        }
+        *bad = -1;
+        return FRAME_OK;
+    }
+    // what a read's read-back says of a slot: n rows in both tables, the counter, one more frame read
+    void points_after_read(int32_t slot, int32_t n, int64_t next_id, double time) {
+        if (!slot_ok(slot)) return;
+        FrameSlot &s = slots[slot];
+        s.n_pts = s.n_prev_un = n < 0 ? 0 : (n > FRAME_MAX_TRACK_POINTS ? FRAME_MAX_TRACK_POINTS : n);
+        s.next_id = next_id;
+        s.n_read += 1u;
+        s.time = time;
+    }
+    // seeding a slot's points needs a frame they lie in
+    FrameCheck check_points_set(int32_t slot, int32_t n) const {
+        if (!slot_ok(slot)) return FRAME_BAD_SLOT;
+        if (slots[slot].n_frames < 1) return FRAME_TOO_FEW;
+        return n < 0 || n > FRAME_MAX_TRACK_POINTS ? FRAME_BAD_POINTS : FRAME_OK;
+    }
+    void points_set(int32_t slot, int32_t n) {
+        if (check_points_set(slot, n) == FRAME_OK) slots[slot].n_pts = n;
     }
 
     // the address of level l of a block laid out by L

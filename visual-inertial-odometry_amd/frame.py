@@ -11,7 +11,12 @@ the image steps of FeatureTracker::readImage (feature_tracker.cpp:87-149) for ma
     fr.push_batch([dict(slot=s, img=a), ...]); fr.track_batch([dict(slot=s, prev_pts=p, guess=None), ...])
     fr.detect_batch([dict(slot=s, tracked=p, track_cnt=c, max_total=150), ...])
 
-A handle is what frontend.FeatureTracker takes as `frames`.
+    fr.set_camera(fx=, fy=, cx=, cy=, k1=, k2=, p1=, p2=, width=, height=); fr.set_tracker(max_cnt=150, border=1)
+    outs = fr.read_batch(imgs, times, slots=[0, 1, ...], publish=True)    # all of readImage and updateID per slot, the points resident:
+                                                                     # dicts of pts, ids, track_cnt, un_pts, velocity, n_new, ...
+    fr.points_set(pts, ids, track_cnt, slot=0); fr.points_get(slot=0)
+
+A handle is what frontend.FeatureTracker takes as `frames`, and what frontend.BatchFeatureTracker drives through read_batch.
 """
 import ctypes as C
 
@@ -20,10 +25,12 @@ import numpy as np
 from .capi import CompanionHandle, VioError, open_lib
 from .clahe import DEFAULT_CLIP_LIMIT, DEFAULT_TILES, VioClaheConfig
 from .detect import DEFAULT_MAX_TOTAL, DEFAULT_MIN_DISTANCE, DEFAULT_QUALITY, VioDetectConfig, VioDetectResult
+from .reject import DEFAULT_F_THRESHOLD, DEFAULT_FOCAL_LENGTH, DEFAULT_HYPOTHESES, MODEL_PINHOLE, VioRejectCamera, VioRejectConfig
 from .flow import DEFAULT_BORDER, DEFAULT_HALF_PATCH, DEFAULT_LEVELS, DEFAULT_MAX_ITER, VioFlowConfig, VioFlowPtInfo, _image
 
 MAX_SLOTS, MAX_DIM = 256, 16384
 PREV, NEXT = 0, 1
+MAX_TRACK_POINTS, DEFAULT_MAX_CNT, DEFAULT_TRACK_BORDER = 1024, 150, 1
 OK, NOT_FINITE = 0, -3
 
 
@@ -40,11 +47,23 @@ class VioFrameDetectItem(C.Structure):
                 ("track_cnt", C.c_void_p), ("keep_order", C.c_void_p), ("new_pts", C.c_void_p)]
 
 
+class VioFrameReadItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("stride", C.c_int32), ("img", C.c_void_p),
+                ("time", C.c_double), ("pts", C.c_void_p), ("ids", C.c_void_p), ("track_cnt", C.c_void_p), ("un_pts", C.c_void_p),
+                ("velocity", C.c_void_p)]
+
+
+class VioFrameReadResult(C.Structure):
+    _fields_ = [(k, C.c_int32) for k in ("status", "n", "n_new", "n_tracked_in", "n_after_track", "n_after_reject", "reject_status",
+                                         "reject_hyp", "n_candidates", "reserved")]
+
+
 class FrameLib:
     """libvio_frame_hip.so: vio_frame_*."""
 
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "push_batch", "track_batch", "set_mask", "detect_batch",
                "download", "reset", "counters", "timing"]
+    READ_SYMBOLS = ["set_camera", "set_tracker", "read_batch", "points_set", "points_get", "read_timing"]      # include/vio_frame_read.h
 
     def __init__(self, path):
         self.path = path
@@ -59,6 +78,13 @@ class FrameLib:
         self.fn["reset"].argtypes = [C.c_void_p, C.c_int32]
         self.fn["counters"].argtypes = [C.c_void_p, C.c_void_p]
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_frame_", self.READ_SYMBOLS)[1])
+        self.fn["set_camera"].argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
+        self.fn["set_tracker"].argtypes = [C.c_void_p, C.c_int32, C.c_int32]
+        self.fn["read_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p]
+        self.fn["points_set"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.fn["points_get"].argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
+        self.fn["read_timing"].argtypes = [C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_frame handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -211,6 +237,76 @@ class FrameHandle(CompanionHandle):
 
     def detect(self, tracked=None, track_cnt=None, max_total=DEFAULT_MAX_TOTAL, slot=0):
         return self.detect_batch([dict(slot=slot, tracked=tracked, track_cnt=track_cnt, max_total=max_total)])[0]
+
+    # ---- readImage on resident points ------------------------------------------------------
+    def set_camera(self, fx, fy, cx, cy, k1=0.0, k2=0.0, p1=0.0, p2=0.0, width=752, height=480, model=MODEL_PINHOLE, seed=0,
+                   ransac_hypotheses=DEFAULT_HYPOTHESES, f_threshold=DEFAULT_F_THRESHOLD, focal_length=DEFAULT_FOCAL_LENGTH):
+        """The camera of RejectHandle.set_camera and the settings of RejectHandle.set_config, for read_batch."""
+        cam = VioRejectCamera(float(fx), float(fy), float(cx), float(cy), float(k1), float(k2), float(p1), float(p2), int(width), int(height),
+                              int(model), 0)
+        cfg = VioRejectConfig(int(seed) & 0xFFFFFFFF, int(ransac_hypotheses), float(f_threshold), float(focal_length))
+        self._ck(self.lib.fn["set_camera"](self.h, C.byref(cam), C.byref(cfg)), "set_camera")
+
+    def set_tracker(self, max_cnt=DEFAULT_MAX_CNT, border=DEFAULT_TRACK_BORDER):
+        """The reference's MAX_CNT (at most MAX_TRACK_POINTS) and inBorder's margin."""
+        self._ck(self.lib.fn["set_tracker"](self.h, C.c_int32(int(max_cnt)), C.c_int32(int(border))), "set_tracker")
+
+    def read_batch(self, imgs, times, slots=None, publish=True):
+        """FeatureTracker.read_image followed by update_ids for one new image of each slot, in one call (include/vio_frame_read.h).
+        imgs: (height, width) uint8 arrays; times: one time stamp per image, or one for all; slots: default 0 .. len(imgs) - 1.  A list
+        of dicts: pts (n, 2) float32, ids (n,) int64 (after updateID), track_cnt (n,) int32, un_pts, velocity (n, 2) float32, and the
+        counts n, n_new, n_tracked_in, n_after_track, n_after_reject, reject_status, reject_hyp, n_candidates."""
+        B = len(imgs)
+        slots = list(range(B)) if slots is None else [int(s) for s in slots]
+        times = [float(times)] * B if np.isscalar(times) else [float(t) for t in times]
+        if len(slots) != B or len(times) != B:
+            raise ValueError("one slot and one time per image")
+        arr = (VioFrameReadItem * max(B, 1))()
+        res = (VioFrameReadResult * max(B, 1))()
+        keep, outs = [], []
+        R = MAX_TRACK_POINTS
+        for i in range(B):
+            a = _image(imgs[i])
+            o = (np.zeros((R, 2), np.float32), np.zeros(R, np.int64), np.zeros(R, np.int32), np.zeros((R, 2), np.float32), np.zeros((R, 2), np.float32))
+            keep.append(a)
+            outs.append(o)
+            arr[i] = VioFrameReadItem(slots[i], a.shape[1], a.shape[0], a.strides[0], a.ctypes.data, times[i], *[x.ctypes.data for x in o])
+        self._ck(self.lib.fn["read_batch"](self.h, C.c_int32(B), C.addressof(arr), C.c_int32(1 if publish else 0), C.addressof(res)), "read_batch")
+        out = []
+        for i in range(B):
+            self.shapes[slots[i]] = keep[i].shape
+            r, n = res[i], int(res[i].n)
+            d = dict(zip(("pts", "ids", "track_cnt", "un_pts", "velocity"), (x[:n].copy() for x in outs[i])))
+            d.update({k: int(getattr(r, k)) for k in ("status", "n", "n_new", "n_tracked_in", "n_after_track", "n_after_reject", "reject_status",
+                                                     "reject_hyp", "n_candidates")})
+            out.append(d)
+        return out
+
+    def points_set(self, pts, ids=None, track_cnt=None, slot=0):
+        """Seeds the slot's points (they lie in its next frame): pts (n, 2); ids default -1, track_cnt default 1."""
+        p = np.ascontiguousarray(pts, dtype=np.float32).reshape(-1, 2)
+        i = np.full(len(p), -1, np.int64) if ids is None else np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        c = np.ones(len(p), np.int32) if track_cnt is None else np.ascontiguousarray(track_cnt, dtype=np.int32).reshape(-1)
+        if len(i) != len(p) or len(c) != len(p):
+            raise ValueError("ids and track_cnt need one entry per point")
+        self._ck(self.lib.fn["points_set"](self.h, C.c_int32(slot), C.c_int32(len(p)), p.ctypes.data, i.ctypes.data, c.ctypes.data), "points_set")
+
+    def points_get(self, slot=0):
+        """The slot's resident points: dict(pts, ids, track_cnt, prev_un_ids, prev_un_pts, next_id)."""
+        R = MAX_TRACK_POINTS
+        n, m, nid = C.c_int32(0), C.c_int32(0), C.c_int64(0)
+        p, i, c = np.zeros((R, 2), np.float32), np.zeros(R, np.int64), np.zeros(R, np.int32)
+        pi, pp = np.zeros(R, np.int64), np.zeros((R, 2), np.float32)
+        self._ck(self.lib.fn["points_get"](self.h, C.c_int32(slot), C.addressof(n), p.ctypes.data, i.ctypes.data, c.ctypes.data, C.addressof(m),
+                                           pi.ctypes.data, pp.ctypes.data, C.addressof(nid)), "points_get")
+        return dict(pts=p[:n.value].copy(), ids=i[:n.value].copy(), track_cnt=c[:n.value].copy(), prev_un_ids=pi[:m.value].copy(),
+                    prev_un_pts=pp[:m.value].copy(), next_id=int(nid.value))
+
+    def read_timing(self):
+        """ms of the last read_batch by stage (include/vio_frame_read.h)."""
+        t = (C.c_double * 8)()
+        self._ck(self.lib.fn["read_timing"](self.h, t), "read_timing")
+        return dict(zip(("host_ms", "push_ms", "track_ms", "reject_ms", "detect_ms", "finish_ms", "readback_ms", "total_ms"), t))
 
     # ---- accounting -----------------------------------------------------------------------
     def counters(self):

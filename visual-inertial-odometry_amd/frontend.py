@@ -34,6 +34,9 @@ handle's business (its equalize setting), so tracker, detector and equalizer may
 None; frames.download(slot, PREV or NEXT) gives them.  With frames=None nothing of this happens.
 
 Missing against the reference: the camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA).
+BatchFeatureTracker is the same front end for many streams at once over a frame.FrameHandle's read_batch: the points stay on the
+device, one call reads one new image of every stream.
+
 One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
 """
@@ -155,3 +158,54 @@ class FeatureTracker:
         self.ids[new] = self.n_id + np.arange(len(new))
         self.n_id += len(new)
         return self.ids.copy()
+
+
+class BatchFeatureTracker:
+    """FeatureTracker(frames=, rejecter=, slot=s) followed by update_ids, for every slot of `slots` in one call per frame: the join of
+    the steps runs on the device (frame.FrameHandle.read_batch, include/vio_frame_read.h), the points never leave it, and every array equals
+    the per-stream loop's byte for byte.
+
+        bt = BatchFeatureTracker(frames, slots=range(64), max_cnt=150, min_dist=30)       # frames.set_camera(...) first
+        outs = bt.read_images(imgs, t)               # dicts of pts, ids (after updateID), track_cnt, un_pts, velocity, n_new
+        for ids, rows in bt.feature_frames(): ...    # per slot, FeatureTracker.feature_frame()'s pair
+
+    masks: None, or {slot: mask}.  The handle's detector gets min_distance = min_dist (its other settings return to their defaults), as
+    in FeatureTracker."""
+
+    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None):
+        self.frames, self.slots = frames, [int(s) for s in slots]
+        if len(set(self.slots)) != len(self.slots):
+            raise ValueError("a slot is listed twice")
+        self.max_cnt, self.min_dist, self.border = int(max_cnt), int(min_dist), int(border)
+        frames.set_config(detect=dict(min_distance=self.min_dist))
+        frames.set_tracker(max_cnt=self.max_cnt, border=self.border)
+        for s, m in (masks or {}).items():
+            frames.set_mask(m, slot=int(s))
+        self.last = [None] * len(self.slots)
+
+    def read_images(self, imgs, t, publish=True):
+        """One new image per slot, in the order of `slots`; t: one time stamp for all, or one per image.  Returns read_batch's dicts."""
+        if len(imgs) != len(self.slots):
+            raise ValueError("one image per slot")
+        for img in imgs:
+            a = np.asarray(img)
+            if a.dtype != np.uint8 or a.ndim != 2:
+                raise ValueError("an image must be a 2-d uint8 array")
+        self.last = self.frames.read_batch(imgs, t, slots=self.slots, publish=publish)
+        return self.last
+
+    def feature_frames(self):
+        """Per slot what the reference publishes of its last frame: (ids (n,) int64, rows (n, 7) float64 of x, y, 1, u, v, vx, vy) of the
+        points with track_cnt > 1."""
+        out = []
+        for o in self.last:
+            if o is None:
+                raise RuntimeError("feature_frames needs a frame: call read_images first")
+            k = np.nonzero(o["track_cnt"] > 1)[0]
+            rows = np.zeros((len(k), 7), dtype=np.float64)
+            rows[:, 0:2] = o["un_pts"][k]
+            rows[:, 2] = 1.0
+            rows[:, 3:5] = o["pts"][k]
+            rows[:, 5:7] = o["velocity"][k]
+            out.append((o["ids"][k].copy(), rows))
+        return out
