@@ -1,19 +1,8 @@
 // vio_clahe.hip — libvio_clahe_hip.so: CLAHE equalisation of many 8-bit images in one call (include/vio_clahe.h).
-//
-//   k_clahe_lut      one 256-thread workgroup per (tile, image).  The tile's histogram in LDS with integer atomicAdd, one private copy
-//                    per wavefront (a flat tile puts every pixel in one bin), the source read through the reflection where the image
-//                    was extended.  Then thread b owns bin b: the merged count, the clip, the tile's excess by a butterfly across the
-//                    wave and one LDS slot per wave, the closed form of the redistribution, an inclusive scan (wave scan plus the
-//                    waves' offsets), and the LUT byte to global memory.
-//   k_clahe_apply    a TX x TY block of pixels per workgroup, every image of the call in the grid (blockIdx.z).  Four pixels per
-//                    thread and pass, one 4-byte load and one 4-byte store (the device copies have a pitch that is a multiple of 4, so
-//                    every row is aligned); the four look-ups per pixel are byte gathers indexed by the pixel's value, out of
-//                    LDS: the LUTs of the tiles the block of pixels can touch (a contiguous range in x and in y, known from the
-//                    block's corners since the tile index is monotone in the position) are copied there first.  Gathering from
-//                    global memory instead was measured and is slower.
 // No floating-point atomics, no spin-waits, nothing between workgroups.  Contraction is off as in vio_flow.hip and vio_detect.hip: here
 // it matters, a fused multiply-add in the blend changes output bytes (vio_clahe_math.h).
-// The kernels themselves are in vio_clahe_body.inc, which libvio_frame_hip compiles too; the host side is here.
+// The kernels, described where they are, are in vio_clahe_body.inc, which libvio_frame_hip compiles too; what the
+// host side shares with that library is in vio_clahe_host.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -21,7 +10,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_clahe.h"
@@ -31,6 +19,7 @@
 
 #include "vio_clahe_math.h"
 
+#include "vio_clahe_host.h"
 #include "vio_clahe_body.inc"
 
 constexpr int MAX_ITEMS = 4096;
@@ -41,7 +30,7 @@ constexpr int MAX_ITEMS = 4096;
 struct vio_clahe {
     int device = 0;
     ErrText err = {0};
-    vio_clahe_config cfg = {VIO_CLAHE_DEFAULT_CLIP_LIMIT, VIO_CLAHE_DEFAULT_TILES, VIO_CLAHE_DEFAULT_TILES};
+    vio_clahe_config cfg = CLAHE_DEFAULTS;
     Twin<char> tab;                                      // item descriptors
     Twin<uint8_t> img;                                   // the sources, rows at the device pitch
     Twin<uint8_t> out;                                   // the LUTs of every item | the results, laid out as the sources
@@ -50,8 +39,6 @@ struct vio_clahe {
 };
 
 namespace {
-
-vio_status fail_synced(vio_clahe *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
 
 size_t last_byte(const vio_clahe_item &it, int stride) { return (size_t)(it.height - 1) * (size_t)stride + (size_t)it.width; }
 
@@ -64,39 +51,16 @@ int32_t vio_clahe_version(void) { return VIO_CLAHE_VERSION; }
 const char *vio_clahe_last_error(const vio_clahe *h) { return h ? h->err : "NULL handle"; }
 
 vio_status vio_clahe_create(int32_t device, void *stream, vio_clahe **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_clahe *h = new (std::nothrow) vio_clahe();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess) { vio_clahe_destroy(h); return VIO_ERR_HIP; }
-    // (16 x 16 tiles stage 64 KB; a launch that asks for more than the kernel may have fails and is reported)
-    (void)hipFuncSetAttribute((const void *)k_clahe_apply, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              VIO_CLAHE_MAX_TILES * VIO_CLAHE_MAX_TILES * BINS);
-    (void)hipGetLastError();
-    *out = h;
-    return VIO_OK;
+    return create_handle(device, stream, out, vio_clahe_destroy, [](vio_clahe *) { clahe_allow_lds(); return true; });
 }
 
-void vio_clahe_destroy(vio_clahe *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                            // (the buffers free themselves)
-}
+void vio_clahe_destroy(vio_clahe *h) { destroy_handle(h); }
 
 vio_status vio_clahe_set_config(vio_clahe *h, const vio_clahe_config *cfg) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    if (!cfg || !std::isfinite(cfg->clip_limit) || cfg->clip_limit < 0.0 || cfg->tiles_x < 1 || cfg->tiles_x > VIO_CLAHE_MAX_TILES ||
-        cfg->tiles_y < 1 || cfg->tiles_y > VIO_CLAHE_MAX_TILES)
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_clahe_set_config: clip_limit finite and >= 0, tiles_x and tiles_y in [1, %d]", VIO_CLAHE_MAX_TILES);
+    const vio_status st = clahe_check_config(h->err, "vio_clahe_set_config", cfg);
+    if (st != VIO_OK) return st;
     h->cfg = *cfg;
     return VIO_OK;
 }
@@ -115,7 +79,7 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
     if (count == 0) return VIO_OK;
     const auto t0 = std::chrono::steady_clock::now();
     // every argument of every item first: nothing is written or launched on an error
-    const int tiles_x = h->cfg.tiles_x, tiles_y = h->cfg.tiles_y, tiles = tiles_x * tiles_y;
+    const int tiles = h->cfg.tiles_x * h->cfg.tiles_y;
     std::vector<ClaheItemD> its((size_t)count);
     std::vector<int64_t> at((size_t)count, 0);           // an item's byte offset in the input buffer and, past the LUTs, in the output buffer
     int64_t b_img = 0;
@@ -129,15 +93,9 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
         if (!it.src || !it.dst) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: src and dst are required", i);
         const uintptr_t s0 = (uintptr_t)it.src, s1 = s0 + last_byte(it, it.src_stride), d0 = (uintptr_t)it.dst, d1 = d0 + last_byte(it, it.dst_stride);
         if (s0 < d1 && d0 < s1) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: dst overlaps src", i);
-        const ClaheGeom g = clahe_geometry(it.width, it.height, tiles_x, tiles_y, h->cfg.clip_limit);
         ClaheItemD &d = its[(size_t)i];
         std::memset(&d, 0, sizeof(d));
-        d.w = it.width; d.h = it.height;
-        d.pitch = (it.width + PX - 1) / PX * PX;
-        d.ext = g.ext; d.tile_w = g.tile_w; d.tile_h = g.tile_h; d.area = g.area; d.clip = g.clip;
-        d.ptiles_x = (it.width + TX - 1) / TX;
-        d.ptiles = d.ptiles_x * ((it.height + TY - 1) / TY);
-        d.lut_scale = g.lut_scale; d.inv_tile_w = g.inv_tile_w; d.inv_tile_h = g.inv_tile_h;
+        clahe_item(d, it.width, it.height, clahe_pitch(it.width), h->cfg);
         at[(size_t)i] = b_img;
         b_img += (int64_t)align256((size_t)d.pitch * (size_t)d.h);
         max_ptiles = std::max(max_ptiles, d.ptiles);
@@ -155,19 +113,9 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
         its[(size_t)i].dst = h->out.d + b_lut + at[(size_t)i];
     }
     std::memcpy(h->tab.h, its.data(), b_tab);
-    for (int i = 0; i < count; ++i) {
-        const vio_clahe_item &it = items[i];
-        const ClaheItemD &d = its[(size_t)i];
-        for (int y = 0; y < d.h; ++y) {
-            uint8_t *row = h->img.h + at[(size_t)i] + (size_t)y * (size_t)d.pitch;
-            std::memcpy(row, it.src + (size_t)y * (size_t)it.src_stride, (size_t)d.w);
-            std::memset(row + d.w, 0, (size_t)(d.pitch - d.w));
-        }
-    }
-    ClaheArgs a;
-    a.items = (const ClaheItemD *)h->tab.d;
-    a.luts = h->out.d;
-    a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.count = count;
+    for (int i = 0; i < count; ++i)
+        pack_rows(h->img.h + at[(size_t)i], its[(size_t)i].pitch, items[i].src, items[i].width, items[i].height, items[i].src_stride);
+    const ClaheArgs a = clahe_args((const ClaheItemD *)h->tab.d, h->out.d, h->cfg, count);
     const auto t1 = std::chrono::steady_clock::now();
     hipStream_t q = h->q.stream;
     (void)hipEventRecord(h->q.ev[0], q);
@@ -175,9 +123,7 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
         hipMemcpyAsync(h->img.d, h->img.h, (size_t)b_img, hipMemcpyHostToDevice, q) != hipSuccess)
         return fail_synced(h, "upload failed");
     (void)hipEventRecord(h->q.ev[1], q);
-    hipLaunchKernelGGL(k_clahe_lut, dim3((unsigned)tiles, 1, (unsigned)count), dim3(NT), 0, q, a);
-    (void)hipEventRecord(h->q.ev[2], q);
-    hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)max_ptiles, 1, (unsigned)count), dim3(NT), (size_t)tiles * BINS, q, a);
+    clahe_launch(q, a, max_ptiles, h->q.ev[2]);
     (void)hipEventRecord(h->q.ev[3], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
     const size_t from = want_luts ? 0 : b_lut;
@@ -189,8 +135,7 @@ vio_status vio_clahe_apply_batch(vio_clahe *h, int32_t count, const vio_clahe_it
         const ClaheItemD &d = its[(size_t)i];
         vio_clahe_result &o = results[i];
         o.status = VIO_OK; o.clip = d.clip; o.tile_w = d.tile_w; o.tile_h = d.tile_h;
-        for (int y = 0; y < d.h; ++y)
-            std::memcpy(it.dst + (size_t)y * (size_t)it.dst_stride, h->out.h + b_lut + at[(size_t)i] + (size_t)y * (size_t)d.pitch, (size_t)d.w);
+        copy_rows(it.dst, it.dst_stride, h->out.h + b_lut + at[(size_t)i], d.pitch, d.w, d.h);
         if (it.luts) std::memcpy(it.luts, h->out.h + (size_t)i * (size_t)tiles * BINS, (size_t)tiles * BINS);
     }
     const auto t2 = std::chrono::steady_clock::now();

@@ -1,7 +1,7 @@
-// vio_clahe_body.inc — the two CLAHE kernels and their descriptor tables, the one copy libvio_clahe_hip (vio_clahe.hip, at file scope)
+// vio_clahe_body.inc — the two CLAHE kernels and their launches, the one copy libvio_clahe_hip (vio_clahe.hip, at file scope)
 // and libvio_frame_hip (vio_frame.hip, inside a namespace of its own) compile (DESIGN.md sections 22 and 23).  The including file has
-// included <hip/hip_runtime.h>, <cstdint> and vio_clahe_math.h, and has contraction off: a fused multiply-add in the blend changes
-// output bytes.
+// included <hip/hip_runtime.h>, <cstdint>, vio_clahe_math.h and vio_clahe_host.h (the descriptor tables, TX, TY and PX), and has
+// contraction off: a fused multiply-add in the blend changes output bytes.
 //
 //   k_clahe_lut      one 256-thread workgroup per (tile, image).  The tile's histogram in LDS with integer atomicAdd, one private copy
 //                    per wavefront (a flat tile puts every pixel in one bin), the source read through the reflection where the image
@@ -20,27 +20,9 @@ constexpr int WAVE = 64;
 constexpr int BINS = VIO_CLAHE_BINS;
 constexpr int NT = 256;                 // threads of both kernels
 constexpr int NW = NT / WAVE;
-constexpr int TX = VIO_CLAHE_TILE_X, TY = VIO_CLAHE_TILE_Y;
-constexpr int PX = 4;                   // pixels of a thread per pass
 constexpr int ROWS = NT / (TX / PX);    // rows of a pass
 static_assert(NT == BINS, "k_clahe_lut: thread b owns bin b");
 static_assert(TX % PX == 0 && NT % (TX / PX) == 0 && TY % ROWS == 0, "k_clahe_apply: whole passes over the block of pixels");
-
-struct ClaheItemD {
-    int32_t w, h, pitch, ext;           // pitch: bytes between rows of the source and of the result, a multiple of PX
-    int32_t tile_w, tile_h, area, clip;
-    int32_t ptiles_x, ptiles;           // the blocks of pixels of k_clahe_apply: across, and in all
-    float lut_scale, inv_tile_w, inv_tile_h;
-    int32_t pad;
-    const uint8_t *src;                 // device addresses, 4-byte aligned
-    uint8_t *dst;
-};
-
-struct ClaheArgs {
-    const ClaheItemD *items;
-    uint8_t *luts;                      // [count][tiles_y][tiles_x][256]
-    int32_t tiles_x, tiles_y, count;
-};
 
 __global__ __launch_bounds__(NT) void k_clahe_lut(ClaheArgs a) {
     __shared__ int32_t hist[NW][BINS];
@@ -143,4 +125,19 @@ __global__ __launch_bounds__(NT) void k_clahe_apply(ClaheArgs a) {
         }
         *(uint32_t *)(D.dst + at) = out4;
     }
+}
+
+// k_clahe_apply stages the LUTs of up to 16 x 16 tiles, 64 KB; a launch that asks for more than the kernel may have fails and is
+// reported.  Once per process and device, from a library's create.
+inline void clahe_allow_lds() {
+    (void)hipFuncSetAttribute((const void *)k_clahe_apply, hipFuncAttributeMaxDynamicSharedMemorySize, VIO_CLAHE_MAX_TILES * VIO_CLAHE_MAX_TILES * BINS);
+    (void)hipGetLastError();
+}
+
+// the two launches of a call on q; between: an event recorded between them, or NULL
+inline void clahe_launch(hipStream_t q, const ClaheArgs &a, int max_ptiles, hipEvent_t between) {
+    const int tiles = a.tiles_x * a.tiles_y;
+    hipLaunchKernelGGL(k_clahe_lut, dim3((unsigned)tiles, 1, (unsigned)a.count), dim3(NT), 0, q, a);
+    if (between) (void)hipEventRecord(between, q);
+    hipLaunchKernelGGL(k_clahe_apply, dim3((unsigned)max_ptiles, 1, (unsigned)a.count), dim3(NT), (size_t)tiles * BINS, q, a);
 }

@@ -1,16 +1,15 @@
-// vio_companion.h — the host plumbing every companion library (libvio_{cov,res,imu,marg,init}_hip) shares: the device scope, the
-// error text, the pinned/device buffers, and the stream and timing events of a handle.  Host code only; every name has internal
-// linkage, so nothing here is exported (the libraries' version scripts export their own prefix alone).
+// vio_companion.h — the host plumbing every companion library shares (libvio_{cov,res,imu,marg,init,sfm,exrot,pnp,flow,detect,
+// reject,clahe,frame}_hip): the device scope, the error text (vio_host_base.h), the pinned/device buffers, the stream and timing events
+// of a handle, and the create / destroy pair of the libraries whose create takes (device, stream).  Host code only; every name has
+// internal linkage, so nothing here is exported (the libraries' version scripts export their own prefix alone).
 #pragma once
 
 #include <hip/hip_runtime.h>
 
 #include <cmath>
-#include <cstdarg>
-#include <cstddef>
-#include <cstdio>
+#include <new>
 
-#include "../../include/vio_backend.h"
+#include "vio_host_base.h"
 
 namespace {
 
@@ -28,17 +27,6 @@ struct DeviceScope {
     DeviceScope(const DeviceScope &) = delete;
     DeviceScope &operator=(const DeviceScope &) = delete;
 };
-
-// a handle's last error, returned by its vio_*_last_error
-typedef char ErrText[512];
-
-__attribute__((format(printf, 3, 4))) inline vio_status fail(ErrText &err, vio_status st, const char *fmt, ...) {
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(err, sizeof(ErrText), fmt, ap);
-    va_end(ap);
-    return st;
-}
 
 inline vio_status hip_ck(ErrText &err, hipError_t e, const char *what) {
     if (e == hipSuccess) return VIO_OK;
@@ -128,12 +116,51 @@ template <int N> struct StreamEvents {
     }
 };
 
-inline size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 // the time between two recorded events, in ms; NaN when it cannot be had
 inline float elapsed_ms(hipEvent_t a, hipEvent_t b) {
     float ms = 0.f;
     return hipEventElapsedTime(&ms, a, b) == hipSuccess ? ms : NAN;
 }
+
+// an error behind work that was enqueued: the stream is drained before the caller sees it
+template <class H> vio_status fail_synced(H *h, const char *msg) {
+    (void)hipStreamSynchronize(h->q.stream);
+    return fail(h->err, VIO_ERR_HIP, "%s", msg);
+}
+
+// The create of a handle H {int device; StreamEvents<N> q; ...} on (device, stream).  `extra(h)` is what a library adds once the stream
+// and the events exist (a kernel's function attribute, more events); false fails the create, and the handle goes through `destroy`,
+// the library's own.
+template <class H, class Extra> vio_status create_handle(int32_t device, void *stream, H **out, void (*destroy)(H *), Extra extra) {
+    if (!out) return VIO_ERR_BAD_ARG;
+    *out = nullptr;
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
+    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
+    DeviceScope dev(device);
+    if (!dev.ok) return VIO_ERR_HIP;
+    H *h = new (std::nothrow) H();
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->device = device;
+    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
+    if (h->q.create_events() != hipSuccess || !extra(h)) { destroy(h); return VIO_ERR_HIP; }
+    *out = h;
+    return VIO_OK;
+}
+
+template <class H> vio_status create_handle(int32_t device, void *stream, H **out, void (*destroy)(H *)) {
+    return create_handle(device, stream, out, destroy, [](H *) { return true; });
+}
+
+// ... and its destroy: waits for the stream, then `extra(h)` frees what the library added; the buffers free themselves.
+template <class H, class Extra> void destroy_handle(H *h, Extra extra) {
+    if (!h) return;
+    DeviceScope dev(h->device);
+    h->q.release();
+    extra(h);
+    delete h;
+}
+
+template <class H> void destroy_handle(H *h) { destroy_handle(h, [](H *) {}); }
 
 }  // namespace

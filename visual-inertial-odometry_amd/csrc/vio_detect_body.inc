@@ -1,7 +1,7 @@
-// vio_detect_body.inc — the four detection kernels, the greedy loop and their descriptor tables, the one copy libvio_detect_hip
+// vio_detect_body.inc — the four detection kernels, the greedy loop and their launches, the one copy libvio_detect_hip
 // (vio_detect.hip, at file scope) and libvio_frame_hip (vio_frame.hip, inside a namespace of its own) compile (DESIGN.md sections 20 and
-// 23).  The including file has included <hip/hip_runtime.h>, <cstdint> and vio_detect_math.h, and has contraction off (with this
-// arithmetic it cannot change a bit).
+// 23).  The including file has included <hip/hip_runtime.h>, <cstdint>, vio_detect_math.h and vio_detect_host.h (the descriptor tables,
+// TX and TY), and has contraction off (with this arithmetic it cannot change a bit).
 //
 //   k_detect_setmask     one workgroup per image: the greedy loop below over the tracked points, key (track_cnt, -index), disc <=.
 //                        Leaves the kept centres and their indices in output order.
@@ -19,46 +19,11 @@
 // An item names its image and its mask by address and row pitch: the host-array library packs rows tightly (pitch = width), the
 // resident library points at a frame's level 0 and at the slot's mask where they lie.  The response map is tightly packed in both.
 constexpr int WAVE = 64;
-constexpr int TX = VIO_DETECT_TILE_X, TY = VIO_DETECT_TILE_Y;
 constexpr int NT = TX * TY;             // threads of a tile
 constexpr int NT_MASK = 256;            // threads of k_detect_setmask
 constexpr int NT_SEL = 1024;            // threads of k_detect_select
 constexpr uint32_t DEAD = 0x80000000u;  // a struck candidate (pixel indices are below 2^28)
 static_assert(NT % WAVE == 0 && NT <= 1024, "a tile is whole wavefronts");
-
-struct DetItemD {
-    int32_t w, h, n_tracked, max_total;
-    int32_t active, has_mask, tiles_x, tiles;
-    const uint8_t *img, *mask;          // device addresses of the image and of the mask (NULL without one)
-    int64_t r;                          // the response map's offset, in doubles
-    int64_t cand;                       // the candidate list's offset, in entries
-    int32_t trk;                        // the first tracked point, in the tables of the call
-    int32_t newp;                       // the first row of new_pts, in the call's
-    int32_t pitch, pad;                 // bytes between the rows of the image and of the mask
-};
-
-struct DetTrk {
-    int32_t cx, cy, cnt, pad;
-};
-
-struct DetRes {
-    int32_t n_kept, n_new, n_cand, pad;
-    unsigned long long maxbits;         // the bits of maxR
-};
-
-struct DetArgs {
-    const DetItemD *items;
-    const DetTrk *trk;
-    double *r;
-    uint32_t *cand;
-    unsigned long long *tkey;           // [tracked points of the call]: the keys of the setMask loop, 0 once struck
-    int32_t *kept_xy;                   // [tracked points of the call][2]: the kept centres in output order
-    DetRes *res;
-    int32_t *keep_order;
-    float *new_pts;
-    double quality;
-    int32_t d2, count;
-};
 
 // ---------------------------------------------------------------------------------------------------------
 // the greedy loop
@@ -279,3 +244,15 @@ __global__ __launch_bounds__(NT_SEL) void k_detect_select(DetArgs a) {
     if (threadIdx.x == 0) a.res[item].n_new = n_new;
 }
 
+// The four launches of a call on q.  mask: some item has tracked points; tiles: some item has an image (max_tiles > 0).  between: three
+// events recorded between the launches, or NULL.
+inline void det_launch(const DetArgs &a, hipStream_t q, bool mask, bool tiles, int max_tiles, hipEvent_t *between) {
+    const dim3 per_item((unsigned)a.count), per_tile((unsigned)max_tiles, 1, (unsigned)a.count);
+    if (mask) hipLaunchKernelGGL(k_detect_setmask, per_item, dim3(NT_MASK), 0, q, a);
+    if (between) (void)hipEventRecord(between[0], q);
+    if (tiles) hipLaunchKernelGGL(k_detect_response, per_tile, dim3(NT), 0, q, a);
+    if (between) (void)hipEventRecord(between[1], q);
+    if (tiles) hipLaunchKernelGGL(k_detect_candidates, per_tile, dim3(NT), 0, q, a);
+    if (between) (void)hipEventRecord(between[2], q);
+    if (tiles) hipLaunchKernelGGL(k_detect_select, per_item, dim3(NT_SEL), 0, q, a);
+}

@@ -21,7 +21,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_exrot.h"
@@ -364,8 +363,6 @@ struct vio_exrot {
 
 namespace {
 
-vio_status fail_synced(vio_exrot *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
-
 vio_status check_item(vio_exrot *h, int i, const vio_exrot_item &it, bool tracks, bool imu) {
     if (it.n_frames < 2 || it.n_frames > VIO_EXROT_MAX_FRAMES)
         return fail(h->err, VIO_ERR_BAD_ARG, "window %d: n_frames must be in [2, %d]", i, VIO_EXROT_MAX_FRAMES);
@@ -550,29 +547,9 @@ int32_t vio_exrot_version(void) { return VIO_EXROT_VERSION; }
 
 const char *vio_exrot_last_error(const vio_exrot *h) { return h ? h->err : "NULL handle"; }
 
-vio_status vio_exrot_create(int32_t device, void *stream, vio_exrot **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_exrot *h = new (std::nothrow) vio_exrot();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess) { vio_exrot_destroy(h); return VIO_ERR_HIP; }
-    *out = h;
-    return VIO_OK;
-}
+vio_status vio_exrot_create(int32_t device, void *stream, vio_exrot **out) { return create_handle(device, stream, out, vio_exrot_destroy); }
 
-void vio_exrot_destroy(vio_exrot *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                            // (the buffers free themselves)
-}
+void vio_exrot_destroy(vio_exrot *h) { destroy_handle(h); }
 
 vio_status vio_exrot_set_config(vio_exrot *h, const vio_exrot_config *cfg) {
     if (!h) return VIO_ERR_BAD_ARG;

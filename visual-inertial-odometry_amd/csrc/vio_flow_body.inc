@@ -1,7 +1,7 @@
-// vio_flow_body.inc — the pyramid and tracking kernels and their descriptor tables, the one copy libvio_flow_hip (vio_flow.hip, at
+// vio_flow_body.inc — the pyramid and tracking kernels and their launches, the one copy libvio_flow_hip (vio_flow.hip, at
 // file scope) and libvio_frame_hip (vio_frame.hip, inside a namespace of its own) compile (DESIGN.md sections 19 and 23).  The including
-// file has included <hip/hip_runtime.h>, <cstdint> and vio_flow_math.h, and has contraction off: products and sums round as the host
-// restatement's (tests/flow_reference.py) do.
+// file has included <hip/hip_runtime.h>, <cstdint>, vio_flow_math.h and vio_flow_host.h (the descriptor tables and MAXL), and has
+// contraction off: products and sums round as the host restatement's (tests/flow_reference.py) do.
 //
 //   k_flow_pyr_down   one launch per level, every image of the call in the grid (blockIdx.y), one thread per output pixel: the 5 x 5
 //                     [1 4 6 4 1] x [1 4 6 4 1] sum of the level below with BORDER_REFLECT_101, (sum + 128) >> 8.  Integers only.
@@ -19,40 +19,7 @@
 constexpr int WAVE = 64;
 constexpr int WAVES = 4;                // keypoints per workgroup
 constexpr int NT = WAVE * WAVES;
-constexpr int MAXL = VIO_FLOW_MAX_LEVELS;
 constexpr int PPL = (4 * VIO_FLOW_MAX_HALF_PATCH * VIO_FLOW_MAX_HALF_PATCH) / WAVE;     // patch pixels per lane at the largest patch
-
-struct FlowItemD {
-    int32_t w[MAXL], h[MAXL];
-    int32_t pitch[MAXL];                // bytes between the rows of a level, the same for both images
-    uint8_t *prev[MAXL], *next[MAXL];   // the levels' device addresses
-    int32_t active, pad;                // 0: an item without keypoints, nothing of it is staged
-};
-
-struct FlowPt {
-    int32_t item, has_guess;
-    float px, py, gx, gy;
-};
-
-struct FlowOut {
-    float x, y;
-    int32_t status, iterations;
-    double cost;
-};
-
-struct PyrArgs {
-    const FlowItemD *items;
-    int32_t level;                      // the source level
-    int32_t nimg;
-    int32_t both, pad;                  // 1: image 2 i is item i's prev and image 2 i + 1 its next; 0: image i is item i's next
-};
-
-struct FlowArgs {
-    const FlowItemD *items;
-    const FlowPt *pts;
-    FlowOut *out;
-    int32_t npts, levels, half_patch, max_iter, border, early_stop;
-};
 
 __global__ __launch_bounds__(NT) void k_flow_pyr_down(PyrArgs a) {
     const int img = blockIdx.y;
@@ -183,4 +150,19 @@ template <bool INV> __global__ __launch_bounds__(NT) void k_flow_track(FlowArgs 
         status = inside ? VIO_OK : VIO_FLOW_FAIL_BORDER;
     }
     if (lane == 0) { o->x = sx; o->y = sy; o->status = status; o->iterations = its; o->cost = cost_last; }
+}
+
+// one k_flow_pyr_down launch per level above 0 of nimg images (PyrArgs::both says which); max_px[l]: the largest level-l image of the call
+inline void flow_launch_pyramids(hipStream_t q, const FlowItemD *items_d, int nimg, int both, int levels, const int64_t *max_px) {
+    for (int l = 0; l + 1 < levels; ++l) {
+        PyrArgs pa;
+        pa.items = items_d; pa.level = l; pa.nimg = nimg; pa.both = both; pa.pad = 0;
+        hipLaunchKernelGGL(k_flow_pyr_down, dim3((unsigned)((max_px[l + 1] + NT - 1) / NT), (unsigned)nimg), dim3(NT), 0, q, pa);
+    }
+}
+
+inline void flow_launch_track(hipStream_t q, const FlowArgs &a, bool inverse) {
+    const dim3 grid((unsigned)((a.npts + WAVES - 1) / WAVES));
+    if (inverse) hipLaunchKernelGGL(k_flow_track<true>, grid, dim3(NT), 0, q, a);
+    else hipLaunchKernelGGL(k_flow_track<false>, grid, dim3(NT), 0, q, a);
 }

@@ -4,9 +4,10 @@
 // The numeric kernels are those of libvio_clahe_hip, libvio_flow_hip, libvio_detect_hip and libvio_reject_hip, compiled from the same
 // four files (vio_clahe_body.inc, vio_flow_body.inc, vio_detect_body.inc, vio_reject_body.inc), each inside a namespace since their
 // constants share names.  The five kernels that join them in vio_frame_read_batch are in vio_front_body.inc.
-// What is here is the host side: the slot table and the block pool (vio_frame_slots.h, plain C++), the descriptor
-// tables that point the kernels at resident frames, and the copies.  A frame is written by one upload (or by k_clahe_apply out of the
-// upload buffer) and the pyramid kernel, and read in place ever after: there is no repacking pass.
+// What is here is the host side that is this library's own: the slot table and the block pool (vio_frame_slots.h, plain C++), the
+// descriptor tables that point the kernels at resident frames, and the copies.  The checks, fills, launches and unpacking of a stage
+// are those of its library, from vio_{clahe,flow,detect,reject}_host.h and the end of each body.  A frame is
+// written by one upload (or by k_clahe_apply out of the upload buffer) and the pyramid kernel, and read in place ever after.
 // Contraction is off for all of it, as in the three libraries; in CLAHE it decides bytes.
 #include <hip/hip_runtime.h>
 
@@ -15,7 +16,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_frame.h"
@@ -32,15 +32,19 @@
 #include "vio_sfm_math.h"
 
 namespace kc {
+#include "vio_clahe_host.h"
 #include "vio_clahe_body.inc"
 }
 namespace kf {
+#include "vio_flow_host.h"
 #include "vio_flow_body.inc"
 }
 namespace kd {
+#include "vio_detect_host.h"
 #include "vio_detect_body.inc"
 }
 namespace kr {
+#include "vio_reject_host.h"
 #include "vio_reject_body.inc"
 }
 #include "vio_front_body.inc"
@@ -57,9 +61,9 @@ struct vio_frame {
     int device = 0;
     ErrText err = {0};
     int32_t equalize = 0;
-    vio_clahe_config ccfg = {VIO_CLAHE_DEFAULT_CLIP_LIMIT, VIO_CLAHE_DEFAULT_TILES, VIO_CLAHE_DEFAULT_TILES};
-    vio_flow_config fcfg = {VIO_FLOW_DEFAULT_LEVELS, VIO_FLOW_DEFAULT_HALF_PATCH, VIO_FLOW_DEFAULT_MAX_ITER, 0, VIO_FLOW_DEFAULT_BORDER, 0};
-    vio_detect_config dcfg = {VIO_DETECT_DEFAULT_QUALITY, VIO_DETECT_DEFAULT_MIN_DISTANCE, 0};
+    vio_clahe_config ccfg = kc::CLAHE_DEFAULTS;
+    vio_flow_config fcfg = kf::FLOW_DEFAULTS;
+    vio_detect_config dcfg = kd::DET_DEFAULTS;
     FrameTable tab;
     // uploads: the pinned staging of the raw images (and of a mask) with its device twin, the upload buffer the CLAHE kernels read; the
     // descriptor tables of a push.  `staged` is recorded behind the copies that read the pinned halves, and waited for before they are
@@ -83,7 +87,7 @@ struct vio_frame {
     bool push_timed = true;                              // false: the last push's events have not been read yet
     // vio_frame_read_batch: the camera and the settings of the join; the point tables of every slot (allocated and zeroed at the first
     // use, SLOT_BYTES each); its descriptor tables, its device work space and its results.  It waits, so they are free when it returns.
-    vio_reject_config rcfg = {0u, VIO_REJECT_DEFAULT_HYPOTHESES, VIO_REJECT_DEFAULT_F_THRESHOLD, VIO_REJECT_DEFAULT_FOCAL_LENGTH};
+    vio_reject_config rcfg = kr::REJ_DEFAULTS;
     vio_reject_camera camera = {};
     RejCam cam = {};
     bool have_camera = false;
@@ -99,8 +103,6 @@ struct vio_frame {
 namespace {
 
 constexpr int MAX_ITEMS = VIO_FRAME_MAX_SLOTS;
-
-vio_status fail_synced(vio_frame *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
 
 void *device_block(int64_t bytes) {
     void *p = nullptr;
@@ -138,13 +140,23 @@ void mark_staged(vio_frame *h) {
     if (!h->staged_pending) (void)hipStreamSynchronize(h->q.stream);
 }
 
-// rows at `pitch`, the padding zero
-void pack_rows(uint8_t *dst, int pitch, const uint8_t *src, int width, int height, int stride) {
-    for (int y = 0; y < height; ++y) {
-        uint8_t *row = dst + (size_t)y * (size_t)pitch;
-        std::memcpy(row, src + (size_t)y * (size_t)stride, (size_t)width);
-        std::memset(row + width, 0, (size_t)(pitch - width));
+// a slot's frames as a flow item: every level's size, pitch and address (prev < 0: the slot's next alone)
+void flow_item_of(const vio_frame *h, kf::FlowItemD &f, const FrameLayout &Y, int prev, int next) {
+    kf::flow_item(f, h->tab.levels, Y.w, Y.h, Y.pitch);
+    for (int l = 0; l < h->tab.levels; ++l) {
+        if (prev >= 0) f.prev[l] = h->tab.level_ptr(prev, Y, l);
+        f.next[l] = h->tab.level_ptr(next, Y, l);
     }
+}
+
+// ... and its newest frame, with the slot's mask if it has one, as a detection item (d zeroed, then d.active decided)
+void det_item_of(const vio_frame *h, kd::DetItemD &d, kd::DetTotals &T, const FrameSlot &s, int n_tracked, int max_total) {
+    FrameLayout Y;
+    frame_layout(s.width, s.height, h->tab.levels, Y);
+    kd::det_item(d, T, s.width, s.height, Y.pitch[0], n_tracked, max_total, s.mask >= 0);
+    if (!d.active) return;
+    d.img = h->tab.level_ptr(s.next, Y, 0);
+    if (d.has_mask) d.mask = (const uint8_t *)h->tab.pool.blocks[(size_t)s.mask].base;
 }
 
 void read_push_timing(vio_frame *h) {
@@ -166,7 +178,7 @@ vio_status check_images(vio_frame *h, const char *fn, int32_t count, const vio_f
 // The push of `count` checked items, which vio_frame_push_batch and vio_frame_read_batch share: the roll, the uploads, the CLAHE and
 // the pyramid kernels, enqueued; it does not wait for them.
 vio_status push_run(vio_frame *h, int32_t count, const vio_frame_push_item *items, std::chrono::steady_clock::time_point t0) {
-    const int L = h->tab.levels, tiles_x = h->ccfg.tiles_x, tiles_y = h->ccfg.tiles_y, tiles = tiles_x * tiles_y;
+    const int L = h->tab.levels, tiles = h->ccfg.tiles_x * h->ccfg.tiles_y;
     std::vector<FrameLayout> lay((size_t)count);
     std::vector<int64_t> at((size_t)count);              // an item's offset in the staging and in the upload buffer
     int64_t b_raw = 0, max_px[FRAME_MAX_LEVELS] = {0};
@@ -195,23 +207,13 @@ vio_status push_run(vio_frame *h, int32_t count, const vio_frame_push_item *item
         const FrameLayout &Y = lay[(size_t)i];
         const int blk = h->tab.push(it.slot, it.width, it.height, device_block);
         if (blk < 0) return fail(h->err, VIO_ERR_HIP, "item %d: no device memory for a frame of %lld bytes", i, (long long)Y.bytes);
-        kf::FlowItemD &f = fi[i];
-        f.active = 1;
-        for (int l = 0; l < L; ++l) {
-            f.w[l] = Y.w[l]; f.h[l] = Y.h[l]; f.pitch[l] = Y.pitch[l];
-            f.next[l] = h->tab.level_ptr(blk, Y, l);
-        }
+        flow_item_of(h, fi[i], Y, -1, blk);
         pack_rows(h->raw.h + at[(size_t)i], Y.pitch[0], it.img, it.width, it.height, it.stride);
         if (!h->equalize) continue;
-        const ClaheGeom g = clahe_geometry(it.width, it.height, tiles_x, tiles_y, h->ccfg.clip_limit);
         kc::ClaheItemD &d = ci[i];
-        d.w = it.width; d.h = it.height; d.pitch = Y.pitch[0];
-        d.ext = g.ext; d.tile_w = g.tile_w; d.tile_h = g.tile_h; d.area = g.area; d.clip = g.clip;
-        d.ptiles_x = (it.width + kc::TX - 1) / kc::TX;
-        d.ptiles = d.ptiles_x * ((it.height + kc::TY - 1) / kc::TY);
-        d.lut_scale = g.lut_scale; d.inv_tile_w = g.inv_tile_w; d.inv_tile_h = g.inv_tile_h;
+        kc::clahe_item(d, it.width, it.height, Y.pitch[0], h->ccfg);
         d.src = h->raw.d + at[(size_t)i];
-        d.dst = f.next[0];
+        d.dst = fi[i].next[0];
         max_ptiles = std::max(max_ptiles, d.ptiles);
     }
     hipStream_t q = h->q.stream;
@@ -227,20 +229,9 @@ vio_status push_run(vio_frame *h, int32_t count, const vio_frame_push_item *item
     mark_staged(h);
     if (!ok) return fail_synced(h, "upload failed");
     (void)hipEventRecord(h->q.ev[1], q);
-    if (h->equalize) {
-        kc::ClaheArgs a;
-        a.items = (const kc::ClaheItemD *)h->ptab.d;
-        a.luts = h->luts.d;
-        a.tiles_x = tiles_x; a.tiles_y = tiles_y; a.count = count;
-        hipLaunchKernelGGL(kc::k_clahe_lut, dim3((unsigned)tiles, 1, (unsigned)count), dim3(kc::NT), 0, q, a);
-        hipLaunchKernelGGL(kc::k_clahe_apply, dim3((unsigned)max_ptiles, 1, (unsigned)count), dim3(kc::NT), (size_t)tiles * kc::BINS, q, a);
-    }
+    if (h->equalize) kc::clahe_launch(q, kc::clahe_args((const kc::ClaheItemD *)h->ptab.d, h->luts.d, h->ccfg, count), max_ptiles, nullptr);
     (void)hipEventRecord(h->q.ev[2], q);
-    for (int l = 0; l + 1 < L; ++l) {
-        kf::PyrArgs pa;
-        pa.items = (const kf::FlowItemD *)(h->ptab.d + b_ci); pa.level = l; pa.nimg = count; pa.both = 0; pa.pad = 0;
-        hipLaunchKernelGGL(kf::k_flow_pyr_down, dim3((unsigned)((max_px[l + 1] + kf::NT - 1) / kf::NT), (unsigned)count), dim3(kf::NT), 0, q, pa);
-    }
+    kf::flow_launch_pyramids(q, (const kf::FlowItemD *)(h->ptab.d + b_ci), count, 0, L, max_px);
     (void)hipEventRecord(h->q.ev[3], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
     for (int i = 0; i < count; ++i) h->counters[0] += (uint64_t)items[i].width * (uint64_t)items[i].height;
@@ -292,59 +283,36 @@ int32_t vio_frame_version(void) { return VIO_FRAME_VERSION; }
 const char *vio_frame_last_error(const vio_frame *h) { return h ? h->err : "NULL handle"; }
 
 vio_status vio_frame_create(int32_t device, void *stream, vio_frame **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_frame *h = new (std::nothrow) vio_frame();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess || hipEventCreate(&h->staged) != hipSuccess) { vio_frame_destroy(h); return VIO_ERR_HIP; }
-    for (hipEvent_t &e : h->rev)
-        if (hipEventCreate(&e) != hipSuccess) { e = nullptr; vio_frame_destroy(h); return VIO_ERR_HIP; }
-    // (16 x 16 tiles stage 64 KB; a launch that asks for more than the kernel may have fails and is reported)
-    (void)hipFuncSetAttribute((const void *)kc::k_clahe_apply, hipFuncAttributeMaxDynamicSharedMemorySize,
-                              VIO_CLAHE_MAX_TILES * VIO_CLAHE_MAX_TILES * kc::BINS);
-    (void)hipGetLastError();
-    *out = h;
-    return VIO_OK;
+    return create_handle(device, stream, out, vio_frame_destroy, [](vio_frame *h) {
+        if (hipEventCreate(&h->staged) != hipSuccess) return false;
+        for (hipEvent_t &e : h->rev)
+            if (hipEventCreate(&e) != hipSuccess) { e = nullptr; return false; }
+        kc::clahe_allow_lds();
+        return true;
+    });
 }
 
 void vio_frame_destroy(vio_frame *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();                                      // (waits for the stream: nothing reads a block any more)
-    if (h->staged) (void)hipEventDestroy(h->staged);
-    for (hipEvent_t e : h->rev)
-        if (e) (void)hipEventDestroy(e);
-    h->tab.pool.destroy([](void *p) { (void)hipFree(p); });
-    delete h;                                            // (the other buffers free themselves)
+    destroy_handle(h, [](vio_frame *h) {                 // (the stream has been waited for: nothing reads a block any more)
+        if (h->staged) (void)hipEventDestroy(h->staged);
+        for (hipEvent_t e : h->rev)
+            if (e) (void)hipEventDestroy(e);
+        h->tab.pool.destroy([](void *p) { (void)hipFree(p); });
+    });
 }
 
 vio_status vio_frame_set_config(vio_frame *h, int32_t equalize, const vio_clahe_config *clahe, const vio_flow_config *flow,
                                 const vio_detect_config *detect) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    const vio_clahe_config c0 = {VIO_CLAHE_DEFAULT_CLIP_LIMIT, VIO_CLAHE_DEFAULT_TILES, VIO_CLAHE_DEFAULT_TILES};
-    const vio_flow_config f0 = {VIO_FLOW_DEFAULT_LEVELS, VIO_FLOW_DEFAULT_HALF_PATCH, VIO_FLOW_DEFAULT_MAX_ITER, 0, VIO_FLOW_DEFAULT_BORDER, 0};
-    const vio_detect_config d0 = {VIO_DETECT_DEFAULT_QUALITY, VIO_DETECT_DEFAULT_MIN_DISTANCE, 0};
-    const vio_clahe_config c = clahe ? *clahe : c0;
-    const vio_flow_config f = flow ? *flow : f0;
-    vio_detect_config d = detect ? *detect : d0;
+    const vio_clahe_config c = clahe ? *clahe : kc::CLAHE_DEFAULTS;
+    const vio_flow_config f = flow ? *flow : kf::FLOW_DEFAULTS;
+    vio_detect_config d = detect ? *detect : kd::DET_DEFAULTS;
     if (equalize != 0 && equalize != 1) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_config: equalize 0 or 1");
-    if (!std::isfinite(c.clip_limit) || c.clip_limit < 0.0 || c.tiles_x < 1 || c.tiles_x > VIO_CLAHE_MAX_TILES || c.tiles_y < 1 ||
-        c.tiles_y > VIO_CLAHE_MAX_TILES)
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_config: clip_limit finite and >= 0, tiles_x and tiles_y in [1, %d]", VIO_CLAHE_MAX_TILES);
-    if (f.levels < 1 || f.levels > VIO_FLOW_MAX_LEVELS || f.half_patch < 1 || f.half_patch > VIO_FLOW_MAX_HALF_PATCH || f.max_iter < 1 ||
-        f.max_iter > 1000 || (f.inverse != 0 && f.inverse != 1) || f.border < 0 || (f.early_stop != 0 && f.early_stop != 1))
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_config: levels in [1, %d], half_patch in [1, %d], max_iter in [1, 1000], "
-                    "inverse and early_stop 0 or 1, border >= 0", VIO_FLOW_MAX_LEVELS, VIO_FLOW_MAX_HALF_PATCH);
-    if (!(d.quality > 0.0 && d.quality <= 1.0) || d.min_distance < 0)
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_config: quality in (0, 1], min_distance >= 0");
+    vio_status st;
+    if ((st = kc::clahe_check_config(h->err, "vio_frame_set_config", &c)) != VIO_OK || (st = kf::flow_check_config(h->err, "vio_frame_set_config", &f)) != VIO_OK ||
+        (st = kd::det_check_config(h->err, "vio_frame_set_config", &d)) != VIO_OK)
+        return st;
     d.reserved = 0;
     h->equalize = equalize; h->ccfg = c; h->fcfg = f; h->dcfg = d;
     h->tab.set_levels(f.levels);
@@ -468,55 +436,22 @@ vio_status vio_frame_track_batch(vio_frame *h, int32_t count, const vio_frame_tr
         const FrameSlot &s = h->tab.slots[it.slot];
         FrameLayout Y;
         frame_layout(s.width, s.height, L, Y);
-        kf::FlowItemD &f = fi[i];
-        f.active = 1;
-        for (int l = 0; l < L; ++l) {
-            f.w[l] = Y.w[l]; f.h[l] = Y.h[l]; f.pitch[l] = Y.pitch[l];
-            f.prev[l] = h->tab.level_ptr(s.prev, Y, l); f.next[l] = h->tab.level_ptr(s.next, Y, l);
-        }
-        for (int k = 0; k < it.n_pts; ++k) {
-            kf::FlowPt &p = hp[row + (size_t)k];
-            p.item = i; p.has_guess = it.guess != nullptr;
-            p.px = it.prev_pts[2 * k]; p.py = it.prev_pts[2 * k + 1];
-            p.gx = it.guess ? it.guess[2 * k] : 0.f; p.gy = it.guess ? it.guess[2 * k + 1] : 0.f;
-        }
+        flow_item_of(h, fi[i], Y, s.prev, s.next);
+        kf::flow_fill_pts(hp + row, i, it);
         row += (size_t)it.n_pts;
     }
-    kf::FlowArgs a;
-    a.items = (const kf::FlowItemD *)h->ttab.d;
-    a.pts = (const kf::FlowPt *)(h->ttab.d + b_it);
-    a.out = h->tout.d;
-    a.npts = (int32_t)total; a.levels = L; a.half_patch = h->fcfg.half_patch; a.max_iter = h->fcfg.max_iter;
-    a.border = h->fcfg.border; a.early_stop = h->fcfg.early_stop;
+    const kf::FlowArgs a = kf::flow_args((const kf::FlowItemD *)h->ttab.d, (const kf::FlowPt *)(h->ttab.d + b_it), h->tout.d, total, L, h->fcfg);
     hipStream_t q = h->q.stream;
     if (hipMemcpyAsync(h->ttab.d, h->ttab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
     (void)hipEventRecord(h->q.ev[4], q);
-    const dim3 grid((unsigned)((total + kf::WAVES - 1) / kf::WAVES));
-    if (h->fcfg.inverse) hipLaunchKernelGGL(kf::k_flow_track<true>, grid, dim3(kf::NT), 0, q, a);
-    else hipLaunchKernelGGL(kf::k_flow_track<false>, grid, dim3(kf::NT), 0, q, a);
+    kf::flow_launch_track(q, a, h->fcfg.inverse != 0);
     (void)hipEventRecord(h->q.ev[5], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
     const size_t outb = sizeof(kf::FlowOut) * total;
     if (hipMemcpyAsync(h->tout.h, h->tout.d, outb, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
         return fail_synced(h, "kernel or read-back failed");
     h->counters[2] += b_tab; h->counters[3] += outb;
-    vio_status ret = VIO_OK;
-    row = 0;
-    for (int i = 0; i < count; ++i) {
-        for (int k = 0; k < items[i].n_pts; ++k) {
-            const kf::FlowOut &o = h->tout.h[row + (size_t)k];
-            next_pts[2 * (row + k)] = o.x; next_pts[2 * (row + k) + 1] = o.y;
-            if (info) {
-                vio_flow_pt_info &pi = info[row + k];
-                pi.status = o.status; pi.iterations = o.iterations; pi.cost = o.cost;
-            }
-            if (o.status == VIO_ERR_NOT_FINITE) {
-                if (ret == VIO_OK) fail(h->err, VIO_ERR_NOT_FINITE, "item %d: keypoint %d or its guess is not finite", i, k);
-                ret = VIO_ERR_NOT_FINITE;
-            }
-        }
-        row += (size_t)items[i].n_pts;
-    }
+    const vio_status ret = kf::flow_unpack(h->err, h->tout.h, count, items, next_pts, info);
     h->timing[4] = elapsed_ms(h->q.ev[4], h->q.ev[5]);
     h->timing[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return ret;
@@ -531,12 +466,11 @@ vio_status vio_frame_detect_batch(vio_frame *h, int32_t count, const vio_frame_d
     const auto t0 = std::chrono::steady_clock::now();
     // every argument of every item first: nothing is written or launched on an error
     std::vector<kd::DetItemD> its((size_t)count);
-    int64_t n_r = 0, n_cand = 0, n_trk = 0, n_new = 0;
-    int max_tiles = 0;
+    kd::DetTotals T;
+    vio_status st;
     for (int i = 0; i < count; ++i) {
         const vio_frame_detect_item &it = items[i];
-        if (it.n_tracked < 0 || it.n_tracked > VIO_DETECT_MAX_POINTS || it.max_total < 0 || it.max_total > VIO_DETECT_MAX_POINTS)
-            return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_detect_batch: item %d: n_tracked and max_total must be in [0, %d]", i, VIO_DETECT_MAX_POINTS);
+        if ((st = kd::det_check_counts(h->err, "vio_frame_detect_batch: ", i, it.n_tracked, it.max_total)) != VIO_OK) return st;
         const FrameCheck ck = h->tab.check_detect(it.slot);
         if (ck != FRAME_OK) return fail_check(h, "vio_frame_detect_batch", ck, i, it.slot);
         if ((it.n_tracked > 0 && (!it.tracked || !it.track_cnt || !it.keep_order)) || (it.max_total > 0 && !it.new_pts))
@@ -544,103 +478,29 @@ vio_status vio_frame_detect_batch(vio_frame *h, int32_t count, const vio_frame_d
         const FrameSlot &s = h->tab.slots[it.slot];
         kd::DetItemD &d = its[(size_t)i];
         std::memset(&d, 0, sizeof(d));
-        d.active = 1;
-        for (int k = 0; k < it.n_tracked; ++k) {
-            const double x = it.tracked[2 * k], y = it.tracked[2 * k + 1];
-            if (!std::isfinite(x) || !std::isfinite(y)) { d.active = 0; continue; }
-            const double rx = std::nearbyint(x), ry = std::nearbyint(y);
-            if (rx < 0.0 || rx >= (double)s.width || ry < 0.0 || ry >= (double)s.height)
-                return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_detect_batch: item %d: tracked point %d (%g, %g) rounds to a pixel outside the %d x %d image",
-                            i, k, x, y, s.width, s.height);
-        }
-        FrameLayout Y;
-        frame_layout(s.width, s.height, h->tab.levels, Y);
-        d.w = s.width; d.h = s.height; d.pitch = Y.pitch[0];
-        d.tiles_x = (s.width + kd::TX - 1) / kd::TX;
-        d.tiles = d.tiles_x * ((s.height + kd::TY - 1) / kd::TY);
-        d.n_tracked = it.n_tracked; d.max_total = it.max_total;
-        d.has_mask = s.mask >= 0;
-        d.trk = (int32_t)n_trk; d.newp = (int32_t)n_new;
-        n_trk += it.n_tracked; n_new += it.max_total;
-        if (!d.active) continue;
-        const int64_t px = (int64_t)s.width * s.height;
-        d.img = h->tab.level_ptr(s.next, Y, 0);
-        if (d.has_mask) d.mask = (const uint8_t *)h->tab.pool.blocks[(size_t)s.mask].base;
-        d.r = n_r; n_r += px;
-        d.cand = n_cand; n_cand += (int64_t)std::max(s.width - 2, 0) * std::max(s.height - 2, 0);
-        max_tiles = std::max(max_tiles, d.tiles);
+        if ((st = kd::det_check_tracked(h->err, "vio_frame_detect_batch: ", i, it.tracked, it.n_tracked, s.width, s.height, &d.active)) != VIO_OK) return st;
+        det_item_of(h, d, T, s, it.n_tracked, it.max_total);
     }
     DeviceScope dev(h->device);
     if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
-    const size_t b_it = align256(sizeof(kd::DetItemD) * (size_t)count), b_tab = b_it + sizeof(kd::DetTrk) * (size_t)n_trk;
-    const size_t b_res = align256(sizeof(kd::DetRes) * (size_t)count), b_keep = align256(sizeof(int32_t) * (size_t)n_trk);
-    const size_t b_out = b_res + b_keep + sizeof(float) * 2 * (size_t)n_new;
-    const size_t b_key = align256(sizeof(unsigned long long) * (size_t)n_trk);
-    vio_status st;
-    if ((st = h->dtab.ensure(h->err, b_tab)) != VIO_OK || (st = h->dout.ensure(h->err, b_out)) != VIO_OK ||
-        (st = h->r.ensure(h->err, sizeof(double) * (size_t)n_r)) != VIO_OK ||
-        (st = h->cand.ensure(h->err, sizeof(uint32_t) * (size_t)n_cand)) != VIO_OK ||
-        (st = h->scratch.ensure(h->err, b_key + sizeof(int32_t) * 2 * (size_t)n_trk)) != VIO_OK)
+    const kd::DetSizes S = kd::det_sizes(count, T.n_trk, T.n_new);
+    if ((st = h->dtab.ensure(h->err, S.b_tab)) != VIO_OK || (st = h->dout.ensure(h->err, S.b_out)) != VIO_OK ||
+        (st = h->r.ensure(h->err, sizeof(double) * (size_t)T.n_r)) != VIO_OK ||
+        (st = h->cand.ensure(h->err, sizeof(uint32_t) * (size_t)T.n_cand)) != VIO_OK || (st = h->scratch.ensure(h->err, S.b_scratch)) != VIO_OK)
         return st;
-    std::memcpy(h->dtab.h, its.data(), sizeof(kd::DetItemD) * (size_t)count);
-    kd::DetTrk *ht = (kd::DetTrk *)(h->dtab.h + b_it);
-    for (int i = 0; i < count; ++i) {
-        const vio_frame_detect_item &it = items[i];
-        const kd::DetItemD &d = its[(size_t)i];
-        for (int k = 0; k < it.n_tracked; ++k) {
-            kd::DetTrk &t = ht[d.trk + k];
-            t.cx = 0; t.cy = 0; t.cnt = 0; t.pad = 0;
-            if (!d.active) continue;
-            t.cx = (int32_t)std::nearbyint((double)it.tracked[2 * k]); t.cy = (int32_t)std::nearbyint((double)it.tracked[2 * k + 1]);
-            t.cnt = it.track_cnt[k];
-        }
-    }
-    kd::DetArgs a;
-    a.items = (const kd::DetItemD *)h->dtab.d;
-    a.trk = (const kd::DetTrk *)(h->dtab.d + b_it);
-    a.r = h->r.d; a.cand = h->cand.d;
-    a.tkey = (unsigned long long *)h->scratch.d;
-    a.kept_xy = (int32_t *)(h->scratch.d + b_key);
-    a.res = (kd::DetRes *)h->dout.d;
-    a.keep_order = (int32_t *)(h->dout.d + b_res);
-    a.new_pts = (float *)(h->dout.d + b_res + b_keep);
-    a.quality = h->dcfg.quality; a.d2 = det_d2(h->dcfg.min_distance); a.count = count;
+    kd::det_fill_table(h->dtab.h, S, count, items, its.data());
+    const kd::DetArgs a = kd::det_args(h->dcfg, count, S, h->dtab.d, h->dout.d, h->scratch.d, h->r.d, h->cand.d);
     hipStream_t q = h->q.stream;
-    if (hipMemcpyAsync(h->dtab.d, h->dtab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess || hipMemsetAsync(h->dout.d, 0, b_res, q) != hipSuccess)
+    if (hipMemcpyAsync(h->dtab.d, h->dtab.h, S.b_tab, hipMemcpyHostToDevice, q) != hipSuccess || hipMemsetAsync(h->dout.d, 0, S.b_res, q) != hipSuccess)
         return fail_synced(h, "upload failed");
     (void)hipEventRecord(h->q.ev[6], q);
-    if (n_trk > 0) hipLaunchKernelGGL(kd::k_detect_setmask, dim3((unsigned)count), dim3(kd::NT_MASK), 0, q, a);
-    if (max_tiles > 0) hipLaunchKernelGGL(kd::k_detect_response, dim3((unsigned)max_tiles, 1, (unsigned)count), dim3(kd::NT), 0, q, a);
-    if (max_tiles > 0) hipLaunchKernelGGL(kd::k_detect_candidates, dim3((unsigned)max_tiles, 1, (unsigned)count), dim3(kd::NT), 0, q, a);
-    if (max_tiles > 0) hipLaunchKernelGGL(kd::k_detect_select, dim3((unsigned)count), dim3(kd::NT_SEL), 0, q, a);
+    kd::det_launch(a, q, T.n_trk > 0, T.max_tiles > 0, T.max_tiles, nullptr);
     (void)hipEventRecord(h->q.ev[7], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
-    if (hipMemcpyAsync(h->dout.h, h->dout.d, b_out, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+    if (hipMemcpyAsync(h->dout.h, h->dout.d, S.b_out, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
         return fail_synced(h, "kernel or read-back failed");
-    h->counters[2] += b_tab; h->counters[3] += b_out;
-    vio_status ret = VIO_OK;
-    const kd::DetRes *res = (const kd::DetRes *)h->dout.h;
-    const int32_t *keep = (const int32_t *)(h->dout.h + b_res);
-    const float *newp = (const float *)(h->dout.h + b_res + b_keep);
-    for (int i = 0; i < count; ++i) {
-        const vio_frame_detect_item &it = items[i];
-        const kd::DetItemD &d = its[(size_t)i];
-        vio_detect_result &o = results[i];
-        o.status = VIO_OK; o.n_kept = 0; o.n_new = 0; o.n_candidates = 0; o.max_response = 0.0;
-        if (d.active) {
-            // (the counts are the device's; they are bounded here so that no copy can leave the caller's arrays whatever they hold)
-            o.n_kept = std::min(std::max(res[i].n_kept, 0), it.n_tracked);
-            o.n_new = std::min(std::max(res[i].n_new, 0), it.max_total);
-            o.n_candidates = res[i].n_cand;
-            std::memcpy(&o.max_response, &res[i].maxbits, sizeof(double));
-        } else {
-            o.status = VIO_ERR_NOT_FINITE;
-            if (ret == VIO_OK) fail(h->err, VIO_ERR_NOT_FINITE, "item %d: a tracked point is not finite", i);
-            ret = VIO_ERR_NOT_FINITE;
-        }
-        for (int k = 0; k < it.n_tracked; ++k) it.keep_order[k] = k < o.n_kept ? keep[d.trk + k] : -1;
-        if (o.n_new > 0) std::memcpy(it.new_pts, newp + 2 * (size_t)d.newp, sizeof(float) * 2 * (size_t)o.n_new);
-    }
+    h->counters[2] += S.b_tab; h->counters[3] += S.b_out;
+    const vio_status ret = kd::det_unpack(h->err, h->dout.h, S, count, items, its.data(), results);
     h->timing[6] = elapsed_ms(h->q.ev[6], h->q.ev[7]);
     h->timing[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return ret;
@@ -649,23 +509,11 @@ vio_status vio_frame_detect_batch(vio_frame *h, int32_t count, const vio_frame_d
 vio_status vio_frame_set_camera(vio_frame *h, const vio_reject_camera *cam, const vio_reject_config *cfg) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    // (the rules of vio_reject_set_camera and vio_reject_set_config)
-    if (!cam) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_camera: NULL camera");
-    if (cam->model != VIO_REJECT_MODEL_PINHOLE) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_camera: model %d: only PINHOLE is built", cam->model);
-    const double v[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2};
-    for (double x : v)
-        if (!std::isfinite(x)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_camera: a parameter is not finite");
-    if (cam->fx == 0.0 || cam->fy == 0.0 || cam->width < 1 || cam->height < 1)
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_camera: fx, fy must not be 0, width and height at least 1");
-    const vio_reject_config c0 = {0u, VIO_REJECT_DEFAULT_HYPOTHESES, VIO_REJECT_DEFAULT_F_THRESHOLD, VIO_REJECT_DEFAULT_FOCAL_LENGTH};
-    const vio_reject_config c = cfg ? *cfg : c0;
-    if (c.ransac_hypotheses < 1 || c.ransac_hypotheses > VIO_REJECT_MAX_HYPOTHESES || !(c.f_threshold > 0.0) || !std::isfinite(c.f_threshold) ||
-        !(c.focal_length > 0.0) || !std::isfinite(c.focal_length))
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_camera: ransac_hypotheses in [1, %d], f_threshold and focal_length finite and > 0",
-                    VIO_REJECT_MAX_HYPOTHESES);
-    h->camera = *cam;
-    h->camera.reserved = 0;
-    h->cam = rej_camera(cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2);
+    const vio_reject_config c = cfg ? *cfg : kr::REJ_DEFAULTS;
+    vio_status st;
+    if ((st = kr::rej_check_camera(h->err, "vio_frame_set_camera", cam)) != VIO_OK || (st = kr::rej_check_config(h->err, "vio_frame_set_camera", &c)) != VIO_OK)
+        return st;
+    kr::rej_set_camera(*cam, h->camera, h->cam);
     h->rcfg = c;
     h->have_camera = true;
     return VIO_OK;
@@ -778,7 +626,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     // what the host knows of each slot before the roll
     std::vector<FrameSlot> was(B);
     int64_t total = 0, n_r = 0, n_cand = 0;
-    int rows_cap = std::max(h->max_cnt, 1), max_tiles = 0;
+    int rows_cap = std::max(h->max_cnt, 1);
     for (size_t i = 0; i < B; ++i) {
         was[i] = h->tab.slots[sl[i]];
         if (was[i].n_frames < 1) was[i].n_pts = 0;          // (points lie in a frame)
@@ -825,38 +673,25 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     kd::DetItemD *di = (kd::DetItemD *)(h->rtab.h + o_det);
     kr::RejPair *rp = (kr::RejPair *)(h->rtab.h + o_pair);
     kr::LiftItem *li = (kr::LiftItem *)(h->rtab.h + o_lift);
-    n_r = 0; n_cand = 0;
+    kd::DetTotals T;
     int64_t flow_off = 0;
     for (size_t i = 0; i < B; ++i) {
         const FrameSlot &s = h->tab.slots[sl[i]];
         const SlotPts p = slot_pts(h, sl[i]);
-        FrameLayout Y;
-        frame_layout(s.width, s.height, L, Y);
         FrontItem &f = fr[i];
         f.cur_pts = p.cur; f.ids = p.ids; f.cnt = p.cnt; f.prev_un_ids = p.prev_ids; f.prev_un_pts = p.prev_pts; f.next_id = p.next_id;
         f.n = s.n_frames == 2 ? was[i].n_pts : 0; f.m = was[i].n_prev_un;
         f.w = s.width; f.h = s.height; f.flow_off = (int32_t)flow_off;
         flow_off += f.n;
         if (f.n > 0) {
-            kf::FlowItemD &d = fi[i];
-            d.active = 1;
-            for (int l = 0; l < L; ++l) {
-                d.w[l] = Y.w[l]; d.h[l] = Y.h[l]; d.pitch[l] = Y.pitch[l];
-                d.prev[l] = h->tab.level_ptr(s.prev, Y, l); d.next[l] = h->tab.level_ptr(s.next, Y, l);
-            }
+            FrameLayout Y;
+            frame_layout(s.width, s.height, L, Y);
+            flow_item_of(h, fi[i], Y, s.prev, s.next);
         }
         kd::DetItemD &d = di[i];
-        d.w = s.width; d.h = s.height; d.pitch = Y.pitch[0];
-        d.tiles_x = (s.width + kd::TX - 1) / kd::TX;
-        d.tiles = d.tiles_x * ((s.height + kd::TY - 1) / kd::TY);
-        d.n_tracked = 0; d.max_total = h->max_cnt;          // (n_tracked is k_front_after_reject's to write)
-        d.active = 1; d.has_mask = s.mask >= 0;
-        d.trk = (int32_t)(i * CAP); d.newp = (int32_t)(i * CAP);
-        d.img = h->tab.level_ptr(s.next, Y, 0);
-        if (d.has_mask) d.mask = (const uint8_t *)h->tab.pool.blocks[(size_t)s.mask].base;
-        d.r = n_r; n_r += (int64_t)s.width * s.height;
-        d.cand = n_cand; n_cand += (int64_t)std::max(s.width - 2, 0) * std::max(s.height - 2, 0);
-        max_tiles = std::max(max_tiles, d.tiles);
+        d.active = 1;
+        det_item_of(h, d, T, s, 0, h->max_cnt);             // (n_tracked is k_front_after_reject's to write)
+        d.trk = (int32_t)(i * CAP); d.newp = (int32_t)(i * CAP);    // (every per-point array has CAP rows per item here)
         kr::RejPair &r = rp[i];
         r.pair = was[i].n_read; r.finite = 1;               // (n and active are k_front_filter's to write)
         r.o_pts = (int64_t)(i * 4 * CAP); r.o_corr = (int64_t)(i * 4 * CAP); r.o_pt = (int64_t)(i * CAP);
@@ -891,42 +726,27 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     // 2 - 4. the slot's points into the new frame, and those that stay
     if (total > 0) {
         hipLaunchKernelGGL(k_front_begin, per_item, fnt, 0, q, a);
-        kf::FlowArgs fa;
-        fa.items = (const kf::FlowItemD *)(h->rtab.d + o_flow);
-        fa.pts = a.fpts; fa.out = (kf::FlowOut *)(W + w_fout);
-        fa.npts = (int32_t)total; fa.levels = L; fa.half_patch = h->fcfg.half_patch; fa.max_iter = h->fcfg.max_iter;
-        fa.border = h->fcfg.border; fa.early_stop = h->fcfg.early_stop;
-        const dim3 grid((unsigned)((total + kf::WAVES - 1) / kf::WAVES));
-        if (h->fcfg.inverse) hipLaunchKernelGGL(kf::k_flow_track<true>, grid, dim3(kf::NT), 0, q, fa);
-        else hipLaunchKernelGGL(kf::k_flow_track<false>, grid, dim3(kf::NT), 0, q, fa);
+        kf::flow_launch_track(q, kf::flow_args((const kf::FlowItemD *)(h->rtab.d + o_flow), a.fpts, (kf::FlowOut *)(W + w_fout), (size_t)total, L, h->fcfg),
+                              h->fcfg.inverse != 0);
     }
     hipLaunchKernelGGL(k_front_filter, per_item, fnt, 0, q, a);
     (void)hipEventRecord(h->rev[0], q);
     if (publish) {
         // 5, 6. rejectWithF and what it keeps
-        kr::RansacArgs ra;
-        std::memset(&ra, 0, sizeof(ra));
+        kr::RansacArgs ra = kr::rej_ransac_args(h->cam, h->camera, h->rcfg);
         ra.pairs = a.pairs; ra.pts = a.rstage;
         ra.corr = (double *)(W + w_corr); ra.flag = (int32_t *)(W + w_flag); ra.mask = (uint8_t *)(W + w_rmask); ra.res = (kr::RejRes *)(W + w_rres);
-        ra.cam = h->cam;
-        ra.focal = h->rcfg.focal_length; ra.half_w = h->camera.width / 2.0; ra.half_h = h->camera.height / 2.0;
-        ra.thr = h->rcfg.f_threshold * h->rcfg.f_threshold;
-        ra.seed = h->rcfg.seed; ra.hyps = h->rcfg.ransac_hypotheses;
         if (total > 0) hipLaunchKernelGGL(kr::k_reject_ransac, per_item, dim3(kr::NT), 0, q, ra);
         hipLaunchKernelGGL(k_front_after_reject, per_item, fnt, 0, q, a);
         (void)hipEventRecord(h->rev[1], q);
         // 7. setMask and the detection
-        kd::DetArgs da;
+        kd::DetArgs da = kd::det_args(h->dcfg, count);
         da.items = a.ditems; da.trk = a.dtrk;
         da.r = h->r.d; da.cand = h->cand.d;
         da.tkey = (unsigned long long *)(W + w_tkey); da.kept_xy = (int32_t *)(W + w_kxy);
         da.res = (kd::DetRes *)(W + w_dres);
         da.keep_order = (int32_t *)(W + w_keep); da.new_pts = (float *)(W + w_new);
-        da.quality = h->dcfg.quality; da.d2 = det_d2(h->dcfg.min_distance); da.count = count;
-        if (total > 0) hipLaunchKernelGGL(kd::k_detect_setmask, per_item, dim3(kd::NT_MASK), 0, q, da);
-        hipLaunchKernelGGL(kd::k_detect_response, dim3((unsigned)max_tiles, 1, (unsigned)count), dim3(kd::NT), 0, q, da);
-        hipLaunchKernelGGL(kd::k_detect_candidates, dim3((unsigned)max_tiles, 1, (unsigned)count), dim3(kd::NT), 0, q, da);
-        hipLaunchKernelGGL(kd::k_detect_select, per_item, dim3(kd::NT_SEL), 0, q, da);
+        kd::det_launch(da, q, total > 0, true, T.max_tiles, nullptr);
     } else {
         (void)hipEventRecord(h->rev[1], q);
     }
@@ -938,7 +758,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     la.items = a.litems; la.pts = a.lstage; la.ids = a.lids;
     la.un = (float *)(W + w_un); la.vel = (float *)(W + w_vel); la.lifted = nullptr;
     la.cam = h->cam; la.bare = 0; la.count = count;
-    hipLaunchKernelGGL(kr::k_reject_lift, dim3((unsigned)((rows_cap + kr::NT - 1) / kr::NT), (unsigned)count), dim3(kr::NT), 0, q, la);
+    kr::rej_launch_lift(q, la, rows_cap);
     hipLaunchKernelGGL(k_front_finish, per_item, fnt, 0, q, a);
     (void)hipEventRecord(h->rev[3], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");

@@ -22,7 +22,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_init.h"
@@ -631,8 +630,6 @@ struct vio_init {
 namespace {
 
 // a failure after work was enqueued: wait for the stream first, so that no copy still reads the pinned staging buffer the next call fills
-vio_status fail_synced(vio_init *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
-
 vio_status check_item(vio_init *h, int i, const vio_init_item &it, int &K) {
     if (it.n_frames < 2 || it.n_frames > VIO_INIT_MAX_FRAMES)
         return fail(h->err, VIO_ERR_BAD_ARG, "window %d: n_frames must be in [2, %d]", i, VIO_INIT_MAX_FRAMES);
@@ -710,32 +707,12 @@ int32_t vio_init_version(void) { return VIO_INIT_VERSION; }
 const char *vio_init_last_error(const vio_init *h) { return h ? h->err : "NULL handle"; }
 
 vio_status vio_init_create(int32_t device, void *stream, vio_init **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_init *h = new (std::nothrow) vio_init();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess) { vio_init_destroy(h); return VIO_ERR_HIP; }
-    if (hipFuncSetAttribute((const void *)k_init_align, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) != hipSuccess) {
-        vio_init_destroy(h);
-        return VIO_ERR_HIP;
-    }
-    *out = h;
-    return VIO_OK;
+    return create_handle(device, stream, out, vio_init_destroy, [](vio_init *) {
+        return hipFuncSetAttribute((const void *)k_init_align, hipFuncAttributeMaxDynamicSharedMemorySize, 64 * 1024) == hipSuccess;
+    });
 }
 
-void vio_init_destroy(vio_init *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                            // (the buffers free themselves)
-}
+void vio_init_destroy(vio_init *h) { destroy_handle(h); }
 
 vio_status vio_init_timing(const vio_init *h, double *out3) {
     if (!h || !out3) return VIO_ERR_BAD_ARG;

@@ -689,12 +689,7 @@ vio_status vio_marg_create(const vio_config *cfg, vio_marg **out) {
     return VIO_OK;
 }
 
-void vio_marg_destroy(vio_marg *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                             // (the buffers free themselves)
-}
+void vio_marg_destroy(vio_marg *h) { destroy_handle(h); }
 
 vio_status vio_marg_timing(vio_marg *h, double *out4) {
     if (!h || !out4) return VIO_ERR_BAD_ARG;

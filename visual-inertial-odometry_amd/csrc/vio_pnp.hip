@@ -18,7 +18,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_pnp.h"
@@ -245,8 +244,6 @@ struct vio_pnp {
 
 namespace {
 
-vio_status fail_synced(vio_pnp *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
-
 vio_status check_item(vio_pnp *h, int i, const vio_pnp_item &it) {
     if (it.n_frames < 0 || it.n_frames > VIO_PNP_MAX_FRAMES)
         return fail(h->err, VIO_ERR_BAD_ARG, "window %d: n_frames must be in [0, %d]", i, VIO_PNP_MAX_FRAMES);
@@ -279,29 +276,9 @@ int32_t vio_pnp_version(void) { return VIO_PNP_VERSION; }
 
 const char *vio_pnp_last_error(const vio_pnp *h) { return h ? h->err : "NULL handle"; }
 
-vio_status vio_pnp_create(int32_t device, void *stream, vio_pnp **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_pnp *h = new (std::nothrow) vio_pnp();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess) { vio_pnp_destroy(h); return VIO_ERR_HIP; }
-    *out = h;
-    return VIO_OK;
-}
+vio_status vio_pnp_create(int32_t device, void *stream, vio_pnp **out) { return create_handle(device, stream, out, vio_pnp_destroy); }
 
-void vio_pnp_destroy(vio_pnp *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                            // (the buffers free themselves)
-}
+void vio_pnp_destroy(vio_pnp *h) { destroy_handle(h); }
 
 vio_status vio_pnp_set_config(vio_pnp *h, const vio_pnp_config *cfg) {
     if (!h) return VIO_ERR_BAD_ARG;

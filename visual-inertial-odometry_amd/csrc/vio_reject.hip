@@ -13,7 +13,8 @@
 //                     round into the running winner (count, lowest h).  The refit: the inlier flags thread per correspondence, the
 //                     centroids, the scales and the 45 entries of the normal matrix's upper triangle each summed by one thread in
 //                     correspondence order, the eigenproblem by thread 0 in the same LDS; the final mask thread per correspondence.
-// The two kernels and their descriptor tables are in vio_reject_body.inc, which libvio_frame_hip compiles too.
+// The two kernels are in vio_reject_body.inc, which libvio_frame_hip compiles too; what the host side shares
+// with it is in vio_reject_host.h.
 // Contraction is off: products and sums round as the restatement's (tests/reject_reference.py) do.  No floating-point atomics; every
 // sum has a fixed order, so repeated calls are bitwise identical and a pair's result does not depend on its batch.
 #include <hip/hip_runtime.h>
@@ -23,7 +24,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_reject.h"
@@ -36,6 +36,7 @@
 
 constexpr int MAX_ITEMS = VIO_REJECT_MAX_ITEMS;
 
+#include "vio_reject_host.h"
 #include "vio_reject_body.inc"
 
 // ---------------------------------------------------------------------------------------------------------
@@ -44,7 +45,7 @@ constexpr int MAX_ITEMS = VIO_REJECT_MAX_ITEMS;
 struct vio_reject {
     int device = 0;
     ErrText err = {0};
-    vio_reject_config cfg = {0u, VIO_REJECT_DEFAULT_HYPOTHESES, VIO_REJECT_DEFAULT_F_THRESHOLD, VIO_REJECT_DEFAULT_FOCAL_LENGTH};
+    vio_reject_config cfg = REJ_DEFAULTS;
     vio_reject_camera camera = {};
     RejCam cam = {};
     bool have_camera = false;
@@ -56,8 +57,6 @@ struct vio_reject {
 };
 
 namespace {
-
-vio_status fail_synced(vio_reject *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
 
 bool finite_pts(const float *p, int n) {
     for (int k = 0; k < 2 * n; ++k)
@@ -82,7 +81,7 @@ vio_status run_lift(vio_reject *h, int count, int max_n, size_t b_tab, size_t o_
     (void)hipEventRecord(h->q.ev[0], q);
     if (hipMemcpyAsync(h->tab.d, h->tab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
     (void)hipEventRecord(h->q.ev[1], q);
-    hipLaunchKernelGGL(k_reject_lift, dim3((unsigned)((max_n + NT - 1) / NT), (unsigned)count), dim3(NT), 0, q, a);
+    rej_launch_lift(q, a, max_n);
     (void)hipEventRecord(h->q.ev[2], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
     if (hipMemcpyAsync(h->out.h, h->out.d, b_out, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
@@ -100,43 +99,16 @@ int32_t vio_reject_version(void) { return VIO_REJECT_VERSION; }
 
 const char *vio_reject_last_error(const vio_reject *h) { return h ? h->err : "NULL handle"; }
 
-vio_status vio_reject_create(int32_t device, void *stream, vio_reject **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_reject *h = new (std::nothrow) vio_reject();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess) { vio_reject_destroy(h); return VIO_ERR_HIP; }
-    *out = h;
-    return VIO_OK;
-}
+vio_status vio_reject_create(int32_t device, void *stream, vio_reject **out) { return create_handle(device, stream, out, vio_reject_destroy); }
 
-void vio_reject_destroy(vio_reject *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                                // (the buffers free themselves)
-}
+void vio_reject_destroy(vio_reject *h) { destroy_handle(h); }
 
 vio_status vio_reject_set_camera(vio_reject *h, const vio_reject_camera *cam) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    if (!cam) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: NULL camera");
-    if (cam->model != VIO_REJECT_MODEL_PINHOLE) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: model %d: only PINHOLE is built", cam->model);
-    const double v[8] = {cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2};
-    for (double x : v)
-        if (!std::isfinite(x)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: a parameter is not finite");
-    if (cam->fx == 0.0 || cam->fy == 0.0 || cam->width < 1 || cam->height < 1)
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_camera: fx, fy must not be 0, width and height at least 1");
-    h->camera = *cam;
-    h->camera.reserved = 0;
-    h->cam = rej_camera(cam->fx, cam->fy, cam->cx, cam->cy, cam->k1, cam->k2, cam->p1, cam->p2);
+    const vio_status st = rej_check_camera(h->err, "vio_reject_set_camera", cam);
+    if (st != VIO_OK) return st;
+    rej_set_camera(*cam, h->camera, h->cam);
     h->have_camera = true;
     return VIO_OK;
 }
@@ -144,10 +116,8 @@ vio_status vio_reject_set_camera(vio_reject *h, const vio_reject_camera *cam) {
 vio_status vio_reject_set_config(vio_reject *h, const vio_reject_config *cfg) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    if (!cfg || cfg->ransac_hypotheses < 1 || cfg->ransac_hypotheses > VIO_REJECT_MAX_HYPOTHESES || !(cfg->f_threshold > 0.0) ||
-        !std::isfinite(cfg->f_threshold) || !(cfg->focal_length > 0.0) || !std::isfinite(cfg->focal_length))
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_reject_set_config: ransac_hypotheses in [1, %d], f_threshold and focal_length finite and > 0",
-                    VIO_REJECT_MAX_HYPOTHESES);
+    const vio_status st = rej_check_config(h->err, "vio_reject_set_config", cfg);
+    if (st != VIO_OK) return st;
     h->cfg = *cfg;
     return VIO_OK;
 }
@@ -209,18 +179,13 @@ vio_status vio_reject_batch(vio_reject *h, int32_t count, const vio_reject_item 
             std::memcpy(hf + p.o_pts, items[i].cur_pts, sizeof(float) * 2 * (size_t)p.n);
             std::memcpy(hf + p.o_pts + 2 * (size_t)p.n, items[i].forw_pts, sizeof(float) * 2 * (size_t)p.n);
         }
-        RansacArgs a;
-        std::memset(&a, 0, sizeof(a));
+        RansacArgs a = rej_ransac_args(h->cam, h->camera, h->cfg);
         a.pairs = (const RejPair *)h->tab.d;
         a.pts = (const float *)(h->tab.d + b_it);
         a.corr = (double *)h->scratch.d;
         a.flag = (int32_t *)(h->scratch.d + b_corr);
         a.res = (RejRes *)h->out.d;
         a.mask = (uint8_t *)(h->out.d + b_res);
-        a.cam = h->cam;
-        a.focal = h->cfg.focal_length; a.half_w = h->camera.width / 2.0; a.half_h = h->camera.height / 2.0;
-        a.thr = h->cfg.f_threshold * h->cfg.f_threshold;
-        a.seed = h->cfg.seed; a.hyps = h->cfg.ransac_hypotheses;
         const auto t1 = std::chrono::steady_clock::now();
         hipStream_t q = h->q.stream;
         (void)hipEventRecord(h->q.ev[0], q);

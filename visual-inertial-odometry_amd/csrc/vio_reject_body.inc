@@ -1,7 +1,7 @@
-// vio_reject_body.inc — k_reject_lift and k_reject_ransac with their descriptor tables, the one copy libvio_reject_hip (vio_reject.hip,
+// vio_reject_body.inc — k_reject_lift and k_reject_ransac with the lift's launch, the one copy libvio_reject_hip (vio_reject.hip,
 // at file scope) and libvio_frame_hip (vio_frame.hip, inside a namespace of its own) compile (DESIGN.md sections 21 and 24; the
 // kernels are described at the top of vio_reject.hip).  The including file has included <hip/hip_runtime.h>, <cstdint>,
-// ../../include/vio_reject.h, vio_reject_math.h and vio_sfm_math.h, and has contraction off.
+// ../../include/vio_reject.h, vio_reject_math.h, vio_sfm_math.h and vio_reject_host.h (the descriptor tables), and has contraction off.
 // The kernels take n, active, m and every offset from the tables in device memory: the host-array library writes them on the host,
 // the resident library's glue kernels (vio_front_body.inc) write the counts on the device.
 constexpr int NT = VIO_REJECT_THREADS;
@@ -11,53 +11,6 @@ constexpr int MINP = VIO_REJECT_MIN_POINTS;
 static_assert(ROUND == 64, "a round is one wavefront");
 static_assert(VIO_REJECT_MAX_HYPOTHESES == VIO_SFM_MAX_HYPOTHESES && VIO_REJECT_DEFAULT_HYPOTHESES == VIO_SFM_DEFAULT_HYPOTHESES, "the RANSAC is vio_sfm.h's");
 static_assert(162 * 8 * ROUND + 9 * 8 * ROUND <= 160 * 1024, "the round's matrices fit a CU's LDS");
-
-struct RejPair {
-    int32_t n, active;
-    uint32_t pair;
-    int32_t finite;     // no point of the pair is NaN or infinite
-    int64_t o_pts;      // staged floats: cur [n][2] | forw [n][2]
-    int64_t o_corr;     // double scratch: corr [n][4]
-    int64_t o_pt;       // the pair's first point in the flat per-point arrays (flags, mask)
-};
-
-struct RejRes {
-    int32_t status, hyp, n_inliers, pad;
-    double F[9];
-};
-
-struct RansacArgs {
-    const RejPair *pairs;
-    const float *pts;
-    double *corr;
-    int32_t *flag;      // [points of the call]: the winner's inliers
-    uint8_t *mask;      // [points of the call]
-    RejRes *res;
-    RejCam cam;
-    double focal, half_w, half_h, thr;
-    uint32_t seed;
-    int32_t hyps;
-};
-
-struct LiftItem {
-    int32_t n, m, active, pad;
-    int64_t o_pts;      // staged floats: pts [n][2]
-    int64_t o_prev;     // staged floats: prev_un_pts [m][2]
-    int64_t o_ids;      // staged int64: ids [n] | prev_ids [m]
-    int64_t o_out;      // the item's first point in the outputs
-    double dt;
-};
-
-struct LiftArgs {
-    const LiftItem *items;
-    const float *pts;
-    const long long *ids;
-    float *un;          // [points][2] un_pts | [points][2] velocity behind them (undistort)
-    float *vel;
-    double *lifted;     // [points][2] (bare lift)
-    RejCam cam;
-    int32_t bare, count;
-};
 
 // ---------------------------------------------------------------------------------------------------------
 // k_reject_lift
@@ -283,4 +236,9 @@ __global__ __launch_bounds__(NT) void k_reject_ransac(RansacArgs a) {
         if (tid == 0) { o->status = VIO_REJECT_FAIL_NO_MODEL; o->hyp = hyp; o->n_inliers = n; o->pad = 0; }
         if (tid < 9) o->F[tid] = NAN;
     }
+}
+
+// the lift of a.count items of at most max_n points each, on q
+inline void rej_launch_lift(hipStream_t q, const LiftArgs &a, int max_n) {
+    hipLaunchKernelGGL(k_reject_lift, dim3((unsigned)((max_n + NT - 1) / NT), (unsigned)a.count), dim3(NT), 0, q, a);
 }

@@ -21,7 +21,6 @@
 #include <cmath>
 #include <cstdint>
 #include <cstring>
-#include <new>
 #include <vector>
 
 #include "../../include/vio_sfm.h"
@@ -844,8 +843,6 @@ struct vio_sfm {
 
 namespace {
 
-vio_status fail_synced(vio_sfm *h, const char *msg) { (void)hipStreamSynchronize(h->q.stream); return fail(h->err, VIO_ERR_HIP, "%s", msg); }
-
 size_t lds_bytes(int F) {
     const size_t n = 6 * (size_t)F;
     return sizeof(double) * (n * (n + 1) / 2 + 4 * n + 36 * (size_t)F + 24 * (size_t)F);     // S | rhs, dc, Dc, gc | Hcc | camR, camt, camR2, camt2
@@ -1027,32 +1024,12 @@ int32_t vio_sfm_version(void) { return VIO_SFM_VERSION; }
 const char *vio_sfm_last_error(const vio_sfm *h) { return h ? h->err : "NULL handle"; }
 
 vio_status vio_sfm_create(int32_t device, void *stream, vio_sfm **out) {
-    if (!out) return VIO_ERR_BAD_ARG;
-    *out = nullptr;
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev <= 0) return VIO_ERR_NO_DEVICE;
-    if (device < 0 || device >= ndev) return VIO_ERR_BAD_ARG;
-    DeviceScope dev(device);
-    if (!dev.ok) return VIO_ERR_HIP;
-    vio_sfm *h = new (std::nothrow) vio_sfm();
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->device = device;
-    if (h->q.open_stream(stream) != hipSuccess) { delete h; return VIO_ERR_HIP; }
-    if (h->q.create_events() != hipSuccess) { vio_sfm_destroy(h); return VIO_ERR_HIP; }
-    if (hipFuncSetAttribute((const void *)k_sfm_construct, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MAXF)) != hipSuccess) {
-        vio_sfm_destroy(h);
-        return VIO_ERR_HIP;
-    }
-    *out = h;
-    return VIO_OK;
+    return create_handle(device, stream, out, vio_sfm_destroy, [](vio_sfm *) {
+        return hipFuncSetAttribute((const void *)k_sfm_construct, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_bytes(MAXF)) == hipSuccess;
+    });
 }
 
-void vio_sfm_destroy(vio_sfm *h) {
-    if (!h) return;
-    DeviceScope dev(h->device);
-    h->q.release();
-    delete h;                                            // (the buffers free themselves)
-}
+void vio_sfm_destroy(vio_sfm *h) { destroy_handle(h); }
 
 vio_status vio_sfm_set_config(vio_sfm *h, const vio_sfm_config *cfg) {
     if (!h) return VIO_ERR_BAD_ARG;
