@@ -5,7 +5,7 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, capi, clahe, covariance, detect, exrot, flow, frame, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
+from . import batch_stream, capi, clahe, covariance, detect, exrot, flow, fm, frame, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
@@ -14,6 +14,7 @@ from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_
 from .detect import DetectHandle, DetectLib
 from .exrot import ExrotHandle, ExrotLib
 from .flow import FlowHandle, FlowLib
+from .fm import BatchFeatureManager, FmHandle, FmLib
 from .frame import FrameHandle, FrameLib
 from .frontend import BatchFeatureTracker, FeatureTracker
 from .imu import ImuHandle, ImuLib
@@ -41,6 +42,7 @@ DETECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_detect_hip.so")   # include/v
 REJECT_LIB = os.path.join(PKG_DIR, "csrc", "libvio_reject_hip.so")   # include/vio_reject.h; calls nothing of libvio_hip.so either
 CLAHE_LIB = os.path.join(PKG_DIR, "csrc", "libvio_clahe_hip.so")     # include/vio_clahe.h; calls nothing of libvio_hip.so either
 FRAME_LIB = os.path.join(PKG_DIR, "csrc", "libvio_frame_hip.so")     # include/vio_frame.h; calls nothing of libvio_hip.so either
+FM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_fm_hip.so")           # include/vio_fm.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -156,3 +158,8 @@ def load_clahe():
 def load_frame():
     """Load the resident-frame library (csrc/libvio_frame_hip.so)."""
     return _load_companion("frame", FrameLib, FRAME_LIB)
+
+
+def load_fm():
+    """Load the batched FeatureManager library (csrc/libvio_fm_hip.so)."""
+    return _load_companion("fm", FmLib, FM_LIB)

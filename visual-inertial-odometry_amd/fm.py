@@ -1,0 +1,269 @@
+"""ctypes binding of include/vio_fm.h (csrc/libvio_fm_hip.so): the reference's FeatureManager for many streams at once, each stream's
+track list resident on the device.
+
+    fh = vio.load_fm().create()                                      # (device 0, its own stream)
+    fm = BatchFeatureManager(fh, slots=range(64))
+    res = fm.add_feature_frames(bt.feature_frames(), frame_counts)   # addFeatureCheckParallax: res[i]["keyframe"]
+    wins = fm.windows(poses, ext)                                    # triangulate + the arrays vio_set_landmarks / _observations take
+    fm.set_depths([w["inv_depth"] for w in solved])                  # setDepth + removeFailures
+    fm.slide([BACK_SHIFT_DEPTH] * 64, marg_R=..., marg_P=..., new_R=..., new_P=...)
+
+A track list as arrays is tests/fm_util.tracks_to_arrays' layout: ids, start, depth, flag, off (n + 1), pts (off[-1], 2).
+"""
+import ctypes as C
+
+import numpy as np
+
+from .capi import CompanionHandle, VioError, open_lib
+
+MAX_SLOTS, MAX_TRACKS, MAX_POINTS, MAX_OBS = 256, 2048, 1024, 11
+DEFAULT_INIT_DEPTH, DEFAULT_MIN_PARALLAX = 5.0, 10.0 / 460.0
+STATUS_OK, STATUS_TABLE_FULL, STATUS_GAP, STATUS_OBS_FULL = 0, 1, 2, 3
+DEPTH_SET, DEPTH_CLEAR = 0, 1
+BACK_SHIFT_DEPTH, BACK, FRONT = 0, 1, 2
+
+
+class VioFmConfig(C.Structure):
+    _fields_ = [("init_depth", C.c_double), ("min_parallax", C.c_double)]
+
+
+class VioFmResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_tracks", C.c_int32), ("n_landmarks", C.c_int32), ("n_observations", C.c_int32),
+                ("keyframe", C.c_int32), ("last_track_num", C.c_int32), ("parallax_num", C.c_int32), ("n_new", C.c_int32),
+                ("n_triangulated", C.c_int32), ("n_rows", C.c_int32), ("parallax_sum", C.c_double)]
+
+
+class VioFmAddItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("frame_count", C.c_int32), ("n", C.c_int32), ("reserved", C.c_int32), ("ids", C.c_void_p),
+                ("pts", C.c_void_p)]
+
+
+class VioFmExportItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("triangulate", C.c_int32), ("cap_landmarks", C.c_int32), ("cap_observations", C.c_int32),
+                ("poses", C.c_void_p), ("ext", C.c_void_p), ("feature_ids", C.c_void_p), ("inv_depth", C.c_void_p), ("lm", C.c_void_p),
+                ("host", C.c_void_p), ("target", C.c_void_p), ("pts_i", C.c_void_p), ("pts_j", C.c_void_p)]
+
+
+class VioFmDepthItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("mode", C.c_int32), ("remove_failures", C.c_int32), ("n", C.c_int32), ("x", C.c_void_p)]
+
+
+class VioFmSlideItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("kind", C.c_int32), ("frame_count", C.c_int32), ("reserved", C.c_int32), ("marg_R", C.c_void_p),
+                ("marg_P", C.c_void_p), ("new_R", C.c_void_p), ("new_P", C.c_void_p)]
+
+
+class VioFmCorrItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("l", C.c_int32), ("r", C.c_int32), ("cap_rows", C.c_int32), ("rows", C.c_void_p)]
+
+
+def _result(r):
+    return {k: getattr(r, k) for k, _ in VioFmResult._fields_}
+
+
+class FmLib:
+    """libvio_fm_hip.so: vio_fm_*."""
+
+    SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "reset", "counts", "add_batch", "export_batch",
+               "set_depth_batch", "slide_batch", "corresponding_batch", "tracks_set", "tracks_get", "timing"]
+
+    def __init__(self, path):
+        self.path = path
+        self.dll, self.fn = open_lib(path, "vio_fm_", self.SYMBOLS)
+        self.fn["create"].argtypes = [C.c_int32, C.c_void_p, C.c_void_p]
+        self.fn["set_config"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn["reset"].argtypes = [C.c_void_p, C.c_int32]
+        self.fn["counts"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        for k in ("add_batch", "export_batch", "set_depth_batch", "slide_batch", "corresponding_batch"):
+            self.fn[k].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        self.fn["tracks_set"].argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
+        self.fn["tracks_get"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7
+        self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
+
+    def create(self, device=0, stream=None):
+        """A vio_fm handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
+        return FmHandle(self, device, stream)
+
+
+class FmHandle(CompanionHandle):
+    PREFIX = "vio_fm_"
+
+    def __init__(self, lib, device=0, stream=None):
+        self.lib = lib
+        self.h = C.c_void_p()
+        st = lib.fn["create"](C.c_int32(device), C.c_void_p(stream) if stream else None, C.byref(self.h))
+        if st != 0:
+            raise VioError(st, "vio_fm_create")
+
+    def set_config(self, init_depth=DEFAULT_INIT_DEPTH, min_parallax=DEFAULT_MIN_PARALLAX):
+        cfg = VioFmConfig(float(init_depth), float(min_parallax))
+        self._ck(self.lib.fn["set_config"](self.h, C.byref(cfg)), "set_config")
+
+    def reset(self, slot):
+        """clearState of one slot."""
+        self._ck(self.lib.fn["reset"](self.h, C.c_int32(slot)), "reset")
+
+    def counts(self, slot):
+        """(n_tracks, n_landmarks, n_observations) of a slot as the last call left them."""
+        a, b, c = C.c_int32(), C.c_int32(), C.c_int32()
+        self._ck(self.lib.fn["counts"](self.h, C.c_int32(slot), C.byref(a), C.byref(b), C.byref(c)), "counts")
+        return a.value, b.value, c.value
+
+    def _call(self, name, items, n):
+        res = (VioFmResult * max(n, 1))()
+        self._ck(self.lib.fn[name](self.h, C.c_int32(n), C.addressof(items), C.addressof(res)), name)
+        return [_result(res[i]) for i in range(n)]
+
+    def add_batch(self, items):
+        """addFeatureCheckParallax per item (slot, frame_count, ids (n,), pts (n, 2)): a list of result dicts (status, the three
+        counts, keyframe, last_track_num, parallax_num, parallax_sum, n_new)."""
+        arr, keep = (VioFmAddItem * max(len(items), 1))(), []
+        for i, (slot, fc, ids, pts) in enumerate(items):
+            ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+            if len(ids) != len(pts):
+                raise ValueError("item %d: ids and pts must have the same length" % i)
+            keep += [ids, pts]
+            arr[i] = VioFmAddItem(int(slot), int(fc), len(ids), 0, ids.ctypes.data, pts.ctypes.data)
+        return self._call("add_batch", arr, len(items))
+
+    def export_batch(self, items, triangulate=True):
+        """Per item (slot, poses (11, 7), ext (7,)): the result dict plus feature_ids, inv_depth, lm, host, target, pts_i, pts_j."""
+        arr, keep, outs = (VioFmExportItem * max(len(items), 1))(), [], []
+        for i, (slot, poses, ext) in enumerate(items):
+            _, nl, no = self.counts(slot)
+            poses = np.ascontiguousarray(poses, dtype=np.float64).reshape(11, 7)
+            ext = np.ascontiguousarray(ext, dtype=np.float64).reshape(7)
+            o = dict(feature_ids=np.zeros(nl, dtype=np.int64), inv_depth=np.zeros(nl), lm=np.zeros(no, dtype=np.int32),
+                     host=np.zeros(no, dtype=np.int32), target=np.zeros(no, dtype=np.int32), pts_i=np.zeros((no, 2)), pts_j=np.zeros((no, 2)))
+            keep += [poses, ext]
+            outs.append(o)
+            arr[i] = VioFmExportItem(int(slot), int(bool(triangulate)), nl, no, poses.ctypes.data, ext.ctypes.data, o["feature_ids"].ctypes.data,
+                                     o["inv_depth"].ctypes.data, o["lm"].ctypes.data, o["host"].ctypes.data, o["target"].ctypes.data,
+                                     o["pts_i"].ctypes.data, o["pts_j"].ctypes.data)
+        res = self._call("export_batch", arr, len(items))
+        for r, o in zip(res, outs):
+            r.update(o)
+        return res
+
+    def set_depth_batch(self, items, mode=DEPTH_SET, remove_failures=False):
+        """Per item (slot, x (n_landmarks,)): setDepth (DEPTH_SET) or clearDepth (DEPTH_CLEAR), then removeFailures if asked."""
+        arr, keep = (VioFmDepthItem * max(len(items), 1))(), []
+        for i, (slot, x) in enumerate(items):
+            x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
+            keep.append(x)
+            arr[i] = VioFmDepthItem(int(slot), int(mode), int(bool(remove_failures)), x.size, x.ctypes.data)
+        return self._call("set_depth_batch", arr, len(items))
+
+    def slide_batch(self, items):
+        """Per item (slot, kind, frame_count, marg_R, marg_P, new_R, new_P); the matrices are read for BACK_SHIFT_DEPTH only (None
+        otherwise), frame_count for FRONT only."""
+        arr, keep = (VioFmSlideItem * max(len(items), 1))(), []
+        for i, it in enumerate(items):
+            slot, kind, fc = int(it[0]), int(it[1]), int(it[2]) if len(it) > 2 and it[2] is not None else 0
+            m = [None] * 4
+            if kind == BACK_SHIFT_DEPTH:
+                m = [np.ascontiguousarray(np.ravel(v), dtype=np.float64) for v in it[3:7]]
+                if [v.size for v in m] != [9, 3, 9, 3]:
+                    raise ValueError("item %d: marg_R (3, 3), marg_P (3,), new_R (3, 3), new_P (3,)" % i)
+                keep += m
+            arr[i] = VioFmSlideItem(slot, kind, fc, 0, *[None if v is None else v.ctypes.data for v in m])
+        return self._call("slide_batch", arr, len(items))
+
+    def corresponding_batch(self, items):
+        """Per item (slot, l, r): the result dict plus rows (n_rows, 4) of x_l, y_l, x_r, y_r in list order."""
+        arr, outs = (VioFmCorrItem * max(len(items), 1))(), []
+        for i, (slot, l, r) in enumerate(items):
+            n = self.counts(slot)[0]
+            rows = np.zeros((n, 4))
+            outs.append(rows)
+            arr[i] = VioFmCorrItem(int(slot), int(l), int(r), n, rows.ctypes.data)
+        res = self._call("corresponding_batch", arr, len(items))
+        for r, rows in zip(res, outs):
+            r["rows"] = rows[:r["n_rows"]].copy()
+        return res
+
+    def tracks_set(self, slot, ids, start, depth, flag, off, pts):
+        ids = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+        start = np.ascontiguousarray(start, dtype=np.int32).reshape(-1)
+        depth = np.ascontiguousarray(depth, dtype=np.float64).reshape(-1)
+        flag = np.ascontiguousarray(flag, dtype=np.int32).reshape(-1)
+        off = np.ascontiguousarray(off, dtype=np.int64).reshape(-1)
+        pts = np.ascontiguousarray(pts, dtype=np.float64).reshape(-1, 2)
+        n = len(ids)
+        if not (len(start) == len(depth) == len(flag) == n and len(off) == n + 1 and (n == 0 or 0 <= off[-1] <= len(pts))):
+            raise ValueError("ids, start, depth, flag need one entry per track, off one more, ending within pts")
+        self._ck(self.lib.fn["tracks_set"](self.h, C.c_int32(slot), C.c_int32(n), ids.ctypes.data, start.ctypes.data, depth.ctypes.data,
+                                           flag.ctypes.data, off.ctypes.data, pts.ctypes.data), "tracks_set")
+
+    def tracks_get(self, slot):
+        """The slot's list: a dict of ids, start, depth, flag, off, pts."""
+        cap = self.counts(slot)[0]
+        ids, start = np.zeros(cap, dtype=np.int64), np.zeros(cap, dtype=np.int32)
+        depth, flag = np.zeros(cap), np.zeros(cap, dtype=np.int32)
+        off, pts = np.zeros(cap + 1, dtype=np.int64), np.zeros((cap * MAX_OBS, 2))
+        n = C.c_int32()
+        self._ck(self.lib.fn["tracks_get"](self.h, C.c_int32(slot), C.c_int32(cap), C.c_int64(cap * MAX_OBS), C.byref(n), ids.ctypes.data,
+                                           start.ctypes.data, depth.ctypes.data, flag.ctypes.data, off.ctypes.data, pts.ctypes.data), "tracks_get")
+        n = n.value
+        return dict(ids=ids[:n], start=start[:n], depth=depth[:n], flag=flag[:n], off=off[:n + 1], pts=pts[:off[n]].copy())
+
+    def timing(self):
+        """ms of the last batched call that launched: host checks, packing and upload; the kernel; the read-back; the whole call."""
+        t = (C.c_double * 4)()
+        self._ck(self.lib.fn["timing"](self.h, t), "timing")
+        return {"host_ms": t[0], "kernel_ms": t[1], "readback_ms": t[2], "total_ms": t[3]}
+
+
+class BatchFeatureManager:
+    """The reference's FeatureManager for every slot of `slots` in one call per method: the counterpart of
+    frontend.BatchFeatureTracker, whose feature_frames() it takes as they are."""
+
+    def __init__(self, handle, slots):
+        self.fm, self.slots = handle, [int(s) for s in slots]
+        if len(set(self.slots)) != len(self.slots):
+            raise ValueError("a slot is listed twice")
+
+    def _per_slot(self, v, what):
+        v = list(v)
+        if len(v) != len(self.slots):
+            raise ValueError("%s: one entry per slot" % what)
+        return v
+
+    def add_feature_frames(self, frames, frame_counts):
+        """frames: per slot (ids (n,), rows (n, >= 2)) with the normalised point in columns 0 and 1 (float32 widens exactly);
+        frame_counts: per slot.  The result dicts of add_batch; ["keyframe"] is the marginalisation decision."""
+        frames, fcs = self._per_slot(frames, "frames"), self._per_slot(frame_counts, "frame_counts")
+        items = []
+        for s, fc, (ids, rows) in zip(self.slots, fcs, frames):
+            rows = np.asarray(rows, dtype=np.float64)
+            if rows.ndim != 2 or rows.shape[0] != len(ids) or rows.shape[1] < 2:
+                raise ValueError("slot %d: rows must be (len(ids), >= 2)" % s)
+            items.append((s, fc, ids, rows[:, 0:2]))
+        return self.fm.add_batch(items)
+
+    def windows(self, poses, ext, triangulate=True):
+        """poses: per slot (11, 7); ext: (7,) for all or per slot.  Per slot a dict of synth.Window's fields inv_depth, lm, host,
+        target, pts_i, pts_j, and feature_ids, after triangulate (if asked)."""
+        poses = self._per_slot(poses, "poses")
+        ext = np.asarray(ext, dtype=np.float64)
+        exts = [ext] * len(self.slots) if ext.ndim == 1 else self._per_slot(ext, "ext")
+        return self.fm.export_batch(list(zip(self.slots, poses, exts)), triangulate=triangulate)
+
+    def set_depths(self, inv_depths, remove_failures=True):
+        """setDepth from each slot's solved inverse depths, then removeFailures."""
+        return self.fm.set_depth_batch(list(zip(self.slots, self._per_slot(inv_depths, "inv_depths"))), DEPTH_SET, remove_failures)
+
+    def clear_depths(self, inv_depths):
+        return self.fm.set_depth_batch(list(zip(self.slots, self._per_slot(inv_depths, "inv_depths"))), DEPTH_CLEAR, False)
+
+    def slide(self, kinds, frame_counts=None, marg_R=None, marg_P=None, new_R=None, new_P=None):
+        """kinds: per slot BACK_SHIFT_DEPTH, BACK or FRONT; frame_counts per slot for FRONT; the four pose arrays per slot for
+        BACK_SHIFT_DEPTH (entries of other slots are not read)."""
+        kinds = self._per_slot(kinds, "kinds")
+        n = len(self.slots)
+        cols = [self._per_slot(v, "slide") if v is not None else [None] * n for v in (frame_counts, marg_R, marg_P, new_R, new_P)]
+        return self.fm.slide_batch([(s, k) + tuple(c[i] for c in cols) for i, (s, k) in enumerate(zip(self.slots, kinds))])
+
+    def corresponding(self, l, r):
+        return self.fm.corresponding_batch([(s, l, r) for s in self.slots])
