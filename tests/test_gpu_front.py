@@ -69,25 +69,26 @@ class Rig:
     """A handle read through BatchFeatureTracker and an oracle handle read by one FeatureTracker per slot; read() holds the first to the
     second and returns, per slot, the handle's dict with the oracle's counts under "oracle"."""
 
-    def __init__(self, libs, slots, max_cnt=MAX_CNT, border=1, equalize=True, inverse=0, masks=None, oracle_slots=None):
+    def __init__(self, libs, slots, max_cnt=MAX_CNT, border=1, equalize=True, inverse=0, masks=None, oracle_slots=None, cam=None, min_dist=None):
         self.vio, flib, rlib = libs
         self.slots = list(slots)
         self.oslots = list(oracle_slots) if oracle_slots is not None else self.slots
         self.masks = dict(masks or {})
         self.fr, self.ofr, self.rej = flib.create(), flib.create(), rlib.create()
+        self.cam, self.min_dist = dict(CAM if cam is None else cam), MIN_DIST if min_dist is None else int(min_dist)
         cfg = dict(equalize=equalize, clahe=dict(clip_limit=3.0, tiles=(8, 8)), flow=dict(levels=2, half_patch=HALF_PATCH, inverse=inverse),
-                   detect=dict(min_distance=MIN_DIST))
+                   detect=dict(min_distance=self.min_dist))
         self.fr.set_config(**cfg)
         self.ofr.set_config(**cfg)
-        self.fr.set_camera(**CAM, **RANSAC)
-        self.rej.set_camera(**CAM)
+        self.fr.set_camera(**self.cam, **RANSAC)
+        self.rej.set_camera(**self.cam)
         self.rej.set_config(**RANSAC)
         self.max_cnt, self.border = max_cnt, border
-        self.bt = self.vio.BatchFeatureTracker(self.fr, self.slots, max_cnt=max_cnt, min_dist=MIN_DIST, border=border, masks=self.masks)
+        self.bt = self.vio.BatchFeatureTracker(self.fr, self.slots, max_cnt=max_cnt, min_dist=self.min_dist, border=border, masks=self.masks)
         self.fts = [self.tracker(i) for i in range(len(self.slots))]
 
     def tracker(self, i):
-        return self.vio.FeatureTracker(None, None, max_cnt=self.max_cnt, min_dist=MIN_DIST, border=self.border, mask=self.masks.get(self.slots[i]),
+        return self.vio.FeatureTracker(None, None, max_cnt=self.max_cnt, min_dist=self.min_dist, border=self.border, mask=self.masks.get(self.slots[i]),
                                        rejecter=RecRejecter(self.rej), frames=RecFrames(self.ofr), slot=self.oslots[i])
 
     def close(self):
