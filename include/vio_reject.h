@@ -12,7 +12,8 @@
  *
  * Camera.  The reference's PINHOLE model (VM/src/camera_models/camera_models/PinholeCamera.cc), the one both of its configurations
  * use (VM/config/euroc_config.yaml:9, VM/config/vio_simulation.yaml:9): fx, fy, cx, cy, the radial k1, k2 and the tangential p1, p2.
- * The other camodocal models (KANNALA_BRANDT, MEI, SCARAMUZZA) are refused with VIO_ERR_BAD_ARG.
+ * The other camodocal models (KANNALA_BRANDT, MEI, SCARAMUZZA) are refused with VIO_ERR_BAD_ARG: include/vio_camera.h
+ * (libvio_camera_hip.so) is the same two stages through all four.
  *
  * Lift.  PinholeCamera::liftProjective (PinholeCamera.cc:461-521) with PinholeCamera::distortion (:657-673), in double:
  *       mx_d = (1 / fx) u + (-cx / fx),  my_d = (1 / fy) v + (-cy / fy)                       (m_inv_K11 .. m_inv_K23, divided once)
@@ -96,9 +97,9 @@ extern "C" {
 #define VIO_REJECT_ID_CHUNK 1024                    /* prev_ids staged through LDS by k_reject_lift */
 
 #define VIO_REJECT_MODEL_PINHOLE 0
-#define VIO_REJECT_MODEL_KANNALA_BRANDT 1           /* refused */
-#define VIO_REJECT_MODEL_MEI 2                      /* refused */
-#define VIO_REJECT_MODEL_SCARAMUZZA 3               /* refused */
+#define VIO_REJECT_MODEL_KANNALA_BRANDT 1           /* refused here: include/vio_camera.h */
+#define VIO_REJECT_MODEL_MEI 2                      /* refused here: include/vio_camera.h */
+#define VIO_REJECT_MODEL_SCARAMUZZA 3               /* refused here: include/vio_camera.h */
 
 /* Per-pair outcome besides VIO_OK and VIO_ERR_NOT_FINITE. */
 #define VIO_REJECT_FAIL_NO_MODEL 1

@@ -4,6 +4,8 @@
 // ../../include/vio_reject.h, vio_reject_math.h, vio_sfm_math.h and vio_reject_host.h (the descriptor tables), and has contraction off.
 // The kernels take n, active, m and every offset from the tables in device memory: the host-array library writes them on the host,
 // the resident library's glue kernels (vio_front_body.inc) write the counts on the device.
+// The lift is reached through the customisation points of vio_reject_host.h (the REJ_RAY ... REJ_PROLOGUE_END macros):
+// libvio_camera_hip (vio_camera.hip) compiles this text against its own, for the four camera models and a camera per item.
 constexpr int NT = VIO_REJECT_THREADS;
 constexpr int ROUND = VIO_REJECT_ROUND;
 constexpr int CHUNK = VIO_REJECT_ID_CHUNK;
@@ -23,16 +25,16 @@ __global__ __launch_bounds__(NT) void k_reject_lift(LiftArgs a) {
     if ((int)blockIdx.x * NT >= D.n) return;                 // (the whole workgroup: no barrier was reached)
     const int i = blockIdx.x * NT + threadIdx.x;
     const bool on = i < D.n;
-    double x = 0.0, y = 0.0;
+    REJ_RAY(r);
     if (on) {
         const float *p = a.pts + D.o_pts + 2 * (int64_t)i;
-        rej_lift(a.cam, (double)p[0], (double)p[1], x, y);
+        REJ_ITEM_LIFT(a, D, i, (double)p[0], (double)p[1], r);
     }
     if (a.bare) {
-        if (on) { a.lifted[2 * (D.o_out + i)] = x; a.lifted[2 * (D.o_out + i) + 1] = y; }
+        if (on) { REJ_STORE_BARE(a, D, i, r); }
         return;
     }
-    const float ux = rej_unpoint(x), uy = rej_unpoint(y);
+    const float ux = REJ_UN_X(r), uy = REJ_UN_Y(r);
     if (!D.active) {                                         // a point of the item is not finite
         if (on) {
             a.un[2 * (D.o_out + i)] = NAN; a.un[2 * (D.o_out + i) + 1] = NAN;
@@ -124,13 +126,15 @@ __global__ __launch_bounds__(NT) void k_reject_ransac(RansacArgs a) {
     // prologue: the lift, the virtual pixels, the float rounding
     {
         const float *cur = a.pts + P.o_pts, *forw = cur + 2 * (int64_t)n;
+        REJ_PROLOGUE_BEGIN;
         for (int k = tid; k < n; k += NT) {
-            double x, y;
-            rej_lift(a.cam, (double)cur[2 * k], (double)cur[2 * k + 1], x, y);
-            corr[4 * k] = rej_virtual(a.focal, x, a.half_w); corr[4 * k + 1] = rej_virtual(a.focal, y, a.half_h);
-            rej_lift(a.cam, (double)forw[2 * k], (double)forw[2 * k + 1], x, y);
-            corr[4 * k + 2] = rej_virtual(a.focal, x, a.half_w); corr[4 * k + 3] = rej_virtual(a.focal, y, a.half_h);
+            REJ_RAY_UNSET(r);
+            REJ_PAIR_LIFT(a, P, (double)cur[2 * k], (double)cur[2 * k + 1], r);
+            corr[4 * k] = REJ_VIRTUAL_X(a, P, r); corr[4 * k + 1] = REJ_VIRTUAL_Y(a, P, r);
+            REJ_PAIR_LIFT(a, P, (double)forw[2 * k], (double)forw[2 * k + 1], r);
+            corr[4 * k + 2] = REJ_VIRTUAL_X(a, P, r); corr[4 * k + 3] = REJ_VIRTUAL_Y(a, P, r);
         }
+        REJ_PROLOGUE_END(n, tid, mask, o);
     }
     if (tid == 0) { s_i[0] = -1; s_i[1] = -1; s_i[2] = 0; s_i[3] = 0; }
     __syncthreads();

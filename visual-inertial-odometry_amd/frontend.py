@@ -33,7 +33,9 @@ one, read_image pushes the raw image into `slot` and tracks and detects through 
 handle's business (its equalize setting), so tracker, detector and equalizer may be None and are not used.  prev_img / cur_img stay
 None; frames.download(slot, PREV or NEXT) gives them.  With frames=None nothing of this happens.
 
-Missing against the reference: the camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA).
+The camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA): pass a camera.CameraHandle (or its bind(slot) view) as
+`rejecter`; it has RejectHandle's .reject / .undistort.  Missing against the reference: those models on the resident read_batch path
+(BatchFeatureTracker), which stays PINHOLE, and the fisheye circle mask as a built-in (it is the `mask` image).
 BatchFeatureTracker is the same front end for many streams at once over a frame.FrameHandle's read_batch: the points stay on the
 device, one call reads one new image of every stream.
 
