@@ -85,7 +85,15 @@ constexpr int NF = VIO_NUM_FRAMES, PD = VIO_POSE_DIM, PRD = VIO_PRIOR_DIM;
 constexpr int LDS_BUDGET_DOUBLES = (160 * 1024 - 512) / 8;   // per linearize workgroup: 160 KiB per CU on gfx950, 112 bytes of it static
 constexpr int LDS_BUDGET_HALF_DOUBLES = (80 * 1024 - 512) / 8;   // two workgroups to a CU (k_linearize_h: plans of the throughput policy)
 constexpr int POSE_SOLVE_TILED = 66 * 272 + 192;   // PS_PACKED of vio_kernels.hip: 66 tiles of 16x17 + the rhs row
-constexpr int POSE_SOLVE_LDS = (POSE_SOLVE_TILED + 176 + 272 + 272 + 192 + 176 + 112 + 176 + 184) * 8 + 176 * 4 + 64;
+constexpr int POSE_SOLVE_LDS = (POSE_SOLVE_TILED + VIO_PD_PAD + 272 + 272 + 192 + VIO_PD_PAD + 112 + VIO_PD_PAD + 184) * 8 + VIO_PD_PAD * 4 + 64;
+static_assert(VIO_DEV_ORDER_EIGEN == VIO_ORDER_EIGEN && VIO_DEV_ORDER_CHAIN == VIO_ORDER_CHAIN, "vio_types.h's solve orders are vio_backend.h's");
+// vio_ctx::ahead: what the device holds newer than the host mirrors (pull_from_device brings the named parts back)
+enum : unsigned {
+    AHEAD_STATES = 1u,           // the pose / speed-bias / extrinsic states
+    AHEAD_LANDMARKS = 2u,        // the inverse depths resp. points
+    AHEAD_PRIOR_VECS = 4u,       // b_prior / err_prior
+    AHEAD_ALL = AHEAD_STATES | AHEAD_LANDMARKS | AHEAD_PRIOR_VECS
+};
 
 template <typename T>
 struct DevBuf {
@@ -263,7 +271,7 @@ struct vio_ctx {
     bool prior_dirty = true, imu_dirty = true; // h_Hprior / h_Jtinv resp. h_pre newer than their device copies
     // dirty tracking
     bool dirty_inputs = true;                  // host mirrors newer than the device
-    unsigned ahead = 0;                        // what the device holds newer than the host mirrors: 1 states, 2 landmarks, 4 b_prior / err_prior
+    unsigned ahead = 0;                        // AHEAD_* bits: what the device holds newer than the host mirrors
     bool topo_dirty = true;
     bool obs_mapped = false;                   // between vio_map_observations and vio_commit_observations: no list
     bool obs_map_stale = false;                // ... and vio_set_landmarks has changed the landmark count meanwhile: the mapped arrays are gone
@@ -472,25 +480,25 @@ vio_status upload_plan(vio_ctx *c, Plan &pl, const double *pts_i, const double *
 // ---- device state management ---------------------------------------------------------------------------
 // The small per-frame inputs — states, b_prior, err_prior (two copies each), LmState, the IMU edges' valid flags — are pieces of ONE device
 // block in this order, so that a frame uploads them with one copy instead of five (a hipMemcpyAsync costs the host 5 us whatever its size).
-constexpr size_t FB_STATE = 0, FB_BPRIOR = FB_STATE + 2 * STATE_STRIDE * 8, FB_ERRPRIOR = FB_BPRIOR + 2 * 176 * 8, FB_LM = FB_ERRPRIOR + 2 * 160 * 8,
+constexpr size_t FB_STATE = 0, FB_BPRIOR = FB_STATE + 2 * STATE_STRIDE * 8, FB_ERRPRIOR = FB_BPRIOR + 2 * VIO_PD_PAD * 8, FB_LM = FB_ERRPRIOR + 2 * VIO_PRD_PAD * 8,
                  FB_IV = (FB_LM + sizeof(LmState) + 15) / 16 * 16, FB_BYTES = FB_IV + 16 * 4;
 vio_status alloc_fixed(vio_ctx *c) {
     if (!c->d_frame_block.p) {
         HIPCHK(c->d_frame_block.resize(FB_BYTES));
         HIPCHK(hipMemsetAsync(c->d_frame_block.p, 0, FB_BYTES, c->stream));
-        c->d_state.view_of(c->d_frame_block.p + FB_STATE, 2 * STATE_STRIDE); c->d_bprior.view_of(c->d_frame_block.p + FB_BPRIOR, 2 * 176);
-        c->d_errprior.view_of(c->d_frame_block.p + FB_ERRPRIOR, 2 * 160); c->d_lm.view_of(c->d_frame_block.p + FB_LM, 1);
+        c->d_state.view_of(c->d_frame_block.p + FB_STATE, 2 * STATE_STRIDE); c->d_bprior.view_of(c->d_frame_block.p + FB_BPRIOR, 2 * VIO_PD_PAD);
+        c->d_errprior.view_of(c->d_frame_block.p + FB_ERRPRIOR, 2 * VIO_PRD_PAD); c->d_lm.view_of(c->d_frame_block.p + FB_LM, 1);
         c->d_imu_valid.view_of(c->d_frame_block.p + FB_IV, 16);
     }
     HIPCHK(c->d_state.resize(2 * STATE_STRIDE)); HIPCHK(c->d_pairtab.resize(2 * PAIRTAB_STRIDE));
     HIPCHK(c->d_vis.resize(VIS_COUNT)); HIPCHK(c->d_pre.resize(VIO_WINDOW_SIZE * PRE_STRIDE));
     HIPCHK(c->d_imu_out.resize(VIO_WINDOW_SIZE * IMU_OUT)); HIPCHK(c->d_Hprior.resize(PD * PD));
-    HIPCHK(c->d_bprior.resize(2 * 176)); HIPCHK(c->d_errprior.resize(2 * 160)); HIPCHK(c->d_Jtinv.resize(PRD * PRD));
-    HIPCHK(c->d_Hs.resize(PD * PD)); HIPCHK(c->d_bs.resize(176)); HIPCHK(c->d_bfull.resize(2 * 176));
-    HIPCHK(c->d_diagfull.resize(176)); HIPCHK(c->d_dx.resize(176)); HIPCHK(c->d_step_tot.resize(8)); HIPCHK(c->d_sp_part.resize(8));
+    HIPCHK(c->d_bprior.resize(2 * VIO_PD_PAD)); HIPCHK(c->d_errprior.resize(2 * VIO_PRD_PAD)); HIPCHK(c->d_Jtinv.resize(PRD * PRD));
+    HIPCHK(c->d_Hs.resize(PD * PD)); HIPCHK(c->d_bs.resize(VIO_PD_PAD)); HIPCHK(c->d_bfull.resize(2 * VIO_PD_PAD));
+    HIPCHK(c->d_diagfull.resize(VIO_PD_PAD)); HIPCHK(c->d_dx.resize(VIO_PD_PAD)); HIPCHK(c->d_step_tot.resize(8)); HIPCHK(c->d_sp_part.resize(8));
     HIPCHK(c->d_imu_chi.resize(16)); HIPCHK(c->d_imu_valid.resize(16)); HIPCHK(c->d_lm.resize(1));
     HIPCHK(c->d_gath.resize((size_t)c->cfg.shard_count * VIS_SEND)); HIPCHK(c->d_step_gath.resize((size_t)c->cfg.shard_count * 2));
-    HIPCHK(c->d_perm.resize(2 * 176)); HIPCHK(c->d_rank.resize(176)); HIPCHK(c->d_Pg.resize(2 * POSE_SOLVE_TILED));     // two sets (vio_solve's loop)
+    HIPCHK(c->d_perm.resize(2 * VIO_PD_PAD)); HIPCHK(c->d_rank.resize(VIO_PD_PAD)); HIPCHK(c->d_Pg.resize(2 * POSE_SOLVE_TILED));     // two sets (vio_solve's loop)
     {
         std::vector<uint32_t> map(10 * 63 * 9);
         vio_chain_imu_map(map.data());
@@ -505,7 +513,7 @@ vio_status alloc_fixed(vio_ctx *c) {
     HIPCHK(hipMemset(c->d_Pg.p, 0, 2 * POSE_SOLVE_TILED * sizeof(double)));   // tile padding (17th column) is never written again (use_pg_layout)
     HIPCHK(hipMemsetAsync(c->d_vis.p, 0, VIS_COUNT * 8, c->stream));
     HIPCHK(hipMemsetAsync(c->d_step_tot.p, 0, 8 * 8, c->stream));
-    HIPCHK(hipMemsetAsync(c->d_dx.p, 0, 176 * 8, c->stream));
+    HIPCHK(hipMemsetAsync(c->d_dx.p, 0, VIO_PD_PAD * 8, c->stream));
     return VIO_OK;
 }
 
@@ -541,7 +549,7 @@ DeviceTables make_tables_raw(vio_ctx *c, Plan &pl) {
     T.has_prior = c->has_prior; T.add_imu_prior = 1; T.natural_hs = (pl.marg || c->want_natural_hs) ? 1 : 0;
     T.Hs = c->d_Hs.p; T.Pg = c->d_Pg.p; T.perm = c->d_perm.p; T.rank = c->d_rank.p; T.bs = c->d_bs.p; T.bfull = c->d_bfull.p; T.diagfull = c->d_diagfull.p; T.dx = c->d_dx.p;
     T.dxl = pl.d_dxl.p; T.step_part = pl.d_step_part.p; T.n_step_blocks = T.n_items + T.n_imu_items;
-    T.gn_flags = 0; T.cur_hint = -1; T.lm_gate = 0;
+    T.gn_flags = 0; T.cur_hint = VIO_CUR_FROM_LM; T.lm_gate = VIO_GATE_RUN;
     T.imu_mask = 0;
     for (int k = 0; k < VIO_WINDOW_SIZE; ++k) T.imu_mask |= (c->imu_valid[k] ? 1 : 0) << k;
     T.chi_part = pl.d_step_part.p + 2 * (size_t)T.n_step_blocks;
@@ -568,16 +576,16 @@ vio_status flush_decide(vio_ctx *c) {
     if (!c->decide_pending || !c->active) return VIO_OK;
     c->decide_pending = false;
     DeviceTables T = make_tables_raw(c, *c->active);
-    T.gn_flags = 8;                                          // the GN step left the prior update of its trial slot undone:
-    vio_launch_backsub(T, 0, c->stream);                     // b_prior' by k_backsub,
+    T.gn_flags = VIO_GN_FLUSH_BPRIOR;                        // the GN step left the prior update of its trial slot undone:
+    vio_launch_backsub(T, VIO_BACKSUB_STEP, c->stream);      // b_prior' by k_backsub,
     T.gn_flags = 0;
     if (T.has_prior) vio_launch_errprior(T, c->stream);      // err_prior' by k_errprior
     if (c->hook || c->comm) {
-        vio_launch_step_sum(T, 0, c->stream);
+        vio_launch_step_sum(T, VIO_DECIDE_LM, c->stream);
         VIOCHK(run_exchange(c, 1));
-        vio_launch_lm_decide(T, 1, 0, c->stream);
+        vio_launch_lm_decide(T, VIO_DECIDE_GN, 0, c->stream);
     } else {
-        vio_launch_lm_decide(T, 1, 1, c->stream);
+        vio_launch_lm_decide(T, VIO_DECIDE_GN, 1, c->stream);
     }
     return VIO_OK;
 }
@@ -614,16 +622,16 @@ vio_status read_lm(vio_ctx *c) {
 }
 
 // bring the host mirrors up to date with the device (states, inverse depths, prior vectors)
-vio_status pull_from_device(vio_ctx *c, unsigned mask = 7u) {
+vio_status pull_from_device(vio_ctx *c, unsigned mask = AHEAD_ALL) {
     const unsigned need = c->ahead & mask;
     if (!need) return VIO_OK;
     VIOCHK(read_lm(c));
     const int cur = c->h_lm.cur;
-    if (need & 1u) HIPCHK(hipMemcpyAsync(c->h_state, c->d_state.p + cur * STATE_STRIDE, STATE_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
+    if (need & AHEAD_STATES) HIPCHK(hipMemcpyAsync(c->h_state, c->d_state.p + cur * STATE_STRIDE, STATE_STRIDE * 8, hipMemcpyDeviceToHost, c->stream));
     Plan &pl = c->solve_plan;
     const size_t ld = (size_t)pl.lm_dim;
     double *tmp = nullptr;
-    if ((need & 2u) && pl.valid && pl.Ns) {
+    if ((need & AHEAD_LANDMARKS) && pl.valid && pl.Ns) {
         // the landmarks come back through a pinned buffer of the context's (a pageable destination is staged by the runtime)
         const size_t cnt = ld * (size_t)pl.Ns;
         if (cnt > c->pull_cap) {
@@ -635,9 +643,9 @@ vio_status pull_from_device(vio_ctx *c, unsigned mask = 7u) {
         tmp = c->pull_stage;
         HIPCHK(hipMemcpyAsync(tmp, pl.d_invd.p + (size_t)cur * ld * pl.Ns, cnt * 8, hipMemcpyDeviceToHost, c->stream));
     }
-    if ((need & 4u) && c->has_prior) {
-        HIPCHK(hipMemcpyAsync(c->h_bprior.data(), c->d_bprior.p + cur * 176, PD * 8, hipMemcpyDeviceToHost, c->stream));
-        HIPCHK(hipMemcpyAsync(c->h_errprior.data(), c->d_errprior.p + cur * 160, PRD * 8, hipMemcpyDeviceToHost, c->stream));
+    if ((need & AHEAD_PRIOR_VECS) && c->has_prior) {
+        HIPCHK(hipMemcpyAsync(c->h_bprior.data(), c->d_bprior.p + cur * VIO_PD_PAD, PD * 8, hipMemcpyDeviceToHost, c->stream));
+        HIPCHK(hipMemcpyAsync(c->h_errprior.data(), c->d_errprior.p + cur * VIO_PRD_PAD, PRD * 8, hipMemcpyDeviceToHost, c->stream));
     }
     HIPCHK(hipStreamSynchronize(c->stream));
     if (tmp)
@@ -819,14 +827,14 @@ vio_status run_exchange(vio_ctx *c, int which) {
 // prepare (if needed) + linearize + reduce + [exchange] + assemble at the current state
 // gn = true: the GN loop (vio_gn_iteration): `cur` comes from the host; when a step is waiting for its test, k_reduce also
 // sums its gain-ratio partials and k_assemble runs the test on the chi2 this very linearisation computes
-// gate != 0: one slot of vio_solve's device-driven loop (the kernels skip themselves when it is not their turn)
-vio_status enqueue_linearize(vio_ctx *c, Plan &pl, bool gn = false, int gate = 0) {
+// gate != VIO_GATE_RUN: one slot of vio_solve's device-driven loop (the kernels skip themselves when it is not their turn)
+vio_status enqueue_linearize(vio_ctx *c, Plan &pl, bool gn = false, int gate = VIO_GATE_RUN) {
     DeviceTables T = gn ? make_tables_raw(c, pl) : make_tables(c, pl);
     if (!gn) VIOCHK(c->flush_status);
     T.lm_gate = gate;
     const bool test_prev = gn && c->decide_pending;
     if (gn) T.cur_hint = c->cur_host;
-    if (test_prev) T.gn_flags = 2;
+    if (test_prev) T.gn_flags = VIO_GN_BACKSUB_PREV;
     if (!c->pairtab_valid && pl.lm_dim == 1) { vio_launch_prepare(T, c->stream); c->pairtab_valid = true; }
     // The GN loop's split solve (VIO_GN_SPLIT=1, off by default): lambda is the caller's, so the speed-bias chain of
     // this iteration's system — IMU factors, prior and lambda, nothing of the landmarks — can be eliminated by one more workgroup of
@@ -842,7 +850,7 @@ vio_status enqueue_linearize(vio_ctx *c, Plan &pl, bool gn = false, int gate = 0
     DeviceTables TL = T;
     if (split) {
         if (T.has_prior && !c->prior_simg_valid) { vio_launch_prior_simg(T, c->stream); c->prior_simg_valid = true; }
-        TL.gn_flags |= 16;
+        TL.gn_flags |= VIO_GN_CHAIN_SPLIT;
         TL.n_imu_items = 0;
         TL.n_step_blocks = T.n_items;          // (the rows of b_prior' are shared out over the item workgroups alone)
         lin_blocks = 1 + T.n_items;
@@ -855,9 +863,9 @@ vio_status enqueue_linearize(vio_ctx *c, Plan &pl, bool gn = false, int gate = 0
     // sharded + gated slot: the all-reduce below runs whether the slot is live or not (every rank enqueues the same
     // collectives), in place on vis; k_reduce therefore always runs and puts this rank's own sums back first (a skipped
     // re-linearisation leaves the slabs as they were), so the buffer never accumulates the sum of sums
-    ReduceTables R{pl.d_list_off.p, pl.d_list.p, pl.d_slab.p, T.vis, test_prev ? T.step_part : nullptr, T.n_items, sharded(c) ? 0 : gate, T.lm,
-                   err_prev ? T.Jtinv : nullptr, err_prev ? T.bprior + c->cur_host * 176 : nullptr,
-                   err_prev ? T.errprior + c->cur_host * 160 : nullptr};
+    ReduceTables R{pl.d_list_off.p, pl.d_list.p, pl.d_slab.p, T.vis, test_prev ? T.step_part : nullptr, T.n_items, sharded(c) ? VIO_GATE_RUN : gate, T.lm,
+                   err_prev ? T.Jtinv : nullptr, err_prev ? T.bprior + c->cur_host * VIO_PD_PAD : nullptr,
+                   err_prev ? T.errprior + c->cur_host * VIO_PRD_PAD : nullptr};
     // Three launches per iteration where nothing sits between the sums and the assembly: the GN loop of an unsharded window in the
     // chain order, nobody waiting for the natural-order matrix.  k_reduce_c writes the image; the step test moves to the head of the
     // k_pose_solve_c that follows (enqueue_trial).
@@ -865,7 +873,7 @@ vio_status enqueue_linearize(vio_ctx *c, Plan &pl, bool gn = false, int gate = 0
     // (round 6: also the linearisation that opens vio_solve / vio_linearize — nothing of the loops' flags is needed for the fused sums;
     //  VIO_FIRST_FOUR_LAUNCHES=1 keeps k_reduce + k_assemble_c there, for A/B)
     static const bool first_four = std::getenv("VIO_FIRST_FOUR_LAUNCHES") != nullptr;
-    if (three_launch(c, T) && (gn || (gate == 0 && !first_four))) {
+    if (three_launch(c, T) && (gn || (gate == VIO_GATE_RUN && !first_four))) {
         { ProfScope ps(c, VIO_K_REDUCE); vio_launch_reduce_assemble(R, T, c->stream); }
         // (VIO_GN_SPLIT=2, diagnostic: the chain eliminated in a launch of its own, from the assembled image)
         if (gn && split_mode == 2) { vio_launch_chain_pre(T, c->stream); c->gn_split = 2; }
@@ -877,7 +885,7 @@ vio_status enqueue_linearize(vio_ctx *c, Plan &pl, bool gn = false, int gate = 0
     }
     { ProfScope ps(c, VIO_K_REDUCE); vio_launch_reduce(R, c->stream); }
     VIOCHK(run_exchange(c, 0));
-    if (test_prev) { T.gn_flags = 1; c->decide_pending = false; }
+    if (test_prev) { T.gn_flags = VIO_GN_TEST_PREV; c->decide_pending = false; }
     { ProfScope ps(c, VIO_K_ASSEMBLE); vio_launch_assemble(T, c->stream); }
     HIPCHK(hipGetLastError());
     c->linearized = true;
@@ -892,16 +900,17 @@ vio_status enqueue_init_lm(vio_ctx *c, const DeviceTables &T, int max_iter) {
     return VIO_OK;
 }
 
-vio_status enqueue_trial(vio_ctx *c, Plan &pl, int mode, bool gn = false, int gate = 0) {
+// mode: VIO_DECIDE_LM / VIO_DECIDE_GN for the k_lm_decide of a trial outside the GN loop
+vio_status enqueue_trial(vio_ctx *c, Plan &pl, int mode, bool gn = false, int gate = VIO_GATE_RUN) {
     DeviceTables T = gn ? make_tables_raw(c, pl) : make_tables(c, pl);
     if (!gn) VIOCHK(c->flush_status);
     T.lm_gate = gate;
-    T.gn_flags = 4;         // bit 2: k_pose_solve leaves the prior update to the kernels that follow (all paths now)
+    T.gn_flags = VIO_GN_PRIOR_LATER;       // k_pose_solve leaves the prior update to the kernels that follow (all paths now)
     if (gn) T.cur_hint = c->cur_host;      // GN: the update rides with the next k_linearize / k_reduce (or with flush_decide)
-    if (gn && c->test_in_solve) { T.gn_flags |= 1; c->test_in_solve = false; }      // three-launch path: the previous step's test at this kernel's head
-    if (gn && c->gn_split) { T.gn_flags |= 16; c->gn_split = 0; }                   // ... and the chain of this system is eliminated already
-    static const bool no_early = std::getenv("VIO_NO_EARLY_START") != nullptr;      // diagnostic / tests: k_pose_solve_c's prologue with its barriers (bit 5)
-    if (no_early) T.gn_flags |= 32;
+    if (gn && c->test_in_solve) { T.gn_flags |= VIO_GN_TEST_PREV; c->test_in_solve = false; }      // three-launch path: the previous step's test at this kernel's head
+    if (gn && c->gn_split) { T.gn_flags |= VIO_GN_CHAIN_SPLIT; c->gn_split = 0; }                  // ... and the chain of this system is eliminated already
+    static const bool no_early = std::getenv("VIO_NO_EARLY_START") != nullptr;      // diagnostic / tests: k_pose_solve_c's prologue with its barriers
+    if (no_early) T.gn_flags |= VIO_GN_NO_EARLY_START;
     { ProfScope ps(c, VIO_K_POSE_SOLVE); vio_launch_pose_solve(T, POSE_SOLVE_LDS, c->stream); }
     if (gn) {
         // the step is accepted whatever chi2 turns out to be: the landmark back-substitution, the chi2 of the new state and
@@ -910,17 +919,17 @@ vio_status enqueue_trial(vio_ctx *c, Plan &pl, int mode, bool gn = false, int ga
         c->decide_pending = true;
         c->cur_host ^= 1;
         HIPCHK(hipGetLastError());
-        c->ahead = 7u;
+        c->ahead = AHEAD_ALL;
         return VIO_OK;
     }
     // the prior update of an LM trial (problem.cc:466-475) is spread over the kernels that follow, like a flushed GN step's:
     // b_prior' by k_backsub's workgroups, err_prior' by k_errprior (one CU alone needs ~10 us for the two matrices)
-    T.gn_flags = 8;
-    { ProfScope ps(c, VIO_K_BACKSUB); vio_launch_backsub(T, 0, c->stream); }
+    T.gn_flags = VIO_GN_FLUSH_BPRIOR;
+    { ProfScope ps(c, VIO_K_BACKSUB); vio_launch_backsub(T, VIO_BACKSUB_STEP, c->stream); }
     T.gn_flags = 0;
     if (T.has_prior) vio_launch_errprior(T, c->stream);
     if (sharded(c)) {
-        vio_launch_step_sum(T, 0, c->stream);
+        vio_launch_step_sum(T, VIO_DECIDE_LM, c->stream);
         VIOCHK(run_exchange(c, 1));
         ProfScope ps(c, VIO_K_LM_DECIDE);
         vio_launch_lm_decide(T, mode, 0, c->stream);
@@ -929,7 +938,7 @@ vio_status enqueue_trial(vio_ctx *c, Plan &pl, int mode, bool gn = false, int ga
         vio_launch_lm_decide(T, mode, 1, c->stream);
     }
     HIPCHK(hipGetLastError());
-    c->ahead = 7u;
+    c->ahead = AHEAD_ALL;
     return VIO_OK;
 }
 
@@ -942,13 +951,13 @@ vio_status enqueue_trial(vio_ctx *c, Plan &pl, int mode, bool gn = false, int ga
 vio_status enqueue_lm_slot(vio_ctx *c, Plan &pl, bool first) {
     DeviceTables T = make_tables_raw(c, pl);
     bool test_in_solve = false;
-    T.cur_hint = -2;
-    T.lm_gate = 2;
+    T.cur_hint = VIO_CUR_LM_LOOP;
+    T.lm_gate = VIO_GATE_UNLESS_STOPPED;
     if (!first) {
-        T.gn_flags = 2;
+        T.gn_flags = VIO_GN_BACKSUB_PREV;
         { ProfScope ps(c, VIO_K_LINEARIZE); vio_launch_linearize(T, T.n_items + T.n_imu_items, (size_t)pl.max_lds_doubles * 8, pl.lin_threads, pl.use_ext, c->stream); }
         // (sharded: k_reduce always runs, see enqueue_linearize)
-        ReduceTables R{pl.d_list_off.p, pl.d_list.p, pl.d_slab.p, T.vis, T.step_part, T.n_items, sharded(c) ? 0 : 2, T.lm,
+        ReduceTables R{pl.d_list_off.p, pl.d_list.p, pl.d_slab.p, T.vis, T.step_part, T.n_items, sharded(c) ? VIO_GATE_RUN : VIO_GATE_UNLESS_STOPPED, T.lm,
                        T.has_prior ? T.Jtinv : nullptr, T.has_prior ? T.bprior : nullptr, T.has_prior ? T.errprior : nullptr, 1};
         if (three_launch(c, T)) {
             { ProfScope ps(c, VIO_K_REDUCE); vio_launch_reduce_assemble(R, T, c->stream); }
@@ -956,14 +965,14 @@ vio_status enqueue_lm_slot(vio_ctx *c, Plan &pl, bool first) {
         } else {
             { ProfScope ps(c, VIO_K_REDUCE); vio_launch_reduce(R, c->stream); }
             VIOCHK(run_exchange(c, 0));
-            T.gn_flags = 1;
+            T.gn_flags = VIO_GN_TEST_PREV;
             { ProfScope ps(c, VIO_K_ASSEMBLE); vio_launch_assemble(T, c->stream); }
         }
     }
-    T.gn_flags = 4 | (test_in_solve ? 1 : 0);
+    T.gn_flags = VIO_GN_PRIOR_LATER | (test_in_solve ? VIO_GN_TEST_PREV : 0);
     { ProfScope ps(c, VIO_K_POSE_SOLVE); vio_launch_pose_solve(T, POSE_SOLVE_LDS, c->stream); }
     HIPCHK(hipGetLastError());
-    c->ahead = 7u;
+    c->ahead = AHEAD_ALL;
     return VIO_OK;
 }
 
@@ -1093,7 +1102,7 @@ const char *vio_last_error(const vio_ctx *c) { return c ? c->err.c_str() : "null
 vio_status vio_set_window(vio_ctx *c, const double *poses, const double *sb, const double *ext) {
     if (!c || !poses || !sb || !ext) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    c->ahead &= ~1u;                 // the states are replaced whole: nothing of the device's to keep
+    c->ahead &= ~AHEAD_STATES;                // the states are replaced whole: nothing of the device's to keep
     std::memcpy(c->h_state + STATE_EXT, ext, 7 * 8);
     std::memcpy(c->h_state + STATE_POSE, poses, 77 * 8);
     std::memcpy(c->h_state + STATE_SB, sb, 99 * 8);
@@ -1107,8 +1116,8 @@ static vio_status set_landmarks_dim(vio_ctx *c, int64_t n, const double *val, in
     const bool resized = (int64_t)c->h_invd.size() != n * dim || c->lm_dim != dim;
     // The same values as the mirror holds, the mirror current: nothing to do.  (The reference's frame sets the window twice,
     // for Solve and for Marginalize, with the landmarks the solve gave it: estimator.cpp:1083-1092.)
-    if (!resized && !(c->ahead & 2u) && (n == 0 || std::memcmp(c->h_invd.data(), val, (size_t)n * dim * 8) == 0)) return VIO_OK;
-    c->ahead &= ~2u;                 // the landmarks are replaced whole
+    if (!resized && !(c->ahead & AHEAD_LANDMARKS) && (n == 0 || std::memcmp(c->h_invd.data(), val, (size_t)n * dim * 8) == 0)) return VIO_OK;
+    c->ahead &= ~AHEAD_LANDMARKS;                // the landmarks are replaced whole
     c->h_invd.assign(val, val + n * dim);
     c->lm_dim = dim;
     if (resized) {      // the observation list refers to landmark indices (of this kind): it must be set again
@@ -1361,10 +1370,10 @@ vio_status vio_set_prior(vio_ctx *c, int32_t dim, const double *H, const double 
         same_mats = std::memcmp(c->h_Jtinv.data(), jt, (size_t)PRD * PRD * 8) == 0;
         for (int i = 0; same_mats && i < PRD; ++i) same_mats = std::memcmp(c->h_Hprior.p + (size_t)i * PD, &H[(size_t)i * PRD], PRD * 8) == 0;
     }
-    const bool same_vecs = same_mats && !(c->ahead & 4u) &&
+    const bool same_vecs = same_mats && !(c->ahead & AHEAD_PRIOR_VECS) &&
                            (dim == 0 || (std::memcmp(c->h_bprior.data(), b, PRD * 8) == 0 && std::memcmp(c->h_errprior.data(), err, PRD * 8) == 0));
     if (same_vecs) return VIO_OK;
-    c->ahead &= ~4u;                 // b_prior and err_prior are replaced whole
+    c->ahead &= ~AHEAD_PRIOR_VECS;                // b_prior and err_prior are replaced whole
     std::fill(c->h_bprior.begin(), c->h_bprior.end(), 0.0); std::fill(c->h_errprior.begin(), c->h_errprior.end(), 0.0);
     if (!same_mats) {
         // (the pinned mirrors may still be the source of the previous activation's upload: long done in practice)
@@ -1439,7 +1448,7 @@ vio_status vio_debug_chain_solve(vio_ctx *c, const double *H, const double *b, d
     }
     DevBuf<double> d_img, d_x, d_dump;
     auto body = [&]() -> vio_status {
-        HIPCHK(d_img.resize(img.size())); HIPCHK(d_x.resize(176));
+        HIPCHK(d_img.resize(img.size())); HIPCHK(d_x.resize(VIO_PD_PAD));
         if (lds_dump) HIPCHK(d_dump.resize((size_t)n_lds));
         HIPCHK(hipMemcpyAsync(d_img.p, img.data(), img.size() * 8, hipMemcpyHostToDevice, c->stream));
         vio_launch_chain_solve_test(d_img.p, lambda, d_x.p, lds_dump ? d_dump.p : nullptr, c->stream);
@@ -1492,7 +1501,7 @@ vio_status vio_solve_linear(vio_ctx *c, double lambda) {
     MAKE_TABLES(T, c, pl);
     vio_launch_set_lambda(c->d_lm.p, lambda, c->stream);
     vio_launch_pose_solve(T, POSE_SOLVE_LDS, c->stream);
-    vio_launch_backsub(T, 0, c->stream);
+    vio_launch_backsub(T, VIO_BACKSUB_STEP, c->stream);
     HIPCHK(hipGetLastError());
     c->stepwise_updated = false;
     return VIO_OK;
@@ -1501,14 +1510,14 @@ vio_status vio_solve_linear(vio_ctx *c, double lambda) {
 vio_status vio_update_states(vio_ctx *c) {
     if (!c || !c->active) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    if (!c->stepwise_updated) { vio_launch_flip(c->d_lm.p, c->stream); c->stepwise_updated = true; c->ahead = 7u; }
+    if (!c->stepwise_updated) { vio_launch_flip(c->d_lm.p, c->stream); c->stepwise_updated = true; c->ahead = AHEAD_ALL; }
     return VIO_OK;
 }
 
 vio_status vio_rollback_states(vio_ctx *c) {
     if (!c || !c->active) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    if (c->stepwise_updated) { vio_launch_flip(c->d_lm.p, c->stream); c->stepwise_updated = false; c->ahead = 7u; }
+    if (c->stepwise_updated) { vio_launch_flip(c->d_lm.p, c->stream); c->stepwise_updated = false; c->ahead = AHEAD_ALL; }
     return VIO_OK;
 }
 
@@ -1520,9 +1529,9 @@ vio_status vio_chi2(vio_ctx *c, double *chi2) {
     MAKE_TABLES(T, c, pl);
     // the chi2 kernels read the pair table of the current state; after a stepwise update it is the trial table
     if (!c->pairtab_valid && pl.lm_dim == 1) { vio_launch_prepare(T, c->stream); c->pairtab_valid = true; }
-    vio_launch_backsub(T, 1, c->stream);
-    if (sharded(c)) { vio_launch_step_sum(T, 2, c->stream); VIOCHK(run_exchange(c, 1)); vio_launch_lm_decide(T, 2, 0, c->stream); }
-    else vio_launch_lm_decide(T, 2, 1, c->stream);
+    vio_launch_backsub(T, VIO_BACKSUB_CHI_CUR, c->stream);
+    if (sharded(c)) { vio_launch_step_sum(T, VIO_DECIDE_CHI_ONLY, c->stream); VIOCHK(run_exchange(c, 1)); vio_launch_lm_decide(T, VIO_DECIDE_CHI_ONLY, 0, c->stream); }
+    else vio_launch_lm_decide(T, VIO_DECIDE_CHI_ONLY, 1, c->stream);
     VIOCHK(read_lm(c));
     *chi2 = c->h_lm.chi_try;
     return VIO_OK;
@@ -1535,8 +1544,8 @@ vio_status vio_eval_step(vio_ctx *c, int32_t *accepted, double *chi2, double *la
     MAKE_TABLES(T, c, pl);
     // the decide kernel expects the trial copy to be "the other one"
     if (c->stepwise_updated) vio_launch_flip(c->d_lm.p, c->stream);
-    if (sharded(c)) { vio_launch_step_sum(T, 0, c->stream); VIOCHK(run_exchange(c, 1)); vio_launch_lm_decide(T, 0, 0, c->stream); }
-    else vio_launch_lm_decide(T, 0, 1, c->stream);
+    if (sharded(c)) { vio_launch_step_sum(T, VIO_DECIDE_LM, c->stream); VIOCHK(run_exchange(c, 1)); vio_launch_lm_decide(T, VIO_DECIDE_LM, 0, c->stream); }
+    else vio_launch_lm_decide(T, VIO_DECIDE_LM, 1, c->stream);
     VIOCHK(read_lm(c));
     const bool ok = c->h_lm.accepted != 0;
     if (ok) {
@@ -1544,7 +1553,7 @@ vio_status vio_eval_step(vio_ctx *c, int32_t *accepted, double *chi2, double *la
     } else if (c->stepwise_updated) {
         vio_launch_flip(c->d_lm.p, c->stream);  // stay on the updated states until the caller rolls back (problem.cc:228-231)
     }
-    c->ahead = 7u;
+    c->ahead = AHEAD_ALL;
     if (accepted) *accepted = ok ? 1 : 0;
     if (chi2) *chi2 = c->h_lm.chi;
     if (lambda) *lambda = c->h_lm.lambda;
@@ -1590,8 +1599,8 @@ vio_status vio_solve(vio_ctx *c, int32_t iterations, vio_solve_report *rep) {
             // (at most 10 slots ahead: a loop that stops early leaves the rest as empty launches)
             const int batch = std::min(iterations - c->h_lm.iter, 10);
             for (int sl = 0; sl < batch && status == VIO_OK; ++sl) {
-                status = enqueue_trial(c, pl, 0, false, 2);
-                if (status == VIO_OK) status = enqueue_linearize(c, pl, false, 3);
+                status = enqueue_trial(c, pl, VIO_DECIDE_LM, false, VIO_GATE_UNLESS_STOPPED);
+                if (status == VIO_OK) status = enqueue_linearize(c, pl, false, VIO_GATE_RELINEARIZE);
             }
             if (status == VIO_OK) status = read_lm(c);
         }
@@ -1647,7 +1656,7 @@ vio_status vio_gn_iteration(vio_ctx *c, double lambda) {
     if (gn && c->cur_host < 0) VIOCHK(read_lm(c));      // once: from here on the host tracks LmState.cur itself
     if (lambda != c->gn_lambda) { vio_launch_set_lambda(c->d_lm.p, lambda, c->stream); c->gn_lambda = lambda; }
     VIOCHK(enqueue_linearize(c, pl, gn));
-    VIOCHK(enqueue_trial(c, pl, 1, gn));
+    VIOCHK(enqueue_trial(c, pl, VIO_DECIDE_GN, gn));
     if (!gn) c->cur_host = -1;
     return VIO_OK;
 }
@@ -1755,7 +1764,7 @@ vio_status vio_batch_gn_iteration(vio_ctx *const *ctxs, int32_t count, double la
         vio_ctx *m = ctxs[i];
         m->decide_pending = true;
         m->cur_host ^= 1;
-        m->ahead = 7u;
+        m->ahead = AHEAD_ALL;
         m->linearized = order == effective_order(m);       // (a window solved in the batch's order, not its own: its image is the other layout)
         m->natural_hs_valid = false;
     }
@@ -1795,7 +1804,7 @@ vio_status vio_batch_solve(vio_ctx *const *ctxs, int32_t count, int32_t iteratio
         st = flush_decide(m);
         if (st != VIO_OK) return m == c ? st : fail(c, st, "window " + std::to_string(i) + ": " + m->err);
         m->cur_host = -1;
-        tabs[i] = make_tables_raw(m, m->solve_plan);         // cur_hint = -1: the kernels take `cur` from the window's LmState
+        tabs[i] = make_tables_raw(m, m->solve_plan);         // cur_hint = VIO_CUR_FROM_LM (-1): the kernels take `cur` from the window's LmState
         if (!m->pairtab_valid && m->lm_dim == 1) { vio_launch_prepare(tabs[i], m->stream); m->pairtab_valid = true; }
         const Plan &pl = m->solve_plan;
         if (pl.lin_threads != lin_threads_half_host()) lin_threads = lin_threads_host();
@@ -1822,8 +1831,9 @@ vio_status vio_batch_solve(vio_ctx *const *ctxs, int32_t count, int32_t iteratio
     int order = VIO_ORDER_CHAIN;
     for (int i = 0; i < count; ++i) if (effective_order(ctxs[i]) != VIO_ORDER_CHAIN) order = VIO_ORDER_EIGEN;
     for (int i = 0; i < count; ++i) use_pg_layout(ctxs[i], order);
-    vio_launch_batch_lm(c->d_batch_tabs.p, count, c->lm_dim, max_blocks, lds, lin_threads, any_prior, POSE_SOLVE_LDS, 0, iterations, order, c->stream);
-    if (!classic && iterations > 0) vio_launch_batch_lm(c->d_batch_tabs.p, count, c->lm_dim, max_blocks, lds, lin_threads, any_prior, POSE_SOLVE_LDS, 3, iterations, order, c->stream);
+    vio_launch_batch_lm(c->d_batch_tabs.p, count, c->lm_dim, max_blocks, lds, lin_threads, any_prior, POSE_SOLVE_LDS, VIO_BLM_INIT, iterations, order, c->stream);
+    if (!classic && iterations > 0)
+        vio_launch_batch_lm(c->d_batch_tabs.p, count, c->lm_dim, max_blocks, lds, lin_threads, any_prior, POSE_SOLVE_LDS, VIO_BLM_LOOP_FIRST, iterations, order, c->stream);
     HIPCHK(hipGetLastError());
     if (classic || iterations <= 0) VIOCHK(read_all());
     else for (int i = 0; i < count; ++i) { ctxs[i]->h_lm.stop = 0; ctxs[i]->h_lm.iter = 0; }
@@ -1845,7 +1855,8 @@ vio_status vio_batch_solve(vio_ctx *const *ctxs, int32_t count, int32_t iteratio
         }
         const int batch = std::min(left, 10);
         for (int sl = 0; sl < batch; ++sl)
-            vio_launch_batch_lm(c->d_batch_tabs.p, (int)live.size(), c->lm_dim, max_blocks, lds, lin_threads, any_prior, POSE_SOLVE_LDS, classic ? 1 : 2, iterations, order, c->stream);
+            vio_launch_batch_lm(c->d_batch_tabs.p, (int)live.size(), c->lm_dim, max_blocks, lds, lin_threads, any_prior, POSE_SOLVE_LDS,
+                                classic ? VIO_BLM_CLASSIC_SLOT : VIO_BLM_LOOP_SLOT, iterations, order, c->stream);
         HIPCHK(hipGetLastError());
         VIOCHK(read_all());
     }
@@ -1853,7 +1864,7 @@ vio_status vio_batch_solve(vio_ctx *const *ctxs, int32_t count, int32_t iteratio
     bool finite = true;
     for (int i = 0; i < count; ++i) {
         vio_ctx *m = ctxs[i];
-        m->ahead = 7u;
+        m->ahead = AHEAD_ALL;
         m->decide_pending = false;
         m->linearized = classic && !(m->h_lm.accepted && m->h_lm.stop);
         m->natural_hs_valid = false;
@@ -1967,7 +1978,7 @@ static vio_status marginalize_begin_impl(vio_ctx *c, int32_t kind, bool inline_t
         c->linearized = false;
     } else {
         // MargNewFrame builds a graph without edges (estimator.cpp:830-901): H_marg is the prior alone
-        VIOCHK(pull_from_device(c, 4u));
+        VIOCHK(pull_from_device(c, AHEAD_PRIOR_VECS));
         std::memcpy(Hm, c->h_Hprior.data(), (size_t)PD * PD * 8);
         std::memcpy(bm, c->h_bprior.data(), (size_t)PD * 8);
     }
@@ -2005,7 +2016,7 @@ vio_status vio_marginalize(vio_ctx *c, int32_t kind, double *H, double *b, doubl
 vio_status vio_get_window(vio_ctx *c, double *poses, double *sb, double *ext) {
     if (!c) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    VIOCHK(pull_from_device(c, 1u));
+    VIOCHK(pull_from_device(c, AHEAD_STATES));
     if (ext) std::memcpy(ext, c->h_state + STATE_EXT, 7 * 8);
     if (poses) std::memcpy(poses, c->h_state + STATE_POSE, 77 * 8);
     if (sb) std::memcpy(sb, c->h_state + STATE_SB, 99 * 8);
@@ -2015,7 +2026,7 @@ vio_status vio_get_window(vio_ctx *c, double *poses, double *sb, double *ext) {
 vio_status vio_get_landmarks(vio_ctx *c, int64_t n, double *invd) {
     if (!c || c->lm_dim != 1 || n != (int64_t)c->h_invd.size() || (n > 0 && !invd)) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    VIOCHK(pull_from_device(c, 2u));
+    VIOCHK(pull_from_device(c, AHEAD_LANDMARKS));
     if (n) std::memcpy(invd, c->h_invd.data(), (size_t)n * 8);
     return VIO_OK;
 }
@@ -2023,7 +2034,7 @@ vio_status vio_get_landmarks(vio_ctx *c, int64_t n, double *invd) {
 vio_status vio_get_landmarks_xyz(vio_ctx *c, int64_t n, double *xyz) {
     if (!c || c->lm_dim != 3 || 3 * n != (int64_t)c->h_invd.size() || (n > 0 && !xyz)) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    VIOCHK(pull_from_device(c, 2u));
+    VIOCHK(pull_from_device(c, AHEAD_LANDMARKS));
     if (n) std::memcpy(xyz, c->h_invd.data(), (size_t)n * 24);
     return VIO_OK;
 }
@@ -2031,7 +2042,7 @@ vio_status vio_get_landmarks_xyz(vio_ctx *c, int64_t n, double *xyz) {
 vio_status vio_get_prior(vio_ctx *c, double *b, double *err) {
     if (!c) return VIO_ERR_BAD_ARG;
     enter_device(c);
-    VIOCHK(pull_from_device(c, 4u));
+    VIOCHK(pull_from_device(c, AHEAD_PRIOR_VECS));
     if (b) std::memcpy(b, c->h_bprior.data(), PD * 8);
     if (err) std::memcpy(err, c->h_errprior.data(), PRD * 8);
     return VIO_OK;

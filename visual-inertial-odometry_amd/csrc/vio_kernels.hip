@@ -70,25 +70,27 @@ __device__ __forceinline__ unsigned d_hwreg_hwid() { unsigned x; asm volatile("s
 // which copy of the double-buffered state is current: the host's hint when it tracks it (GN mode), else LmState
 __device__ __forceinline__ int d_cur(const DeviceTables &T) {
     if (T.cur_hint >= 0) return T.cur_hint;
-    return T.cur_hint == -2 ? (T.lm->cur ^ T.lm->pending) : T.lm->cur;
+    return T.cur_hint == VIO_CUR_LM_LOOP ? (T.lm->cur ^ T.lm->pending) : T.lm->cur;
 }
 // vio_solve's loop keeps two sets of what a linearisation leaves for later launches (the landmark rows lw, the permuted system
 // Pg / perm, b_ of the pose block): the set a launch reads — the system the pending step came from — and the one it writes
-__device__ __forceinline__ int d_set_r(const DeviceTables &T) { return T.cur_hint == -2 ? T.lm->sys : 0; }
-__device__ __forceinline__ int d_set_w(const DeviceTables &T) { return T.cur_hint == -2 ? (T.lm->sys ^ T.lm->pending) : 0; }
+__device__ __forceinline__ int d_set_r(const DeviceTables &T) { return T.cur_hint == VIO_CUR_LM_LOOP ? T.lm->sys : 0; }
+__device__ __forceinline__ int d_set_w(const DeviceTables &T) { return T.cur_hint == VIO_CUR_LM_LOOP ? (T.lm->sys ^ T.lm->pending) : 0; }
 #define PS_SET_STRIDE (66 * 272 + 192)      // PS_PACKED (defined with k_pose_solve)
-// bit 0 / bit 1 of gn_flags ("the previous step waits for its test / its landmark back-substitution"): in vio_solve's loop
-// (cur_hint -2) the host sets them on every slot and the device knows whether there is such a step
+#define PS_NP VIO_PD_PAD                    // the solve's name for it: 171 padded to 11 block rows of 16 with identity pivots
+// VIO_GN_TEST_PREV / VIO_GN_BACKSUB_PREV (bits 0 / 1 of gn_flags: "the previous step waits for its test / its landmark
+// back-substitution"): in vio_solve's loop (cur_hint VIO_CUR_LM_LOOP (-2)) the host sets them on every slot and the device knows
+// whether there is such a step
 __device__ __forceinline__ bool d_step_owed(const DeviceTables &T, int bit) {
-    return (T.gn_flags & bit) && (T.cur_hint != -2 || T.lm->pending != 0);
+    return (T.gn_flags & bit) && (T.cur_hint != VIO_CUR_LM_LOOP || T.lm->pending != 0);
 }
 
 // Device-driven LM loop (vio_solve): the host enqueues whole iterations ahead; a kernel whose turn has not come
 // (the loop has stopped, or the last trial was rejected and there is nothing to re-linearise) returns at once.
 __device__ __forceinline__ bool d_gated_off(const LmState *lm, int gate) {
-    if (gate == 0) return false;
+    if (gate == VIO_GATE_RUN) return false;
     if (lm->stop) return true;
-    return (gate & 1) && !lm->need_linearize;
+    return (gate & 1) && !lm->need_linearize;       // (bit 0: VIO_GATE_RELINEARIZE)
 }
 
 __device__ __forceinline__ int cam_to_full(int c) { return c < 6 ? c : 6 + 15 * ((c - 6) / 6) + (c - 6) % 6; }
@@ -301,8 +303,8 @@ __device__ __forceinline__ void d_bprior_rows(const DeviceTables &T, int from, i
     const double x0 = T.dx[lane], x1 = T.dx[lane + 64], x2 = in2 ? T.dx[lane + 128] : 0.0;
     for (int i = first; i < VIO_PD; i += step) {
         const double *h = T.Hprior + (size_t)i * VIO_PD;
-        const double v = d_bprior_dot(h[lane], h[lane + 64], in2 ? h[lane + 128] : 0.0, x0, x1, x2, T.bprior[from * 176 + i]);
-        if (lane == 63) T.bprior[to * 176 + i] = v;
+        const double v = d_bprior_dot(h[lane], h[lane + 64], in2 ? h[lane + 128] : 0.0, x0, x1, x2, T.bprior[from * VIO_PD_PAD + i]);
+        if (lane == 63) T.bprior[to * VIO_PD_PAD + i] = v;
     }
 }
 
@@ -310,11 +312,11 @@ __device__ __forceinline__ void d_bprior_rows(const DeviceTables &T, int from, i
 __device__ __forceinline__ void d_chain_pre_item(const DeviceTables &T);
 // NT: threads of the workgroup.  UE = 0: the plan has no extrinsic block (vio_config.ext_fixed, the reference's ESTIMATE_EXTRINSIC = 0) —
 // row-record sizes and operand-stream strides are compile-time constants (phase 2: 7.3 k -> 6.8 k cycles); UE = 1: read from the item.
-// CH = 1 (the 1024-thread single-window kernels): with gn_flags bit 4 the grid's first workgroup is the chain workgroup, the items follow.
+// CH = 1 (the 1024-thread single-window kernels): with VIO_GN_CHAIN_SPLIT (gn_flags bit 4) the grid's first workgroup is the chain workgroup, the items follow.
 template <int NT, int UE, int CH = 0> __device__ __forceinline__ void d_linearize_body(const DeviceTables &T) {
     const int tid = threadIdx.x;
     int b = blockIdx.x;
-    if (CH && (T.gn_flags & 16)) {
+    if (CH && (T.gn_flags & VIO_GN_CHAIN_SPLIT)) {
         if (b == 0) { d_chain_pre_item(T); return; }
         b -= 1;
     }
@@ -322,9 +324,9 @@ template <int NT, int UE, int CH = 0> __device__ __forceinline__ void d_lineariz
     int32_t desc_word = 0;
     if (b < T.n_items && tid < (int)(sizeof(ItemDesc) / 4)) desc_word = ((const int32_t *)(T.items + b))[tid];
     if (d_gated_off(T.lm, T.lm_gate)) return;
-    // GN mode (gn_flags bit 1) with a prior: the previous step also owes b_prior' = b_prior - H_prior dx (problem.cc:473).
+    // GN mode (VIO_GN_BACKSUB_PREV, gn_flags bit 1) with a prior: the previous step also owes b_prior' = b_prior - H_prior dx (problem.cc:473).
     // Row r belongs to workgroup r mod grid, to its last wave: idle in phase 1 of a landmark item, first thing in an IMU item.
-    const bool owe = d_step_owed(T, 2);
+    const bool owe = d_step_owed(T, VIO_GN_BACKSUB_PREV);
     const bool owe_prior = owe && T.has_prior;
     if (b >= T.n_items) {
         STAMP(T, 0);
@@ -382,7 +384,7 @@ template <int NT, int UE, int CH = 0> __device__ __forceinline__ void d_lineariz
         pv = ptab[(it.host * 11 + it.target[k]) * PAIR_STRIDE + o];
     }
     if (tid < 12) cv = ptab[121 * PAIR_STRIDE + tid];
-    // GN mode (gn_flags bit 1): the landmarks still owe the back-substitution of the PREVIOUS step (problem.cc:445):
+    // GN mode (VIO_GN_BACKSUB_PREV): the landmarks still owe the back-substitution of the PREVIOUS step (problem.cc:445):
     // delta_lambda = (b_l - w . dx_pose) / h from the rows this item's workgroup stored at the end of the previous
     // linearisation.  The new inverse depth goes to the current copy of invd and, through the landmark record, to
     // phase 1; the landmark part of the gain-ratio denominator goes to the record for the combine phase.
@@ -401,7 +403,7 @@ template <int NT, int UE, int CH = 0> __device__ __forceinline__ void d_lineariz
         const double lambda_lm = T.lm->lambda;
 #pragma unroll
         for (int q = 0; q < 7; ++q) { const int e = tid + q * NT; if (e < nlw) sStage[e] = stv[q]; }
-        if (tid < 176) sDxS[tid] = dxv;
+        if (tid < VIO_PD_PAD) sDxS[tid] = dxv;
         __syncthreads();
         if (tid < G) {
             const int g = tid;
@@ -879,8 +881,9 @@ __global__ __launch_bounds__(LIN_THREADS_H, 4) void k_linearize_gh(DeviceTables 
 struct BatchArgs {
     const DeviceTables *tabs;
     int32_t gn_flags;
-    int32_t parity;              // GN loop: 0 / 1, flips the window's cur_hint; -1 (batched LM solve): `cur` comes from the window's LmState
-    int32_t gate;                // d_gated_off's gate (batched LM solve: every window follows its own LmState)
+    int32_t parity;              // GN loop: 0 / 1, flips the window's cur_hint; negative (batched LM solve): VIO_CUR_FROM_LM / VIO_CUR_LM_LOOP, it
+                                 // replaces cur_hint: `cur` comes from the window's LmState
+    int32_t gate;                // VIO_GATE_* of d_gated_off (batched LM solve: every window follows its own LmState)
 };
 __device__ __forceinline__ DeviceTables d_batch_tables(const BatchArgs &a) {
     DeviceTables T = a.tabs[blockIdx.y];
@@ -923,7 +926,7 @@ struct ReduceTables {
     double *vis;
     const double *step_part;     // GN mode: per-item partials of the previous step (k_backsub), or null
     int32_t n_step;              // items
-    int32_t gate;                // see d_gated_off
+    int32_t gate;                // VIO_GATE_*, see d_gated_off
     const LmState *lm;
     const double *jtinv;         // GN mode with a prior: err_prior of the previous step is formed here (blocks >= 91), or null
     const double *bprior;        // b_prior after that step
@@ -985,7 +988,7 @@ __device__ __forceinline__ void d_reduce_body(const ReduceTables &R, const Devic
     if (b >= VIO_NPAIR + VIO_NCB + 1) {          // GN mode: err_prior of the step k_pose_solve took (it left b_prior' only)
         const int row = (b - (VIO_NPAIR + VIO_NCB + 1) - (FUSED ? RED_SB_BLOCKS : 0)) * (RED_THREADS / 64) + (tid >> 6);
         const int copy = R.lm_loop ? (R.lm->cur ^ 1) : 0;
-        if (row < VIO_PRD && step_owed) d_errprior_row(R.jtinv, R.bprior + copy * 176, R.errprior + copy * 160, row, tid & 63);
+        if (row < VIO_PRD && step_owed) d_errprior_row(R.jtinv, R.bprior + copy * VIO_PD_PAD, R.errprior + copy * VIO_PRD_PAD, row, tid & 63);
         return;
     }
     const int lo = lo_pre, hi = hi_pre;
@@ -1088,14 +1091,14 @@ __device__ __forceinline__ void d_reduce_body(const ReduceTables &R, const Devic
     }
 }
 __global__ __launch_bounds__(RED_THREADS) void k_reduce(ReduceTables R) { d_reduce_body<false>(R); }
-// batched: the tables of k_reduce are made of the window's DeviceTables; bit 0 of gn_flags here = "a step is waiting for its test"
+// batched: the tables of k_reduce are made of the window's DeviceTables; VIO_GN_TEST_PREV (bit 0 of gn_flags) here = "a step is waiting for its test"
 __global__ __launch_bounds__(RED_THREADS) void k_reduce_b(BatchArgs a) {
     const DeviceTables T = d_batch_tables(a);
-    const bool test_prev = (a.gn_flags & 1) != 0, err_prev = test_prev && T.has_prior;
+    const bool test_prev = (a.gn_flags & VIO_GN_TEST_PREV) != 0, err_prev = test_prev && T.has_prior;
     if ((int)blockIdx.x >= VIO_NPAIR + VIO_NCB + 1 && !err_prev) return;
-    const int loop = T.cur_hint == -2, cur = loop ? 0 : T.cur_hint;
+    const int loop = T.cur_hint == VIO_CUR_LM_LOOP, cur = loop ? 0 : T.cur_hint;
     ReduceTables R{T.list_off, T.list, T.slab, T.vis, test_prev ? T.step_part : nullptr, T.n_items, a.gate, T.lm,
-                   err_prev ? T.Jtinv : nullptr, err_prev ? T.bprior + cur * 176 : nullptr, err_prev ? T.errprior + cur * 160 : nullptr, loop};
+                   err_prev ? T.Jtinv : nullptr, err_prev ? T.bprior + cur * VIO_PD_PAD : nullptr, err_prev ? T.errprior + cur * VIO_PRD_PAD : nullptr, loop};
     d_reduce_body<false>(R);
 }
 
@@ -1106,7 +1109,6 @@ __global__ __launch_bounds__(RED_THREADS) void k_reduce_b(BatchArgs a) {
 __device__ __forceinline__ int imu_vblock(int a) { return a < 6 ? 0 : (a < 15 ? 1 : (a < 21 ? 2 : 3)); }
 
 #define PS_N VIO_PD
-#define PS_NP 176       // 171 padded to 11 block rows of 16 with identity pivots
 // The permuted lower triangle is kept as 16x16 tiles (block row I >= block column J), each tile row-major with a row
 // stride of 17 doubles: with that stride both the C/D image of v_mfma_f64_16x16x4_f64 (lane -> row (l>>4)+4v,
 // column l&15) and its A/B image (lane -> row l&15, k = (l>>4)+4s) read and write LDS without bank conflicts.
@@ -1176,7 +1178,7 @@ __device__ __forceinline__ double d_rhs_rest(const DeviceTables &T, int valid, i
             extra -= T.imu_out[k * IMU_OUT + IMU_G + a];
         }
     }
-    if (T.has_prior && !mask_i) extra += T.bprior[cur * 176 + i];
+    if (T.has_prior && !mask_i) extra += T.bprior[cur * VIO_PD_PAD + i];
     return extra;
 }
 __device__ __forceinline__ double d_rhs_entries(const DeviceTables &T, int valid, int i, int cur, int wset) {
@@ -1185,7 +1187,7 @@ __device__ __forceinline__ double d_rhs_entries(const DeviceTables &T, int valid
     if (ci >= 0) { bred = d_vis(T, VIS_BRED + ci); bdir = d_vis(T, VIS_BDIR + ci); }
     const double extra = d_rhs_rest(T, valid, i, cur);
     T.bs[i] = bred + extra;
-    T.bfull[wset * 176 + i] = bdir + extra;
+    T.bfull[wset * VIO_PD_PAD + i] = bdir + extra;
     d_hs_entry(T, valid, i, i, dv, dr);
     T.diagfull[i] = ((ci >= 0) ? d_vis(T, VIS_DIAG + ci) : 0.0) + dr;
     return bred + extra;
@@ -1209,19 +1211,19 @@ __device__ __forceinline__ void d_rank_sort(const double *sDg, int *sCnt, int t)
             const double dj = sDg[j];
             rank += (dj > di || (dj == di && j < i)) ? 1 : 0;
         }
-        sCnt[part * 176 + i] = rank;
+        sCnt[part * PS_NP + i] = rank;
     }
     __syncthreads();
 }
-__device__ __forceinline__ int d_rank_of(const int *sCnt, int i) { return sCnt[i] + sCnt[176 + i] + sCnt[352 + i] + sCnt[528 + i] + sCnt[704 + i]; }
+__device__ __forceinline__ int d_rank_of(const int *sCnt, int i) { return sCnt[i] + sCnt[PS_NP + i] + sCnt[2 * PS_NP + i] + sCnt[3 * PS_NP + i] + sCnt[4 * PS_NP + i]; }
 
 // RANKS_GIVEN (batched launches): the ranks come from k_rank_b (T.rank, T.perm), the workgroup has 192 threads and skips the
 // sort every workgroup of the single-window kernel repeats (one launch more is nothing once it is shared by the batch)
 template <bool RANKS_GIVEN>
 __device__ __forceinline__ void d_assemble_body(const DeviceTables &T) {
-    __shared__ double sDg[176];
-    __shared__ int sPerm[176];
-    __shared__ int sCnt[RANKS_GIVEN ? 8 : 5 * 176];
+    __shared__ double sDg[PS_NP];
+    __shared__ int sPerm[PS_NP];
+    __shared__ int sCnt[RANKS_GIVEN ? 8 : 5 * PS_NP];
     const int b = blockIdx.x, t = threadIdx.x;
     if (d_gated_off(T.lm, T.lm_gate)) return;
     const int cur = d_cur(T);
@@ -1234,15 +1236,15 @@ __device__ __forceinline__ void d_assemble_body(const DeviceTables &T) {
     // loads are issued where they are used.  Everything it reads that does not depend on the ranks is requested here, before
     // the diagonal: the previous step's dx / b_ / err_prior, the scalars of the test, the terms of the right-hand sides.
     const bool last_wg = b == PS_NP;
-    const bool test_prev = last_wg && d_step_owed(T, 1);
+    const bool test_prev = last_wg && d_step_owed(T, VIO_GN_TEST_PREV);
     const int rset = d_set_r(T), wset = d_set_w(T);
     double *Pg = T.Pg + wset * PS_SET_STRIDE;
-    int32_t *perm_w = T.perm + wset * 176;
+    int32_t *perm_w = T.perm + wset * VIO_PD_PAD;
     double p_dx = 0.0, p_bf = 0.0, p_er = 0.0, p_lambda = 0.0, p_chi = 0.0, p_step = 0.0, p_lmchi = 0.0, p_imu[10], rhs_v = 0.0;
     if (test_prev) {
         p_lambda = T.lm->lambda;
-        if (t < VIO_PD) { p_dx = T.dx[t]; p_bf = T.bfull[rset * 176 + t]; }          // b_ of the previous linearisation: read before d_rhs_entries replaces it
-        if (T.has_prior && t < VIO_PRD) p_er = T.errprior[cur * 160 + t];
+        if (t < VIO_PD) { p_dx = T.dx[t]; p_bf = T.bfull[rset * VIO_PD_PAD + t]; }          // b_ of the previous linearisation: read before d_rhs_entries replaces it
+        if (T.has_prior && t < VIO_PRD) p_er = T.errprior[cur * VIO_PRD_PAD + t];
         if (t == 0) {
             p_chi = d_vis(T, VIS_CHI); p_step = d_vis(T, VIS_STEP + 1); p_lmchi = T.lm->chi;
 #pragma unroll
@@ -1323,7 +1325,7 @@ __device__ __forceinline__ void d_assemble_body(const DeviceTables &T) {
                 lm->scale = scale;
                 // vio_solve's loop: IsGoodStepInLM's verdict on these two numbers is k_pose_solve's first act (other workgroups
                 // of this kernel are still reading lm->cur)
-                if (T.cur_hint != -2) {
+                if (T.cur_hint != VIO_CUR_LM_LOOP) {
                     lm->rho = (p_lmchi - tempChi) / scale;
                     lm->trials += 1;
                     lm->chi = tempChi;
@@ -1343,15 +1345,15 @@ __device__ __forceinline__ void d_assemble_body(const DeviceTables &T) {
 __global__ __launch_bounds__(ASM_THREADS) void k_assemble(DeviceTables T) { d_assemble_body<false>(T); }
 // batched: the ranks once per window (k_rank_b), then 177 light workgroups of 192 threads per window
 __global__ __launch_bounds__(ASM_THREADS) void k_rank_b(BatchArgs a) {
-    __shared__ double sDg[176];
-    __shared__ int sCnt[5 * 176];
+    __shared__ double sDg[PS_NP];
+    __shared__ int sCnt[5 * PS_NP];
     const DeviceTables T = d_batch_tables(a);
     const int t = threadIdx.x;
     if (d_gated_off(T.lm, T.lm_gate)) return;
     if (t < VIO_PD) { double vv, vr; d_hs_entry(T, d_imu_mask(T), t, t, vv, vr); sDg[t] = d_rank_key(vv + vr); }
     __syncthreads();
     d_rank_sort(sDg, sCnt, t);
-    if (t < VIO_PD) { const int r = d_rank_of(sCnt, t); T.rank[t] = r; T.perm[d_set_w(T) * 176 + r] = t; }
+    if (t < VIO_PD) { const int r = d_rank_of(sCnt, t); T.rank[t] = r; T.perm[d_set_w(T) * VIO_PD_PAD + r] = t; }
 }
 __global__ __launch_bounds__(192) void k_assemble_b(BatchArgs a) { const DeviceTables T = d_batch_tables(a); d_assemble_body<true>(T); }
 
@@ -1465,15 +1467,15 @@ __device__ __forceinline__ void d_lm_store(LmState *lm, const LmRegs &r) {
     lm->naccepted = r.naccepted; lm->need_linearize = r.need_linearize; lm->finite = r.finite; lm->stop_reason = r.stop_reason;
 }
 // IsGoodStepInLM's verdict on a trial state's chi2 (problem.cc:541-573) and Problem::Solve's bookkeeping around it (:169-250).
-// `cur` is the accepted copy the step started from.  mode 0: LM; 1: always accept, no damping update (a flushed GN step).
+// `cur` is the accepted copy the step started from.  mode VIO_DECIDE_LM (0): LM; VIO_DECIDE_GN (1): always accept, no damping update (a flushed GN step).
 // (the traces go straight to `trace`: nobody but the host reads them)
 __device__ void d_lm_verdict(LmRegs &lm, LmState *trace, int mode, double tempChi, double scale, int cur) {
     const double rho = (lm.chi - tempChi) / scale;
     lm.rho = rho; lm.scale = scale;
     lm.trials += 1;
     const bool finite = isfinite(tempChi);
-    if (mode == 1 || (rho > 0 && finite)) {
-        if (mode == 0) {
+    if (mode == VIO_DECIDE_GN || (rho > 0 && finite)) {
+        if (mode == VIO_DECIDE_LM) {
             // (problem.cc:561: 1 - pow(2 rho - 1, 3).  The cube as two products: within an ulp of the power function's value, like the device's own
             //  pow — neither is the host library's —, and 200 instructions less on the one lane the whole LM slot waits for)
             const double t2r = 2 * rho - 1;
@@ -1497,7 +1499,7 @@ __device__ void d_lm_verdict(LmRegs &lm, LmState *trace, int mode, double tempCh
         lm.false_cnt += 1;
     }
     if (!finite) lm.finite = 0;
-    if (mode == 0 && (lm.accepted || lm.false_cnt >= 10)) {     // the inner while of Problem::Solve ends
+    if (mode == VIO_DECIDE_LM && (lm.accepted || lm.false_cnt >= 10)) {     // the inner while of Problem::Solve ends
         lm.iter += 1;
         lm.false_cnt = 0;
         if (lm.last_chi - lm.chi < 1e-5) { lm.stop = 1; lm.stop_reason = 1; }
@@ -1511,23 +1513,23 @@ __device__ __forceinline__ void d_pose_solve_body(const DeviceTables &T) {
     double *P = dyn_smem;                          // 66 tiles of 16x17, then the rhs row (192)
     double *sY = P + PS_YOFF;
     double *sDinv = P + PS_PACKED;                 // 176
-    double *sM = sDinv + 176;                      // 16 x 17: the panel's column operations applied to the identity
+    double *sM = sDinv + PS_NP;                    // 16 x 17: the panel's column operations applied to the identity
     double *sI = sM + PS_TS;                       // 16 x 17 identity
     double *sX = sI + PS_TS;                       // 192 solution in pivot order
     double *sDx = sX + 192;                        // 176 solution in natural order
-    double *sR = sDx + 176;                        // 108 rotations
+    double *sR = sDx + PS_NP;                      // 108 rotations
     double *sB = sR + 112;                         // 176 trial b_prior
-    int *sPerm = (int *)(sB + 176);                // 176
-    double *sState = sB + 176 + 88;                // 184: the current pose / speed-bias states
+    int *sPerm = (int *)(sB + PS_NP);              // 176
+    double *sState = sB + PS_NP + PS_NP / 2;       // 184: the current pose / speed-bias states
     const int tid = threadIdx.x;
     const int wave = tid >> 6, lane = tid & 63;
     const int uwave = __builtin_amdgcn_readfirstlane(wave);
     LmState *lm = T.lm;
     __shared__ LmRegs sLm;
     if (d_gated_off(lm, T.lm_gate)) return;
-    // vio_solve's loop (cur_hint -2): this kernel opens with the verdict on the step the previous one took — k_assemble has
+    // vio_solve's loop (cur_hint VIO_CUR_LM_LOOP (-2)): this kernel opens with the verdict on the step the previous one took — k_assemble has
     // just put the chi2 of its trial state and the gain ratio's denominator into LmState — by thread 0, under the copy below.
-    const bool lm_loop = T.cur_hint == -2;
+    const bool lm_loop = T.cur_hint == VIO_CUR_LM_LOOP;
     int cur = lm_loop ? 0 : d_cur(T);
     double lambda = lm_loop ? 0.0 : lm->lambda;
     const int n = PS_N, NP = PS_NP;
@@ -1559,7 +1561,7 @@ __device__ __forceinline__ void d_pose_solve_body(const DeviceTables &T) {
 #define PS_LD(q) const double2 v##q = src[min(tid + q * PS_THREADS, PS_PACKED / 2 - 1)];
 #define PS_ST(q) dst[min(tid + q * PS_THREADS, PS_PACKED / 2 - 1)] = v##q;          /* clamped lanes rewrite the last pair */
         PS_LD(0) PS_LD(1) PS_LD(2) PS_LD(3) PS_LD(4) PS_LD(5) PS_LD(6) PS_LD(7) PS_LD(8)
-        const int pm = (tid < n) ? T.perm[set * 176 + tid] : 0;
+        const int pm = (tid < n) ? T.perm[set * VIO_PD_PAD + tid] : 0;
         if (pass == 0) {
             // the states, for the update at the end (which copy is current is known after the verdict: both are requested)
             double stv = (tid < STATE_STRIDE) ? T.state[cur * STATE_STRIDE + tid] : 0.0;
@@ -1873,10 +1875,10 @@ __device__ __forceinline__ void d_pose_solve_body(const DeviceTables &T) {
     __syncthreads();
 
     // prior: b' = b - H_prior*dx ; err' = -Jt_prior_inv * b'.head(156)   (problem.cc:466-475).  In the GN loop
-    // (gn_flags bit 2) both are left to the next iteration, where they cost nothing: the rows of b' to the head of
+    // (VIO_GN_PRIOR_LATER, gn_flags bit 2) both are left to the next iteration, where they cost nothing: the rows of b' to the head of
     // k_linearize, err' to k_reduce (flush_decide does them when anybody else asks first).  An LM trial needs them
     // before its k_lm_decide: here, by waves 2..15, every load of a pass requested before the first is used.
-    const bool prior_here = T.has_prior && !(T.gn_flags & 4);
+    const bool prior_here = T.has_prior && !(T.gn_flags & VIO_GN_PRIOR_LATER);
     // The waves split by role (wave-uniform branches; both sides pass the same two barriers):
     //   waves 0,1: trial states = current (+) dx (UpdateStates, problem.cc:456-463) in place in the LDS copy of the states
     //              and out to the trial slot, then the pair table of the trial states, read from that LDS copy;
@@ -1909,14 +1911,14 @@ __device__ __forceinline__ void d_pose_solve_body(const DeviceTables &T) {
                     const int j = lane + 64 * q;
                     hp[r][q] = (i < n && j < n) ? T.Hprior[i * n + j] : 0.0;
                 }
-                bp[r] = (i < n) ? T.bprior[cur * 176 + i] : 0.0;
+                bp[r] = (i < n) ? T.bprior[cur * VIO_PD_PAD + i] : 0.0;
             }
             const double x0 = sDx[lane], x1 = sDx[lane + 64], x2 = (lane + 128 < n) ? sDx[lane + 128] : 0.0;
 #pragma unroll
             for (int r = 0; r < PS_PRIOR_ROWS; ++r) {
                 const int i = (uwave - 2) + 14 * r;
                 const double v = d_bprior_dot(hp[r][0], hp[r][1], hp[r][2], x0, x1, x2, bp[r]);
-                if (lane == 63 && i < n) { sB[i] = v; T.bprior[trial * 176 + i] = v; }
+                if (lane == 63 && i < n) { sB[i] = v; T.bprior[trial * VIO_PD_PAD + i] = v; }
             }
         }
         __syncthreads();
@@ -1939,7 +1941,7 @@ __device__ __forceinline__ void d_pose_solve_body(const DeviceTables &T) {
             for (int r = 0; r < PS_JT_ROWS; ++r) {
                 const int i = (uwave - 2) + 14 * r;
                 const double s = d_errprior_dot(jp[r][0], jp[r][1], jp[r][2], y0, y1, y2);
-                if (lane == 63 && i < VIO_PRD) T.errprior[trial * 160 + i] = s;
+                if (lane == 63 && i < VIO_PRD) T.errprior[trial * VIO_PRD_PAD + i] = s;
             }
         }
     }
@@ -1955,7 +1957,8 @@ __global__ __launch_bounds__(PS_THREADS) void k_pose_solve_b(BatchArgs a) { cons
 
 // ---------------------------------------------------------------------------------------------------------
 // k_backsub: one wave per item.  delta_lambda = Hmm^-1 (bmm - Hmp dx_p) (problem.cc:445), trial inverse depth,
-// chi2 of the trial state, landmark part of the gain-ratio denominator.  mode 1: chi2 of the CURRENT state only.
+// chi2 of the trial state, landmark part of the gain-ratio denominator (mode VIO_BACKSUB_STEP (0)).  Mode VIO_BACKSUB_CHI_CUR (1): chi2 of the
+// CURRENT state only.
 // Blocks >= n_items evaluate the IMU chi2.
 // ---------------------------------------------------------------------------------------------------------
 #define BS_THREADS 128      // one thread per landmark of the item (G <= 128)
@@ -1978,7 +1981,7 @@ __device__ void d_backsub_imu_block(const DeviceTables &T, int mode, int which, 
             chi += r[i] * t;
         }
     }
-    double *part = (mode == 1) ? T.chi_part : T.step_part;
+    double *part = (mode == VIO_BACKSUB_CHI_CUR) ? T.chi_part : T.step_part;
     part[2 * b + STEP_CHI] = chi;
     part[2 * b + STEP_SCALE] = 0.0;
 }
@@ -1988,15 +1991,15 @@ __device__ __forceinline__ void d_backsub_body(const DeviceTables &T, int mode) 
     const LmState *lm = T.lm;
     if (d_gated_off(lm, T.lm_gate)) return;
     const int cur = d_cur(T);
-    const int which = (mode == 1) ? cur : (cur ^ 1);
-    // flush of a GN step (gn_flags bit 3): its b_prior' rows, which the next k_linearize would have formed
-    if ((T.gn_flags & 8) && T.has_prior && (lane >> 6) == 1) d_bprior_rows(T, cur, cur ^ 1, b, T.n_step_blocks, lane & 63);
+    const int which = (mode == VIO_BACKSUB_CHI_CUR) ? cur : (cur ^ 1);
+    // flush of a GN step (VIO_GN_FLUSH_BPRIOR, gn_flags bit 3): its b_prior' rows, which the next k_linearize would have formed
+    if ((T.gn_flags & VIO_GN_FLUSH_BPRIOR) && T.has_prior && (lane >> 6) == 1) d_bprior_rows(T, cur, cur ^ 1, b, T.n_step_blocks, lane & 63);
     if (b >= T.n_items) { d_backsub_imu_block(T, mode, which, b, lane); return; }
     __shared__ double sPairCD[VIO_MAXK * 12];
-    __shared__ double sDxp[176];
+    __shared__ double sDxp[VIO_PD_PAD];
     __shared__ ItemDesc sIt;
     // the pose update is the same for every item: requested together with the descriptor (both cold after the boundary)
-    if (mode == 0) { sDxp[lane] = T.dx[lane]; if (lane + BS_THREADS < 176) sDxp[lane + BS_THREADS] = T.dx[lane + BS_THREADS]; }
+    if (mode == VIO_BACKSUB_STEP) { sDxp[lane] = T.dx[lane]; if (lane + BS_THREADS < VIO_PD_PAD) sDxp[lane + BS_THREADS] = T.dx[lane + BS_THREADS]; }
     if (lane < (int)(sizeof(ItemDesc) / 4)) ((int32_t *)&sIt)[lane] = ((const int32_t *)(T.items + b))[lane];
     __syncthreads();
     const ItemDesc &it = sIt;
@@ -2012,7 +2015,7 @@ __device__ __forceinline__ void d_backsub_body(const DeviceTables &T, int mode) 
         const int g = lane;
         const size_t li = (size_t)it.lm_base + g;
         double lam = T.invd[(size_t)cur * T.Ns + li];
-        if (mode == 0) {
+        if (mode == VIO_BACKSUB_STEP) {
             const double *lw = T.lw + it.lw_base;
             double t = 0.0;
             for (int p = 0; p < nb; ++p) {
@@ -2057,8 +2060,8 @@ __device__ __forceinline__ void d_backsub_body(const DeviceTables &T, int mode) 
         double c = 0.0, sc = 0.0;
 #pragma unroll
         for (int w = 0; w < BS_THREADS / 64; ++w) { c += sSum[2 * w]; sc += sSum[2 * w + 1]; }
-        // vio_chi2 (mode 1) has partials of its own so that it never disturbs a pending step test
-        double *part = (mode == 1) ? T.chi_part : T.step_part;
+        // vio_chi2 (mode VIO_BACKSUB_CHI_CUR) has partials of its own so that it never disturbs a pending step test
+        double *part = (mode == VIO_BACKSUB_CHI_CUR) ? T.chi_part : T.step_part;
         part[2 * b + STEP_CHI] = c; part[2 * b + STEP_SCALE] = sc;
     }
 }
@@ -2072,12 +2075,13 @@ __global__ __launch_bounds__(BS_THREADS) void k_backsub_b(BatchArgs a, int mode)
 // ---------------------------------------------------------------------------------------------------------
 // k_step_sum: fixed-order sum of the visual per-item partials -> step_tot[0..1] (the second exchange buffer)
 // k_lm_decide: IsGoodStepInLM (problem.cc:541-573) + the loop bookkeeping of Problem::Solve (:188-245)
-//   mode 0: LM trial   mode 1: fixed-lambda GN step (always accept)   mode 2: chi2 only (no state change)
+//   mode VIO_DECIDE_LM (0): LM trial   VIO_DECIDE_GN (1): fixed-lambda GN step (always accept)   VIO_DECIDE_CHI_ONLY (2): chi2 only (no state change)
+//   (k_step_sum tells VIO_DECIDE_CHI_ONLY from the other two only: which partials it sums)
 // ---------------------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void k_step_sum(DeviceTables T, int mode) {
     __shared__ double s0[256];
     const int tid = threadIdx.x;
-    const double *part = (mode == 2) ? T.chi_part : T.step_part;
+    const double *part = (mode == VIO_DECIDE_CHI_ONLY) ? T.chi_part : T.step_part;
     double c = 0, s = 0;
     for (int e = tid; e < T.n_items; e += 256) { c += part[2 * e + STEP_CHI]; s += part[2 * e + STEP_SCALE]; }
     d_block_sum2<256>(c, s, s0, tid);        // the same reduction as k_lm_decide's: sharded and unsharded runs agree bit for bit
@@ -2092,7 +2096,7 @@ __global__ __launch_bounds__(256) void k_step_sum(DeviceTables T, int mode) {
 template <int NT>
 __device__ void d_lm_decide(const DeviceTables &T, int mode, int sum_local, double *s0, double *sImu, int tid) {
     LmState *lm = T.lm;
-    const double *part = (mode == 2) ? T.chi_part : T.step_part;
+    const double *part = (mode == VIO_DECIDE_CHI_ONLY) ? T.chi_part : T.step_part;
     // everything this kernel reads is requested before anything is waited for: one round trip, not five.  The prior
     // error is read from both state copies because which one counts depends on lm->cur, itself still in flight.
     const int cur = lm->cur;
@@ -2102,11 +2106,11 @@ __device__ void d_lm_decide(const DeviceTables &T, int mode, int sum_local, doub
     if (sum_local && act)   // unsharded: fold k_step_sum in (same fixed order)
         for (int e = tid; e < T.n_items; e += 256) { c += part[2 * e + STEP_CHI]; s += part[2 * e + STEP_SCALE]; }
     if (T.has_prior && act)
-        for (int i = tid; i < VIO_PRD; i += 256) { const double v0 = T.errprior[i], v1 = T.errprior[160 + i]; e0 += v0 * v0; e1 += v1 * v1; }
-    if (mode != 2 && act)
+        for (int i = tid; i < VIO_PRD; i += 256) { const double v0 = T.errprior[i], v1 = T.errprior[VIO_PRD_PAD + i]; e0 += v0 * v0; e1 += v1 * v1; }
+    if (mode != VIO_DECIDE_CHI_ONLY && act)
         for (int i = tid; i < VIO_PD; i += 256) { const double d = T.dx[i]; sp += d * (lambda * d + T.bfull[i]); }
     if (tid < T.n_imu_items) sImu[tid] = part[2 * (T.n_items + tid) + STEP_CHI];
-    const int which = (mode == 2) ? cur : (cur ^ 1);
+    const int which = (mode == VIO_DECIDE_CHI_ONLY) ? cur : (cur ^ 1);
     double e = which ? e1 : e0;
     if (sum_local) {
         d_block_sum2<NT>(c, s, s0, tid);
@@ -2123,7 +2127,7 @@ __device__ void d_lm_decide(const DeviceTables &T, int mode, int sum_local, doub
     if (T.has_prior) total += sqrt(en2);            // err_prior_.norm(), not squared (problem.cc:554-556)
     const double tempChi = 0.5 * total;
     lm->chi_try = tempChi;
-    if (mode == 2) return;
+    if (mode == VIO_DECIDE_CHI_ONLY) return;
     double scale = 0.5 * ((sum_local ? s : d_step_tot(T, 1)) + scale_p);
     scale += 1e-6;
     LmRegs regs;
@@ -2160,7 +2164,7 @@ __device__ __forceinline__ void d_init_lm_body(const DeviceTables &T, int max_it
     const int cur = lm->cur;
     double e = 0.0, md = 0.0;
     if (T.has_prior)
-        for (int i = tid; i < VIO_PRD; i += 256) { const double v = T.errprior[cur * 160 + i]; e += v * v; }
+        for (int i = tid; i < VIO_PRD; i += 256) { const double v = T.errprior[cur * VIO_PRD_PAD + i]; e += v * v; }
     for (int i = tid; i < VIO_PD; i += 256) md = fmax(md, fabs(T.diagfull[i]));
     const double en2 = d_block_sum<256>(e, s0, tid);
     const double maxd = d_block_max<256>(md, s0, tid);
@@ -2255,103 +2259,115 @@ static void launch_linearize_b(const BatchArgs &a, int lm_dim, int max_blocks, i
     else if (!ext) hipLaunchKernelGGL(k_linearize_b, dim3(max_blocks, B), dim3(LIN_THREADS), lin_lds, s, a);
     else hipLaunchKernelGGL(k_linearize_gb, dim3(max_blocks, B), dim3(LIN_THREADS), lin_lds, s, a);
 }
-// order 1: the chain order for every window of the batch (no rank kernel: every entry's place is static)
+// the grid of k_reduce*: the 78 pair lists, the 12 vector lists and the chi / max h list; chain: the speed-bias rows of the chain image behind
+// them (k_reduce_c, k_reduce_cb); err: the rows of the previous step's err_prior' last
+static inline unsigned reduce_blocks(bool chain, bool err) {
+    return VIO_NPAIR + VIO_NCB + 1 + (chain ? RED_SB_BLOCKS : 0) + (err ? RED_ERR_BLOCKS : 0);
+}
+// VIO_DEV_ORDER_CHAIN: the chain order for every window of the batch (no rank kernel: every entry's place is static)
 static void launch_assemble_b(const BatchArgs &a, int B, int order, hipStream_t s) {
-    if (order == 1) { hipLaunchKernelGGL(k_assemble_cb, dim3(ASMC_BLOCKS, B), dim3(ASMC_THREADS), 0, s, a); return; }
+    if (order == VIO_DEV_ORDER_CHAIN) { hipLaunchKernelGGL(k_assemble_cb, dim3(ASMC_BLOCKS, B), dim3(ASMC_THREADS), 0, s, a); return; }
     hipLaunchKernelGGL(k_rank_b, dim3(1, B), dim3(ASM_THREADS), 0, s, a);
     hipLaunchKernelGGL(k_assemble_b, dim3(PS_NP + 1, B), dim3(192), 0, s, a);
 }
 static void launch_pose_solve_b(const BatchArgs &a, int B, size_t ps_lds, int order, hipStream_t s) {
-    if (order == 1) hipLaunchKernelGGL(k_pose_solve_cb, dim3(1, B), dim3(PS_THREADS), CH_LDS_DOUBLES * sizeof(double), s, a);
+    if (order == VIO_DEV_ORDER_CHAIN) hipLaunchKernelGGL(k_pose_solve_cb, dim3(1, B), dim3(PS_THREADS), CH_LDS_DOUBLES * sizeof(double), s, a);
     else hipLaunchKernelGGL(k_pose_solve_b, dim3(1, B), dim3(PS_THREADS), ps_lds, s, a);
 }
-// batched GN iteration (windows of one landmark kind): grid.y = window
+// batched GN iteration (windows of one landmark kind): grid.y = window; the sequence of enqueue_linearize(gn) + enqueue_trial(gn) of vio_api.cpp
 // ev_kernel (VIO_K_* of vio_profile_begin, -1: none): an event pair around that kernel's launch (bench.py's batched roofline)
 void vio_launch_batch_gn(const DeviceTables *tabs, int B, int lm_dim, int max_blocks, size_t lin_lds, int lin_threads, int test_prev, int any_prior,
                          int parity, size_t ps_lds, int order, hipStream_t s, int ev_kernel, hipEvent_t *ev) {
-    BatchArgs a{tabs, test_prev ? 2 : 0, parity, 0};
+    BatchArgs a{tabs, test_prev ? VIO_GN_BACKSUB_PREV : 0, parity, VIO_GATE_RUN};
     auto mark = [&](int k, int which) { if (ev_kernel == k) (void)hipEventRecord(ev[which], s); };
     mark(0, 0);
     launch_linearize_b(a, lm_dim, max_blocks, B, lin_lds, lin_threads, s);
     mark(0, 1);
-    a.gn_flags = test_prev ? 1 : 0;
-    if (order == 1) {
-        // three launches: the sums, the assembly of the chain image and (k_pose_solve_cb, bit 0) the previous step's test
+    a.gn_flags = test_prev ? VIO_GN_TEST_PREV : 0;
+    if (order == VIO_DEV_ORDER_CHAIN) {
+        // three launches: the sums, the assembly of the chain image and (k_pose_solve_cb, VIO_GN_TEST_PREV) the previous step's test
         mark(1, 0);
-        hipLaunchKernelGGL(k_reduce_cb, dim3(VIO_NPAIR + VIO_NCB + 1 + RED_SB_BLOCKS + ((test_prev && any_prior) ? RED_ERR_BLOCKS : 0), B), dim3(RED_THREADS), 0, s, a);
+        hipLaunchKernelGGL(k_reduce_cb, dim3(reduce_blocks(true, test_prev && any_prior), B), dim3(RED_THREADS), 0, s, a);
         mark(1, 1);
-        a.gn_flags = 4 | (test_prev ? 1 : 0);
+        a.gn_flags = VIO_GN_PRIOR_LATER | (test_prev ? VIO_GN_TEST_PREV : 0);
         mark(3, 0);
         launch_pose_solve_b(a, B, ps_lds, order, s);
         mark(3, 1);
         return;
     }
     mark(1, 0);
-    hipLaunchKernelGGL(k_reduce_b, dim3(VIO_NPAIR + VIO_NCB + 1 + ((test_prev && any_prior) ? RED_ERR_BLOCKS : 0), B), dim3(RED_THREADS), 0, s, a);
+    hipLaunchKernelGGL(k_reduce_b, dim3(reduce_blocks(false, test_prev && any_prior), B), dim3(RED_THREADS), 0, s, a);
     mark(1, 1);
     mark(2, 0);
     launch_assemble_b(a, B, order, s);
     mark(2, 1);
-    a.gn_flags = 4;
+    a.gn_flags = VIO_GN_PRIOR_LATER;
     mark(3, 0);
     launch_pose_solve_b(a, B, ps_lds, order, s);
     mark(3, 1);
 }
 __global__ __launch_bounds__(RED_THREADS) void k_errprior_b(BatchArgs a);
 // Batched LM solve (vio_batch_solve): the kernels of vio_solve's device-driven loop with grid.y = window;
-// every window follows its own LmState (parity -1: `cur` from LmState; gate as in the single-window loop).
-//   what 0: first linearisation + ComputeLambdaInitLM      what 1: one slot = trial (gate 2) + re-linearisation (gate 3)
+// every window follows its own LmState (parity negative: `cur` from LmState; gate as in the single-window loop).  `what`: VIO_BLM_*.
 void vio_launch_batch_lm(const DeviceTables *tabs, int B, int lm_dim, int max_blocks, size_t lin_lds, int lin_threads, int any_prior, size_t ps_lds,
                          int what, int max_iter, int order, hipStream_t s) {
+    // enqueue_linearize of vio_api.cpp outside the GN loop
     auto linearize = [&](int gate) {
-        BatchArgs a{tabs, 0, -1, gate};
+        BatchArgs a{tabs, 0, VIO_CUR_FROM_LM, gate};
         launch_linearize_b(a, lm_dim, max_blocks, B, lin_lds, lin_threads, s);
-        if (order == 1) { hipLaunchKernelGGL(k_reduce_cb, dim3(VIO_NPAIR + VIO_NCB + 1 + RED_SB_BLOCKS, B), dim3(RED_THREADS), 0, s, a); return; }
-        hipLaunchKernelGGL(k_reduce_b, dim3(VIO_NPAIR + VIO_NCB + 1, B), dim3(RED_THREADS), 0, s, a);
+        if (order == VIO_DEV_ORDER_CHAIN) { hipLaunchKernelGGL(k_reduce_cb, dim3(reduce_blocks(true, false), B), dim3(RED_THREADS), 0, s, a); return; }
+        hipLaunchKernelGGL(k_reduce_b, dim3(reduce_blocks(false, false), B), dim3(RED_THREADS), 0, s, a);
         launch_assemble_b(a, B, order, s);
     };
-    if (what == 0) {
-        linearize(0);
-        BatchArgs a{tabs, 0, -1, 0};
+    switch (what) {
+    case VIO_BLM_INIT: {
+        linearize(VIO_GATE_RUN);
+        BatchArgs a{tabs, 0, VIO_CUR_FROM_LM, VIO_GATE_RUN};
         hipLaunchKernelGGL(k_init_lm_b, dim3(1, B), dim3(256), 0, s, a, max_iter);
         return;
     }
-    if (what >= 2) {
-        // vio_solve's loop, batched: what 3 = the first step (k_pose_solve alone); what 2 = one slot: linearise at the step's trial state
-        // (its landmark back-substitution first), sum, assemble (chi2 and gain-ratio terms of the step), then k_pose_solve: verdict, next step
-        BatchArgs a{tabs, 2, -2, 2};
-        if (what == 2) {
+    case VIO_BLM_LOOP_SLOT:
+    case VIO_BLM_LOOP_FIRST: {
+        // vio_solve's loop, batched (enqueue_lm_slot of vio_api.cpp): the first step is k_pose_solve alone; a slot linearises at the step's trial state
+        // (its landmark back-substitution first), sums, assembles (chi2 and gain-ratio terms of the step), then k_pose_solve: verdict, next step
+        BatchArgs a{tabs, VIO_GN_BACKSUB_PREV, VIO_CUR_LM_LOOP, VIO_GATE_UNLESS_STOPPED};
+        if (what == VIO_BLM_LOOP_SLOT) {
             launch_linearize_b(a, lm_dim, max_blocks, B, lin_lds, lin_threads, s);
-            a.gn_flags = 1;
-            if (order == 1) {
-                hipLaunchKernelGGL(k_reduce_cb, dim3(VIO_NPAIR + VIO_NCB + 1 + RED_SB_BLOCKS + (any_prior ? RED_ERR_BLOCKS : 0), B), dim3(RED_THREADS), 0, s, a);
-                a.gn_flags = 4 | 1;
+            a.gn_flags = VIO_GN_TEST_PREV;
+            if (order == VIO_DEV_ORDER_CHAIN) {
+                hipLaunchKernelGGL(k_reduce_cb, dim3(reduce_blocks(true, any_prior), B), dim3(RED_THREADS), 0, s, a);
+                a.gn_flags = VIO_GN_PRIOR_LATER | VIO_GN_TEST_PREV;
                 launch_pose_solve_b(a, B, ps_lds, order, s);
                 return;
             }
-            hipLaunchKernelGGL(k_reduce_b, dim3(VIO_NPAIR + VIO_NCB + 1 + (any_prior ? RED_ERR_BLOCKS : 0), B), dim3(RED_THREADS), 0, s, a);
+            hipLaunchKernelGGL(k_reduce_b, dim3(reduce_blocks(false, any_prior), B), dim3(RED_THREADS), 0, s, a);
             launch_assemble_b(a, B, order, s);
         }
-        a.gn_flags = 4;
+        a.gn_flags = VIO_GN_PRIOR_LATER;
         launch_pose_solve_b(a, B, ps_lds, order, s);
         return;
     }
-    BatchArgs a{tabs, 4, -1, 2};
-    launch_pose_solve_b(a, B, ps_lds, order, s);
-    a.gn_flags = 8;
-    if (lm_dim == 3) hipLaunchKernelGGL(k_backsub_xyz_b, dim3(max_blocks, B), dim3(BS_THREADS), 0, s, a, 0);
-    else hipLaunchKernelGGL(k_backsub_b, dim3(max_blocks, B), dim3(BS_THREADS), 0, s, a, 0);
-    a.gn_flags = 0;
-    if (any_prior) hipLaunchKernelGGL(k_errprior_b, dim3(RED_ERR_BLOCKS, B), dim3(RED_THREADS), 0, s, a);
-    hipLaunchKernelGGL(k_lm_decide_b, dim3(1, B), dim3(256), 0, s, a, 0);
-    linearize(3);
+    case VIO_BLM_CLASSIC_SLOT: {
+        // enqueue_trial (gate VIO_GATE_UNLESS_STOPPED) + enqueue_linearize (gate VIO_GATE_RELINEARIZE) of vio_api.cpp
+        BatchArgs a{tabs, VIO_GN_PRIOR_LATER, VIO_CUR_FROM_LM, VIO_GATE_UNLESS_STOPPED};
+        launch_pose_solve_b(a, B, ps_lds, order, s);
+        a.gn_flags = VIO_GN_FLUSH_BPRIOR;
+        if (lm_dim == 3) hipLaunchKernelGGL(k_backsub_xyz_b, dim3(max_blocks, B), dim3(BS_THREADS), 0, s, a, VIO_BACKSUB_STEP);
+        else hipLaunchKernelGGL(k_backsub_b, dim3(max_blocks, B), dim3(BS_THREADS), 0, s, a, VIO_BACKSUB_STEP);
+        a.gn_flags = 0;
+        if (any_prior) hipLaunchKernelGGL(k_errprior_b, dim3(RED_ERR_BLOCKS, B), dim3(RED_THREADS), 0, s, a);
+        hipLaunchKernelGGL(k_lm_decide_b, dim3(1, B), dim3(256), 0, s, a, VIO_DECIDE_LM);
+        linearize(VIO_GATE_RELINEARIZE);
+        return;
+    }
+    }
 }
 void vio_launch_reduce(const ReduceTables &R, hipStream_t s) {
-    hipLaunchKernelGGL(k_reduce, dim3(VIO_NPAIR + VIO_NCB + 1 + (R.errprior ? RED_ERR_BLOCKS : 0)), dim3(RED_THREADS), 0, s, R);
+    hipLaunchKernelGGL(k_reduce, dim3(reduce_blocks(false, R.errprior != nullptr)), dim3(RED_THREADS), 0, s, R);
 }
 // the three-launch path (chain order, unsharded): k_reduce + k_assemble_c in one launch
 void vio_launch_reduce_assemble(const ReduceTables &R, const DeviceTables &T, hipStream_t s) {
-    hipLaunchKernelGGL(k_reduce_c, dim3(VIO_NPAIR + VIO_NCB + 1 + RED_SB_BLOCKS + (R.errprior ? RED_ERR_BLOCKS : 0)), dim3(RED_THREADS), 0, s, R, T);
+    hipLaunchKernelGGL(k_reduce_c, dim3(reduce_blocks(true, R.errprior != nullptr)), dim3(RED_THREADS), 0, s, R, T);
 }
 // err_prior of a trial step (an LM trial, or a GN step whose test is flushed the classic way): the trial slot, before
 // k_lm_decide reads it
@@ -2359,14 +2375,14 @@ __global__ __launch_bounds__(RED_THREADS) void k_errprior(DeviceTables T) {
     if (d_gated_off(T.lm, T.lm_gate)) return;
     const int trial = 1 - d_cur(T);
     const int row = blockIdx.x * (RED_THREADS / 64) + (threadIdx.x >> 6);
-    if (row < VIO_PRD) d_errprior_row(T.Jtinv, T.bprior + trial * 176, T.errprior + trial * 160, row, threadIdx.x & 63);
+    if (row < VIO_PRD) d_errprior_row(T.Jtinv, T.bprior + trial * VIO_PD_PAD, T.errprior + trial * VIO_PRD_PAD, row, threadIdx.x & 63);
 }
 __global__ __launch_bounds__(RED_THREADS) void k_errprior_b(BatchArgs a) {
     const DeviceTables T = d_batch_tables(a);
     if (!T.has_prior || d_gated_off(T.lm, T.lm_gate)) return;
     const int trial = 1 - d_cur(T);
     const int row = blockIdx.x * (RED_THREADS / 64) + (threadIdx.x >> 6);
-    if (row < VIO_PRD) d_errprior_row(T.Jtinv, T.bprior + trial * 176, T.errprior + trial * 160, row, threadIdx.x & 63);
+    if (row < VIO_PRD) d_errprior_row(T.Jtinv, T.bprior + trial * VIO_PD_PAD, T.errprior + trial * VIO_PRD_PAD, row, threadIdx.x & 63);
 }
 void vio_launch_errprior(const DeviceTables &T, hipStream_t s) { hipLaunchKernelGGL(k_errprior, dim3(RED_ERR_BLOCKS), dim3(RED_THREADS), 0, s, T); }
 // the landmarks of one plan out of another's, at the current slot of both double buffers (MargOldFrame straight after a solve:
@@ -2399,13 +2415,13 @@ void vio_launch_gather_landmarks(const LmState *lm, const double *src, int ns_sr
     hipLaunchKernelGGL(k_gather_landmarks, dim3((ns_dst + 255) / 256), dim3(256), 0, s, lm, src, ns_src, dst, ns_dst, map);
 }
 void vio_launch_assemble(const DeviceTables &T, hipStream_t s) {
-    if (T.solve_order == 1) hipLaunchKernelGGL(k_assemble_c, dim3(ASMC_BLOCKS), dim3(ASMC_THREADS), 0, s, T);
+    if (T.solve_order == VIO_DEV_ORDER_CHAIN) hipLaunchKernelGGL(k_assemble_c, dim3(ASMC_BLOCKS), dim3(ASMC_THREADS), 0, s, T);
     else hipLaunchKernelGGL(k_assemble, dim3(PS_NP + 1), dim3(ASM_THREADS), 0, s, T);
 }
 // lds_bytes: what the Eigen-order kernel needs (the chain kernel's size is its own)
 void vio_launch_pose_solve(const DeviceTables &T, size_t lds_bytes, hipStream_t s) {
-    if (T.solve_order == 1 && (T.gn_flags & 16)) hipLaunchKernelGGL(k_pose_solve_cs, dim3(1), dim3(PS_THREADS), CH_LDS_DOUBLES * sizeof(double), s, T);
-    else if (T.solve_order == 1) hipLaunchKernelGGL(k_pose_solve_c, dim3(1), dim3(PS_THREADS), CH_LDS_DOUBLES * sizeof(double), s, T);
+    if (T.solve_order == VIO_DEV_ORDER_CHAIN && (T.gn_flags & VIO_GN_CHAIN_SPLIT)) hipLaunchKernelGGL(k_pose_solve_cs, dim3(1), dim3(PS_THREADS), CH_LDS_DOUBLES * sizeof(double), s, T);
+    else if (T.solve_order == VIO_DEV_ORDER_CHAIN) hipLaunchKernelGGL(k_pose_solve_c, dim3(1), dim3(PS_THREADS), CH_LDS_DOUBLES * sizeof(double), s, T);
     else hipLaunchKernelGGL(k_pose_solve, dim3(1), dim3(PS_THREADS), lds_bytes, s, T);
 }
 // test entry of the chain solve: one image, one lambda (tests/test_gpu_chain_solve.py)
@@ -2480,27 +2496,24 @@ int lin_lds_doubles_host(int G, int K, int nb, int use_ext) {
     return lin_lds_doubles(G, K, nb, use_ext);
 }
 int xyz_lds_doubles_host(int G, int K) { return xyz_lds_doubles(G, K); }
+// the dynamic LDS the kernels may ask for; every entry is tried, -1 if any failed
 int vio_set_kernel_attributes() {
-    hipError_t e1 = hipFuncSetAttribute((const void *)k_linearize, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    hipError_t e2 = hipFuncSetAttribute((const void *)k_pose_solve, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024);
-    if (hipFuncSetAttribute((const void *)k_linearize_b, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_linearize_h, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_linearize_hb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_linearize_g, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_linearize_gh, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_linearize_gb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_linearize_ghb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_pose_solve_b, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_pose_solve_c, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_pose_solve_cb, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_pose_solve_cs, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return -1;
-    if (hipFuncSetAttribute((const void *)k_chain_pre, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return -1;
+    constexpr int LIN_LDS_MAX = 160 * 1024 - 512;       // the linearise kernels: a CU's 160 KiB less their static LDS
+    constexpr int SOLVE_LDS_MAX = 156 * 1024;           // the solve kernels
+    const struct { const void *fn; int bytes; } attrs[] = {
+        {(const void *)k_linearize, LIN_LDS_MAX}, {(const void *)k_linearize_b, LIN_LDS_MAX}, {(const void *)k_linearize_h, LIN_LDS_MAX},
+        {(const void *)k_linearize_hb, LIN_LDS_MAX}, {(const void *)k_linearize_g, LIN_LDS_MAX}, {(const void *)k_linearize_gh, LIN_LDS_MAX},
+        {(const void *)k_linearize_gb, LIN_LDS_MAX}, {(const void *)k_linearize_ghb, LIN_LDS_MAX},
+        {(const void *)k_linearize_xyz, LIN_LDS_MAX}, {(const void *)k_linearize_xyz_b, LIN_LDS_MAX}, {(const void *)k_linearize_xyz_h, LIN_LDS_MAX},
+        {(const void *)k_linearize_xyz_hb, LIN_LDS_MAX},
+        {(const void *)k_pose_solve, SOLVE_LDS_MAX}, {(const void *)k_pose_solve_b, SOLVE_LDS_MAX}, {(const void *)k_pose_solve_c, SOLVE_LDS_MAX},
+        {(const void *)k_pose_solve_cb, SOLVE_LDS_MAX}, {(const void *)k_pose_solve_cs, SOLVE_LDS_MAX}, {(const void *)k_chain_pre, SOLVE_LDS_MAX},
 #ifdef VIO_DEBUG_ENTRY_POINTS
-    if (hipFuncSetAttribute((const void *)k_chain_solve_test, hipFuncAttributeMaxDynamicSharedMemorySize, 156 * 1024) != hipSuccess) return -1;
+        {(const void *)k_chain_solve_test, SOLVE_LDS_MAX},
 #endif
-    hipError_t e3 = hipFuncSetAttribute((const void *)k_linearize_xyz, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    if (e3 == hipSuccess) e3 = hipFuncSetAttribute((const void *)k_linearize_xyz_b, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    if (e3 == hipSuccess) e3 = hipFuncSetAttribute((const void *)k_linearize_xyz_h, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    if (e3 == hipSuccess) e3 = hipFuncSetAttribute((const void *)k_linearize_xyz_hb, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024 - 512);
-    return (e1 == hipSuccess && e2 == hipSuccess && e3 == hipSuccess) ? 0 : -1;
+    };
+    int rc = 0;
+    for (const auto &a : attrs)
+        if (hipFuncSetAttribute(a.fn, hipFuncAttributeMaxDynamicSharedMemorySize, a.bytes) != hipSuccess) rc = -1;
+    return rc;
 }

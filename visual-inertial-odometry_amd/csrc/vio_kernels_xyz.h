@@ -40,14 +40,14 @@ __host__ __device__ inline int xyz_tiles(int K) { const int ts = (6 * K + 15) >>
 // tile is formed in three parts over a third of the landmarks each (83 / 83 / 83 / 63) and the combine phase adds the parts in order.
 __host__ __device__ inline int xyz_split(int G, int K) {
     const int ts = (6 * K + 15) >> 4, nts = ts * (ts + 1) / 2;
-    const int aux = G * K * 9, head = 3 * G * K + 12 * K + 12 + 176 + 12 * G;
+    const int aux = G * K * 9, head = 3 * G * K + 12 * K + 12 + VIO_PD_PAD + 12 * G;
     const int room = aux > head ? aux : head;
     return ((xyz_ntd(K) + 3 * nts) * 256 + 6 * K * LIN_VS <= room && G >= 64) ? 3 : 1;      // (items of the half-width kernel stay whole: 12 chains on 8 waves wrap)
 }
 __host__ __device__ inline int xyz_lds_doubles(int G, int K) {
     const int ts_ = (6 * K + 15) >> 4, nts_ = ts_ * (ts_ + 1) / 2;
     int aux = G * K * 9, part = (xyz_ntd(K) + xyz_split(G, K) * nts_) * 256 + 6 * K * LIN_VS;
-    int head = 3 * G * K + 12 * K + 12 + 176 + 12 * G;      // GN head: W^T dx per observation, the old camera maps, dx, (H_ll, b_l, point) per landmark
+    int head = 3 * G * K + 12 * K + 12 + VIO_PD_PAD + 12 * G;      // GN head: W^T dx per observation, the old camera maps, dx, (H_ll, b_l, point) per landmark
     int shared = aux > part ? aux : part;
     if (head > shared) shared = head;
     shared = (shared + 1) & ~1;
@@ -246,8 +246,8 @@ template <int NT> __device__ __forceinline__ void d_linearize_xyz_body(const Dev
     const int tid = threadIdx.x;
     const int b = blockIdx.x;
     if (d_gated_off(T.lm, T.lm_gate)) return;
-    // GN mode (gn_flags bit 1), as in k_linearize: the previous step's b_prior' rows and landmark back-substitution come first
-    const bool owe = d_step_owed(T, 2), owe_prior = owe && T.has_prior;
+    // GN mode (VIO_GN_BACKSUB_PREV, gn_flags bit 1), as in k_linearize: the previous step's b_prior' rows and landmark back-substitution come first
+    const bool owe = d_step_owed(T, VIO_GN_BACKSUB_PREV), owe_prior = owe && T.has_prior;
     if (b >= T.n_items) {
         if (owe_prior && (tid >> 6) == NT / 64 - 1) { const int c = d_cur(T); d_bprior_rows(T, c ^ 1, c, b, T.n_step_blocks, tid & 63); }
         d_imu_item<NT>(T, b - T.n_items, dyn_smem);
@@ -307,13 +307,13 @@ template <int NT> __device__ __forceinline__ void d_linearize_xyz_body(const Dev
         const double *sto = T.state + (cur ^ 1) * STATE_STRIDE;
         const double *xyzo = T.invd + (size_t)(cur ^ 1) * 3 * T.Ns + it.lm_base;
         const double *lw = T.lw + lw_r + it.lw_base;
-        double *sHb = sDx + 176;                           // 12 per landmark: H_ll (6), b_l (3), the old point
+        double *sHb = sDx + VIO_PD_PAD;                          // 12 per landmark: H_ll (6), b_l (3), the old point
         for (int e = tid; e < 12 * G; e += NT) {
             const int q = e / G, g = e - q * G;
             sHb[12 * g + q] = q < 9 ? lw[e] : xyzo[(size_t)(q - 9) * T.Ns + g];
         }
         const double lambda_lm = T.lm->lambda;
-        if (tid < 176) sDx[tid] = T.dx[tid];
+        if (tid < VIO_PD_PAD) sDx[tid] = T.dx[tid];
         if (tid >= 192 && tid < 192 + K) {
             const int k = tid - 192;
             double ric[9], o[12];
@@ -675,14 +675,14 @@ __device__ __forceinline__ void d_backsub_xyz_body(const DeviceTables &T, int mo
     const LmState *lm = T.lm;
     if (d_gated_off(lm, T.lm_gate)) return;
     const int cur = d_cur(T);
-    const int which = (mode == 1) ? cur : (cur ^ 1);
-    if ((T.gn_flags & 8) && T.has_prior && (lane >> 6) == 1) d_bprior_rows(T, cur, cur ^ 1, b, T.n_step_blocks, lane & 63);
+    const int which = (mode == VIO_BACKSUB_CHI_CUR) ? cur : (cur ^ 1);
+    if ((T.gn_flags & VIO_GN_FLUSH_BPRIOR) && T.has_prior && (lane >> 6) == 1) d_bprior_rows(T, cur, cur ^ 1, b, T.n_step_blocks, lane & 63);
     if (b >= T.n_items) { d_backsub_imu_block(T, mode, which, b, lane); return; }
     __shared__ double sFr[VIO_NF * 12];       // camera maps at the state whose chi2 is wanted
-    __shared__ double sFrO[VIO_NF * 12 + 12]; // mode 0: the maps (and ric, tic) at the state the step was linearised at
-    __shared__ double sDxp[176];
+    __shared__ double sFrO[VIO_NF * 12 + 12]; // VIO_BACKSUB_STEP: the maps (and ric, tic) at the state the step was linearised at
+    __shared__ double sDxp[VIO_PD_PAD];
     __shared__ ItemDesc sIt;
-    if (mode == 0) { sDxp[lane] = T.dx[lane]; if (lane + BS_THREADS < 176) sDxp[lane + BS_THREADS] = T.dx[lane + BS_THREADS]; }
+    if (mode == VIO_BACKSUB_STEP) { sDxp[lane] = T.dx[lane]; if (lane + BS_THREADS < VIO_PD_PAD) sDxp[lane + BS_THREADS] = T.dx[lane + BS_THREADS]; }
     if (lane < (int)(sizeof(ItemDesc) / 4)) ((int32_t *)&sIt)[lane] = ((const int32_t *)(T.items + b))[lane];
     __syncthreads();
     const ItemDesc &it = sIt;
@@ -694,7 +694,7 @@ __device__ __forceinline__ void d_backsub_xyz_body(const DeviceTables &T, int mo
         d_xyz_frame(st, it.cam_block[lane] - 1, ric, o);
 #pragma unroll
         for (int k = 0; k < 12; ++k) sFr[12 * lane + k] = o[k];
-    } else if (mode == 0 && lane >= 64 && lane < 64 + K) {
+    } else if (mode == VIO_BACKSUB_STEP && lane >= 64 && lane < 64 + K) {
         const int k = lane - 64;
         const double *sto = T.state + cur * STATE_STRIDE;
         double ric[9], o[12];
@@ -717,7 +717,7 @@ __device__ __forceinline__ void d_backsub_xyz_body(const DeviceTables &T, int mo
         const size_t li = (size_t)it.lm_base + g;
         const size_t Ns = (size_t)T.Ns;
         double pw[3] = {T.invd[(size_t)cur * 3 * Ns + li], T.invd[(size_t)cur * 3 * Ns + Ns + li], T.invd[(size_t)cur * 3 * Ns + 2 * Ns + li]};
-        if (mode == 0) {
+        if (mode == VIO_BACKSUB_STEP) {
             // W^T dx_pose with W formed again from the linearisation state (k_linearize_xyz keeps H_ll and b_l only);
             // summed per observation, then over the observations: the association of the GN head of k_linearize_xyz
             const double *lw = T.lw + it.lw_base;
@@ -764,7 +764,7 @@ __device__ __forceinline__ void d_backsub_xyz_body(const DeviceTables &T, int mo
         double c = 0.0, sc = 0.0;
 #pragma unroll
         for (int w = 0; w < BS_THREADS / 64; ++w) { c += sSum[2 * w]; sc += sSum[2 * w + 1]; }
-        double *part = (mode == 1) ? T.chi_part : T.step_part;
+        double *part = (mode == VIO_BACKSUB_CHI_CUR) ? T.chi_part : T.step_part;
         part[2 * b + STEP_CHI] = c; part[2 * b + STEP_SCALE] = sc;
     }
 }

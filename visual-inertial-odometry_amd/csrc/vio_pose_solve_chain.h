@@ -218,13 +218,13 @@ __device__ __forceinline__ void d_assemble_chain_body(const DeviceTables &T) {
     }
     // the last workgroup: right-hand sides + the step test of the PREVIOUS iteration (see d_assemble_body)
     __shared__ double sSum[8];
-    const bool test_prev = d_step_owed(T, 1);
+    const bool test_prev = d_step_owed(T, VIO_GN_TEST_PREV);
     const int rset = d_set_r(T);
     double p_dx = 0.0, p_bf = 0.0, p_er = 0.0, p_lambda = 0.0, p_chi = 0.0, p_step = 0.0, p_lmchi = 0.0, p_imu[10];
     if (test_prev) {
         p_lambda = T.lm->lambda;
-        if (t < VIO_PD) { p_dx = T.dx[t]; p_bf = T.bfull[rset * 176 + t]; }
-        if (T.has_prior && t < VIO_PRD) p_er = T.errprior[cur * 160 + t];
+        if (t < VIO_PD) { p_dx = T.dx[t]; p_bf = T.bfull[rset * VIO_PD_PAD + t]; }
+        if (T.has_prior && t < VIO_PRD) p_er = T.errprior[cur * VIO_PRD_PAD + t];
         if (t == 0) {
             p_chi = d_vis(T, VIS_CHI); p_step = d_vis(T, VIS_STEP + 1); p_lmchi = T.lm->chi;
 #pragma unroll
@@ -248,7 +248,7 @@ __device__ __forceinline__ void d_assemble_chain_body(const DeviceTables &T) {
             const double scale = 0.5 * (p_step + sp) + 1e-6;
             lm->chi_try = tempChi;
             lm->scale = scale;
-            if (T.cur_hint != -2) {
+            if (T.cur_hint != VIO_CUR_LM_LOOP) {
                 lm->rho = (p_lmchi - tempChi) / scale;
                 lm->trials += 1;
                 lm->chi = tempChi;
@@ -302,7 +302,7 @@ __device__ void d_fused_vec(const DeviceTables &T, int P, int tid, double bd, do
     const int i = cam_to_full(6 * P + tid);
     const double bred = bd - bc;
     T.bs[i] = bred + extra;
-    T.bfull[wset * 176 + i] = bd + extra;
+    T.bfull[wset * VIO_PD_PAD + i] = bd + extra;
     T.diagfull[i] = dg + dgrest;
     T.Pg[wset * CH_SET_STRIDE + CH_OFF_Y + ch_dim(i)] = bred + extra;
 }
@@ -320,7 +320,7 @@ __device__ void d_fused_sb_row(const DeviceTables &T, int blk, int tid) {
     if (t == i) {
         const double extra = d_rhs_rest(T, valid, i, cur);
         T.bs[i] = extra;
-        T.bfull[wset * 176 + i] = extra;
+        T.bfull[wset * VIO_PD_PAD + i] = extra;
         T.diagfull[i] = d_hs_rest(T, valid, i, i);
         T.Pg[wset * CH_SET_STRIDE + CH_OFF_Y + ch_dim(i)] = extra;
     }
@@ -328,11 +328,11 @@ __device__ void d_fused_sb_row(const DeviceTables &T, int blk, int tid) {
 __global__ __launch_bounds__(RED_THREADS) void k_reduce_c(ReduceTables R, DeviceTables T) { d_reduce_body<true>(R, &T); }
 __global__ __launch_bounds__(RED_THREADS) void k_reduce_cb(BatchArgs a) {
     const DeviceTables T = d_batch_tables(a);
-    const bool test_prev = (a.gn_flags & 1) != 0, err_prev = test_prev && T.has_prior;
+    const bool test_prev = (a.gn_flags & VIO_GN_TEST_PREV) != 0, err_prev = test_prev && T.has_prior;
     if ((int)blockIdx.x >= VIO_NPAIR + VIO_NCB + 1 + RED_SB_BLOCKS && !err_prev) return;
-    const int loop = T.cur_hint == -2, cur = loop ? 0 : T.cur_hint;
+    const int loop = T.cur_hint == VIO_CUR_LM_LOOP, cur = loop ? 0 : T.cur_hint;
     ReduceTables R{T.list_off, T.list, T.slab, T.vis, test_prev ? T.step_part : nullptr, T.n_items, a.gate, T.lm,
-                   err_prev ? T.Jtinv : nullptr, err_prev ? T.bprior + cur * 176 : nullptr, err_prev ? T.errprior + cur * 160 : nullptr, loop};
+                   err_prev ? T.Jtinv : nullptr, err_prev ? T.bprior + cur * VIO_PD_PAD : nullptr, err_prev ? T.errprior + cur * VIO_PRD_PAD : nullptr, loop};
     d_reduce_body<true>(R, &T);
 }
 __global__ __launch_bounds__(ASMC_THREADS) void k_assemble_cb(BatchArgs a) { const DeviceTables T = d_batch_tables(a); d_assemble_chain_body(T); }
@@ -342,9 +342,9 @@ __global__ __launch_bounds__(ASMC_THREADS) void k_assemble_cb(BatchArgs a) { con
 // stepwise prior update) around ch_factor_solve.
 // ---------------------------------------------------------------------------------------------------------
 #define CH_OFF_DX CH_LDS_CORE                       // 176 solution in natural order
-#define CH_OFF_R (CH_OFF_DX + 176)                  // 112 rotations
+#define CH_OFF_R (CH_OFF_DX + VIO_PD_PAD)           // 112 rotations
 #define CH_OFF_B (CH_OFF_R + 112)                   // 176 trial b_prior
-#define CH_OFF_STATE (CH_OFF_B + 176)               // 184
+#define CH_OFF_STATE (CH_OFF_B + VIO_PD_PAD)        // 184
 #define CH_LDS_DOUBLES (CH_OFF_STATE + 184)         // 17448
 template <bool SPLIT>
 __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
@@ -356,7 +356,7 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
     LmState *lm = T.lm;
     __shared__ LmRegs sLm;
     if (d_gated_off(lm, T.lm_gate)) return;
-    const bool lm_loop = T.cur_hint == -2;
+    const bool lm_loop = T.cur_hint == VIO_CUR_LM_LOOP;
     int cur = lm_loop ? 0 : d_cur(T);
     double lambda = lm_loop ? 0.0 : lm->lambda;
     const int n = PS_N;
@@ -367,14 +367,14 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
 #define CH_OUT(slot) do { } while (0)
 #endif
     // the image k_assemble_c wrote (vio_solve's loop: the set of the trial state first; a rejected step solves the other set again)
-    // SPLIT (the GN loop, gn_flags bit 4): the speed-bias chain of this system was eliminated under the linearisation (d_chain_pre_item, a
+    // SPLIT (the GN loop, VIO_GN_CHAIN_SPLIT (gn_flags bit 4)): the speed-bias chain of this system was eliminated under the linearisation (d_chain_pre_item, a
     // workgroup of k_linearize's grid: it depends on the IMU factors, the prior and lambda only); what it left — L_SC, L_SO, M_e, the pivots,
     // w_e and the tile mask, at their LDS offsets in T.cfi — comes in with the camera block and the camera right-hand side of the image
     int set = lm_loop ? (lm->sys ^ lm->pending) : 0;
     const double *cfi = SPLIT ? T.cfi : nullptr;
     double xs0 = 0.0, xs1 = 0.0, xd = 0.0, xy = 0.0, xe = 0.0;
 #ifndef CH_NO_EARLY_START
-    const bool early = !SPLIT && !lm_loop && !(T.gn_flags & 32);
+    const bool early = !SPLIT && !lm_loop && !(T.gn_flags & VIO_GN_NO_EARLY_START);
 #else
     const bool early = false;
 #endif
@@ -423,7 +423,7 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
             for (int q = 0; q < 3; ++q) vc[q] = src2[min((CH_OFF_CC + 1) / 2 + wt + 896 * q, CH_PACKED / 2 - 1)];
             const double vc0 = img[CH_OFF_CC];                          // (the block starts at an odd offset: its first element apart)
             double st[3] = {0.0, 0.0, 0.0}, er[3] = {0.0, 0.0, 0.0};
-            const bool test_here = uwave == 2 && d_step_owed(T, 1);
+            const bool test_here = uwave == 2 && d_step_owed(T, VIO_GN_TEST_PREV);
             double tv[6] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, ichi = 0.0;
             if (test_here) {
                 // everything the test reads, requested with the image — the IMU edges' chi2 as ONE load (lane = edge): one at a time behind
@@ -436,7 +436,7 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
                 for (int k = 0; k < 3; ++k) st[k] = T.state[cur * STATE_STRIDE + min(lane + 64 * k, STATE_STRIDE - 1)];
                 if (test_here && T.has_prior) {
 #pragma unroll
-                    for (int k = 0; k < 3; ++k) if (lane + 64 * k < VIO_PRD) er[k] = T.errprior[cur * 160 + lane + 64 * k];
+                    for (int k = 0; k < 3; ++k) if (lane + 64 * k < VIO_PRD) er[k] = T.errprior[cur * VIO_PRD_PAD + lane + 64 * k];
                 }
             }
             // under the latency: the 16 x 16 identity, the camera part's pivots = 1
@@ -522,16 +522,16 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
         if (pass == 0) {
             double stv = (tid < STATE_STRIDE) ? T.state[cur * STATE_STRIDE + tid] : 0.0;
             const double stv1 = (lm_loop && tid < STATE_STRIDE) ? T.state[STATE_STRIDE + tid] : 0.0;
-            // Three-launch path (gn_flags bit 0): the test of the PREVIOUS step, which k_assemble's last workgroup runs in the four-launch
+            // Three-launch path (VIO_GN_TEST_PREV, gn_flags bit 0): the test of the PREVIOUS step, which k_assemble's last workgroup runs in the four-launch
             // path, is formed here: chi2 of the state that step led to (this linearisation's, summed by k_reduce_c, + IMU + ||err_prior||)
             // and the gain ratio's denominator (the landmark part from k_reduce_c, the pose part left by the previous k_pose_solve_c
             // in sp_part).  The sums are k_assemble's: three wave partials added in wave order.
-            const bool test_here = d_step_owed(T, 1);
+            const bool test_here = d_step_owed(T, VIO_GN_TEST_PREV);
             double t_chi = 0.0, t_step = 0.0, t_lmchi = 0.0, t_imu = 0.0, t_sp = 0.0;
             if (test_here) {
                 const int lc = lm_loop ? (lm->cur ^ lm->pending) : cur;          // the copy this linearisation was made at
                 double e2 = 0.0;
-                if (T.has_prior && tid < VIO_PRD) { const double er = T.errprior[lc * 160 + tid]; e2 = er * er; }
+                if (T.has_prior && tid < VIO_PRD) { const double er = T.errprior[lc * VIO_PRD_PAD + tid]; e2 = er * er; }
                 if (tid < 192) { const double w = d_wave_sum_to_lane63(e2); if (lane == 63) sB[tid >> 6] = w; }
                 if (uwave == 0) {
                     // (the IMU edges' chi2 as ONE load, lane = edge: one at a time behind its valid bit they are ten dependent round trips)
@@ -636,7 +636,7 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
     // (UpdateStates, problem.cc:456-463; vertex_pose.cc:7-19) and their rotations while the speed-bias owners finish their sums, and the
     // fourteen waves that do not walk the chains form the pair table of the trial states meanwhile (in the camera tiles' space, free once
     // the camera part is solved).  The stepwise path (prior update here) keeps k_pose_solve's serial tail.
-    const bool prior_here = T.has_prior && !(T.gn_flags & 4);
+    const bool prior_here = T.has_prior && !(T.gn_flags & VIO_GN_PRIOR_LATER);
     const int lm_dim = T.lm_dim;
     double *pairtab_trial = T.pairtab + trial * PAIRTAB_STRIDE;
     double *pw = P + CH_OFF_CC;                                 // trial ext + poses at [0, 84), rotations at [96, 204)
@@ -680,7 +680,7 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
         // sum_i dx_i (lambda dx_i + b_i), b_ of the system just solved: three wave partials, as k_assemble's step test sums them
         const int i = tid - 192;
         const double dxi = (i < n) ? sX[ch_dim(min(i, n - 1))] : 0.0;
-        const double bi = early ? bf_early : ((i < n) ? T.bfull[set * 176 + i] : 0.0);
+        const double bi = early ? bf_early : ((i < n) ? T.bfull[set * VIO_PD_PAD + i] : 0.0);
         const double w = d_wave_sum_to_lane63((i < n) ? dxi * (lambda * dxi + bi) : 0.0);
         if (lane == 63) T.sp_part[i >> 6] = w;
     }
@@ -722,14 +722,14 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
                     const int j = lane + 64 * q;
                     hp[r][q] = (i < n && j < n) ? T.Hprior[i * n + j] : 0.0;
                 }
-                bp[r] = (i < n) ? T.bprior[cur * 176 + i] : 0.0;
+                bp[r] = (i < n) ? T.bprior[cur * VIO_PD_PAD + i] : 0.0;
             }
             const double x0 = sDx[lane], x1 = sDx[lane + 64], x2 = (lane + 128 < n) ? sDx[lane + 128] : 0.0;
 #pragma unroll
             for (int r = 0; r < PS_PRIOR_ROWS; ++r) {
                 const int i = (uwave - 2) + 14 * r;
                 const double v = d_bprior_dot(hp[r][0], hp[r][1], hp[r][2], x0, x1, x2, bp[r]);
-                if (lane == 63 && i < n) { sB[i] = v; T.bprior[trial * 176 + i] = v; }
+                if (lane == 63 && i < n) { sB[i] = v; T.bprior[trial * VIO_PD_PAD + i] = v; }
             }
         }
         __syncthreads();
@@ -750,7 +750,7 @@ __device__ __forceinline__ void d_pose_solve_chain_body(const DeviceTables &T) {
             for (int r = 0; r < PS_JT_ROWS; ++r) {
                 const int i = (uwave - 2) + 14 * r;
                 const double s = d_errprior_dot(jp[r][0], jp[r][1], jp[r][2], y0, y1, y2);
-                if (lane == 63 && i < VIO_PRD) T.errprior[trial * 160 + i] = s;
+                if (lane == 63 && i < VIO_PRD) T.errprior[trial * VIO_PRD_PAD + i] = s;
             }
         }
     }
@@ -793,7 +793,7 @@ __device__ __forceinline__ void ch_chain_pre_init(double *P, int tid) {
     else if (tid >= 640 && tid < 640 + CH_YC) P[CH_OFF_D + tid - 640] = 1.0;
     for (int i = tid; i < CH_NS * CH_S9SZ; i += PS_THREADS) P[CH_OFF_SM + i] = 0.0;
 }
-// ---- the chain workgroup of k_linearize's grid (GN loop, gn_flags bit 4; blockIdx 0) ------------------------------------------------
+// ---- the chain workgroup of k_linearize's grid (GN loop, VIO_GN_CHAIN_SPLIT; blockIdx 0) ------------------------------------------------
 // It forms the ten IMU items itself (nobody to wait for: the IMU workgroups that follow the items in the other paths are not launched),
 // writes them to imu_out for k_reduce_c, assembles the chain's blocks from them and the prior, eliminates the chain, stores the factors.
 // Same arithmetic as d_imu_item + d_hs_rest / d_rhs_rest + the chain phase of k_pose_solve_c, operation for operation:
@@ -813,7 +813,7 @@ __device__ __forceinline__ void ch_chain_pre_init(double *P, int tid) {
 #define CPI_JTI(k) ((k) < 9 ? CH_OFF_CC + 450 * (k) : CH_LDS_CORE)       // J^T Info [30 x 15] of edge k (the camera tiles' place; edge 9 behind the core)
 #define CPI_VEC (CH_LDS_CORE + 450)             // per edge 64: r (15) | Info r (15, at 16) | g (30, at 32)
 #define CPI_BP (CPI_VEC + 640)                  // b_prior of the linearisation state (176)
-#define CPI_PN (CPI_BP + 176)                   // the prior's list sizes (2 ints)
+#define CPI_PN (CPI_BP + VIO_PD_PAD)                  // the prior's list sizes (2 ints)
 #define CPI_END (CPI_PN + 2)
 #define CPI_NTILES (55 + 10 + 11)               // SC, SO, SD tiles of the chain image
 #define CPI_FLAGS (CPI_NTILES + 99)             // prior_flags: tiles, then speed-bias rows
@@ -843,7 +843,7 @@ __device__ __forceinline__ void d_chain_pre_item(const DeviceTables &T) {
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cur = d_cur(T);
     const int valid = d_imu_mask(T);
-    const bool owe_prior = d_step_owed(T, 2) && T.has_prior;
+    const bool owe_prior = d_step_owed(T, VIO_GN_BACKSUB_PREV) && T.has_prior;
     const double lambda = T.lm->lambda;
 #ifdef VIO_STAMPS
     // diagnostic build: phase stamps of this workgroup behind the items' and IMU workgroups' slots (tools/diag_chain_pre_stamps.py)
@@ -871,7 +871,7 @@ __device__ __forceinline__ void d_chain_pre_item(const DeviceTables &T) {
             // of H_prior holds anything)
             if (tid >= 128 && tid < 128 + 99) {
                 const int r = tid - 128;
-                bpv = T.bprior[(owe_prior ? cur ^ 1 : cur) * 176 + 12 + 15 * (r / 9) + r % 9];
+                bpv = T.bprior[(owe_prior ? cur ^ 1 : cur) * VIO_PD_PAD + 12 + 15 * (r / 9) + r % 9];
                 bp_skip = owe_prior && T.prior_flags[CPI_NTILES + r] != 0;        // (a listed row: its dot product is the value)
             }
             if (owe_prior && wave < 15) prow = T.prior_list[2 + min(wave, 98)];         // (wave w: listed rows w, w + 15, ...: the first one now)
@@ -908,7 +908,7 @@ __device__ __forceinline__ void d_chain_pre_item(const DeviceTables &T) {
                 const int r = q == wave ? prow : T.prior_list[2 + q];
                 const int i = 12 + 15 * (r / 9) + r % 9;
                 const double *hr = T.Hprior + (size_t)i * VIO_PD;
-                const double v = d_bprior_dot(hr[lane], hr[lane + 64], in2 ? hr[lane + 128] : 0.0, x0, x1, x2, T.bprior[(cur ^ 1) * 176 + i]);
+                const double v = d_bprior_dot(hr[lane], hr[lane + 64], in2 ? hr[lane + 128] : 0.0, x0, x1, x2, T.bprior[(cur ^ 1) * VIO_PD_PAD + i]);
                 if (lane == 63) P[CPI_BP + i] = v;
             }
         }

@@ -154,6 +154,77 @@ struct LmState {
     double lambda_trace[128];
 };
 
+// ---- The protocol between the launches of the GN / LM loop ----
+// k_linearize*, k_reduce*, k_assemble*, k_pose_solve*, k_backsub*, k_errprior* and k_lm_decide* agree through the integers below, which
+// travel in DeviceTables (gn_flags, cur_hint, lm_gate, solve_order), BatchArgs (gn_flags, parity, gate) and ReduceTables (gate).
+
+// Padded lengths of the pose-dimension vectors.  bprior, perm and bfull hold two slots (the current / trial copy, resp. the two sets
+// of vio_solve's loop) VIO_PD_PAD apart, errprior two slots VIO_PRD_PAD apart; dx, bs, diagfull and rank are VIO_PD_PAD long.
+#define VIO_PD_PAD 176           // VIO_PD padded to 11 block rows of 16 (identity pivots behind the 171)
+#define VIO_PRD_PAD 160          // slot stride of errprior (VIO_PRD padded)
+static_assert(VIO_PD_PAD >= VIO_PD && VIO_PD_PAD % 16 == 0 && VIO_PD_PAD - VIO_PD < 16, "VIO_PD_PAD: VIO_PD rounded up to block rows of 16");
+static_assert(VIO_PRD_PAD >= VIO_PRD, "VIO_PRD_PAD: a slot of errprior holds VIO_PRD entries");
+
+// DeviceTables::gn_flags / BatchArgs::gn_flags.  Each bit is read by the kernels named with it and means nothing to the others, so a
+// launch sequence sets the field anew in front of each launch.  "The previous step" is the one the last k_pose_solve* took.
+enum {
+    VIO_GN_TEST_PREV = 1,        // the previous step's test runs in this launch: k_assemble* (four launches), the head of k_pose_solve_c*
+                                 // (three launches); for k_reduce_b / k_reduce_cb: sum that step's gain-ratio partials (and err_prior')
+    VIO_GN_BACKSUB_PREV = 2,     // k_linearize*: apply the previous step's landmark back-substitution and its b_prior' rows first
+    VIO_GN_PRIOR_LATER = 4,      // k_pose_solve*: this step's prior update is left to the launches that follow (b_prior' to the next
+                                 // k_linearize* or to k_backsub*, err_prior' to the next k_reduce* or to k_errprior*)
+    VIO_GN_FLUSH_BPRIOR = 8,     // k_backsub*: the step is flushed the classic way, form its b_prior' here
+    VIO_GN_CHAIN_SPLIT = 16,     // k_linearize (GN loop): the grid's first workgroup eliminates the speed-bias chain (and forms the IMU items:
+                                 // no IMU workgroups follow the items); vio_launch_pose_solve: k_pose_solve_cs, which starts behind that chain
+    VIO_GN_NO_EARLY_START = 32   // k_pose_solve_c (diagnostic, VIO_NO_EARLY_START): the prologue with its barriers instead of the early start
+};
+static_assert((VIO_GN_TEST_PREV | VIO_GN_BACKSUB_PREV | VIO_GN_PRIOR_LATER | VIO_GN_FLUSH_BPRIOR | VIO_GN_CHAIN_SPLIT | VIO_GN_NO_EARLY_START) == 63 &&
+              VIO_GN_TEST_PREV + VIO_GN_BACKSUB_PREV + VIO_GN_PRIOR_LATER + VIO_GN_FLUSH_BPRIOR + VIO_GN_CHAIN_SPLIT + VIO_GN_NO_EARLY_START == 63,
+              "the gn_flags bits are six distinct powers of two");
+
+// DeviceTables::cur_hint, and BatchArgs::parity where it is negative.  >= 0: LmState.cur as the host tracks it through GN iterations (the
+// kernels skip the dependent load; a batched launch flips it by the parity 0 / 1 of the iteration count).
+enum {
+    VIO_CUR_FROM_LM = -1,        // read lm->cur (d_cur)
+    VIO_CUR_LM_LOOP = -2         // vio_solve's loop: the copy to linearise at is lm->cur ^ lm->pending, the sets are lm->sys's (d_cur, d_set_r,
+                                 // d_set_w), and VIO_GN_TEST_PREV / VIO_GN_BACKSUB_PREV count only while lm->pending (d_step_owed)
+};
+
+// DeviceTables::lm_gate / BatchArgs::gate / ReduceTables::gate: the device-driven LM loop enqueues launches ahead, and a gated kernel
+// returns at once when it is not its turn.  d_gated_off tests bit 0 for "needs lm->need_linearize": the values cannot be renumbered.
+enum {
+    VIO_GATE_RUN = 0,            // always run
+    VIO_GATE_UNLESS_STOPPED = 2, // skip if lm->stop (a trial, a slot of vio_solve's loop)
+    VIO_GATE_RELINEARIZE = 3     // skip unless lm->need_linearize && !lm->stop (the classic loop's re-linearisation)
+};
+static_assert(!(VIO_GATE_UNLESS_STOPPED & 1) && (VIO_GATE_RELINEARIZE & 1), "d_gated_off: bit 0 of the gate asks for lm->need_linearize");
+
+// DeviceTables::solve_order on the device side (vio_backend.h's vio_solve_order; vio_api.cpp asserts that the two agree)
+enum {
+    VIO_DEV_ORDER_EIGEN = 0,     // Eigen's pivot order: k_assemble / k_pose_solve
+    VIO_DEV_ORDER_CHAIN = 1      // the static chain order: k_assemble_c / k_pose_solve_c (vio_pose_solve_chain.h)
+};
+
+// `what` of vio_launch_batch_lm: the stages of a batched LM solve (vio_batch_solve), each the batched form of a single-window sequence
+enum {
+    VIO_BLM_INIT = 0,            // the initial linearisation + k_init_lm (ComputeLambdaInitLM)
+    VIO_BLM_CLASSIC_SLOT = 1,    // VIO_LM_CLASSIC: one trial (k_pose_solve, k_backsub, k_errprior, k_lm_decide) + the gated re-linearisation
+    VIO_BLM_LOOP_SLOT = 2,       // vio_solve's loop: linearise at the pending step's trial state, sum, assemble, k_pose_solve (verdict, next step)
+    VIO_BLM_LOOP_FIRST = 3       // vio_solve's loop: the first step, k_pose_solve alone on the initial linearisation
+};
+
+// `mode` of k_backsub* (d_backsub_body)
+enum {
+    VIO_BACKSUB_STEP = 0,        // the step just solved: landmark update into the trial copy, its chi2 and gain-ratio partials -> step_part
+    VIO_BACKSUB_CHI_CUR = 1      // vio_chi2: chi2 of the CURRENT state only -> chi_part (never disturbs a pending step test)
+};
+// `mode` of k_step_sum and k_lm_decide* (d_lm_decide, d_lm_verdict)
+enum {
+    VIO_DECIDE_LM = 0,           // an LM trial: IsGoodStepInLM with its damping update
+    VIO_DECIDE_GN = 1,           // a fixed-lambda GN step: always accepted, no damping update
+    VIO_DECIDE_CHI_ONLY = 2      // vio_chi2: the sum of chi_part, no state change
+};
+
 struct DeviceTables {            // everything a kernel needs, passed by value
     const ItemDesc *items;
     int32_t n_items;
@@ -183,35 +254,28 @@ struct DeviceTables {            // everything a kernel needs, passed by value
     const int16_t *pair_slot;    // [n_items][78]
     const int8_t *blk_slot;      // [n_items][12]
     const double *Hprior;        // [171x171]
-    double *bprior;              // [2][176]
-    double *errprior;            // [2][160]
+    double *bprior;              // [2][VIO_PD_PAD]
+    double *errprior;            // [2][VIO_PRD_PAD]
     const double *Jtinv;         // [156x156]
     int32_t has_prior;
     int32_t natural_hs;          // 1: k_assemble also writes H_pp_schur_ in natural order (getters, marginalisation)
     int32_t add_imu_prior;       // 1 on every rank: IMU and prior terms are replicated and added after the exchange
     double *Hs;                  // [171x171]
     double *Pg;                  // permuted, padded, packed lower triangle + rhs row, written by k_assemble
-    int32_t *perm;               // [176] pivot order found by k_assemble
-    int32_t *rank;               // [176] its inverse (batched launches: k_rank_b writes both, k_assemble_b reads them)
+    int32_t *perm;               // [2][VIO_PD_PAD] pivot order found by k_assemble (two sets: vio_solve's loop)
+    int32_t *rank;               // [VIO_PD_PAD] its inverse (batched launches: k_rank_b writes both, k_assemble_b reads them)
     double *bs;                  // [171]
     double *bfull;               // [171] pose part of b_ (direct + imu + prior), for the gain ratio
     double *diagfull;            // [171] diag(Hessian_) pose part, for lambda_0
-    double *dx;                  // [176] pose part of delta_x_
+    double *dx;                  // [VIO_PD_PAD] pose part of delta_x_
     double *dxl;                 // [Ns]  landmark part of delta_x_
     double *step_part;           // [n_step_blocks][2]
     double *chi_part;            // [n_step_blocks][2] partials of vio_chi2 (kept apart from a pending step test)
     int32_t n_step_blocks;
-    int32_t gn_flags;            // GN mode, for the PREVIOUS step: bit 0: k_assemble runs its test (its chi2 is the one this linearisation
-                                 // computed); bit 1: k_linearize applies its landmark back-substitution first; bit 2 (k_pose_solve):
-                                 // this step's prior update is left to the next k_linearize (b_prior') and k_reduce (err_prior');
-                                 // bit 3 (k_backsub): flush of such a step, form b_prior' here; bit 4 (k_linearize, GN loop): the grid's first
-                                 // workgroup eliminates the speed-bias chain (and forms the IMU items: no IMU workgroups follow the items)
-                                 // bit 5 (k_pose_solve_c, diagnostic: VIO_NO_EARLY_START): the prologue with its barriers instead of the early start
-    int32_t cur_hint;            // >= 0: LmState.cur as the host tracks it through GN iterations (kernels skip the dependent load); -1: read lm->cur;
-                                 // -2 (vio_solve's loop): the copy to linearise at is lm->cur ^ lm->pending, and bits 0 / 1 of gn_flags
-                                 // count only while lm->pending
+    int32_t gn_flags;            // VIO_GN_* bits
+    int32_t cur_hint;            // >= 0: LmState.cur as the host tracks it, or VIO_CUR_FROM_LM / VIO_CUR_LM_LOOP
     int32_t imu_mask;            // bit k: IMU edge k exists (the host's copy of imu_valid: saves the kernels a dependent load)
-    int32_t lm_gate;             // device-driven LM loop: 0 run; 2: skip if lm->stop; 3: skip unless lm->need_linearize && !lm->stop
+    int32_t lm_gate;             // VIO_GATE_*
     const int32_t *list_off;     // k_reduce's inverted lists (a batched launch builds its ReduceTables from here)
     const int32_t *list;
     double *step_tot;            // [8] exchange buffer: chi2 of the trial state, gain-ratio scale
@@ -223,7 +287,7 @@ struct DeviceTables {            // everything a kernel needs, passed by value
     const double *gath;          // [n_shards][VIS_SEND]
     const double *step_gath;     // [n_shards][2]
     int32_t n_shards;
-    int32_t solve_order;         // 0: Eigen's pivot order (k_assemble / k_pose_solve); 1: the static chain order (k_assemble_c / k_pose_solve_c, vio_pose_solve_chain.h)
+    int32_t solve_order;         // VIO_DEV_ORDER_EIGEN (0) / VIO_DEV_ORDER_CHAIN (1)
     double *cfi;                 // the GN loop's pre-eliminated speed-bias chain (vio_pose_solve_chain.h: d_chain_pre_item -> k_pose_solve_cs), laid out
                                  // as the solve's LDS image
     double *prior_simg;          // H_prior's entries of the speed-bias rows at their places in the chain image (k_prior_simg), CH_OFF_CC doubles
