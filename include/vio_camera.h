@@ -69,8 +69,9 @@
  * result depends neither on its batch nor on its slot's number; the calling thread's current HIP device is restored; one handle is
  * used by one caller thread at a time.
  *
- * Not built: spaceToPlane (and with it SCARAMUZZA's inv_poly); the resident read_batch path of include/vio_frame_read.h, whose
- * vio_frame_set_camera stays PINHOLE; the fisheye circle mask, which is the mask image the tracker already takes.
+ * Not built: spaceToPlane (and with it SCARAMUZZA's inv_poly); the fisheye circle mask, which is the mask image the tracker already
+ * takes.  The resident read_batch path of include/vio_frame_read.h takes these cameras per slot through include/vio_frame_camera.h
+ * (vio_frame_set_slot_camera; its handle-wide vio_frame_set_camera stays PINHOLE).
  */
 #ifndef VIO_CAMERA_H
 #define VIO_CAMERA_H

@@ -39,7 +39,8 @@
  *   - the calling thread's current HIP device is restored; one handle is used by one caller thread at a time.
  *
  * Resident points (VIO_FRAME_HAS_READ): include/vio_frame_read.h, which this header includes, declares vio_frame_read_batch and what
- * goes with it: all of readImage for one new image per slot, the points kept on the device.
+ * goes with it: all of readImage for one new image per slot, the points kept on the device.  include/vio_frame_camera.h, included behind
+ * it (VIO_FRAME_HAS_SLOT_CAMERAS), gives every slot a camera of its own, of any model of include/vio_camera.h.
  */
 #ifndef VIO_FRAME_H
 #define VIO_FRAME_H
@@ -133,5 +134,6 @@ vio_status vio_frame_timing(vio_frame *h, double *out8);
 #endif
 
 #include "vio_frame_read.h"
+#include "vio_frame_camera.h"
 
 #endif

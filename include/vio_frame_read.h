@@ -21,7 +21,7 @@
  *                             vio_frame_push_batch / _track_batch / _detect_batch and vio_reject_batch / _undistort_batch gives,
  *                             followed by its update_ids.
  * Rules, besides those above:
- *   - a camera is required (vio_frame_set_camera); a time that is not finite, or that does not increase while the slot's prev_un holds
+ *   - a camera is required (vio_frame_set_camera, or for a slot its own: include/vio_frame_camera.h, any of the four models); a time that is not finite, or that does not increase while the slot's prev_un holds
  *     rows, is VIO_ERR_BAD_ARG, as are a slot listed twice, a geometry change and, with publish, a mask of another geometry: nothing is
  *     written, launched or rolled, and the slot's frames and points are as they were;
  *   - vio_frame_reset also drops the slot's points, its prev_un rows, its count of frames read and its time stamp; it keeps the slot's
@@ -48,7 +48,8 @@ extern "C" {
 #define VIO_FRAME_DEFAULT_BORDER 1                  /* inBorder's BORDER_SIZE */
 
 /* The camera and the RANSAC settings of the slots' rejectWithF and undistortedPoints, under the validity rules of
- * include/vio_reject.h (PINHOLE only); cfg NULL: its defaults.  A read needs a camera. */
+ * include/vio_reject.h (PINHOLE only); cfg NULL: its defaults.  A read needs a camera: this one, or the slot's own
+ * (vio_frame_set_slot_camera of include/vio_frame_camera.h, any model of include/vio_camera.h). */
 vio_status vio_frame_set_camera(vio_frame *h, const vio_reject_camera *cam, const vio_reject_config *cfg);
 
 /* max_cnt: the reference's MAX_CNT, in [0, VIO_FRAME_MAX_TRACK_POINTS]; border: inBorder's margin, >= 0.  A new handle has
@@ -71,13 +72,13 @@ typedef struct vio_frame_read_item {
 } vio_frame_read_item;
 
 typedef struct vio_frame_read_result {
-    int32_t status;                 /* VIO_OK */
+    int32_t status;                 /* VIO_OK; VIO_ERR_NOT_FINITE: the slot's own camera could not lift a point (vio_frame_camera.h) */
     int32_t n;                      /* the slot's points after the call: the rows written */
     int32_t n_new;                  /* of those, detected in this image (the last n_new rows; their ids are the counter's) */
     int32_t n_tracked_in;           /* the points the slot held */
     int32_t n_after_track;          /* ... still there after the tracker and the border */
     int32_t n_after_reject;         /* ... and after rejectWithF */
-    int32_t reject_status;          /* VIO_OK or VIO_REJECT_FAIL_NO_MODEL (VIO_OK where nothing ran) */
+    int32_t reject_status;          /* VIO_OK or VIO_REJECT_FAIL_NO_MODEL (VIO_OK where nothing ran); VIO_ERR_NOT_FINITE as for status */
     int32_t reject_hyp;             /* the winning hypothesis, -1 where nothing ran */
     int32_t n_candidates;           /* the detector's */
     int32_t reserved;

@@ -10,7 +10,13 @@ the median of --reps frames after --warmup, with the least and the most; for leg
 --repeats runs the whole measurement again that many times with the order of the legs alternating, for the spread.  Both legs see the
 same images and times from the same empty state, and the outputs of the last frame are compared byte for byte (`same`).
 
-    python tools/bench_front_batch.py [--batches 1,16,64] [--reps 20] [--warmup 3] [--repeats 3] [--out profiles/NAME.json]
+    python tools/bench_front_batch.py [--batches 1,16,64] [--reps 20] [--warmup 3] [--repeats 3] [--slot-cameras none|pinhole|mixed]
+                                      [--out profiles/NAME.json]
+
+--slot-cameras (include/vio_frame_camera.h): none: the handle's camera alone, the PINHOLE kernels; pinhole: every
+slot has that same camera as its own, so the same arithmetic runs through the general kernels and the camera table; mixed: slot s has
+the handle's camera, a KANNALA_BRANDT, a MEI or a SCARAMUZZA camera of its own by s mod 4, and leg loop's rejecter is a
+camera.CameraHandle.bind(s) with the same cameras.
 
 Stream k sees the fixture pair (tests/golden/flow_image_1.npz, flow_image_2.npz) alternating, shifted down by k rows (wrapped).
 """
@@ -30,6 +36,13 @@ GOLDEN = os.path.join(ROOT, "tests", "golden")
 MAX_CNT, MIN_DIST, DT = 150, 30, 0.05
 # VM/config/euroc_config.yaml:11-22
 EUROC = dict(fx=4.616e+02, fy=4.603e+02, cx=3.630e+02, cy=2.481e+02, k1=-2.917e-01, k2=8.228e-02, p1=5.333e-05, p2=-1.578e-04, width=752, height=480)
+# the other three models at 752 x 480 (KANNALA_BRANDT and MEI: tests/camera_reference.py's)
+SLOT_CAMERAS = [
+    None,
+    dict(model=1, width=752, height=480, k2=-0.0125, k3=0.0045, k4=-0.0031, k5=0.00052, mu=150.0, mv=150.5, u0=376.0, v0=240.5, theta_max=1.6),
+    dict(model=2, width=752, height=480, xi=0.9, k1=-0.12, k2=0.03, p1=2e-4, p2=-3e-4, gamma1=830.0, gamma2=828.0, u0=371.5, v0=243.25),
+    dict(model=3, width=752, height=480, poly0=-260.0, poly1=0.0, poly2=6e-4, ac=0.9995, ad=2.5e-4, ae=-1.5e-4, cx=375.25, cy=240.5),
+]
 KEYS = ("pts", "ids", "track_cnt", "un_pts", "velocity")
 STAGES = ("host_ms", "push_ms", "track_ms", "reject_ms", "detect_ms", "finish_ms", "readback_ms", "total_ms")
 
@@ -40,6 +53,7 @@ def main():
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
+    ap.add_argument("--slot-cameras", choices=("none", "pinhole", "mixed"), default="none")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     vio = g.load_package()
@@ -58,12 +72,21 @@ def main():
             lo.set_config(**cfg)
             fr.set_camera(**EUROC)
             rh.set_camera(**EUROC)
+            own = {}
+            if args.slot_cameras == "pinhole":
+                own = {s: dict(model=0, **EUROC) for s in range(B)}
+            elif args.slot_cameras == "mixed":
+                own = {s: SLOT_CAMERAS[s % 4] for s in range(B) if s % 4}
+                ch = vio.load_camera().create()
+                for s in range(B):
+                    ch.set_camera(slot=s, **own.get(s, dict(model=0, **EUROC)))
             for leg in (("read", "loop") if rep % 2 == 0 else ("loop", "read")):
                 wall, parts, moved = [], [], None
                 if leg == "read":
-                    bt = vio.BatchFeatureTracker(fr, range(B), max_cnt=MAX_CNT, min_dist=MIN_DIST)
+                    bt = vio.BatchFeatureTracker(fr, range(B), max_cnt=MAX_CNT, min_dist=MIN_DIST, cameras=own)
                 else:
-                    fts = [vio.FeatureTracker(None, None, max_cnt=MAX_CNT, min_dist=MIN_DIST, rejecter=rh, frames=lo, slot=s) for s in range(B)]
+                    fts = [vio.FeatureTracker(None, None, max_cnt=MAX_CNT, min_dist=MIN_DIST, rejecter=ch.bind(s) if args.slot_cameras == "mixed" else rh,
+                                              frames=lo, slot=s) for s in range(B)]
                 for t in range(frames):
                     imgs = raw[t & 1][:B]
                     c0 = fr.counters() if leg == "read" else None
@@ -98,9 +121,9 @@ def main():
             same = all(a[k].tobytes() == b[k].tobytes() for a, b in zip(last["read"], last["loop"]) for k in KEYS)
             rows.append(dict(repeat=rep, batch=B, same=bool(same)))
             print("repeat %d  B %3d  outputs of the two legs identical: %s" % (rep, B, same), flush=True)
-            for h in (fr, lo, rh):
+            for h in (fr, lo, rh) + ((ch,) if args.slot_cameras == "mixed" else ()):
                 h.close()
-    res = dict(bench="front_batch", image="%dx%d" % (pair[0].shape[1], pair[0].shape[0]), max_cnt=MAX_CNT, min_dist=MIN_DIST, reps=args.reps,
+    res = dict(bench="front_batch", slot_cameras=args.slot_cameras, image="%dx%d" % (pair[0].shape[1], pair[0].shape[0]), max_cnt=MAX_CNT, min_dist=MIN_DIST, reps=args.reps,
                warmup=args.warmup, repeats=args.repeats, rows=rows)
     print(json.dumps(res))
     if args.out:

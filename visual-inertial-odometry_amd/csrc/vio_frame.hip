@@ -4,6 +4,9 @@
 // The numeric kernels are those of libvio_clahe_hip, libvio_flow_hip, libvio_detect_hip and libvio_reject_hip, compiled from the same
 // four files (vio_clahe_body.inc, vio_flow_body.inc, vio_detect_body.inc, vio_reject_body.inc), each inside a namespace since their
 // constants share names.  The five kernels that join them in vio_frame_read_batch are in vio_front_body.inc.
+// vio_frame_set_slot_camera (include/vio_frame_camera.h) gives a slot a camera of its own, of any of the four models:
+// a read that lists such a slot runs a second instantiation of vio_reject_body.inc (namespace kq, against vio_camera_math.h through
+// vio_camera_host.h, as libvio_camera_hip compiles it) and of vio_front_body.inc (namespace fq), every descriptor carrying its slot.
 // What is here is the host side that is this library's own: the slot table and the block pool (vio_frame_slots.h, plain C++), the
 // descriptor tables that point the kernels at resident frames, and the copies.  The checks, fills, launches and unpacking of a stage
 // are those of its library, from vio_{clahe,flow,detect,reject}_host.h and the end of each body.  A frame is
@@ -24,6 +27,7 @@
 
 #pragma clang fp contract(off)
 
+#include "vio_camera_math.h"
 #include "vio_clahe_math.h"
 #include "vio_detect_math.h"
 #include "vio_flow_math.h"
@@ -47,8 +51,37 @@ namespace kr {
 #include "vio_reject_host.h"
 #include "vio_reject_body.inc"
 }
+#define FRONT_REJ kr
 #include "vio_front_body.inc"
+#undef FRONT_REJ
 
+// the same two texts against the four camera models and a camera per slot: the lift's customisation points change hands
+#undef REJ_RAY
+#undef REJ_RAY_UNSET
+#undef REJ_ITEM_LIFT
+#undef REJ_STORE_BARE
+#undef REJ_UN_X
+#undef REJ_UN_Y
+#undef REJ_PROLOGUE_BEGIN
+#undef REJ_PAIR_LIFT
+#undef REJ_VIRTUAL_X
+#undef REJ_VIRTUAL_Y
+#undef REJ_PROLOGUE_END
+namespace kq {
+#include "vio_camera_host.h"
+#include "vio_reject_body.inc"
+}
+namespace fq {
+#define FRONT_REJ kq
+#define FRONT_CAMERAS
+#include "vio_front_body.inc"
+#undef FRONT_CAMERAS
+#undef FRONT_REJ
+}
+#include "vio_frame_cameras.h"
+
+static_assert(FRAME_CAM_SLOTS == VIO_FRAME_MAX_SLOTS && FRAME_CAM_SLOTS == VIO_CAMERA_MAX_SLOTS, "a camera per slot");
+static_assert(sizeof(fq::FrontItem) == sizeof(FrontItem), "one item table for both sets of joining kernels");
 static_assert(FRAME_MAX_SLOTS == VIO_FRAME_MAX_SLOTS && FRAME_MAX_LEVELS == VIO_FLOW_MAX_LEVELS && FRAME_MAX_DIM == VIO_FRAME_MAX_DIM,
               "vio_frame_slots.h restates the header's limits");
 static_assert(FRAME_MAX_TRACK_POINTS == VIO_FRAME_MAX_TRACK_POINTS && FRONT_CAP == VIO_FRAME_MAX_TRACK_POINTS, "one capacity");
@@ -98,6 +131,9 @@ struct vio_frame {
     Twin<char> rout;                                     // FrontRes per item | the result rows
     hipEvent_t rev[5] = {};                              // behind the filter, the reject, the detection, the finish, the read-back
     double rtiming[8] = {NAN, NAN, NAN, NAN, NAN, NAN, NAN, NAN};
+    // the slots' own cameras (vio_frame_cameras.h) and the table's twin, which goes up ahead of a read that needs it when it has changed
+    FrameCameras cams;
+    Twin<CamDev> camtab;
 };
 
 namespace {
@@ -274,6 +310,36 @@ vio_status ensure_points(vio_frame *h) {
     return VIO_OK;
 }
 
+// the camera table's twin, allocated at the first read that needs it
+vio_status ensure_cameras(vio_frame *h) {
+    if (h->camtab.d) return VIO_OK;
+    h->cams.dirty = true;
+    return h->camtab.ensure(h->err, sizeof(h->cams.table));
+}
+
+// The two sets of kernels a read runs (read_run, at the end of the file): the tables and the kernels of each.
+template <bool CAMS> struct ReadPath;
+template <> struct ReadPath<false> {
+    using RejPair = kr::RejPair; using LiftItem = kr::LiftItem; using RejRes = kr::RejRes;
+    using RansacArgs = kr::RansacArgs; using LiftArgs = kr::LiftArgs;
+    using Item = ::FrontItem; using Res = ::FrontRes; using Args = ::FrontArgs;
+    static constexpr auto begin = ::k_front_begin, filter = ::k_front_filter, after_reject = ::k_front_after_reject, merge = ::k_front_merge,
+                          finish = ::k_front_finish;
+    static constexpr auto ransac = kr::k_reject_ransac;
+};
+template <> struct ReadPath<true> {
+    using RejPair = kq::RejPair; using LiftItem = kq::LiftItem; using RejRes = kq::RejRes;
+    using RansacArgs = kq::RansacArgs; using LiftArgs = kq::LiftArgs;
+    using Item = fq::FrontItem; using Res = fq::FrontRes; using Args = fq::FrontArgs;
+    static constexpr auto begin = fq::k_front_begin, filter = fq::k_front_filter, after_reject = fq::k_front_after_reject, merge = fq::k_front_merge,
+                          finish = fq::k_front_finish;
+    static constexpr auto ransac = kq::k_reject_ransac;
+};
+
+template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_frame_read_item *items, int32_t publish, vio_frame_read_result *results,
+                                         std::chrono::steady_clock::time_point t0, const std::vector<int32_t> &sl, const std::vector<int32_t> &ww,
+                                         const std::vector<int32_t> &hh, const std::vector<double> &tt, const std::vector<vio_frame_push_item> &push);
+
 }  // namespace
 
 extern "C" {
@@ -338,6 +404,7 @@ vio_status vio_frame_reset(vio_frame *h, int32_t slot) {
     h->err[0] = 0;
     if (!FrameTable::slot_ok(slot)) return fail_check(h, "vio_frame_reset", FRAME_BAD_SLOT, 0, slot);
     h->tab.reset(slot);
+    h->cams.lift_info_set(slot, 0, 0);
     return VIO_OK;
 }
 
@@ -516,6 +583,36 @@ vio_status vio_frame_set_camera(vio_frame *h, const vio_reject_camera *cam, cons
     kr::rej_set_camera(*cam, h->camera, h->cam);
     h->rcfg = c;
     h->have_camera = true;
+    h->cams.set_handle_camera(h->camera);
+    return VIO_OK;
+}
+
+vio_status vio_frame_set_slot_camera(vio_frame *h, int32_t slot, const vio_camera_model *cam) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    return cam ? h->cams.set(h->err, slot, cam) : h->cams.clear(h->err, slot);
+}
+
+vio_status vio_frame_get_slot_camera(const vio_frame *h, int32_t slot, int32_t *is_set, vio_camera_model *cam) {
+    if (!h || !FrameCameras::slot_ok(slot)) return VIO_ERR_BAD_ARG;
+    if (is_set) *is_set = h->cams.own[slot];
+    if (cam && h->cams.own[slot]) *cam = h->cams.model[slot];
+    return VIO_OK;
+}
+
+vio_status vio_frame_set_reject_config(vio_frame *h, const vio_reject_config *cfg) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    const vio_status st = kr::rej_check_config(h->err, "vio_frame_set_reject_config", cfg);
+    if (st != VIO_OK) return st;
+    h->rcfg = *cfg;
+    return VIO_OK;
+}
+
+vio_status vio_frame_read_lift_info(const vio_frame *h, int32_t slot, int32_t *n_clamped, int32_t *n_bad) {
+    if (!h || !FrameCameras::slot_ok(slot)) return VIO_ERR_BAD_ARG;
+    if (n_clamped) *n_clamped = h->cams.n_clamped[slot];
+    if (n_bad) *n_bad = h->cams.n_bad[slot];
     return VIO_OK;
 }
 
@@ -603,7 +700,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
         return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_read_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
     if (publish != 0 && publish != 1) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_read_batch: publish 0 or 1");
     if (count == 0) return VIO_OK;
-    if (!h->have_camera) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_read_batch: no camera set");
+    if (!h->have_camera && h->cams.n_own == 0) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_read_batch: no camera set");
     const auto t0 = std::chrono::steady_clock::now();
     // every argument of every item first: nothing is written, launched or rolled on an error
     const size_t B = (size_t)count;
@@ -623,6 +720,33 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     for (int i = 0; i < count; ++i)
         if (!items[i].pts || !items[i].ids || !items[i].track_cnt || !items[i].un_pts || !items[i].velocity)
             return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_read_batch: item %d: pts, ids, track_cnt, un_pts and velocity are required", i);
+    // the cameras: every listed slot needs one; a call without a slot camera among them is the handle's camera through the PINHOLE kernels
+    const FrameCamPath path = h->cams.path(count, sl.data(), &bad);
+    if (path == FRAME_CAM_MISSING)
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_read_batch: item %d: slot %d has no camera of its own, and the handle has none", bad, sl[(size_t)bad]);
+    return path == FRAME_CAM_TABLE ? read_run<true>(h, count, items, publish, results, t0, sl, ww, hh, tt, push)
+                                   : read_run<false>(h, count, items, publish, results, t0, sl, ww, hh, tt, push);
+}
+
+}  // extern "C"
+
+namespace {
+
+// The read of `count` checked items.  CAMS false: the handle's camera through the kr kernels and the joining kernels at file scope,
+// the launches of include/vio_frame_read.h as they always were.  CAMS true: the camera table through the kq kernels and the joining
+// kernels of namespace fq, a slot in every descriptor (include/vio_frame_camera.h).
+template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_frame_read_item *items, int32_t publish, vio_frame_read_result *results,
+                                         std::chrono::steady_clock::time_point t0, const std::vector<int32_t> &sl, const std::vector<int32_t> &ww,
+                                         const std::vector<int32_t> &hh, const std::vector<double> &tt, const std::vector<vio_frame_push_item> &push) {
+    using P = ReadPath<CAMS>;
+    using RejPair = typename P::RejPair;
+    using LiftItem = typename P::LiftItem;
+    using RejRes = typename P::RejRes;
+    using FrontItem = typename P::Item;
+    using FrontRes = typename P::Res;
+    using FrontArgs = typename P::Args;
+    const size_t B = (size_t)count;
+    vio_status st;
     // what the host knows of each slot before the roll
     std::vector<FrameSlot> was(B);
     int64_t total = 0, n_r = 0, n_cand = 0;
@@ -637,13 +761,13 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
     // the tables that travel: their size depends on the count of items alone
     const size_t o_flow = align256(sizeof(FrontItem) * B), o_det = o_flow + align256(sizeof(kf::FlowItemD) * B);
-    const size_t o_pair = o_det + align256(sizeof(kd::DetItemD) * B), o_lift = o_pair + align256(sizeof(kr::RejPair) * B);
-    const size_t b_tab = o_lift + align256(sizeof(kr::LiftItem) * B);
+    const size_t o_pair = o_det + align256(sizeof(kd::DetItemD) * B), o_lift = o_pair + align256(sizeof(RejPair) * B);
+    const size_t b_tab = o_lift + align256(sizeof(LiftItem) * B);
     // the device work space, every per-point array at FRONT_CAP rows per item
     size_t b_work = 0;
     const auto carve = [&](size_t bytes) { const size_t at = b_work; b_work += align256(bytes); return at; };
     const size_t rowsN = B * CAP;
-    const size_t w_dres = carve(sizeof(kd::DetRes) * B), w_rres = carve(sizeof(kr::RejRes) * B), b_zero = b_work;
+    const size_t w_dres = carve(sizeof(kd::DetRes) * B), w_rres = carve(sizeof(RejRes) * B), b_zero = b_work;
     const size_t w_fpts = carve(sizeof(kf::FlowPt) * rowsN), w_fout = carve(sizeof(kf::FlowOut) * rowsN);
     const size_t w_rstage = carve(sizeof(float) * 4 * rowsN), w_corr = carve(sizeof(double) * 4 * rowsN);
     const size_t w_flag = carve(sizeof(int32_t) * rowsN), w_rmask = carve(rowsN);
@@ -653,6 +777,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     const size_t w_kxy = carve(sizeof(int32_t) * 2 * rowsN), w_keep = carve(sizeof(int32_t) * rowsN), w_new = carve(sizeof(float) * 2 * rowsN);
     const size_t w_lstage = carve(sizeof(float) * 4 * rowsN), w_lids = carve(sizeof(long long) * 2 * rowsN);
     const size_t w_un = carve(sizeof(float) * 2 * rowsN), w_vel = carve(sizeof(float) * 2 * rowsN), w_cntm = carve(sizeof(int32_t) * rowsN);
+    const size_t w_lflag = CAMS ? carve(rowsN) : 0;        // k_reject_lift's flag byte per point
     const size_t row_bytes = (36 * (size_t)rows_cap + 7) & ~(size_t)7;
     const size_t b_res = align256(sizeof(FrontRes) * B), b_out = b_res + row_bytes * B;
     for (size_t i = 0; i < B; ++i) {
@@ -660,7 +785,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
         n_cand += (int64_t)std::max(ww[i] - 2, 0) * std::max(hh[i] - 2, 0);
     }
     if ((st = ensure_points(h)) != VIO_OK || (st = h->rtab.ensure(h->err, b_tab)) != VIO_OK || (st = h->rwork.ensure(h->err, b_work)) != VIO_OK ||
-        (st = h->rout.ensure(h->err, b_out)) != VIO_OK ||
+        (st = h->rout.ensure(h->err, b_out)) != VIO_OK || (CAMS && (st = ensure_cameras(h)) != VIO_OK) ||
         (publish && ((st = h->r.ensure(h->err, sizeof(double) * (size_t)n_r)) != VIO_OK ||
                      (st = h->cand.ensure(h->err, sizeof(uint32_t) * (size_t)n_cand)) != VIO_OK)))
         return st;
@@ -671,8 +796,8 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     FrontItem *fr = (FrontItem *)h->rtab.h;
     kf::FlowItemD *fi = (kf::FlowItemD *)(h->rtab.h + o_flow);
     kd::DetItemD *di = (kd::DetItemD *)(h->rtab.h + o_det);
-    kr::RejPair *rp = (kr::RejPair *)(h->rtab.h + o_pair);
-    kr::LiftItem *li = (kr::LiftItem *)(h->rtab.h + o_lift);
+    RejPair *rp = (RejPair *)(h->rtab.h + o_pair);
+    LiftItem *li = (LiftItem *)(h->rtab.h + o_lift);
     kd::DetTotals T;
     int64_t flow_off = 0;
     for (size_t i = 0; i < B; ++i) {
@@ -692,14 +817,15 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
         d.active = 1;
         det_item_of(h, d, T, s, 0, h->max_cnt);             // (n_tracked is k_front_after_reject's to write)
         d.trk = (int32_t)(i * CAP); d.newp = (int32_t)(i * CAP);    // (every per-point array has CAP rows per item here)
-        kr::RejPair &r = rp[i];
+        RejPair &r = rp[i];
         r.pair = was[i].n_read; r.finite = 1;               // (n and active are k_front_filter's to write)
         r.o_pts = (int64_t)(i * 4 * CAP); r.o_corr = (int64_t)(i * 4 * CAP); r.o_pt = (int64_t)(i * CAP);
-        kr::LiftItem &u = li[i];
+        LiftItem &u = li[i];
         u.active = 1;                                       // (n and m are k_front_merge's to write)
         u.o_pts = (int64_t)(i * 4 * CAP); u.o_prev = (int64_t)(i * 4 * CAP + 2 * CAP);
         u.o_ids = (int64_t)(i * 2 * CAP); u.o_out = (int64_t)(i * CAP);
         u.dt = was[i].n_prev_un > 0 ? tt[i] - was[i].time : 1.0;
+        if constexpr (CAMS) { r.slot = sl[i]; u.slot = sl[i]; }
     }
     total = flow_off;
     char *W = h->rwork.d;
@@ -707,37 +833,57 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     std::memset(&a, 0, sizeof(a));
     a.items = (const FrontItem *)h->rtab.d;
     a.fpts = (kf::FlowPt *)(W + w_fpts); a.fout = (const kf::FlowOut *)(W + w_fout);
-    a.pairs = (kr::RejPair *)(h->rtab.d + o_pair);
-    a.rstage = (float *)(W + w_rstage); a.rmask = (const uint8_t *)(W + w_rmask); a.rres = (const kr::RejRes *)(W + w_rres);
+    a.pairs = (RejPair *)(h->rtab.d + o_pair);
+    a.rstage = (float *)(W + w_rstage); a.rmask = (const uint8_t *)(W + w_rmask); a.rres = (const RejRes *)(W + w_rres);
     a.fa = (float *)(W + w_fa); a.ida = (long long *)(W + w_ida); a.cnta = (int32_t *)(W + w_cnta);
     a.fb = (float *)(W + w_fb); a.idb = (long long *)(W + w_idb); a.cntb = (int32_t *)(W + w_cntb);
     a.ditems = (kd::DetItemD *)(h->rtab.d + o_det); a.dtrk = (kd::DetTrk *)(W + w_trk); a.dres = (const kd::DetRes *)(W + w_dres);
     a.keep_order = (const int32_t *)(W + w_keep); a.new_pts = (const float *)(W + w_new);
-    a.litems = (kr::LiftItem *)(h->rtab.d + o_lift);
+    a.litems = (LiftItem *)(h->rtab.d + o_lift);
     a.lstage = (float *)(W + w_lstage); a.lids = (long long *)(W + w_lids);
     a.un = (const float *)(W + w_un); a.vel = (const float *)(W + w_vel); a.cntm = (int32_t *)(W + w_cntm);
     a.res = (FrontRes *)h->rout.d; a.rows = h->rout.d + b_res; a.row_bytes = (int64_t)row_bytes; a.rows_cap = rows_cap;
     a.count = count; a.publish = publish; a.border = h->border;
+    if constexpr (CAMS) a.lflags = (const uint8_t *)(W + w_lflag);
     hipStream_t q = h->q.stream;
     if (hipMemcpyAsync(h->rtab.d, h->rtab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess || hipMemsetAsync(W, 0, b_zero, q) != hipSuccess)
         return fail_synced(h, "upload failed");
+    if constexpr (CAMS) {                                    // the camera table, if a slot changed: on the stream, ahead of the kernels
+        if (h->cams.take_dirty()) {
+            std::memcpy(h->camtab.h, h->cams.table, sizeof(h->cams.table));
+            if (hipMemcpyAsync(h->camtab.d, h->camtab.h, sizeof(h->cams.table), hipMemcpyHostToDevice, q) != hipSuccess) {
+                h->cams.dirty = true;
+                return fail_synced(h, "upload failed");
+            }
+            h->counters[2] += sizeof(h->cams.table);
+        }
+    }
     const auto t1 = std::chrono::steady_clock::now();
     const dim3 per_item((unsigned)count), fnt(FNT);
+    const auto front = [&](auto kernel) { hipLaunchKernelGGL(kernel, per_item, fnt, 0, q, a); };
     // 2 - 4. the slot's points into the new frame, and those that stay
     if (total > 0) {
-        hipLaunchKernelGGL(k_front_begin, per_item, fnt, 0, q, a);
+        front(P::begin);
         kf::flow_launch_track(q, kf::flow_args((const kf::FlowItemD *)(h->rtab.d + o_flow), a.fpts, (kf::FlowOut *)(W + w_fout), (size_t)total, L, h->fcfg),
                               h->fcfg.inverse != 0);
     }
-    hipLaunchKernelGGL(k_front_filter, per_item, fnt, 0, q, a);
+    front(P::filter);
     (void)hipEventRecord(h->rev[0], q);
     if (publish) {
         // 5, 6. rejectWithF and what it keeps
-        kr::RansacArgs ra = kr::rej_ransac_args(h->cam, h->camera, h->rcfg);
+        typename P::RansacArgs ra;
+        if constexpr (CAMS) {
+            std::memset(&ra, 0, sizeof(ra));
+            ra.cams = h->camtab.d;
+            ra.focal = h->rcfg.focal_length; ra.thr = h->rcfg.f_threshold * h->rcfg.f_threshold;
+            ra.seed = h->rcfg.seed; ra.hyps = h->rcfg.ransac_hypotheses;
+        } else {
+            ra = kr::rej_ransac_args(h->cam, h->camera, h->rcfg);
+        }
         ra.pairs = a.pairs; ra.pts = a.rstage;
-        ra.corr = (double *)(W + w_corr); ra.flag = (int32_t *)(W + w_flag); ra.mask = (uint8_t *)(W + w_rmask); ra.res = (kr::RejRes *)(W + w_rres);
-        if (total > 0) hipLaunchKernelGGL(kr::k_reject_ransac, per_item, dim3(kr::NT), 0, q, ra);
-        hipLaunchKernelGGL(k_front_after_reject, per_item, fnt, 0, q, a);
+        ra.corr = (double *)(W + w_corr); ra.flag = (int32_t *)(W + w_flag); ra.mask = (uint8_t *)(W + w_rmask); ra.res = (RejRes *)(W + w_rres);
+        if (total > 0) hipLaunchKernelGGL(P::ransac, per_item, dim3(kr::NT), 0, q, ra);
+        front(P::after_reject);
         (void)hipEventRecord(h->rev[1], q);
         // 7. setMask and the detection
         kd::DetArgs da = kd::det_args(h->dcfg, count);
@@ -752,14 +898,20 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     }
     (void)hipEventRecord(h->rev[2], q);
     // 8 - 10. the merged point set, undistortedPoints, updateID and the roll
-    hipLaunchKernelGGL(k_front_merge, per_item, fnt, 0, q, a);
-    kr::LiftArgs la;
+    front(P::merge);
+    typename P::LiftArgs la;
     std::memset(&la, 0, sizeof(la));
     la.items = a.litems; la.pts = a.lstage; la.ids = a.lids;
     la.un = (float *)(W + w_un); la.vel = (float *)(W + w_vel); la.lifted = nullptr;
-    la.cam = h->cam; la.bare = 0; la.count = count;
-    kr::rej_launch_lift(q, la, rows_cap);
-    hipLaunchKernelGGL(k_front_finish, per_item, fnt, 0, q, a);
+    la.bare = 0; la.count = count;
+    if constexpr (CAMS) {
+        la.cams = h->camtab.d; la.flags = (uint8_t *)(W + w_lflag);
+        kq::rej_launch_lift(q, la, rows_cap);
+    } else {
+        la.cam = h->cam;
+        kr::rej_launch_lift(q, la, rows_cap);
+    }
+    front(P::finish);
     (void)hipEventRecord(h->rev[3], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
     // 11. what is published comes down, and the call waits
@@ -768,6 +920,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     if (hipStreamSynchronize(q) != hipSuccess) return fail_synced(h, "kernel or read-back failed");
     h->counters[2] += b_tab; h->counters[3] += b_out;
     const FrontRes *res = (const FrontRes *)h->rout.h;
+    vio_status ret = VIO_OK;
     for (size_t i = 0; i < B; ++i) {
         const vio_frame_read_item &it = items[i];
         const FrontRes &r = res[i];
@@ -779,7 +932,12 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
         std::memcpy(it.velocity, base + 24 * R, sizeof(float) * 2 * n);
         std::memcpy(it.track_cnt, base + 32 * R, sizeof(int32_t) * n);
         vio_frame_read_result &o = results[i];
-        o.status = VIO_OK; o.n = (int32_t)n; o.n_new = front_clamp(r.n_new, 0, (int32_t)n);
+        int32_t n_clamped = 0, n_bad = 0;
+        if constexpr (CAMS) { n_clamped = std::max(r.n_clamped, 0); n_bad = std::max(r.n_bad, 0); }
+        const bool bad_lift = n_bad > 0 || r.reject_status == VIO_ERR_NOT_FINITE;       // (in undistortedPoints, in rejectWithF)
+        if (bad_lift && ret == VIO_OK) ret = fail(h->err, VIO_ERR_NOT_FINITE, "item %d: slot %d: a lift is not finite", (int)i, it.slot);
+        h->cams.lift_info_set(it.slot, n_clamped, n_bad);
+        o.status = bad_lift ? VIO_ERR_NOT_FINITE : VIO_OK; o.n = (int32_t)n; o.n_new = front_clamp(r.n_new, 0, (int32_t)n);
         o.n_tracked_in = r.n_tracked_in; o.n_after_track = r.n_after_track; o.n_after_reject = r.n_after_reject;
         o.reject_status = r.reject_status; o.reject_hyp = r.reject_hyp; o.n_candidates = r.n_candidates; o.reserved = 0;
         h->tab.points_after_read(it.slot, (int32_t)n, r.next_id, it.time);
@@ -790,7 +948,7 @@ vio_status vio_frame_read_batch(vio_frame *h, int32_t count, const vio_frame_rea
     h->rtiming[2] = elapsed_ms(h->q.ev[3], h->rev[0]);
     for (int k = 0; k < 4; ++k) h->rtiming[3 + k] = elapsed_ms(h->rev[k], h->rev[k + 1]);
     h->rtiming[7] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return VIO_OK;
+    return ret;
 }
 
-}  // extern "C"
+}  // namespace

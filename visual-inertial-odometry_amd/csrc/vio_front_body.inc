@@ -14,6 +14,14 @@
 // A compaction is stable: a ballot per wavefront, the sixteen wavefront counts through LDS, every thread adds the counts before its
 // own (front_scan; the arithmetic is csrc/vio_front_math.h's).  Integers and float copies only, no atomics: every order is fixed.
 // Every count a kernel reads from device memory is held to the rows there are before it indexes anything.
+//
+// The including file names the namespace of the reject tables as FRONT_REJ.  vio_frame.hip includes this text twice: at file scope with
+// FRONT_REJ = kr (the PINHOLE tables of vio_reject_host.h), and inside namespace fq with FRONT_REJ = kq (the tables of
+// vio_camera_host.h, a camera slot in each) and FRONT_CAMERAS defined (DESIGN.md section 29).  With FRONT_CAMERAS k_front_finish folds
+// the flag bytes k_reject_lift left: one bad lift makes every un_pts and velocity of the slot NaN, in the rows and in prev_un, which is
+// what vio_camera_undistort_batch does to the item on the host.  k_front_after_reject needs nothing more: a pair whose prologue found
+// a bad lift is active, its mask is all zeros and its result says VIO_ERR_NOT_FINITE with hyp -1, so every row goes and the status is
+// reported; the keep-everything branch is the inactive pair's alone.
 constexpr int FNT = FRONT_CAP;
 static_assert(FNT == 1024 && FNT % FRONT_WAVE == 0, "a slot's table is one workgroup of whole wavefronts");
 
@@ -33,16 +41,19 @@ struct FrontItem {
 struct FrontRes {
     int32_t n, n_new, n_tracked_in, n_after_track, n_after_reject, reject_status, reject_hyp, n_candidates;
     long long next_id;
+#ifdef FRONT_CAMERAS
+    int32_t n_clamped, n_bad;           // of the undistort stage: the clamped points (0 where a lift is bad), the bad lifts
+#endif
 };
 
 struct FrontArgs {
     const FrontItem *items;
     kf::FlowPt *fpts;
     const kf::FlowOut *fout;
-    kr::RejPair *pairs;
+    FRONT_REJ::RejPair *pairs;
     float *rstage;                      // k_reject_ransac's staged floats
     const uint8_t *rmask;
-    const kr::RejRes *rres;
+    const FRONT_REJ::RejRes *rres;
     float *fa;                          // after the filter, item i at row i * FRONT_CAP: forw [2], ids, track_cnt
     long long *ida;
     int32_t *cnta;
@@ -54,7 +65,7 @@ struct FrontArgs {
     const kd::DetRes *dres;
     const int32_t *keep_order;
     const float *new_pts;
-    kr::LiftItem *litems;
+    FRONT_REJ::LiftItem *litems;
     float *lstage;                      // k_reject_lift's staged floats and ids
     long long *lids;
     const float *un, *vel;
@@ -64,6 +75,9 @@ struct FrontArgs {
     int64_t row_bytes;
     int32_t rows_cap;                   // rows of an item's result arrays
     int32_t count, publish, border;
+#ifdef FRONT_CAMERAS
+    const uint8_t *lflags;              // k_reject_lift's flag byte per point: CAM_FLAG_BAD | CAM_FLAG_CLAMPED
+#endif
 };
 
 // the exclusive prefix of `keep` over the workgroup's rows, and their total; every thread of the workgroup calls it
@@ -102,7 +116,7 @@ __global__ __launch_bounds__(FNT) void k_front_filter(FrontArgs a) {
     }
     int nk;
     const int dst = front_scan(keep, s_w, nk);
-    kr::RejPair &P = a.pairs[item];
+    FRONT_REJ::RejPair &P = a.pairs[item];
     const int64_t row = (int64_t)item * FRONT_CAP + dst;
     if (keep) {
         float *cur = a.rstage + P.o_pts, *forw = cur + 2 * (int64_t)nk;
@@ -124,7 +138,7 @@ __global__ __launch_bounds__(FNT) void k_front_filter(FrontArgs a) {
 __global__ __launch_bounds__(FNT) void k_front_after_reject(FrontArgs a) {
     __shared__ int32_t s_w[FRONT_WAVES];
     const int item = blockIdx.x, t = threadIdx.x;
-    const kr::RejPair &P = a.pairs[item];
+    const FRONT_REJ::RejPair &P = a.pairs[item];
     const int nk = front_clamp(P.n, 0, FRONT_CAP);
     const bool keep = t < nk && (!P.active || a.rmask[P.o_pt + t] != 0);
     int n2;
@@ -152,7 +166,7 @@ __global__ __launch_bounds__(FNT) void k_front_after_reject(FrontArgs a) {
 __global__ __launch_bounds__(FNT) void k_front_merge(FrontArgs a) {
     const int item = blockIdx.x, t = threadIdx.x;
     const FrontItem &I = a.items[item];
-    kr::LiftItem &L = a.litems[item];
+    FRONT_REJ::LiftItem &L = a.litems[item];
     const float *sf = a.publish ? a.fb : a.fa;
     const long long *si = a.publish ? a.idb : a.ida;
     const int32_t *sc = a.publish ? a.cntb : a.cnta;
@@ -202,7 +216,7 @@ __global__ __launch_bounds__(FNT) void k_front_finish(FrontArgs a) {
     __shared__ int32_t s_w[FRONT_WAVES];
     const int item = blockIdx.x, t = threadIdx.x;
     const FrontItem &I = a.items[item];
-    const kr::LiftItem &L = a.litems[item];
+    const FRONT_REJ::LiftItem &L = a.litems[item];
     const int n = front_clamp(L.n, 0, FRONT_CAP);
     const long long next = *I.next_id;
     long long id = 0;
@@ -213,6 +227,13 @@ __global__ __launch_bounds__(FNT) void k_front_finish(FrontArgs a) {
         ux = a.un[2 * (L.o_out + t)]; uy = a.un[2 * (L.o_out + t) + 1];
         vx = a.vel[2 * (L.o_out + t)]; vy = a.vel[2 * (L.o_out + t) + 1];
     }
+#ifdef FRONT_CAMERAS
+    const int lf = t < n ? (int)a.lflags[L.o_out + t] : 0;
+    int n_bad, n_clamped;
+    (void)front_scan((lf & FRONT_REJ::CAM_FLAG_BAD) != 0, s_w, n_bad);      // (ballots and sixteen integer counts: the order is fixed)
+    (void)front_scan((lf & FRONT_REJ::CAM_FLAG_CLAMPED) != 0, s_w, n_clamped);
+    if (n_bad > 0) { ux = NAN; uy = NAN; vx = NAN; vy = NAN; }
+#endif
     int n_fresh;
     const int rank = front_scan(t < n && id == -1ll, s_w, n_fresh);             // (every thread has read the counter behind its barriers)
     if (t < n) {
@@ -239,5 +260,9 @@ __global__ __launch_bounds__(FNT) void k_front_finish(FrontArgs a) {
     if (t == 0) {
         *I.next_id = next + n_fresh;
         a.res[item].next_id = next + n_fresh;
+#ifdef FRONT_CAMERAS
+        a.res[item].n_clamped = n_bad > 0 ? 0 : n_clamped;
+        a.res[item].n_bad = n_bad;
+#endif
     }
 }

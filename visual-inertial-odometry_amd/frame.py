@@ -16,12 +16,17 @@ the image steps of FeatureTracker::readImage (feature_tracker.cpp:87-149) for ma
                                                                      # dicts of pts, ids, track_cnt, un_pts, velocity, n_new, ...
     fr.points_set(pts, ids, track_cnt, slot=0); fr.points_get(slot=0)
 
+    fr.set_slot_camera(3, model=camera.MODEL_KANNALA_BRANDT, width=752, height=480, k2=.., mu=.., mv=.., u0=.., v0=..)   # slot 3's own camera
+    fr.set_slot_camera(4, **camera.parse_camodocal_yaml(text)); fr.clear_slot_camera(4); fr.slot_camera(3)               # (include/vio_frame_camera.h)
+    fr.set_reject_config(seed=0, ransac_hypotheses=128); fr.read_lift_info(3)                 # dict(n_clamped, n_bad) of slot 3's last read
+
 A handle is what frontend.FeatureTracker takes as `frames`, and what frontend.BatchFeatureTracker drives through read_batch.
 """
 import ctypes as C
 
 import numpy as np
 
+from .camera import MAX_PARAMS, PARAMS, VioCameraModel, model_params
 from .capi import CompanionHandle, VioError, open_lib
 from .clahe import DEFAULT_CLIP_LIMIT, DEFAULT_TILES, VioClaheConfig
 from .detect import DEFAULT_MAX_TOTAL, DEFAULT_MIN_DISTANCE, DEFAULT_QUALITY, VioDetectConfig, VioDetectResult
@@ -64,6 +69,7 @@ class FrameLib:
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "push_batch", "track_batch", "set_mask", "detect_batch",
                "download", "reset", "counters", "timing"]
     READ_SYMBOLS = ["set_camera", "set_tracker", "read_batch", "points_set", "points_get", "read_timing"]      # include/vio_frame_read.h
+    CAMERA_SYMBOLS = ["set_slot_camera", "get_slot_camera", "set_reject_config", "read_lift_info"]            # include/vio_frame_camera.h
 
     def __init__(self, path):
         self.path = path
@@ -85,6 +91,11 @@ class FrameLib:
         self.fn["points_set"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         self.fn["points_get"].argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 8
         self.fn["read_timing"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_frame_", self.CAMERA_SYMBOLS)[1])
+        self.fn["set_slot_camera"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        self.fn["get_slot_camera"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        self.fn["set_reject_config"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn["read_lift_info"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_frame handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -247,6 +258,38 @@ class FrameHandle(CompanionHandle):
         cfg = VioRejectConfig(int(seed) & 0xFFFFFFFF, int(ransac_hypotheses), float(f_threshold), float(focal_length))
         self._ck(self.lib.fn["set_camera"](self.h, C.byref(cam), C.byref(cfg)), "set_camera")
 
+    def set_slot_camera(self, slot, model=MODEL_PINHOLE, width=752, height=480, **params):
+        """The slot's own camera, of any model of camera.PARAMS, by camera.model_params' keywords (camera.parse_camodocal_yaml's dict goes
+        straight in).  A refused camera raises and leaves the slot as it was."""
+        p = model_params(int(model), **params)
+        cam = VioCameraModel(int(model), int(width), int(height), 0, (C.c_double * MAX_PARAMS)(*(p + [0.0] * (MAX_PARAMS - len(p)))))
+        self._ck(self.lib.fn["set_slot_camera"](self.h, C.c_int32(int(slot)), C.byref(cam)), "set_slot_camera")
+
+    def clear_slot_camera(self, slot):
+        """The slot lifts through the handle's camera (set_camera) again."""
+        self._ck(self.lib.fn["set_slot_camera"](self.h, C.c_int32(int(slot)), None), "set_slot_camera")
+
+    def slot_camera(self, slot):
+        """None, or set_slot_camera's keywords of the slot's own camera."""
+        on, cam = C.c_int32(0), VioCameraModel()
+        self._ck(self.lib.fn["get_slot_camera"](self.h, C.c_int32(int(slot)), C.addressof(on), C.addressof(cam)), "get_slot_camera")
+        if not on.value:
+            return None
+        out = dict(model=int(cam.model), width=int(cam.width), height=int(cam.height))
+        out.update({name: float(cam.params[i]) for i, (name, _) in enumerate(PARAMS[int(cam.model)])})
+        return out
+
+    def set_reject_config(self, seed=0, ransac_hypotheses=DEFAULT_HYPOTHESES, f_threshold=DEFAULT_F_THRESHOLD, focal_length=DEFAULT_FOCAL_LENGTH):
+        """RejectHandle.set_config's settings for read_batch, without a handle-wide camera."""
+        cfg = VioRejectConfig(int(seed) & 0xFFFFFFFF, int(ransac_hypotheses), float(f_threshold), float(focal_length))
+        self._ck(self.lib.fn["set_reject_config"](self.h, C.byref(cfg)), "set_reject_config")
+
+    def read_lift_info(self, slot=0):
+        """dict(n_clamped, n_bad) of the undistortedPoints stage of the slot's last read_batch."""
+        c, b = C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.fn["read_lift_info"](self.h, C.c_int32(int(slot)), C.addressof(c), C.addressof(b)), "read_lift_info")
+        return dict(n_clamped=int(c.value), n_bad=int(b.value))
+
     def set_tracker(self, max_cnt=DEFAULT_MAX_CNT, border=DEFAULT_TRACK_BORDER):
         """The reference's MAX_CNT (at most MAX_TRACK_POINTS) and inBorder's margin."""
         self._ck(self.lib.fn["set_tracker"](self.h, C.c_int32(int(max_cnt)), C.c_int32(int(border))), "set_tracker")
@@ -255,7 +298,9 @@ class FrameHandle(CompanionHandle):
         """FeatureTracker.read_image followed by update_ids for one new image of each slot, in one call (include/vio_frame_read.h).
         imgs: (height, width) uint8 arrays; times: one time stamp per image, or one for all; slots: default 0 .. len(imgs) - 1.  A list
         of dicts: pts (n, 2) float32, ids (n,) int64 (after updateID), track_cnt (n,) int32, un_pts, velocity (n, 2) float32, and the
-        counts n, n_new, n_tracked_in, n_after_track, n_after_reject, reject_status, reject_hyp, n_candidates."""
+        counts n, n_new, n_tracked_in, n_after_track, n_after_reject, reject_status, reject_hyp, n_candidates; status (OK, or NOT_FINITE for
+        a slot whose camera could not lift a point: its un_pts and velocity are NaN, or its tracked points were dropped; the call does not
+        raise for it) with n_clamped and n_bad of read_lift_info."""
         B = len(imgs)
         slots = list(range(B)) if slots is None else [int(s) for s in slots]
         times = [float(times)] * B if np.isscalar(times) else [float(t) for t in times]
@@ -271,7 +316,8 @@ class FrameHandle(CompanionHandle):
             keep.append(a)
             outs.append(o)
             arr[i] = VioFrameReadItem(slots[i], a.shape[1], a.shape[0], a.strides[0], a.ctypes.data, times[i], *[x.ctypes.data for x in o])
-        self._ck(self.lib.fn["read_batch"](self.h, C.c_int32(B), C.addressof(arr), C.c_int32(1 if publish else 0), C.addressof(res)), "read_batch")
+        self._ck(self.lib.fn["read_batch"](self.h, C.c_int32(B), C.addressof(arr), C.c_int32(1 if publish else 0), C.addressof(res)), "read_batch",
+                 allow_not_finite=True)
         out = []
         for i in range(B):
             self.shapes[slots[i]] = keep[i].shape
@@ -279,6 +325,7 @@ class FrameHandle(CompanionHandle):
             d = dict(zip(("pts", "ids", "track_cnt", "un_pts", "velocity"), (x[:n].copy() for x in outs[i])))
             d.update({k: int(getattr(r, k)) for k in ("status", "n", "n_new", "n_tracked_in", "n_after_track", "n_after_reject", "reject_status",
                                                      "reject_hyp", "n_candidates")})
+            d.update(self.read_lift_info(slots[i]))
             out.append(d)
         return out
 

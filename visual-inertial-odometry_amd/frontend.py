@@ -34,8 +34,9 @@ handle's business (its equalize setting), so tracker, detector and equalizer may
 None; frames.download(slot, PREV or NEXT) gives them.  With frames=None nothing of this happens.
 
 The camera models besides PINHOLE (KANNALA_BRANDT for FISHEYE, MEI, SCARAMUZZA): pass a camera.CameraHandle (or its bind(slot) view) as
-`rejecter`; it has RejectHandle's .reject / .undistort.  Missing against the reference: those models on the resident read_batch path
-(BatchFeatureTracker), which stays PINHOLE, and the fisheye circle mask as a built-in (it is the `mask` image).
+`rejecter`; it has RejectHandle's .reject / .undistort.  On the resident read_batch path (BatchFeatureTracker) every slot may have a camera
+of its own, of any of the four models: cameras={slot: dict(model=, width=, height=, ...)} (frame.FrameHandle.set_slot_camera).  Missing
+against the reference: the fisheye circle mask as a built-in (it is the `mask` image).
 BatchFeatureTracker is the same front end for many streams at once over a frame.FrameHandle's read_batch: the points stay on the
 device, one call reads one new image of every stream.
 
@@ -171,10 +172,11 @@ class BatchFeatureTracker:
         outs = bt.read_images(imgs, t)               # dicts of pts, ids (after updateID), track_cnt, un_pts, velocity, n_new
         for ids, rows in bt.feature_frames(): ...    # per slot, FeatureTracker.feature_frame()'s pair
 
-    masks: None, or {slot: mask}.  The handle's detector gets min_distance = min_dist (its other settings return to their defaults), as
+    masks: None, or {slot: mask}.  cameras: None, or {slot: set_slot_camera's keywords}: the slot's own camera, of any model; a slot
+    without one lifts through the handle's (frames.set_camera).  The handle's detector gets min_distance = min_dist (its other settings return to their defaults), as
     in FeatureTracker."""
 
-    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None):
+    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None, cameras=None):
         self.frames, self.slots = frames, [int(s) for s in slots]
         if len(set(self.slots)) != len(self.slots):
             raise ValueError("a slot is listed twice")
@@ -183,6 +185,8 @@ class BatchFeatureTracker:
         frames.set_tracker(max_cnt=self.max_cnt, border=self.border)
         for s, m in (masks or {}).items():
             frames.set_mask(m, slot=int(s))
+        for s, cam in (cameras or {}).items():
+            frames.set_slot_camera(int(s), **cam)
         self.last = [None] * len(self.slots)
 
     def read_images(self, imgs, t, publish=True):
