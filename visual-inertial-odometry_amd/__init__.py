@@ -5,7 +5,7 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, camera, capi, clahe, covariance, detect, exrot, flow, fm, frame, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
+from . import batch_stream, camera, capi, clahe, covariance, detect, est, exrot, flow, fm, frame, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
@@ -13,6 +13,7 @@ from .camera import CameraHandle, CameraLib, parse_camodocal_yaml
 from .clahe import ClaheHandle, ClaheLib
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
 from .detect import DetectHandle, DetectLib
+from .est import BatchEstimatorState, EstHandle, EstLib
 from .exrot import ExrotHandle, ExrotLib
 from .flow import FlowHandle, FlowLib
 from .fm import BatchFeatureManager, FmHandle, FmLib
@@ -45,6 +46,7 @@ CLAHE_LIB = os.path.join(PKG_DIR, "csrc", "libvio_clahe_hip.so")     # include/v
 FRAME_LIB = os.path.join(PKG_DIR, "csrc", "libvio_frame_hip.so")     # include/vio_frame.h; calls nothing of libvio_hip.so either
 FM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_fm_hip.so")           # include/vio_fm.h; calls nothing of libvio_hip.so either
 CAMERA_LIB = os.path.join(PKG_DIR, "csrc", "libvio_camera_hip.so")   # include/vio_camera.h; calls nothing of libvio_hip.so either
+EST_LIB = os.path.join(PKG_DIR, "csrc", "libvio_est_hip.so")         # include/vio_est.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -165,6 +167,11 @@ def load_frame():
 def load_fm():
     """Load the batched FeatureManager library (csrc/libvio_fm_hip.so)."""
     return _load_companion("fm", FmLib, FM_LIB)
+
+
+def load_est():
+    """Load the batched Estimator state library (csrc/libvio_est_hip.so)."""
+    return _load_companion("est", EstLib, EST_LIB)
 
 
 def load_camera():

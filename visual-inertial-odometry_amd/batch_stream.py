@@ -27,10 +27,20 @@ def _check(drivers):
     streams = {d.ctx.get_stream() for d in drivers}
     if len(streams) > 1:
         raise ValueError("run_batched: the drivers' contexts must share one stream (ctx_kwargs=dict(stream=...))")
+    if len({id(d.est) for d in drivers}) > 1:
+        raise ValueError("run_batched: the drivers must share one estimator-state handle (state=(handle, slot)), or none has one")
+    if drivers and drivers[0].est is not None and len({d.est_slot for d in drivers}) != len(drivers):
+        raise ValueError("run_batched: two drivers share an estimator-state slot")
 
 
 def step_batched(drivers, marg):
-    """One frame of every driver in `drivers` (all not finished).  Returns, per driver, whether it has another frame."""
+    """One frame of every driver in `drivers` (all not finished).  Returns, per driver, whether it has another frame.  Drivers
+    created with state= share a handle (_check): the frame then makes one window, one update, one slide and one processIMU call (and
+    one for the headers) for all of them."""
+    est = drivers[0].est
+    if est is not None:
+        for d, win in zip(drivers, est.window_batch([d.est_slot for d in drivers])):
+            d.pull_window(win)
     for d in drivers:
         d.ensure_depths()
     loaded = []
@@ -40,13 +50,17 @@ def step_batched(drivers, marg):
         loaded.append((w, ids))
     reps = drivers[0].lib.batch_solve([d.ctx for d in drivers], 10)
     jobs = []
-    for d, (w, ids), rep in zip(drivers, loaded, reps):
-        poses, sb, _ = d.ctx.get_window()
+    solved = [d.ctx.get_window() for d in drivers]
+    if est is not None:             # double2vector + failureDetection of every window in one call
+        for d, r in zip(drivers, est.update_batch([(d.est_slot, s[0], s[1], d.ext, True) for d, s in zip(drivers, solved)])):
+            d.apply_update(r)
+    for d, (w, ids), rep, (poses, sb, _) in zip(drivers, loaded, reps, solved):
         invd = d.ctx.get_landmarks()
         if d.prior is not None:      # estimator.cpp:1040-1049: b/err prior come back updated, H/Jt stay
             b, e = d.ctx.get_prior()
             d.prior = dict(d.prior, b=b[:156].copy(), err=e.copy())
-        d.poses, d.sb = anchor_gauge(w.poses, poses, sb)
+        if est is None:
+            d.poses, d.sb = anchor_gauge(w.poses, poses, sb)
         for l, v in zip(ids, invd):
             d.depth[l] = 1.0 / v
         newest = d.frames[WINDOW_SIZE]
@@ -60,6 +74,20 @@ def step_batched(drivers, marg):
         jobs.append((kind, w2, d.prior))
     priors = marg.compute_batch(jobs)
     more = []
+    if est is not None:             # slideWindow, then processIMU and the headers of the next frame, one call each
+        for d, p in zip(drivers, priors):
+            d.prior = p
+            more.append(d.next_frame < d.s.n_frames)
+        go = [(d, kind) for d, m, (kind, _, _) in zip(drivers, more, jobs) if m]
+        if go:
+            for (d, kind), r in zip(go, est.slide_batch([(d.est_slot, kind, True) for d, kind in go])):
+                d.apply_slide(r, kind == MARG_OLD)
+            begun = [d.begin_next_frame() for d, _ in go]
+            est.imu_batch([b[1] for b in begun])
+            est.image_batch([b[2] for b in begun])
+            for (d, _), b in zip(go, begun):
+                d.add_frame_observations(b[0])
+        return more
     for d, p, (kind, _, _) in zip(drivers, priors, jobs):
         d.prior = p
         if d.next_frame >= d.s.n_frames:

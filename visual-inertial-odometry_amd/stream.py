@@ -358,7 +358,7 @@ class SimulatorFileStream:
 
 class StreamDriver:
     def __init__(self, lib, stream, ctx_kwargs=None, pos_noise=0.02, rot_noise=0.005, depth_noise=0.05, seed=1,
-                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None, initialize=None):
+                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None, initialize=None, state=None):
         """triangulate=True: a landmark's first depth comes from FeatureManager::triangulate (vio_triangulate, on the
         current pose estimates, feature_manager.cpp:203-257) the first time it enters a solve, as in
         Estimator::solveOdometry (estimator.cpp:489-503), instead of from the perturbed ground truth.
@@ -393,7 +393,14 @@ class StreamDriver:
         counts as failed with status exrot.TRY_FAILED_EXROT + |status| and the calibration's status under `exrot_status`
         (self.init_exrot_status records every try's).  True: the library's defaults; a dict(min_sigma=, min_frames=, huber_deg=):
         its gate; a callable(items) returning the dicts ExrotHandle.exrot_batch returns replaces the library.  None: the
-        ground-truth start below."""
+        ground-truth start below.
+        state=(est_handle, slot): the window states, the intervals' samples and pre-integrations live in slot `slot` of an
+        est.EstHandle (include/vio_est.h; or anything with its batched methods): the ground-truth start is written there as an
+        initialisation result would be, every step reads the window from it (vector2double and the ten records), re-anchors through it
+        (double2vector, with failureDetection's verdict appended to self.failures; a failure raises, there is no reboot policy here),
+        slides through it and feeds the next interval's samples to its processIMU.  Not with initialize= or bias_relinearize=."""
+        if state is not None and (initialize is not None or bias_relinearize is not None):
+            raise ValueError("StreamDriver: state= cannot be combined with initialize= or bias_relinearize=")
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -454,6 +461,56 @@ class StreamDriver:
             self._init_h = self._init_imu = self._sfm_h = self._exrot_h = None
             self.init_sfm_status = []
             self.init_exrot_status = []
+        self.est, self.est_slot = (None, None) if state is None else (state[0], int(state[1]))
+        self.failures = []          # failureDetection's verdict of every step (state set): the update's result dicts
+        if self.est is not None:
+            self._seed_state()
+
+    # ---- the window state in an estimator-state slot (state) -------------------------------------------
+    def _seed_state(self):
+        """The ground-truth start as a full window in the slot: frame_count = WINDOW_SIZE, interval j + 1 = self.intervals[j] at zero
+        linearisation biases, last_R / last_P / last_R0 / last_P0 as after a first solve (estimator.cpp:198-201)."""
+        nz = dict(acc_n=synth.ACC_N, gyr_n=synth.GYR_N, acc_w=synth.ACC_W, gyr_w=synth.GYR_W)
+        nz.update(self.noise)
+        g = (0.0, 0.0, self.g_norm)
+        self.est.set_config(self.ext[0:3], self.ext[3:7], g, nz)
+        ivs = self.intervals
+        off = np.concatenate([[0, 0], np.cumsum([len(iv["dt"]) for iv in ivs])]).astype(np.int64)
+        S = int(off[-1])
+        cat = lambda key, w: np.concatenate([np.asarray(iv[key], dtype=np.float64).reshape(-1, w) for iv in ivs]).reshape(S, w)
+        R = np.array([synth.quat_to_rot(q).reshape(9) for q in self.poses[:, 3:7]])
+        first = np.zeros((NUM_FRAMES, 6))
+        for j, iv in enumerate(ivs):
+            first[j + 1, 0:3], first[j + 1, 3:6] = iv["acc0"], iv["gyr0"]
+        acc, gyr = cat("acc", 3), cat("gyr", 3)
+        self.est.state_set(self.est_slot, dict(
+            frame_count=WINDOW_SIZE, first_imu=1, failure_occur=0, exists=np.ones(NUM_FRAMES, dtype=np.int32), Ps=self.poses[:, 0:3], Rs=R,
+            Vs=self.sb[:, 0:3], Bas=self.sb[:, 3:6], Bgs=self.sb[:, 6:9], Headers=np.array([self.s.times[f] for f in self.frames], dtype=np.float64),
+            tic=self.ext[0:3], ric=synth.quat_to_rot(self.ext[3:7]).reshape(9), g=np.array(g), acc_0=acc[-1], gyr_0=gyr[-1], first=first,
+            lin_bias=np.zeros((NUM_FRAMES, 6)), last_R=R[WINDOW_SIZE], last_P=self.poses[WINDOW_SIZE, 0:3], last_R0=R[0],
+            last_P0=self.poses[0, 0:3], off=off, dt=cat("dt", 1).reshape(S), acc=acc, gyr=gyr))
+
+    def pull_window(self, win=None):
+        """poses, speed-biases and the ten pre-integrations from the slot (win: this slot's entry of a batched window call)."""
+        if win is None:
+            win = self.est.window_batch([self.est_slot])[0]
+        self.poses, self.sb = np.array(win["poses"], dtype=np.float64), np.array(win["speed_bias"], dtype=np.float64)
+        self.preint = [p if isinstance(p, dict) else record_dict(p) for p in win["preint"]]
+
+    def apply_update(self, res):
+        """What double2vector + failureDetection returned for this slot: the re-anchored window and the verdict."""
+        self.failures.append({k: res[k] for k in ("failure", "gate", "singular")})
+        self.poses, self.sb = np.array(res["poses"], dtype=np.float64), np.array(res["speed_bias"], dtype=np.float64)
+        if res["failure"]:
+            raise RuntimeError("StreamDriver: failureDetection fired (gate %d) at frame %d; no reboot policy here" % (res["gate"], self.frames[-1]))
+
+    def begin_next_frame(self):
+        """The next frame's number and the processIMU / processImage items that bring it into the slot."""
+        f = self.next_frame
+        self.next_frame += 1
+        iv = self.s.imu[self.frames[-1]]
+        self.frames.append(f)
+        return f, (self.est_slot, iv["dt"], iv["acc"], iv["gyr"]), (self.est_slot, float(self.s.times[f]), False)
 
     # ---- initialisation (initialize) ------------------------------------------------------------------
     def init_request(self):
@@ -706,6 +763,8 @@ class StreamDriver:
             self.ensure_initialized()
         if self.bias_relinearize is not None:
             self.repropagated.append(self.relinearize_biases())
+        if self.est is not None:
+            self.pull_window()
         self.ensure_depths()
         w, ids = self.window_arrays()
         self.ctx.load(w)
@@ -715,7 +774,10 @@ class StreamDriver:
         if self.prior is not None:      # estimator.cpp:1040-1049: b/err prior come back updated, H/Jt stay
             b, e = self.ctx.get_prior()
             self.prior = dict(self.prior, b=b[:156].copy(), err=e.copy())
-        self.poses, self.sb = anchor_gauge(w.poses, poses, sb)
+        if self.est is not None:
+            self.apply_update(self.est.update_batch([(self.est_slot, poses, sb, self.ext, True)])[0])
+        else:
+            self.poses, self.sb = anchor_gauge(w.poses, poses, sb)
         for l, v in zip(ids, invd):
             self.depth[l] = 1.0 / v
         newest = self.frames[WINDOW_SIZE]
@@ -740,19 +802,34 @@ class StreamDriver:
             self.rejected_ids.extend(bad)
         if self.next_frame >= st.n_frames:
             return False
-        if margin_old:
+        if self.est is not None:
+            self.apply_slide(self.est.slide_batch([(self.est_slot, MARG_OLD if margin_old else MARG_SECOND_NEW, True)])[0], margin_old)
+        elif margin_old:
             self.slide_window_old()
         else:
             self.slide_window_new()
         self.take_next_frame()
         return True
 
-    def slide_window_old(self):
-        """slideWindowOld (estimator.cpp:1144-1199) + removeBackShiftDepth (feature_manager.cpp:276-312)."""
+    def apply_slide(self, res, margin_old):
+        """The FeatureManager side of a slide the slot has made: res is this slot's entry of slide_batch's results."""
+        if not res["slid"]:
+            raise RuntimeError("StreamDriver: the slot's window is not full (frame_count %d)" % res["frame_count"])
+        if margin_old:
+            self.slide_window_old((res["marg_R"], res["marg_P"], res["new_R"], res["new_P"]))
+        else:
+            self.slide_window_new()
+
+    def slide_window_old(self, mats=None):
+        """slideWindowOld (estimator.cpp:1144-1199) + removeBackShiftDepth (feature_manager.cpp:276-312).  mats: the four arrays of
+        slideWindowOld where the slot computed them (state set)."""
         gone = self.frames[0]
-        R0 = synth.quat_to_rot(self.poses[0, 3:7]); R1 = synth.quat_to_rot(self.poses[1, 3:7])
-        ric, tic = synth.quat_to_rot(self.ext[3:7]), self.ext[0:3]
-        mR, mP, nR, nP = R0 @ ric, self.poses[0, 0:3] + R0 @ tic, R1 @ ric, self.poses[1, 0:3] + R1 @ tic
+        if mats is None:
+            R0 = synth.quat_to_rot(self.poses[0, 3:7]); R1 = synth.quat_to_rot(self.poses[1, 3:7])
+            ric, tic = synth.quat_to_rot(self.ext[3:7]), self.ext[0:3]
+            mR, mP, nR, nP = R0 @ ric, self.poses[0, 0:3] + R0 @ tic, R1 @ ric, self.poses[1, 0:3] + R1 @ tic
+        else:
+            mR, mP, nR, nP = mats
         for l in list(self.tracks.keys()):
             tr = self.tracks[l]
             if tr[0][0] != gone:
@@ -767,6 +844,8 @@ class StreamDriver:
                 pj = nR.T @ (mR @ (uv * self.depth[l]) + mP - nP)
                 self.depth[l] = float(pj[2]) if pj[2] > 0 else 5.0       # INIT_DEPTH
         self.frames.pop(0)
+        if self.est is not None:            # (the states and the intervals slid in the slot; the next step pulls them)
+            return
         self.intervals.pop(0)
         self.preint.pop(0)
         if self.bias_relinearize is not None:
@@ -783,6 +862,9 @@ class StreamDriver:
                 self.depth.pop(l, None)
             else:
                 self.tracks[l] = tr
+        if self.est is not None:            # (the slot merged the intervals and copied the state)
+            self.frames.pop(WINDOW_SIZE - 1)
+            return
         # the IMU samples of the newest interval are appended to the one before it
         a, b = self.intervals[WINDOW_SIZE - 2], self.intervals[WINDOW_SIZE - 1]
         merged = dict(acc0=a["acc0"], gyr0=a["gyr0"], dt=a["dt"] + b["dt"], acc=a["acc"] + b["acc"], gyr=a["gyr"] + b["gyr"])
@@ -799,6 +881,12 @@ class StreamDriver:
 
     def take_next_frame(self):
         """The next image: processIMU's propagation of the newest state, then the frame's observations."""
+        if self.est is not None:            # processIMU over the interval's samples, Headers[frame_count], in the slot
+            f, imu_item, image_item = self.begin_next_frame()
+            self.est.imu_batch([imu_item])
+            self.est.image_batch([image_item])
+            self.add_frame_observations(f)
+            return
         st = self.s
         f = self.next_frame
         self.next_frame += 1
