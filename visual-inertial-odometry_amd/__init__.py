@@ -5,10 +5,11 @@ include/vio_backend.h).  There is no CPU fallback: `load_hip()` raises if the li
 """
 import os
 
-from . import batch_stream, camera, capi, clahe, covariance, detect, est, exrot, flow, fm, frame, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
+from . import aif, batch_stream, camera, capi, clahe, covariance, detect, est, exrot, flow, fm, frame, frontend, imu, init, marg, pnp, reject, residuals, sfm, sharded, stream, synth
 from .capi import (CAM_DIM, LOSS_CAUCHY, LOSS_HUBER, LOSS_TRIVIAL, LOSS_TUKEY, MARG_OLD, MARG_SECOND_NEW,
                    NUM_FRAMES, POSE_DIM, PRIOR_DIM, WINDOW_SIZE, VioConfig, VioContext, VioError, VioLib,
                    VioPreint, VioSolveReport)
+from .aif import AifHandle, AifLib, BatchImageFrames, initialize_from_frames
 from .camera import CameraHandle, CameraLib, parse_camodocal_yaml
 from .clahe import ClaheHandle, ClaheLib
 from .covariance import GAUGE_FIX_OLDEST, GAUGE_NONE, CovLib, pose_block, speed_bias_block
@@ -47,6 +48,7 @@ FRAME_LIB = os.path.join(PKG_DIR, "csrc", "libvio_frame_hip.so")     # include/v
 FM_LIB = os.path.join(PKG_DIR, "csrc", "libvio_fm_hip.so")           # include/vio_fm.h; calls nothing of libvio_hip.so either
 CAMERA_LIB = os.path.join(PKG_DIR, "csrc", "libvio_camera_hip.so")   # include/vio_camera.h; calls nothing of libvio_hip.so either
 EST_LIB = os.path.join(PKG_DIR, "csrc", "libvio_est_hip.so")         # include/vio_est.h; calls nothing of libvio_hip.so either
+AIF_LIB = os.path.join(PKG_DIR, "csrc", "libvio_aif_hip.so")         # include/vio_aif.h; calls nothing of libvio_hip.so either
 
 _hip = None
 
@@ -172,6 +174,11 @@ def load_fm():
 def load_est():
     """Load the batched Estimator state library (csrc/libvio_est_hip.so)."""
     return _load_companion("est", EstLib, EST_LIB)
+
+
+def load_aif():
+    """Load the resident all_image_frame library (csrc/libvio_aif_hip.so)."""
+    return _load_companion("aif", AifLib, AIF_LIB)
 
 
 def load_camera():

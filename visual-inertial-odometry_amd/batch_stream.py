@@ -104,13 +104,13 @@ def step_batched(drivers, marg):
 
 def _init_group_key(d):
     """What one alignment call shares across its windows: the extrinsic translation (TIC[0]), G, the IMU noise of the re-propagation,
-    the aligner, the SfM, the extrinsic rotation calibration and the device the group's handles are created on.  Drivers that differ in any of them are aligned in separate calls."""
+    the aligner, the SfM, the extrinsic rotation calibration, the all_image_frame handle (all_frames) and the device the group's handles are created on.  Drivers that differ in any of them are aligned in separate calls."""
     noise = tuple(sorted((k, float(v)) for k, v in d.noise.items()))
     sfm = d.initialize.get("sfm")
     cal = d.initialize.get("calibrate_ric")
     cal = id(cal) if callable(cal) else (tuple(sorted(cal.items())) if isinstance(cal, dict) else bool(cal))
     return (tuple(float(v) for v in d.ext[0:3]), float(d.g_norm), noise, id(d.initialize.get("aligner")),
-            id(sfm) if callable(sfm) else bool(sfm), cal, int(d.ctx.cfg.device))
+            id(sfm) if callable(sfm) else bool(sfm), cal, int(d.ctx.cfg.device), id(d.aif))
 
 
 def initialize_batched(drivers):
@@ -119,7 +119,9 @@ def initialize_batched(drivers):
     drivers still trying that share an extrinsic, G, IMU noise and aligner (usually one group), then applies each outcome as
     StreamDriver.ensure_initialized does.  Drivers created with `sfm` get their camera poses from one SfM call per group and round
     (SfmHandle.sfm_batch) in front of the alignment call, and drivers created with `calibrate_ric` their camera-IMU rotation from one
-    calibration call per group and round (ExrotHandle.exrot_batch) in front of that.  Returns the number of rounds."""
+    calibration call per group and round (ExrotHandle.exrot_batch) in front of that.  Drivers created with `all_frames` take the try
+    from their resident all_image_frame slots: aif.initialize_from_frames' four calls per group and round in the alignment call's
+    place.  Returns the number of rounds."""
     pending = [d for d in drivers if not d.initialized]
     rounds = 0
     while pending:

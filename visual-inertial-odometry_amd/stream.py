@@ -356,6 +356,24 @@ class SimulatorFileStream:
         self.init_noise = np.random.RandomState(seed).normal(size=(len(self.lm_host),))
 
 
+def aif_flush(drivers):
+    """Feeds the INITIAL-state steps that `drivers` (all on one aif.AifHandle) have queued into their all_image_frame slots: per step
+    one slide_batch, one imu_batch and one image_batch over every driver that has one.  A refused item (POOL_FULL, FRAMES_FULL,
+    NO_FRAME) would leave its slot out of step with the driver's lists, so it raises."""
+    todo = [d for d in drivers if d._aif_queue]
+    while todo:
+        steps = [(d, d._aif_queue.pop(0)) for d in todo]
+        for part, name in enumerate(("slide_batch", "imu_batch", "image_batch")):
+            who = [d for d, st in steps if st[part] is not None]
+            if not who:
+                continue
+            res = getattr(who[0].aif, name)([(d.aif_slot,) + st[part] for d, st in steps if st[part] is not None])
+            for d, r in zip(who, res):
+                if r["status"] != 0:
+                    raise RuntimeError("StreamDriver: vio_aif_%s refused slot %d with status %d" % (name, d.aif_slot, r["status"]))
+        todo = [d for d in todo if d._aif_queue]
+
+
 class StreamDriver:
     def __init__(self, lib, stream, ctx_kwargs=None, pos_noise=0.02, rot_noise=0.005, depth_noise=0.05, seed=1,
                  triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None, initialize=None, state=None):
@@ -392,7 +410,14 @@ class StreamDriver:
         InitialEXRotation::CalibrationExRotation); on success self.ext[3:7] is set before the SfM and the alignment, on failure the try
         counts as failed with status exrot.TRY_FAILED_EXROT + |status| and the calibration's status under `exrot_status`
         (self.init_exrot_status records every try's).  True: the library's defaults; a dict(min_sigma=, min_frames=, huber_deg=):
-        its gate; a callable(items) returning the dicts ExrotHandle.exrot_batch returns replaces the library.  None: the
+        its gate; a callable(items) returning the dicts ExrotHandle.exrot_batch returns replaces the library.  An `all_frames` entry
+        (with `sfm`), (aif_handle, slot): the window's images and samples are fed into slot `slot` of an aif.AifHandle
+        (include/vio_aif.h) while the driver is in the INITIAL state, and every try comes from aif.initialize_from_frames over that
+        slot (the structure call on the SfM's result, the gyro bias, the re-propagation and the alignment) instead of
+        InitHandle.initialize_batch over the driver's lists; a key walk or PnP that fails is a failed try with status
+        sfm.TRY_FAILED_SFM.  The slot is fed in steps that are queued and sent in front of a try, for every driver of a group in
+        one call each (aif_flush).  The handle's IMU noise is the caller's to set (AifHandle.set_config) and must equal the
+        stream's; an `aligner` cannot be combined with `all_frames` (both raise ValueError).  None: the
         ground-truth start below.
         state=(est_handle, slot): the window states, the intervals' samples and pre-integrations live in slot `slot` of an
         est.EstHandle (include/vio_est.h; or anything with its batched methods): the ground-truth start is written there as an
@@ -461,6 +486,19 @@ class StreamDriver:
             self._init_h = self._init_imu = self._sfm_h = self._exrot_h = None
             self.init_sfm_status = []
             self.init_exrot_status = []
+        self.aif, self.aif_slot = None, None
+        if self.initialize is not None and self.initialize.get("all_frames") is not None:
+            if not self.initialize.get("sfm"):
+                raise ValueError("StreamDriver: all_frames needs sfm (initialStructure's frame work starts from the SfM)")
+            if self.initialize.get("aligner") is not None:
+                raise ValueError("StreamDriver: all_frames takes the try from the library (aif.initialize_from_frames); it cannot be combined with an aligner")
+            self.aif, self.aif_slot = self.initialize["all_frames"][0], int(self.initialize["all_frames"][1])
+            nz = dict(acc_n=synth.ACC_N, gyr_n=synth.GYR_N, acc_w=synth.ACC_W, gyr_w=synth.GYR_W)
+            nz.update(self.noise)
+            held = getattr(self.aif, "noise", None)         # (an AifHandle remembers its set_config; a stand-in without one is not checked)
+            if held is not None and tuple(float(nz[k]) for k in ("acc_n", "gyr_n", "acc_w", "gyr_w")) != tuple(float(v) for v in held):
+                raise ValueError("StreamDriver: the stream's IMU noise differs from the all_frames handle's (AifHandle.set_config); the slot's records would not be the driver's")
+            self._aif_seed()
         self.est, self.est_slot = (None, None) if state is None else (state[0], int(state[1]))
         self.failures = []          # failureDetection's verdict of every step (state set): the update's result dicts
         if self.est is not None:
@@ -513,6 +551,37 @@ class StreamDriver:
         return f, (self.est_slot, iv["dt"], iv["acc"], iv["gyr"]), (self.est_slot, float(self.s.times[f]), False)
 
     # ---- initialisation (initialize) ------------------------------------------------------------------
+    def _aif_push(self, k, slide=None, first=None):
+        """Queues window frame k for the all_image_frame slot as one step (slide, imu, image): the erase up to header `slide`
+        (slideWindow) if given, the samples since frame k - 1 (processIMU; `first`: one sample in front of the first image), then the
+        image (processImage).  aif_flush feeds the queued steps of many drivers in one call each."""
+        f = self.frames[k]
+        iv = first if k == 0 else self.intervals[k - 1]
+        imu = None if iv is None else (np.array(iv["dt"], dtype=np.float64), np.array(iv["acc"], dtype=np.float64), np.array(iv["gyr"], dtype=np.float64))
+        # a track's observations are consecutive window frames from its first one, so frame k's is entry k - (index of that first frame):
+        # one look per track, not a scan of its list
+        pos = {fr: i for i, fr in enumerate(self.frames)}
+        obs = []
+        for l, tr in self.tracks.items():
+            j = k - pos[tr[0][0]]
+            if 0 <= j < len(tr):
+                if tr[j][0] != f:
+                    raise RuntimeError("StreamDriver: track %d is not consecutive in the window's frames" % l)
+                obs.append((l, tr[j][1]))
+        ids = np.array([l for l, _ in obs], dtype=np.int64)
+        pts = np.array([p for _, p in obs], dtype=np.float64).reshape(-1, 2)
+        image = (float(self.s.times[f]), ids, pts, self.sb[k, 3:6].copy(), self.sb[k, 6:9].copy())
+        self._aif_queue.append((None if slide is None else (float(slide),), imu, image))
+
+    def _aif_seed(self):
+        """The window as the INITIAL state has seen it, queued for the slot.  One sample in front of the first image carries the first
+        interval's acc_0 / gyr_0 (it is dropped: no image yet; acc_0 / gyr_0 follow)."""
+        self.aif.reset(self.aif_slot)
+        self._aif_queue = []
+        iv = self.intervals[0]
+        for k in range(len(self.frames)):
+            self._aif_push(k, first=dict(dt=[0.0], acc=[iv["acc0"]], gyr=[iv["gyr0"]]))
+
     def init_request(self):
         """The current window as an alignment item (visual_trajectory's R / T, the zero-bias records) and its raw intervals."""
         c = self.initialize
@@ -540,6 +609,7 @@ class StreamDriver:
                 self._sfm_h = load_sfm().create(device=self.ctx.cfg.device)
             res = self._sfm_h.sfm_batch([it["sfm_item"] for it in items])
         for it, r in zip(items, res):
+            it["sfm_result"] = r
             ric = synth.quat_to_rot(it["owner"].ext[3:7])
             done = sfm_items_to_init_items([r], ric, [it["pre"]])[0]
             if done is not None:
@@ -589,12 +659,38 @@ class StreamDriver:
                 out[i] = dict(status=TRY_FAILED_SFM + abs(st), sfm_status=st)               # an SfM failure: a failed try
                 if st == 0:
                     ok.append(i)
-            if ok:
-                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "exrot_item", "owner")} for i in ok]
+            if ok and c.get("all_frames") is not None:
+                for i, r in zip(ok, self._init_from_frames([items[i] for i in ok])):
+                    out[i] = r
+            elif ok:
+                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "exrot_item", "owner", "sfm_result")} for i in ok]
                 for i, r in zip(ok, self._init_align(plain, [intervals[i] for i in ok])):
                     out[i] = r
             return out
         return self._init_align(items, intervals)
+
+    def _init_from_frames(self, items):
+        """One try of every item's owner from its all_image_frame slot (aif.initialize_from_frames: four calls for the group).  The
+        items' R / T become the structure call's; a slot whose key walk or PnP failed is a failed try."""
+        from .aif import BatchImageFrames, initialize_from_frames
+        from .sfm import TRY_FAILED_SFM, item_from_tracks
+        if self._init_h is None:
+            from . import load_init
+            self._init_h = load_init().create(device=self.ctx.cfg.device)
+        owners = [it["owner"] for it in items]
+        aif_flush(owners)
+        res = initialize_from_frames(BatchImageFrames(self.aif, [d.aif_slot for d in owners]), self._init_h, [it["sfm_result"] for it in items],
+                                     [[float(d.s.times[f]) for f in d.frames] for d in owners],
+                                     [np.array(item_from_tracks(d.tracks, d.frames)[1], dtype=np.int64) for d in owners],
+                                     np.stack([synth.quat_to_rot(d.ext[3:7]) for d in owners]), self.ext[0:3].copy(), self.g_norm)
+        out = []
+        for it, r in zip(items, res):
+            if r is None:
+                out.append(dict(status=TRY_FAILED_SFM, sfm_status=0))
+                continue
+            it["R"], it["T"] = r["structure"]["R"], r["structure"]["T"]
+            out.append(r)
+        return out
 
     def _init_align(self, items, intervals):
         c = self.initialize
@@ -652,6 +748,8 @@ class StreamDriver:
         self.preint.pop(0)
         self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
         self.take_next_frame()
+        if self.aif is not None:
+            self._aif_push(len(self.frames) - 1, slide=self.s.times[gone])
         return False
 
     def ensure_initialized(self):
