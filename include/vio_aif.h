@@ -159,7 +159,9 @@ vio_status vio_aif_propagate_batch(vio_aif *h, int32_t count, const vio_aif_prop
  *   1. the records of intervals 1 .. F - 1, each at its constructor biases (k_imu_propagate), byte for byte ImuHandle.load + propagate;
  *   2. the excitation check over them: sum_g from zero (the reference leaves it uninitialised), frames 1 .. F - 1 in time order,
  *      tmp_g = delta_v / sum_dt, aver_g = (sum_g * 1.0) / (F - 1), var += (x x + y y) + z z of tmp_g - aver_g, var = sqrt(var / (F - 1)).
- *      Returned with the flag var < 0.25; the reference's `return false` is commented out, so it never fails a window;
+ *      Returned with the flag var < 0.25; the reference's `return false` is commented out, so it never fails a window.  var is NaN
+ *      (0 / 0, as the lines give) and the flag 0 where F <= 1 or an interval has no samples (its record's sum_dt is 0); which NaN, its
+ *      sign and payload, is not specified: a host's 0 / 0 and the device's differ in the sign bit;
  *   3. the key walk as written, i from 0: a frame whose header equals headers[i] is a keyframe, R = Q[i].toRotationMatrix() ric^T
  *      (Eigen's, of the quaternion as given; (A_i0 ric_j0 + A_i1 ric_j1) + A_i2 ric_j2), T = T[i], i++; otherwise
  *      `if (header > headers[i]) i++`, once, and the guess is keyframe i.  A leading non-keyframe gets guess 0.  i reaching n_key where
@@ -172,7 +174,8 @@ vio_status vio_aif_propagate_batch(vio_aif *h, int32_t count, const vio_aif_prop
  *   6. R = toRotationMatrix(Q_pnp) ric^T, T = T_pnp for the non-keyframes (:365-373); R, T, is_key go into the slot and to the caller.
  * A frame that fails leaves NaN in its R and T; the frames after it are still computed (as in vio_pnp.h).  A slot one of whose
  * frames is VIO_ERR_NOT_FINITE has NaN in every non-keyframe and pnp_status VIO_ERR_NOT_FINITE; the other slots are not touched and
- * the call returns VIO_OK. */
+ * the call returns VIO_OK.  An empty slot (F = 0) is VIO_AIF_STATUS_WALK, as the walk over no frames finds none of the n_key >= 1 headers:
+ * n_frames 0, n_key 0, var NaN, and no out array of the item is written. */
 typedef struct vio_aif_structure_item {
     int32_t slot;
     int32_t n_key;                  /* in [1, VIO_AIF_MAX_KEY] */

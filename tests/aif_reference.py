@@ -158,16 +158,16 @@ def excitation(records):
     """aif_excitation over the (n, 467) records of frames 1 .. F - 1: sum_dt at [0], delta_v at [8:11].  n = 0 gives NaN."""
     rec = np.asarray(records, dtype=np.float64).reshape(-1, 467)
     n = len(rec)
-    sum_g = [0.0, 0.0, 0.0]
-    for r in rec:
-        for c in range(3):
-            sum_g[c] = sum_g[c] + float(r[8 + c]) / float(r[0])
-    with np.errstate(all="ignore"):
+    sum_g = [np.float64(0.0)] * 3
+    with np.errstate(all="ignore"):                         # (a record with sum_dt 0, an interval without samples, divides 0 by 0)
+        for r in rec:
+            for c in range(3):
+                sum_g[c] = sum_g[c] + r[8 + c] / r[0]
         dn = np.float64(n)
         aver = [np.float64(sum_g[c] * 1.0) / dn for c in range(3)]
         var = np.float64(0.0)
         for r in rec:
-            x, y, z = (np.float64(float(r[8 + c]) / float(r[0])) - aver[c] for c in range(3))
+            x, y, z = (r[8 + c] / r[0] - aver[c] for c in range(3))
             var = var + ((x * x + y * y) + z * z)
         return float(np.sqrt(var / dn))
 

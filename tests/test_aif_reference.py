@@ -1,7 +1,9 @@
 """tests/aif_reference.py, the pin of libvio_aif_hip.so, against what it restates: its key walk against pnp.guess_keys where that one
 is defined, its map and erase rule against a plain dict on random call sequences, the host build of csrc/vio_aif_math.h
 (tests/cpp/aif_math_main.cpp, under ASan and UBSan with VIO_TEST_SANITIZE=1) bit for bit, and the scenes of tests/test_gpu_aif.py
-against tests/pnp_reference.py alone, so that no frame of them is left out on the device."""
+against tests/pnp_reference.py alone, so that no frame of them is left out on the device; for the scenes of
+tests/test_gpu_aif_limits.py (aif_scenes.LIMIT_SCENES) also which frames fail and how, that none is undecidable, the sizes and
+positions the device tests name, and var's distance from the flag's threshold."""
 import os
 import shutil
 import subprocess
@@ -94,6 +96,99 @@ def test_scenes_of_the_device_tests_are_solved_by_the_pnp_restatement_alone():
         sc.feed(ref, 0, scene)
         out = pr.frames(ar.pnp_item(ref.frames_get(0), scene["item"], scene["is_key"], ar.walk([f["t"] for f in ref.frames_get(0)["frames"]], scene["item"]["headers"].tolist())[2]))
         assert out["frame_status"].tolist() == [status, 0, 0, 0] and out["n_used"][0] == keep
+
+
+FEW = pr.FAIL_FEW_POINTS
+# what tests/test_gpu_aif_limits.py relies on, per scene of aif_scenes.LIMIT_SCENES: (status, n_used) of every non-keyframe in order
+LIMIT_OUTCOMES = {
+    "tracks0": [(FEW, 0)], "tracks1": [(FEW, 1)], "tracks255": [(0, 251)], "tracks256": [(0, 252)], "tracks257": [(0, 253)], "tracks4096": [(0, 1017)],
+    "sizes": [(FEW, 0), (FEW, 5), (0, 6), (0, 61), (0, 62), (0, 62), (0, 251), (0, 252), (0, 252), (0, 1018)],
+    "five_six_of_1024": [(FEW, 5), (0, 6)], "nkk257": [(0, None)], "pool": [(0, None)] * 8, "one": [], "two": [(0, None)], "all_key": [],
+    "gap": [(0, None)], "no_gap": [(0, None)], "rest": [(0, None)], "nineteen_twenty": [(0, 19), (0, 20)], "longer": [(0, None)] * 5,
+}
+
+
+def solved_on_the_cpu(scene, cfg=None):
+    ref = ar.ImageFramesReference()
+    sc.feed(ref, 0, scene)
+    slot = ref.frames_get(0)
+    st, is_key, guess = ar.walk([f["t"] for f in slot["frames"]], scene["item"]["headers"].tolist())
+    assert st == ar.STATUS_OK and is_key == scene["is_key"]
+    item = ar.pnp_item(slot, scene["item"], is_key, guess)
+    return slot, item, pr.frames(item, cfg)
+
+
+@pytest.mark.parametrize("name", sorted(sc.LIMIT_SCENES))
+def test_limit_scenes_do_on_the_cpu_what_the_device_tests_rely_on(vio, name):
+    """Conditions on the inputs of tests/test_gpu_aif_limits.py, from the restatements alone: every frame meant to solve does, every
+    frame meant to fail fails as intended, no solved frame is undecidable (cap 0), and var is far from the flag's threshold."""
+    from vio_amd import synth
+    assert set(LIMIT_OUTCOMES) == set(sc.LIMIT_SCENES)
+    scene = sc.limit_scene(name)
+    slot, item, out = solved_on_the_cpu(scene)
+    want = LIMIT_OUTCOMES[name]
+    usable = [u for u, k in zip(sc.usable_counts(scene), scene["is_key"]) if not k]
+    assert out["n_used"].tolist() == usable                 # the restatement's join against plain numpy on the ids
+    assert len(want) == len(usable) and out["frame_status"].tolist() == [w[0] for w in want]
+    assert all(w[1] is None or w[1] == u for w, u in zip(want, usable)) and all(u >= 6 for w, u in zip(want, usable) if w[0] == 0)
+    first_bad = [k for k, w in enumerate(want) if w[0] != 0]
+    assert (out["status"], out["fail_frame"]) == ((want[first_bad[0]][0], first_bad[0]) if first_bad else (pr.OK, -1))
+    assert pr.undecidable(item) == 0, "an undecidable frame: take another seed"
+    ids = scene["item"]["track_ids"]
+    if len(ids) >= 3:
+        assert ids.min() < 0 and ids.max() > 1 << 32 and np.any(np.diff(ids) > 0) and np.any(np.diff(ids) < 0)
+        table = set(ids.tolist())
+        for f, key in zip(scene["frames"], scene["is_key"]):           # a non-keyframe sees the ends of the table, and strangers all around it
+            if key or len(f["ids"]) < 2:
+                continue
+            assert {int(ids.min()), int(ids.max())} <= set(f["ids"].tolist())
+            strangers = [v for v in f["ids"].tolist() if v not in table]
+            if len(strangers) >= 3:
+                assert min(strangers) < ids.min() and max(strangers) > ids.max()
+                # (at 65 stored observations the unusable positions 0, 63 and 64 are the first and the two behind the last usable one)
+                assert any(ids.min() < v < ids.max() for v in strangers) or len(f["ids"]) == 65
+    F = len(slot["frames"])
+    if F >= 2:
+        pre = [synth.preintegrate(iv["acc0"], iv["gyr0"], f["bias"][0:3], f["bias"][3:6], iv["dt"], iv["acc"], iv["gyr"])
+               for iv, f in zip(ar.intervals(slot), slot["frames"][1:]) if len(iv["dt"])]
+        rec = np.zeros((len(pre), 467))
+        rec[:, 0], rec[:, 8:11] = [p["sum_dt"] for p in pre], [p["delta_v"] for p in pre]
+        var = ar.excitation(rec)
+        print(name, "var", var)
+        assert abs(var - 0.25) >= 0.1 and (var < 0.25) == (name in ("rest", "two"))           # (one record is its own average: var is 0)
+
+
+def test_limit_scenes_have_the_sizes_and_the_unusable_positions_the_device_tests_name():
+    sizes = sc.limit_scene("sizes")
+    stored = [len(f["ids"]) for f, k in zip(sizes["frames"], sizes["is_key"]) if not k]
+    assert tuple(stored) == sc.SIZES and sum(stored) == 1995
+    for k, n in enumerate(sc.SIZES):
+        want = sorted(set([p for p in sc.SIZES_BAD if p < n] + [n - 1])) if n >= 63 else []
+        assert sc.unusable_positions(sizes, 2 * k + 1) == want, n
+    item = sizes["item"]
+    bad = np.concatenate([np.sort(f["ids"])[sc.unusable_positions(sizes, j)] for j, f in enumerate(sizes["frames"]) if not sizes["is_key"][j]])
+    is_dead = np.isin(bad, item["track_ids"][item["state"] == 0])
+    assert is_dead.any() and not is_dead.all()              # both kinds of unusable observation: a dead track and an id no track has
+    few = sc.limit_scene("five_six_of_1024")
+    assert [len(f["ids"]) for f in few["frames"][1:3]] == [1024, 1024] and sc.usable_counts(few)[1:3] == [5, 6]
+    big = sc.limit_scene("tracks4096")
+    item = big["item"]
+    srt = np.argsort(item["track_ids"])
+    assert np.nonzero(item["state"][srt] == 0)[0].tolist() == [0, 255, 256, 4095] and set(item["track_ids"][item["state"] == 0].tolist()) <= set(big["frames"][0]["ids"].tolist())
+    assert len(big["frames"][0]["ids"]) == 1024
+    pool = sc.limit_scene("pool")
+    ref = ar.ImageFramesReference()
+    sc.feed(ref, 0, pool)
+    assert ar.n_points(ref.frames_get(0)) == ar.MAX_POINTS == 8192 and len(pool["frames"]) == 19 and len(pool["item"]["track_ids"]) == 4096
+    assert [len(f["ids"]) for f, k in zip(pool["frames"], pool["is_key"]) if not k] == [1003] * 8 and int((pool["item"]["state"] == 0).sum()) == 300
+    gap, no_gap = sc.limit_scene("gap"), sc.limit_scene("no_gap")
+    assert [len(f["samples"][0]) for f in gap["frames"]] == [20] * 5 + [0] + [20] * 6
+    for j, (f, g) in enumerate(zip(gap["frames"], no_gap["frames"])):      # the two differ in that interval's samples alone
+        assert np.array_equal(f["ids"], g["ids"]) and np.array_equal(f["pts"], g["pts"]) and (j == 5 or np.array_equal(f["samples"][1], g["samples"][1]))
+    # min_points = 20: 19 usable points fail, 20 solve
+    scene = sc.limit_scene("nineteen_twenty")
+    out = solved_on_the_cpu(scene, dict(min_points=20))[2]
+    assert out["frame_status"].tolist() == [FEW, 0] and out["n_used"].tolist() == [19, 20]
 
 
 def test_windows_of_the_end_to_end_test_are_aligned_by_the_restatements_alone(vio, oracle_lib):
@@ -196,6 +291,17 @@ def test_host_build_of_the_math_equals_the_restatement_bit_for_bit(driver):
             script.append("S %d %s %d" % (n, ints(srt), probe))
             hit = np.nonzero(srt == probe)[0]
             want.append(([int(hit[0]) if len(hit) else -1], []))
+    # the largest track table: every rank, and the bisection at the ends, at a thread's second row, in a gap and beyond
+    ids = (rng.choice(1 << 20, 4096, replace=False).astype(np.int64) - (1 << 19)) * 64
+    ids[::3] += 1 << 33
+    script.append("K 4096 %s" % ints(ids))
+    want.append(([ar.rank(ids.tolist(), i) for i in range(4096)], []))
+    assert sorted(want[-1][0]) == list(range(4096)) and np.array_equal(ids[np.argsort(want[-1][0])], np.sort(ids))
+    srt = np.sort(ids)
+    for probe in [int(srt[k]) for k in (0, 255, 256, 2047, 2048, 4095)] + [int(srt[0]) - 1, int(srt[100]) + 1, int(srt[4095]) + 1]:
+        script.append("S 4096 %s %d" % (ints(srt), probe))
+        hit = np.nonzero(srt == probe)[0]
+        want.append(([int(hit[0]) if len(hit) else -1], []))
     ts = np.cumsum(rng.uniform(0.01, 0.1, 32))
     for n, t_0 in ((0, 1.0), (1, ts[0]), (32, ts[0]), (32, ts[31]), (32, ts[7]), (32, 0.5 * (ts[3] + ts[4])), (5, ts[5])):
         script.append("F %d %s" % (n, hexs(np.concatenate([ts[:n], [t_0]]))))
@@ -224,7 +330,15 @@ def test_host_build_of_the_math_equals_the_restatement_bit_for_bit(driver):
         rec[:, 0], rec[:, 8:11] = rng.uniform(0.05, 0.2, n), rng.randn(n, 3) + [0, 0, 1]
         script.append("E %d %s" % (n, hexs(rec[:, [0, 8, 9, 10]])))
         want.append(([], [ar.excitation(rec)]))
-    cases = [(list(range(1, 7)), [2, 4, 6]), ([1, 2, 3], [1, 2.5, 3]), ([1, 2], [1]), ([1, 2, 3, 4], [3, 4]), ([1], [1]), ([1, 2], [0.5, 2])]
+    for zero in (0, 3):                                     # a record whose sum_dt is 0 (an interval without samples): 0 / 0 in the sums
+        rec = np.zeros((5, 467))
+        rec[:, 0], rec[:, 8:11] = rng.uniform(0.05, 0.2, 5), rng.randn(5, 3)
+        rec[zero, 0], rec[zero, 8:11] = 0.0, 0.0
+        script.append("E 5 %s" % hexs(rec[:, [0, 8, 9, 10]]))
+        want.append(([], [ar.excitation(rec)]))
+        assert np.isnan(want[-1][1][0])
+    full = np.cumsum(rng.uniform(0.01, 0.1, 32)).tolist()
+    cases = [(list(range(1, 7)), [2, 4, 6]), ([], [1.0]), (full, full), (full, full[:31]), (full[:31], full), ([1, 2, 3], [1, 2.5, 3]), ([1, 2], [1]), ([1, 2, 3, 4], [3, 4]), ([1], [1]), ([1, 2], [0.5, 2])]
     for t, hd in cases:
         script.append("W %d %s %d %s" % (len(t), hexs(t), len(hd), hexs(hd)))
         st, key, guess = ar.walk([float(v) for v in t], [float(v) for v in hd])
@@ -236,7 +350,7 @@ def test_host_build_of_the_math_equals_the_restatement_bit_for_bit(driver):
     lines = [ln.split() for ln in open(fout).read().splitlines()]
     assert len(lines) == len(script)
     for ln, sc_, (iv, fv) in zip(lines, script, want):
-        assert ln[0] == sc_[0]
+        assert ln[0] == sc_[0] and len(ln) == 1 + len(iv) + len(fv)
         assert [int(v) for v in ln[1:1 + len(iv)]] == [int(v) for v in iv], (sc_[:40], ln[:6])
         got = [float.fromhex(v) for v in ln[1 + len(iv):]]
         assert len(got) == len(fv) and all(np.float64(a).tobytes() == np.float64(b).tobytes() for a, b in zip(got, fv)), (sc_[:40], got, fv)

@@ -258,7 +258,10 @@ def expect(vio, imu_handle, pnp_handle, ref_slot, item, got):
     rec = records(got["preint"], F - 1)
     assert rec.tobytes() == constructor_records(vio, imu_handle, ref_slot).tobytes()
     var = ar.excitation(rec)                                # the restatement's sums over the device's own records
-    assert np.float64(got["var"]).tobytes() == np.float64(var).tobytes() and got["low_excitation"] == int(var < 0.25)
+    # var is bit for bit the restatement's where it is a number.  Where it is NaN (F = 1, or an interval without samples) this is
+    # looser than "bit for bit": any NaN of the device is taken.  include/vio_aif.h leaves that NaN's sign and payload open, because
+    # 0 / 0 sets the sign bit on an x86 host (the restatement here) and clears it on the device; the flag is held either way.
+    assert (np.float64(got["var"]).tobytes() == np.float64(var).tobytes() or (np.isnan(var) and np.isnan(got["var"]))) and got["low_excitation"] == int(var < 0.25)
     st, is_key, guess = ar.walk([f["t"] for f in ref_slot["frames"]], item["headers"].tolist())
     assert got["status"] == st == ar.STATUS_OK and got["is_key"].tolist() == is_key and got["n_key"] == sum(is_key) and got["n_frames"] == F
     pitem = ar.pnp_item(ref_slot, item, is_key, guess)
