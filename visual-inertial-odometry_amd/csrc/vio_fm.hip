@@ -1,7 +1,7 @@
 // vio_fm.hip — libvio_fm_hip.so: the FeatureManager of many streams in one call, each stream's track list resident on the device
 // (include/vio_fm.h).
 // Contraction is off (vio_fm_math.h): the parallax term and the depth shift are evaluated as written.  No floating-point atomics.
-// The kernels, described where they are, are in vio_fm_body.inc; the triangulation is vio_triangulate_body.h, a function around the
+// The kernels, described where they are, are in vio_fm_body.inc and (include/vio_fm_stream.h's two) vio_fm_stream_body.inc; the triangulation is vio_triangulate_body.h, a function around the
 // text (vio_triangulate_body.inc) that k_triangulate of libvio_hip includes.
 #include <hip/hip_runtime.h>
 
@@ -13,6 +13,7 @@
 #include <vector>
 
 #include "../../include/vio_fm.h"
+#include "../../include/vio_fm_stream.h"
 #include "vio_companion.h"
 #include "vio_device_math.h"
 #include "vio_types.h"
@@ -22,6 +23,7 @@
 #include "vio_fm_math.h"
 
 #include "vio_fm_body.inc"
+#include "vio_fm_stream_body.inc"
 
 static_assert(FM_MAX_TRACKS == VIO_FM_MAX_TRACKS && FM_MAX_OBS == VIO_FM_MAX_OBS && FM_MAX_POINTS == VIO_FM_MAX_POINTS &&
               FM_BACK_SHIFT_DEPTH == VIO_FM_BACK_SHIFT_DEPTH && FM_BACK == VIO_FM_BACK && FM_FRONT == VIO_FM_FRONT &&
@@ -429,6 +431,73 @@ vio_status vio_fm_tracks_get(vio_fm *h, int32_t slot, int32_t cap, int64_t cap_p
         off[i + 1] = off[i] + k;
     }
     return VIO_OK;
+}
+
+// ---- include/vio_fm_stream.h ---------------------------------------------------------------------------------
+
+vio_status vio_fm_init_depth_batch(vio_fm *h, int32_t count, const vio_fm_init_depth_item *items, vio_fm_result *results) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    const Tick t0 = std::chrono::steady_clock::now();
+    vio_status st = begin_call(h, "vio_fm_init_depth_batch", count, items, results);
+    if (st != VIO_OK || count == 0) return st;
+    const size_t b_pose = align256(8 * (FM_INIT_S + 1));
+    for (int i = 0; i < count; ++i) {
+        const vio_fm_init_depth_item &it = items[i];
+        if (!it.poses || !it.ext) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_init_depth_batch: item %d: poses and ext are required", i);
+        if (!all_finite(it.poses, 7 * VIO_NF) || !all_finite(it.ext, 7)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_init_depth_batch: item %d: a pose is not finite", i);
+        if (!std::isfinite(it.s) || !(it.s > 0)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_init_depth_batch: item %d: s must be finite and > 0", i);
+        h->its[(size_t)i].o_in = (int64_t)(b_pose * (size_t)i);
+    }
+    return run_call(h, t0, count, items, results, b_pose * (size_t)count, 0, k_fm_init_depth, FM_EXPORT_NT,
+                    [&](char *in) {
+                        for (int i = 0; i < count; ++i) {
+                            double *p = (double *)(in + h->its[(size_t)i].o_in);
+                            std::memcpy(p, items[i].poses, 8 * 7 * VIO_NF);
+                            std::memcpy(p + 7 * VIO_NF, items[i].ext, 8 * 7);
+                            p[FM_INIT_S] = items[i].s;
+                        }
+                    },
+                    [](const char *) {});
+}
+
+vio_status vio_fm_tracks_batch(vio_fm *h, int32_t count, const vio_fm_tracks_item *items, vio_fm_result *results) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    const Tick t0 = std::chrono::steady_clock::now();
+    vio_status st = begin_call(h, "vio_fm_tracks_batch", count, items, results);
+    if (st != VIO_OK || count == 0) return st;
+    size_t b_out = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_fm_tracks_item &it = items[i];
+        if (it.cap_tracks < 0 || it.cap_obs < 0) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_tracks_batch: item %d: a negative capacity", i);
+        if (!it.off || (it.cap_tracks > 0 && (!it.ids || !it.start || !it.depth || !it.flag)) || (it.cap_obs > 0 && !it.pts))
+            return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_tracks_batch: item %d: a NULL array", i);
+        FmItemD &d = h->its[(size_t)i];
+        d.b = std::min<int32_t>(it.cap_tracks, FM_MAX_TRACKS);
+        d.c = (int32_t)std::min<int64_t>(it.cap_obs, (int64_t)FM_MAX_TRACKS * FM_MAX_OBS);
+        d.o_out = (int64_t)b_out;
+        const size_t nt = (size_t)std::min(d.n_tracks, d.b), no = (size_t)std::min(d.n_tracks * FM_MAX_OBS, d.c);   // (the kernel's layout)
+        b_out += align256(fm_tracks_bytes(nt, no));
+    }
+    return run_call(h, t0, count, items, results, 0, b_out, k_fm_tracks, FM_NT, [](char *) {},
+                    [&](const char *out) {
+                        for (int i = 0; i < count; ++i) {
+                            const vio_fm_tracks_item &it = items[i];
+                            const FmItemD &d = h->its[(size_t)i];
+                            if (results[i].status != VIO_FM_STATUS_OK) continue;         // (nothing is written for a refused slot)
+                            const size_t nt = (size_t)std::min(d.n_tracks, d.b), no = (size_t)std::min(d.n_tracks * FM_MAX_OBS, d.c);
+                            const size_t n = (size_t)d.n_tracks;
+                            if (n > nt) continue;                                        // (the kernel refused it)
+                            const char *p = out + d.o_out;
+                            const int64_t *off = (const int64_t *)(p + 16 * nt);
+                            const size_t total = (size_t)fm_clamp((int32_t)off[n], 0, (int32_t)no);
+                            std::memcpy(it.off, off, 8 * (n + 1));
+                            if (n) { std::memcpy(it.ids, p, 8 * n); std::memcpy(it.depth, p + 8 * nt, 8 * n); }
+                            p += 8 * (3 * nt + 1);
+                            if (total) std::memcpy(it.pts, p, 16 * total);
+                            p += 16 * no;
+                            if (n) { std::memcpy(it.start, p, 4 * n); std::memcpy(it.flag, p + 4 * nt, 4 * n); }
+                        }
+                    });
 }
 
 }  // extern "C"

@@ -19,6 +19,7 @@ from .capi import CompanionHandle, VioError, open_lib
 MAX_SLOTS, MAX_TRACKS, MAX_POINTS, MAX_OBS = 256, 2048, 1024, 11
 DEFAULT_INIT_DEPTH, DEFAULT_MIN_PARALLAX = 5.0, 10.0 / 460.0
 STATUS_OK, STATUS_TABLE_FULL, STATUS_GAP, STATUS_OBS_FULL = 0, 1, 2, 3
+STATUS_CAPACITY = 4                                                    # include/vio_fm_stream.h
 DEPTH_SET, DEPTH_CLEAR = 0, 1
 BACK_SHIFT_DEPTH, BACK, FRONT = 0, 1, 2
 
@@ -57,6 +58,15 @@ class VioFmCorrItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("l", C.c_int32), ("r", C.c_int32), ("cap_rows", C.c_int32), ("rows", C.c_void_p)]
 
 
+class VioFmInitDepthItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("s", C.c_double), ("poses", C.c_void_p), ("ext", C.c_void_p)]
+
+
+class VioFmTracksItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("cap_tracks", C.c_int32), ("cap_obs", C.c_int64), ("ids", C.c_void_p), ("start", C.c_void_p),
+                ("depth", C.c_void_p), ("flag", C.c_void_p), ("off", C.c_void_p), ("pts", C.c_void_p)]
+
+
 def _result(r):
     return {k: getattr(r, k) for k, _ in VioFmResult._fields_}
 
@@ -66,6 +76,7 @@ class FmLib:
 
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "reset", "counts", "add_batch", "export_batch",
                "set_depth_batch", "slide_batch", "corresponding_batch", "tracks_set", "tracks_get", "timing"]
+    STREAM_SYMBOLS = ["init_depth_batch", "tracks_batch"]                                  # include/vio_fm_stream.h
 
     def __init__(self, path):
         self.path = path
@@ -79,6 +90,9 @@ class FmLib:
         self.fn["tracks_set"].argtypes = [C.c_void_p, C.c_int32, C.c_int32] + [C.c_void_p] * 6
         self.fn["tracks_get"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_fm_", self.STREAM_SYMBOLS)[1])
+        for k in self.STREAM_SYMBOLS:
+            self.fn[k].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_fm handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -208,6 +222,50 @@ class FmHandle(CompanionHandle):
         n = n.value
         return dict(ids=ids[:n], start=start[:n], depth=depth[:n], flag=flag[:n], off=off[:n + 1], pts=pts[:off[n]].copy())
 
+    def init_depth_batch(self, items):
+        """visualInitialAlign's depth hand-over per item (slot, poses (11, 7), ext (7,), s): every usable track is triangulated anew
+        on the poses (the SfM's, with tic = 0 in ext) and holds that depth times s.  The result dicts; n_triangulated is the usable
+        count."""
+        arr, keep = (VioFmInitDepthItem * max(len(items), 1))(), []
+        for i, (slot, poses, ext, s) in enumerate(items):
+            poses, ext = np.ascontiguousarray(poses, dtype=np.float64), np.ascontiguousarray(ext, dtype=np.float64)
+            if poses.shape != (11, 7) or ext.shape != (7,) or np.ndim(s) != 0:
+                raise ValueError("item %d: poses (11, 7), ext (7,), s a scalar" % i)
+            keep += [poses, ext]
+            arr[i] = VioFmInitDepthItem(int(slot), 0, float(s), poses.ctypes.data, ext.ctypes.data)
+        return self._call("init_depth_batch", arr, len(items))
+
+    def tracks_batch(self, slots, cap_tracks=None, cap_obs=None):
+        """The lists of `slots` in one call: per slot the dict tracks_get returns (ids, start, depth, flag, off, pts) plus the
+        result's fields.  The arrays are sized from the handle's n_tracks and n_tracks * MAX_OBS (cap_tracks / cap_obs: per slot
+        capacities in their place); a slot they are too small for comes back with status STATUS_CAPACITY, n_rows the observations it
+        needs, and its arrays as they were allocated (zeros)."""
+        slots = [int(s) for s in np.asarray(slots, dtype=np.int64).reshape(-1)]
+        for name, v in (("cap_tracks", cap_tracks), ("cap_obs", cap_obs)):
+            if v is not None and len(v) != len(slots):
+                raise ValueError("%s: one entry per slot" % name)
+        arr, outs = (VioFmTracksItem * max(len(slots), 1))(), []
+        for i, slot in enumerate(slots):
+            n = self.counts(slot)[0]
+            ct = n if cap_tracks is None else int(cap_tracks[i])
+            co = n * MAX_OBS if cap_obs is None else int(cap_obs[i])
+            if ct < 0 or co < 0:
+                raise ValueError("item %d: a negative capacity" % i)
+            o = dict(ids=np.zeros(ct, dtype=np.int64), start=np.zeros(ct, dtype=np.int32), depth=np.zeros(ct), flag=np.zeros(ct, dtype=np.int32),
+                     off=np.zeros(ct + 1, dtype=np.int64), pts=np.zeros((co, 2)))
+            outs.append(o)
+            arr[i] = VioFmTracksItem(slot, ct, co, o["ids"].ctypes.data, o["start"].ctypes.data, o["depth"].ctypes.data, o["flag"].ctypes.data,
+                                     o["off"].ctypes.data, o["pts"].ctypes.data)
+        res = self._call("tracks_batch", arr, len(slots))
+        for r, o in zip(res, outs):
+            if r["status"] != STATUS_OK:                 # (nothing was written: the arrays as they were allocated)
+                r.update(o)
+                continue
+            n = r["n_tracks"]
+            r.update(ids=o["ids"][:n], start=o["start"][:n], depth=o["depth"][:n], flag=o["flag"][:n], off=o["off"][:n + 1],
+                     pts=o["pts"][:o["off"][n]].copy())
+        return res
+
     def timing(self):
         """ms of the last batched call that launched: host checks, packing and upload; the kernel; the read-back; the whole call."""
         t = (C.c_double * 4)()
@@ -267,3 +325,15 @@ class BatchFeatureManager:
 
     def corresponding(self, l, r):
         return self.fm.corresponding_batch([(s, l, r) for s in self.slots])
+
+    def init_depths(self, poses, exts, scales):
+        """visualInitialAlign's depth hand-over: poses per slot (11, 7) (the un-scaled SfM poses), exts (7,) for all or per slot (tic
+        = 0), scales per slot."""
+        poses, scales = self._per_slot(poses, "poses"), self._per_slot(scales, "scales")
+        ext = np.asarray(exts, dtype=np.float64)
+        exts = [ext] * len(self.slots) if ext.ndim == 1 else self._per_slot(ext, "exts")
+        return self.fm.init_depth_batch(list(zip(self.slots, poses, exts, scales)))
+
+    def tracks(self):
+        """Every slot's list (sfm_f) in one call."""
+        return self.fm.tracks_batch(self.slots)

@@ -374,9 +374,79 @@ def aif_flush(drivers):
         todo = [d for d in todo if d._aif_queue]
 
 
+# ---- the FeatureManager of `drivers` (all on one fm.FmHandle, features=) in one call each ------------------------
+FM_DEPTH_SET, FM_BACK_SHIFT_DEPTH, FM_BACK, FM_FRONT = 0, 0, 1, 2        # include/vio_fm.h
+
+
+def _fm_checked(drivers, res, what):
+    """A slot the device refused is as it was and out of step with its driver, so it raises."""
+    for d, r in zip(drivers, res):
+        if r["status"] != 0:
+            raise RuntimeError("StreamDriver: vio_fm_%s refused slot %d with status %d" % (what, d.fm_slot, r["status"]))
+    return res
+
+
+def fm_add(drivers, frames, frame_count=WINDOW_SIZE):
+    """addFeatureCheckParallax of global frame frames[i] of every driver as window frame `frame_count`: one add_batch."""
+    items = [(d.fm_slot, frame_count) + d.frame_points(f) for d, f in zip(drivers, frames)]
+    for d, r in zip(drivers, _fm_checked(drivers, drivers[0].fm.add_batch(items), "add_batch")):
+        d.fm_keyframe.append(int(r["keyframe"]))
+
+
+def fm_windows(drivers, triangulate):
+    """[f_manager.triangulate,] getDepthVector and the edge loop on every driver's current poses: one export_batch.  Per driver
+    (Window, feature ids), what ensure_depths + window_arrays give."""
+    res = _fm_checked(drivers, drivers[0].fm.export_batch([(d.fm_slot, d.poses, d.ext) for d in drivers], triangulate=triangulate), "export_batch")
+    out = []
+    for d, r in zip(drivers, res):
+        d.n_triangulated += int(r["n_triangulated"])
+        w = synth.Window(poses=d.poses.copy(), speed_bias=d.sb.copy(), ext=d.ext.copy(), inv_depth=r["inv_depth"], lm=r["lm"],
+                         host=r["host"], target=r["target"], pts_i=r["pts_i"], pts_j=r["pts_j"], preint=list(d.preint), prior=d.prior,
+                         n_landmarks=len(r["feature_ids"]), n_observations=len(r["lm"]))
+        out.append((w, [int(l) for l in r["feature_ids"]]))
+    return out
+
+
+def fm_set_depths(drivers, inv_depths):
+    """setDepth from every driver's solved inverse depths [and removeFailures]: one set_depth_batch per setting of the option."""
+    for flag in (False, True):
+        who = [(d, x) for d, x in zip(drivers, inv_depths) if d.fm_remove_failures == flag]
+        if who:
+            ds = [d for d, _ in who]
+            _fm_checked(ds, ds[0].fm.set_depth_batch([(d.fm_slot, x) for d, x in who], FM_DEPTH_SET, flag), "set_depth_batch")
+
+
+def fm_slide(drivers, kinds, mats=None):
+    """kinds[i]: FM_BACK_SHIFT_DEPTH with mats[i] = (marg_R, marg_P, new_R, new_P), FM_BACK, or FM_FRONT (frame_count WINDOW_SIZE): one
+    slide_batch."""
+    items = []
+    for i, (d, k) in enumerate(zip(drivers, kinds)):
+        items.append((d.fm_slot, k, WINDOW_SIZE) + (tuple(mats[i]) if k == FM_BACK_SHIFT_DEPTH else ()))
+    _fm_checked(drivers, drivers[0].fm.slide_batch(items), "slide_batch")
+
+
+def fm_tracks(drivers):
+    """Every driver's list (sfm_f) in one tracks_batch."""
+    return _fm_checked(drivers, drivers[0].fm.tracks_batch([d.fm_slot for d in drivers]), "tracks_batch")
+
+
+def fm_init_depths(drivers, items, scales):
+    """visualInitialAlign's depth hand-over of every driver that initialised: clearDepth, triangulate on items[i]'s SfM poses with
+    tic = 0, estimated_depth *= scales[i] (estimator.cpp:406-442): one init_depth_batch."""
+    args = []
+    for d, it, s in zip(drivers, items, scales):
+        sfm = np.zeros((NUM_FRAMES, 7))
+        sfm[:, 0:3] = it["T"]
+        for i in range(NUM_FRAMES):
+            sfm[i, 3:7] = synth.rot_to_quat(it["R"][i])
+        args.append((d.fm_slot, sfm, np.concatenate([np.zeros(3), d.ext[3:7]]), float(s)))
+    for d, r in zip(drivers, _fm_checked(drivers, drivers[0].fm.init_depth_batch(args), "init_depth_batch")):
+        d.n_triangulated += int(r["n_triangulated"])
+
+
 class StreamDriver:
     def __init__(self, lib, stream, ctx_kwargs=None, pos_noise=0.02, rot_noise=0.005, depth_noise=0.05, seed=1,
-                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None, initialize=None, state=None):
+                 triangulate=False, nonkey_every=0, outlier_px=None, bias_relinearize=None, initialize=None, state=None, features=None):
         """triangulate=True: a landmark's first depth comes from FeatureManager::triangulate (vio_triangulate, on the
         current pose estimates, feature_manager.cpp:203-257) the first time it enters a solve, as in
         Estimator::solveOdometry (estimator.cpp:489-503), instead of from the perturbed ground truth.
@@ -423,9 +493,32 @@ class StreamDriver:
         est.EstHandle (include/vio_est.h; or anything with its batched methods): the ground-truth start is written there as an
         initialisation result would be, every step reads the window from it (vector2double and the ten records), re-anchors through it
         (double2vector, with failureDetection's verdict appended to self.failures; a failure raises, there is no reboot policy here),
-        slides through it and feeds the next interval's samples to its processIMU.  Not with initialize= or bias_relinearize=."""
+        slides through it and feeds the next interval's samples to its processIMU.  Not with initialize= or bias_relinearize=.
+        features=(fm_handle, slot), or dict(handle=, slot=, remove_failures=False): the FeatureManager lives in slot `slot` of an
+        fm.FmHandle (include/vio_fm.h and vio_fm_stream.h; or anything with its batched methods) and the driver holds no tracks /
+        depth dicts.  The slot is reset and fed every stream observation of the eleven window frames (add_batch, frame_count 0 .. 10;
+        ids are landmark numbers); a step exports the window arrays with triangulation (export_batch), writes the solved inverse
+        depths back (set_depth_batch; remove_failures=True also erases the tracks solved to a negative depth, as the reference's
+        removeFailures does), exports the marginalisation's edges, slides (slide_batch: BACK_SHIFT_DEPTH on the four arrays of
+        slideWindowOld, FRONT for a non-keyframe) and adds the next frame.  An INITIAL try reads sfm_f with tracks_batch, a failed
+        one slides with BACK, a successful one ends in init_depth_batch on the SfM poses with tic = 0 and s.  The library's own
+        keyframe decision of every add is recorded in self.fm_keyframe and not used.  A slot status other than OK raises.  Not with
+        outlier_px, and not with triangulate=False unless initialize= is given (both raise ValueError): erasing by id and the perturbed
+        ground-truth depths are not FeatureManager behaviour."""
         if state is not None and (initialize is not None or bias_relinearize is not None):
             raise ValueError("StreamDriver: state= cannot be combined with initialize= or bias_relinearize=")
+        self.fm, self.fm_slot, self.fm_remove_failures = None, None, False
+        if features is not None:
+            if outlier_px is not None:
+                raise ValueError("StreamDriver: features= cannot be combined with outlier_px (removeOutlier by id is not in the slot)")
+            if not triangulate and initialize is None:
+                raise ValueError("StreamDriver: features= needs triangulate=True or initialize= (the perturbed ground-truth depths are not a FeatureManager behaviour)")
+            if isinstance(features, dict):
+                self.fm, self.fm_slot = features["handle"], int(features["slot"])
+                self.fm_remove_failures = bool(features.get("remove_failures", False))
+            else:
+                self.fm, self.fm_slot = features[0], int(features[1])
+        self.fm_keyframe = []       # addFeatureCheckParallax's own decision of every frame added (features set): recorded, not used
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
         self.g_norm = float(getattr(stream, "g_norm", synth.G_NORM))
@@ -455,10 +548,15 @@ class StreamDriver:
                 raise ValueError("StreamDriver: calibrate_ric needs sfm (the stand-in's poses are made with the true rotation)")
             self.ext[3:7] = (0.0, 0.0, 0.0, 1.0)
         # tracks (FeaturePerId): landmark -> list of (global frame, normalised point), the first one is the host
-        self.tracks = {}
-        for f in self.frames:
-            self.add_frame_observations(f)
-        self.depth = {}                                    # landmark -> estimated depth in its current host frame
+        if self.fm is not None:                            # (the slot holds them)
+            self.fm.reset(self.fm_slot)
+            for k, f in enumerate(self.frames):
+                fm_add([self], [f], k)
+        else:
+            self.tracks = {}
+            for f in self.frames:
+                self.add_frame_observations(f)
+            self.depth = {}                                # landmark -> estimated depth in its current host frame
         self.init_depth = np.array(st.lm_depth) * (1.0 + depth_noise * st.init_noise)
         self.triangulate = triangulate
         self.prior = None
@@ -551,7 +649,7 @@ class StreamDriver:
         return f, (self.est_slot, iv["dt"], iv["acc"], iv["gyr"]), (self.est_slot, float(self.s.times[f]), False)
 
     # ---- initialisation (initialize) ------------------------------------------------------------------
-    def _aif_push(self, k, slide=None, first=None):
+    def _aif_push(self, k, slide=None, first=None, tracks=None):
         """Queues window frame k for the all_image_frame slot as one step (slide, imu, image): the erase up to header `slide`
         (slideWindow) if given, the samples since frame k - 1 (processIMU; `first`: one sample in front of the first image), then the
         image (processImage).  aif_flush feeds the queued steps of many drivers in one call each."""
@@ -560,16 +658,23 @@ class StreamDriver:
         imu = None if iv is None else (np.array(iv["dt"], dtype=np.float64), np.array(iv["acc"], dtype=np.float64), np.array(iv["gyr"], dtype=np.float64))
         # a track's observations are consecutive window frames from its first one, so frame k's is entry k - (index of that first frame):
         # one look per track, not a scan of its list
-        pos = {fr: i for i, fr in enumerate(self.frames)}
-        obs = []
-        for l, tr in self.tracks.items():
-            j = k - pos[tr[0][0]]
-            if 0 <= j < len(tr):
-                if tr[j][0] != f:
-                    raise RuntimeError("StreamDriver: track %d is not consecutive in the window's frames" % l)
-                obs.append((l, tr[j][1]))
-        ids = np.array([l for l, _ in obs], dtype=np.int64)
-        pts = np.array([p for _, p in obs], dtype=np.float64).reshape(-1, 2)
+        if self.fm is not None:     # the slot's rows that have window frame k
+            tr = fm_tracks([self])[0] if tracks is None else tracks
+            n_obs = np.diff(tr["off"])
+            has = (tr["start"] <= k) & (k < tr["start"] + n_obs)
+            ids = np.array(tr["ids"][has], dtype=np.int64)
+            pts = np.array(tr["pts"][(tr["off"][:-1] + k - tr["start"])[has]], dtype=np.float64).reshape(-1, 2)
+        else:
+            pos = {fr: i for i, fr in enumerate(self.frames)}
+            obs = []
+            for l, tr in self.tracks.items():
+                j = k - pos[tr[0][0]]
+                if 0 <= j < len(tr):
+                    if tr[j][0] != f:
+                        raise RuntimeError("StreamDriver: track %d is not consecutive in the window's frames" % l)
+                    obs.append((l, tr[j][1]))
+            ids = np.array([l for l, _ in obs], dtype=np.int64)
+            pts = np.array([p for _, p in obs], dtype=np.float64).reshape(-1, 2)
         image = (float(self.s.times[f]), ids, pts, self.sb[k, 3:6].copy(), self.sb[k, 6:9].copy())
         self._aif_queue.append((None if slide is None else (float(slide),), imu, image))
 
@@ -579,16 +684,25 @@ class StreamDriver:
         self.aif.reset(self.aif_slot)
         self._aif_queue = []
         iv = self.intervals[0]
+        tr = fm_tracks([self])[0] if self.fm is not None else None
         for k in range(len(self.frames)):
-            self._aif_push(k, first=dict(dt=[0.0], acc=[iv["acc0"]], gyr=[iv["gyr0"]]))
+            self._aif_push(k, first=dict(dt=[0.0], acc=[iv["acc0"]], gyr=[iv["gyr0"]]), tracks=tr)
 
-    def init_request(self):
-        """The current window as an alignment item (visual_trajectory's R / T, the zero-bias records) and its raw intervals."""
+    def init_request(self, tracks=None):
+        """The current window as an alignment item (visual_trajectory's R / T, the zero-bias records) and its raw intervals.  tracks
+        (features set): this slot's entry of a batched tracks call."""
         c = self.initialize
         if c.get("sfm"):            # R / T are filled in by init_align's SfM call
             from .sfm import item_from_tracks
-            item = dict(sfm_item=item_from_tracks(self.tracks, self.frames)[0], owner=self, R=None, T=None, pre=list(self.preint),
-                        is_key=None)
+            if self.fm is not None:     # sfm_f is the slot's list as it stands
+                tr = fm_tracks([self])[0] if tracks is None else tracks
+                sfm_item = dict(n_frames=len(self.frames), start_frame=np.array(tr["start"], dtype=np.int32),
+                                obs_offset=np.array(tr["off"], dtype=np.int64), pts=np.array(tr["pts"], dtype=np.float64).reshape(-1, 2))
+                item = dict(sfm_item=sfm_item, owner=self, R=None, T=None, pre=list(self.preint), is_key=None,
+                            fm_ids=np.array(tr["ids"], dtype=np.int64))
+            else:
+                item = dict(sfm_item=item_from_tracks(self.tracks, self.frames)[0], owner=self, R=None, T=None, pre=list(self.preint),
+                            is_key=None)
             if c.get("calibrate_ric"):
                 from .exrot import delta_q_wxyz
                 item["exrot_item"] = dict(item["sfm_item"], delta_q=delta_q_wxyz(self.preint))
@@ -663,7 +777,7 @@ class StreamDriver:
                 for i, r in zip(ok, self._init_from_frames([items[i] for i in ok])):
                     out[i] = r
             elif ok:
-                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "exrot_item", "owner", "sfm_result")} for i in ok]
+                plain = [{k: v for k, v in items[i].items() if k not in ("sfm_item", "exrot_item", "owner", "sfm_result", "fm_ids")} for i in ok]
                 for i, r in zip(ok, self._init_align(plain, [intervals[i] for i in ok])):
                     out[i] = r
             return out
@@ -681,7 +795,8 @@ class StreamDriver:
         aif_flush(owners)
         res = initialize_from_frames(BatchImageFrames(self.aif, [d.aif_slot for d in owners]), self._init_h, [it["sfm_result"] for it in items],
                                      [[float(d.s.times[f]) for f in d.frames] for d in owners],
-                                     [np.array(item_from_tracks(d.tracks, d.frames)[1], dtype=np.int64) for d in owners],
+                                     [it["fm_ids"] if d.fm is not None else np.array(item_from_tracks(d.tracks, d.frames)[1], dtype=np.int64)
+                                      for d, it in zip(owners, items)],
                                      np.stack([synth.quat_to_rot(d.ext[3:7]) for d in owners]), self.ext[0:3].copy(), self.g_norm)
         out = []
         for it, r in zip(items, res):
@@ -702,14 +817,23 @@ class StreamDriver:
             self._init_imu = load_imu().create(device=self.ctx.cfg.device)
         return self._init_h.initialize_batch(items, intervals, self._init_imu, self.ext[0:3].copy(), self.g_norm, self.noise)
 
-    def init_apply(self, item, res):
-        """One try's outcome: visualInitialAlign's state change on success, else the INITIAL slide and the next frame."""
+    def init_apply(self, item, res, fm_batched=False):
+        """One try's outcome: visualInitialAlign's state change on success, else the INITIAL slide and the next frame.  fm_batched
+        (features set): the slot's part is the caller's, for a group in one call each (batch_stream.initialize_batched):
+        fm_init_depths after a success; fm_slide(FM_BACK), fm_add of the new frame and the all_image_frame push after a failure."""
         self.init_tries += 1
         if res["status"] == 0:
             s = float(res["s"])
             self.poses = np.asarray(res["poses"], dtype=np.float64).reshape(NUM_FRAMES, 7).copy()
             self.sb = np.asarray(res["speed_bias"], dtype=np.float64).reshape(NUM_FRAMES, 9).copy()
             self.preint = list(res["pre"])
+            self.init_result = res
+            self.init_frame = self.frames[WINDOW_SIZE]
+            self.initialized = True
+            if self.fm is not None:
+                if not fm_batched:
+                    fm_init_depths([self], [item], [s])
+                return True
             # f_manager.clearDepth; triangulate on the SfM poses with TIC_TMP = 0 and RIC; estimated_depth *= s (estimator.cpp:407-439)
             self.depth = {}
             sfm = np.zeros((NUM_FRAMES, 7))
@@ -737,18 +861,24 @@ class StreamDriver:
             raise RuntimeError("StreamDriver: the stream ended before the initialisation succeeded")
         # slideWindow in the INITIAL state: the oldest frame leaves, no prior, no depth shift (f_manager.removeBack)
         gone = self.frames[0]
-        for l in list(self.tracks.keys()):
-            tr = self.tracks[l]
-            if tr[0][0] == gone:
-                del tr[0]
-                if not tr:
-                    del self.tracks[l]
+        if self.fm is not None:
+            if not fm_batched:
+                fm_slide([self], [FM_BACK])
+        else:
+            for l in list(self.tracks.keys()):
+                tr = self.tracks[l]
+                if tr[0][0] == gone:
+                    del tr[0]
+                    if not tr:
+                        del self.tracks[l]
         self.frames.pop(0)
         self.intervals.pop(0)
         self.preint.pop(0)
         self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
-        self.take_next_frame()
-        if self.aif is not None:
+        self.take_next_frame(observe=not fm_batched)
+        if fm_batched:
+            self._fm_gone = gone        # (for the caller's all_image_frame push, behind its add)
+        elif self.aif is not None:
             self._aif_push(len(self.frames) - 1, slide=self.s.times[gone])
         return False
 
@@ -759,7 +889,22 @@ class StreamDriver:
             self.init_apply(item, self.init_align([item], [ivs])[0])
 
     # ---- feature bookkeeping (FeatureManager) ---------------------------------------------------------
+    def frame_points(self, f):
+        """Every stream observation of global frame f as the front end would hand it over: (ids, points), ids the landmark numbers,
+        the point lm_px for the frame that hosts the landmark, else lm_obs[l][f]."""
+        st = self.s
+        ids, pts = [], []
+        for l, h in enumerate(st.lm_host):
+            if h == f:
+                ids.append(l); pts.append(st.lm_px[l])
+            elif f in st.lm_obs[l]:
+                ids.append(l); pts.append(st.lm_obs[l][f])
+        return np.array(ids, dtype=np.int64), np.array(pts, dtype=np.float64).reshape(-1, 2)
+
     def add_frame_observations(self, f):
+        if self.fm is not None:
+            fm_add([self], [f])
+            return
         st = self.s
         for l, h in enumerate(st.lm_host):
             if h == f:
@@ -822,6 +967,11 @@ class StreamDriver:
     def inv_depth(self):
         """Inverse depths by landmark id (NaN where the landmark never got one) — what the tests compare."""
         out = np.full(len(self.s.lm_host), np.nan)
+        if self.fm is not None:     # (a row's depth is -1 until it gets one)
+            tr = fm_tracks([self])[0]
+            got = tr["depth"] != -1.0
+            out[tr["ids"][got]] = 1.0 / tr["depth"][got]
+            return out
         for l, d in self.depth.items():
             out[l] = 1.0 / d
         return out
@@ -829,6 +979,10 @@ class StreamDriver:
     @property
     def have_depth(self):
         out = np.zeros(len(self.s.lm_host), dtype=bool)
+        if self.fm is not None:
+            tr = fm_tracks([self])[0]
+            out[tr["ids"][tr["depth"] != -1.0]] = True
+            return out
         out[list(self.depth.keys())] = True
         return out
 
@@ -863,8 +1017,11 @@ class StreamDriver:
             self.repropagated.append(self.relinearize_biases())
         if self.est is not None:
             self.pull_window()
-        self.ensure_depths()
-        w, ids = self.window_arrays()
+        if self.fm is not None:
+            w, ids = fm_windows([self], True)[0]
+        else:
+            self.ensure_depths()
+            w, ids = self.window_arrays()
         self.ctx.load(w)
         rep = self.ctx.solve(10)
         poses, sb, _ = self.ctx.get_window()
@@ -876,8 +1033,11 @@ class StreamDriver:
             self.apply_update(self.est.update_batch([(self.est_slot, poses, sb, self.ext, True)])[0])
         else:
             self.poses, self.sb = anchor_gauge(w.poses, poses, sb)
-        for l, v in zip(ids, invd):
-            self.depth[l] = 1.0 / v
+        if self.fm is not None:
+            fm_set_depths([self], [invd])
+        else:
+            for l, v in zip(ids, invd):
+                self.depth[l] = 1.0 / v
         newest = self.frames[WINDOW_SIZE]
         self.trajectory.append((st.times[newest], self.poses[WINDOW_SIZE].copy()))
         self.reports.append(rep)
@@ -889,7 +1049,7 @@ class StreamDriver:
         margin_old = not (self.nonkey_every and second_new % self.nonkey_every == self.nonkey_every - 1)
         self.flags.append(MARG_OLD if margin_old else MARG_SECOND_NEW)
         # backendOptimization marginalises on the re-anchored states (estimator.cpp:1086-1102)
-        w2, _ = self.window_arrays()
+        w2, _ = fm_windows([self], False)[0] if self.fm is not None else self.window_arrays()
         self.ctx.load(w2)
         self.prior = self.ctx.marginalize(MARG_OLD if margin_old else MARG_SECOND_NEW)
         if self.outlier_px is not None:         # removeOutlier + removeFailures, before the slide
@@ -909,26 +1069,33 @@ class StreamDriver:
         self.take_next_frame()
         return True
 
-    def apply_slide(self, res, margin_old):
+    def apply_slide(self, res, margin_old, fm_done=False):
         """The FeatureManager side of a slide the slot has made: res is this slot's entry of slide_batch's results."""
         if not res["slid"]:
             raise RuntimeError("StreamDriver: the slot's window is not full (frame_count %d)" % res["frame_count"])
         if margin_old:
-            self.slide_window_old((res["marg_R"], res["marg_P"], res["new_R"], res["new_P"]))
+            self.slide_window_old((res["marg_R"], res["marg_P"], res["new_R"], res["new_P"]), fm_done)
         else:
-            self.slide_window_new()
+            self.slide_window_new(fm_done)
 
-    def slide_window_old(self, mats=None):
+    def slide_mats(self, mats=None):
+        """The four arrays of slideWindowOld (marg_R, marg_P, new_R, new_P): the slot's where it computed them (state set), else from
+        the poses of the two oldest frames."""
+        if mats is not None:
+            return mats
+        R0 = synth.quat_to_rot(self.poses[0, 3:7]); R1 = synth.quat_to_rot(self.poses[1, 3:7])
+        ric, tic = synth.quat_to_rot(self.ext[3:7]), self.ext[0:3]
+        return R0 @ ric, self.poses[0, 0:3] + R0 @ tic, R1 @ ric, self.poses[1, 0:3] + R1 @ tic
+
+    def slide_window_old(self, mats=None, fm_done=False):
         """slideWindowOld (estimator.cpp:1144-1199) + removeBackShiftDepth (feature_manager.cpp:276-312).  mats: the four arrays of
-        slideWindowOld where the slot computed them (state set)."""
+        slideWindowOld where the slot computed them (state set).  fm_done (features set): the caller has slid the slot already, in a
+        group's one call."""
         gone = self.frames[0]
-        if mats is None:
-            R0 = synth.quat_to_rot(self.poses[0, 3:7]); R1 = synth.quat_to_rot(self.poses[1, 3:7])
-            ric, tic = synth.quat_to_rot(self.ext[3:7]), self.ext[0:3]
-            mR, mP, nR, nP = R0 @ ric, self.poses[0, 0:3] + R0 @ tic, R1 @ ric, self.poses[1, 0:3] + R1 @ tic
-        else:
-            mR, mP, nR, nP = mats
-        for l in list(self.tracks.keys()):
+        mR, mP, nR, nP = self.slide_mats(mats)
+        if self.fm is not None and not fm_done:
+            fm_slide([self], [FM_BACK_SHIFT_DEPTH], [(mR, mP, nR, nP)])
+        for l in list(self.tracks.keys()) if self.fm is None else ():
             tr = self.tracks[l]
             if tr[0][0] != gone:
                 continue
@@ -950,10 +1117,12 @@ class StreamDriver:
             self._imu_stale = True
         self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
 
-    def slide_window_new(self):
+    def slide_window_new(self, fm_done=False):
         """slideWindowNew (estimator.cpp:1201-1206, the frame_count - 1 branch of :1163-1186) + removeFront."""
         gone = self.frames[WINDOW_SIZE - 1]
-        for l in list(self.tracks.keys()):
+        if self.fm is not None and not fm_done:
+            fm_slide([self], [FM_FRONT])
+        for l in list(self.tracks.keys()) if self.fm is None else ():
             tr = [o for o in self.tracks[l] if o[0] != gone]
             if not tr:
                 del self.tracks[l]
@@ -977,13 +1146,14 @@ class StreamDriver:
         self.frames.pop(WINDOW_SIZE - 1)
         self.poses[WINDOW_SIZE - 1], self.sb[WINDOW_SIZE - 1] = self.poses[WINDOW_SIZE].copy(), self.sb[WINDOW_SIZE].copy()
 
-    def take_next_frame(self):
+    def take_next_frame(self, observe=True):
         """The next image: processIMU's propagation of the newest state, then the frame's observations."""
         if self.est is not None:            # processIMU over the interval's samples, Headers[frame_count], in the slot
             f, imu_item, image_item = self.begin_next_frame()
             self.est.imu_batch([imu_item])
             self.est.image_batch([image_item])
-            self.add_frame_observations(f)
+            if observe:
+                self.add_frame_observations(f)
             return
         st = self.s
         f = self.next_frame
@@ -1008,7 +1178,8 @@ class StreamDriver:
         self.poses[WINDOW_SIZE, 3:7] = synth.quat_mul(self.poses[i, 3:7], pre["delta_q"])
         self.sb[WINDOW_SIZE, 0:3] = Vi - g * dt + Ri @ pre["delta_v"]
         self.sb[WINDOW_SIZE, 3:9] = self.sb[i, 3:9]
-        self.add_frame_observations(f)
+        if observe:                         # (False, features set: the caller adds a group's frames in one call)
+            self.add_frame_observations(f)
 
     def run(self):
         while self.step():
