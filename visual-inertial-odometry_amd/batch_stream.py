@@ -13,7 +13,8 @@ fm.FmHandle, and the frame's FeatureManager work is then one batched call per st
 import numpy as np
 
 from .capi import MARG_OLD, MARG_SECOND_NEW, WINDOW_SIZE
-from .stream import FM_BACK, FM_BACK_SHIFT_DEPTH, FM_FRONT, anchor_gauge, fm_add, fm_init_depths, fm_set_depths, fm_slide, fm_tracks, fm_windows
+from .stream import (FM_BACK, FM_BACK_SHIFT_DEPTH, FM_FRONT, anchor_gauge, est_flush, est_init_apply, est_relinearize, fm_add, fm_init_depths,
+                     fm_set_depths, fm_slide, fm_tracks, fm_windows)
 
 
 def _check(drivers):
@@ -42,9 +43,11 @@ def step_batched(drivers, marg):
     """One frame of every driver in `drivers` (all not finished).  Returns, per driver, whether it has another frame.  Drivers
     created with state= share a handle (_check): the frame then makes one window, one update, one slide and one processIMU call (and
     one for the headers) for all of them.  Drivers created with features= share a handle too: the frame then makes one export, one
-    set-depth, one second export, one slide and one add call for all of them."""
+    set-depth, one second export, one slide and one add call for all of them.  Where a driver was created with
+    state=dict(relinearize=), one relinearize_batch goes in front of the window call."""
     est, fm = drivers[0].est, drivers[0].fm
     if est is not None:
+        est_relinearize(drivers)    # (state=dict(relinearize=): one relinearize_batch in front of the window call)
         for d, win in zip(drivers, est.window_batch([d.est_slot for d in drivers])):
             d.pull_window(win)
     if fm is not None:
@@ -147,13 +150,13 @@ def _fm_slide_group(go, mats):
 
 def _init_group_key(d):
     """What one alignment call shares across its windows: the extrinsic translation (TIC[0]), G, the IMU noise of the re-propagation,
-    the aligner, the SfM, the extrinsic rotation calibration, the all_image_frame handle (all_frames), the FeatureManager handle (features) and the device the group's handles are created on.  Drivers that differ in any of them are aligned in separate calls."""
+    the aligner, the SfM, the extrinsic rotation calibration, the all_image_frame handle (all_frames), the FeatureManager handle (features), the estimator-state handle (state) and the device the group's handles are created on.  Drivers that differ in any of them are aligned in separate calls."""
     noise = tuple(sorted((k, float(v)) for k, v in d.noise.items()))
     sfm = d.initialize.get("sfm")
     cal = d.initialize.get("calibrate_ric")
     cal = id(cal) if callable(cal) else (tuple(sorted(cal.items())) if isinstance(cal, dict) else bool(cal))
     return (tuple(float(v) for v in d.ext[0:3]), float(d.g_norm), noise, id(d.initialize.get("aligner")),
-            id(sfm) if callable(sfm) else bool(sfm), cal, int(d.ctx.cfg.device), id(d.aif), id(d.fm))
+            id(sfm) if callable(sfm) else bool(sfm), cal, int(d.ctx.cfg.device), id(d.aif), id(d.fm), id(d.est))
 
 
 def initialize_batched(drivers):
@@ -164,7 +167,9 @@ def initialize_batched(drivers):
     (SfmHandle.sfm_batch) in front of the alignment call, and drivers created with `calibrate_ric` their camera-IMU rotation from one
     calibration call per group and round (ExrotHandle.exrot_batch) in front of that.  Drivers created with `all_frames` take the try
     from their resident all_image_frame slots: aif.initialize_from_frames' four calls per group and round in the alignment call's
-    place.  Returns the number of rounds."""
+    place.  Drivers created with a `state` entry live in estimator-state slots: their initial feeding is one call per step for the
+    group (est_flush), and every round then makes one slide_batch, one imu_batch and one image_batch for the last round's failures
+    and one init_apply_batch for its successes.  Returns the number of rounds."""
     pending = [d for d in drivers if not d.initialized]
     rounds = 0
     while pending:
@@ -172,19 +177,23 @@ def initialize_batched(drivers):
         for d in pending:
             groups.setdefault(_init_group_key(d), []).append(d)
         for group in groups.values():
+            est = group[0].est is not None
+            if est:                 # the slots' feeding: the window in the first round, the last round's failures afterwards
+                est_flush(group)
             if group[0].fm is not None:
-                _init_round_fm(group)
-                continue
-            reqs = [d.init_request() for d in group]
-            res = group[0].init_align([r[0] for r in reqs], [r[1] for r in reqs])
-            for d, (item, _), r in zip(group, reqs, res):
-                d.init_apply(item, r)
+                won = _init_round_fm(group, est)
+            else:
+                reqs = [d.init_request() for d in group]
+                res = group[0].init_align([r[0] for r in reqs], [r[1] for r in reqs])
+                won = [(d, r) for d, (item, _), r in zip(group, reqs, res) if d.init_apply(item, r, est_batched=est)]
+            if est and won:
+                est_init_apply([d for d, _ in won], [r for _, r in won])
         pending = [d for d in pending if not d.initialized]
         rounds += 1
     return rounds
 
 
-def _init_round_fm(group):
+def _init_round_fm(group, est_batched=False):
     """One round of a group whose FeatureManagers live in slots (features=): one tracks_batch gives every window's sfm_f, the tries
     run as ever, and their outcomes end in one init_depth_batch for the successes and one slide_batch (BACK) and one add_batch for
     the failures (StreamDriver.init_apply does each driver's own part)."""
@@ -194,7 +203,7 @@ def _init_round_fm(group):
     res = group[0].init_align([r[0] for r in reqs], [r[1] for r in reqs])
     won, lost = [], []
     for d, (item, _), r in zip(group, reqs, res):
-        (won if d.init_apply(item, r, fm_batched=True) else lost).append((d, item, r))
+        (won if d.init_apply(item, r, fm_batched=True, est_batched=est_batched) else lost).append((d, item, r))
     if won:
         fm_init_depths([d for d, _, _ in won], [item for _, item, _ in won], [float(r["s"]) for _, _, r in won])
     if lost:
@@ -204,6 +213,7 @@ def _init_round_fm(group):
         aif = [d for d in ds if d.aif is not None]
         for d, tr in zip(aif, fm_tracks(aif) if aif else []):
             d._aif_push(len(d.frames) - 1, slide=d.s.times[d._fm_gone], tracks=tr)
+    return [(d, r) for d, _, r in won]
 
 
 def run_batched(drivers, marg):

@@ -12,6 +12,7 @@
 //   k_est_update   one wavefront per item: every lane computes rot_diff, lane i < 11 writes frame i and its vector2double, lane 10
 //                  holds the verdict
 //   k_est_slide    one workgroup of EST_NT threads per item: the samples move down in chunks, read, barrier, write, barrier
+// csrc/vio_est_init_body.inc, included at the end, adds k_est_init_apply and k_est_relinearize (include/vio_est_init.h).
 // No atomics; every sum has the order the header writes down, so a slot's bits depend neither on the batch nor on the slot index.
 #include <hip/hip_runtime.h>
 
@@ -429,14 +430,15 @@ struct CallClock {
     double ms() const { return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count(); }
 };
 
-// the tail every batched call shares: results (and `extra` bytes behind them) down, one wait, the timing
-vio_status finish(vio_est *h, const CallClock &clk, double t_host, int32_t count, size_t nout, vio_est_result *results, const char *what) {
+// the tail every batched call shares: results of result_size bytes each (and `extra` bytes behind them) down, one wait, the timing
+vio_status finish(vio_est *h, const CallClock &clk, double t_host, int32_t count, size_t nout, void *results, const char *what,
+                  size_t result_size = sizeof(vio_est_result)) {
     vio_status st;
     hipEventRecord(h->q.ev[1], h->q.stream);
     if ((st = hip_ck(h->err, hipMemcpyAsync(h->out.h, h->out.d, nout, hipMemcpyDeviceToHost, h->q.stream), "read-back")) != VIO_OK) return st;
     hipEventRecord(h->q.ev[2], h->q.stream);
     if ((st = hip_ck(h->err, hipStreamSynchronize(h->q.stream), what)) != VIO_OK) return st;
-    std::memcpy(results, h->out.h, sizeof(vio_est_result) * (size_t)count);
+    std::memcpy(results, h->out.h, result_size * (size_t)count);
     h->timing[0] = t_host;
     h->timing[1] = elapsed_ms(h->q.ev[0], h->q.ev[1]);
     h->timing[2] = elapsed_ms(h->q.ev[1], h->q.ev[2]);
@@ -808,3 +810,5 @@ vio_status vio_est_timing(const vio_est *h, double *out4) {
 }
 
 }   // extern "C"
+
+#include "vio_est_init_body.inc"                    // include/vio_est_init.h: vio_est_init_apply_batch, vio_est_relinearize_batch

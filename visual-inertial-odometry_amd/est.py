@@ -9,6 +9,8 @@ streams at once, each stream's state resident on the device (DESIGN.md section 3
     wins = est.windows()                                             # vector2double + the ten pre-integrations per slot
     res = est.update(poses, speed_bias, ext)                         # double2vector + failureDetection: res[i]["failure"]
     out = est.slide(kinds)                                           # slideWindow; out["marg_R"], ... go to BatchFeatureManager.slide
+    est.init_apply(poses, speed_bias, g, rot)                        # visualInitialAlign's writes (include/vio_est_init.h)
+    res = est.relinearize(ba_thresh, bg_thresh)                      # repropagate where a bias moved: res[i]["n_relinearized"], ["mask"]
 
 A slot's state as a dict is tests/est_reference.py's layout: the fields of VioEstState as arrays, plus off (12,), dt, acc, gyr.
 """
@@ -19,7 +21,7 @@ import numpy as np
 from .capi import CompanionHandle, VioError, VioPreint, open_lib
 
 MAX_SLOTS, MAX_SAMPLES, WINDOW_SIZE, FRAMES = 256, 4096, 10, 11
-STATUS_OK, STATUS_POOL_FULL = 0, 1
+STATUS_OK, STATUS_POOL_FULL, STATUS_NOT_READY = 0, 1, 2
 MARG_OLD, MARG_SECOND_NEW = 0, 1
 GATE_NONE, GATE_BA, GATE_BG, GATE_TRANSLATION, GATE_Z = 0, 1, 2, 3, 4
 DEFAULT_G = (0.0, 0.0, 9.81)
@@ -73,6 +75,20 @@ class VioEstSlideItem(C.Structure):
     _fields_ = [("slot", C.c_int32), ("kind", C.c_int32), ("nonlinear", C.c_int32), ("reserved", C.c_int32)]
 
 
+class VioEstInitItem(C.Structure):
+    """include/vio_est_init.h"""
+    _fields_ = [("slot", C.c_int32), ("commit_last", C.c_int32), ("poses", C.c_double * 77), ("speed_bias", C.c_double * 99), ("g", C.c_double * 3),
+                ("rot", C.c_double * 9)]
+
+
+class VioEstRelinItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("reserved", C.c_int32), ("ba_thresh", C.c_double), ("bg_thresh", C.c_double)]
+
+
+class VioEstRelinResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("frame_count", C.c_int32), ("n_relinearized", C.c_int32), ("mask", C.c_int32)]
+
+
 def _result(r):
     out = {k: getattr(r, k) for k, _ in VioEstResult._fields_[:8]}
     out.update(marg_R=np.array(r.marg_R).reshape(3, 3), marg_P=np.array(r.marg_P), new_R=np.array(r.new_R).reshape(3, 3), new_P=np.array(r.new_P))
@@ -111,6 +127,7 @@ class EstLib:
 
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "reset", "state_set", "state_get", "imu_batch", "image_batch",
                "window_batch", "update_batch", "slide_batch", "timing"]
+    INIT_SYMBOLS = ["init_apply_batch", "relinearize_batch"]                               # include/vio_est_init.h
 
     def __init__(self, path):
         self.path = path
@@ -120,7 +137,8 @@ class EstLib:
         self.fn["reset"].argtypes = [C.c_void_p, C.c_int32]
         self.fn["state_set"].argtypes = [C.c_void_p, C.c_int32] + [C.c_void_p] * 5
         self.fn["state_get"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int64] + [C.c_void_p] * 4
-        for k in ("imu_batch", "image_batch", "window_batch", "update_batch", "slide_batch"):
+        self.fn.update(open_lib(path, "vio_est_", self.INIT_SYMBOLS)[1])
+        for k in ["imu_batch", "image_batch", "window_batch", "update_batch", "slide_batch"] + self.INIT_SYMBOLS:
             self.fn[k].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
 
@@ -244,6 +262,37 @@ class EstHandle(CompanionHandle):
             arr[i] = VioEstSlideItem(int(slot), int(kind), int(bool(nonlinear)), 0)
         return self._call("slide_batch", arr, len(items))
 
+    def init_apply_batch(self, items):
+        """visualInitialAlign's writes per item (slot, poses (11, 7), speed_bias (11, 9), g (3,), rot (3, 3)[, commit_last]): the rows and
+        the result fields of a successful alignment; commit_last (default False) also sets last_R / last_P / last_R0 / last_P0 from the
+        window written.  Result dicts (status: STATUS_NOT_READY where the window is not full or an interval is missing, and the slot is
+        as it was)."""
+        arr = (VioEstInitItem * max(len(items), 1))()
+        for i, (slot, poses, sb, g, rot, *commit) in enumerate(items):
+            vals = [np.ascontiguousarray(v, dtype=np.float64) for v in (poses, sb, g, rot)]
+            if [v.size for v in vals] != [77, 99, 3, 9] or vals[0].shape != (11, 7) or vals[1].shape != (11, 9):
+                raise ValueError("item %d: poses (11, 7), speed_bias (11, 9), g (3,), rot (3, 3)" % i)
+            if not all(np.isfinite(v).all() for v in vals):
+                raise ValueError("item %d: a non-finite entry (a failed alignment's rows are NaN: list the successes only)" % i)
+            arr[i].slot, arr[i].commit_last = int(slot), int(bool(commit[0])) if commit else 0
+            for k, v in zip(("poses", "speed_bias", "g", "rot"), vals):
+                C.memmove(C.addressof(getattr(arr[i], k)), v.ctypes.data, v.nbytes)
+        return self._call("init_apply_batch", arr, len(items))
+
+    def relinearize_batch(self, items):
+        """repropagate per item (slot, ba_thresh, bg_thresh) for the intervals whose start frame's bias moved past a threshold: dicts
+        (status, frame_count, n_relinearized, mask: bit j for interval j)."""
+        arr = (VioEstRelinItem * max(len(items), 1))()
+        for i, (slot, tba, tbg) in enumerate(items):
+            tba, tbg = float(tba), float(tbg)
+            if not (np.isfinite(tba) and np.isfinite(tbg) and tba >= 0.0 and tbg >= 0.0):
+                raise ValueError("item %d: thresholds are finite and >= 0" % i)
+            arr[i] = VioEstRelinItem(int(slot), 0, tba, tbg)
+        n = len(items)
+        res = (VioEstRelinResult * max(n, 1))()
+        self._ck(self.lib.fn["relinearize_batch"](self.h, C.c_int32(n), C.addressof(arr), C.addressof(res)), "relinearize_batch")
+        return [{k: int(getattr(res[i], k)) for k, _ in VioEstRelinResult._fields_} for i in range(n)]
+
     def timing(self):
         """ms of the last batched call that launched: host checks, packing and upload; the kernels; the read-back; the whole call."""
         t = (C.c_double * 4)()
@@ -294,3 +343,15 @@ class BatchEstimatorState:
         res = self.est.slide_batch([(s, k, nonlinear) for s, k in zip(self.slots, self._per_slot(kinds, "kinds"))])
         return dict(results=res, marg_R=[r["marg_R"] for r in res], marg_P=[r["marg_P"] for r in res], new_R=[r["new_R"] for r in res],
                     new_P=[r["new_P"] for r in res])
+
+    def init_apply(self, poses, speed_bias, g, rot, commit_last=False):
+        """visualInitialAlign's writes from each slot's alignment result (its poses, speed_bias, g and rot); commit_last: also
+        last_R / last_P / last_R0 / last_P0 from the window written."""
+        cols = [self._per_slot(v, k) for v, k in ((poses, "poses"), (speed_bias, "speed_bias"), (g, "g"), (rot, "rot"))]
+        return self.est.init_apply_batch([(s,) + tuple(c) + (commit_last,) for s, *c in zip(self.slots, *cols)])
+
+    def relinearize(self, ba_thresh, bg_thresh):
+        """repropagate, per slot, the intervals whose start frame's bias moved past the thresholds (scalars, or one per slot)."""
+        ta = [ba_thresh] * len(self.slots) if np.isscalar(ba_thresh) else self._per_slot(ba_thresh, "ba_thresh")
+        tg = [bg_thresh] * len(self.slots) if np.isscalar(bg_thresh) else self._per_slot(bg_thresh, "bg_thresh")
+        return self.est.relinearize_batch(list(zip(self.slots, ta, tg)))

@@ -374,6 +374,56 @@ def aif_flush(drivers):
         todo = [d for d in todo if d._aif_queue]
 
 
+def est_flush(drivers):
+    """Feeds the INITIAL-state steps that `drivers` (all on one est.EstHandle, initialize=dict(state=)) have queued into their
+    estimator-state slots, as aif_flush does for all_image_frame: per step one slide_batch (a failed try's slideWindow), one imu_batch
+    (processIMU) and one image_batch (processImage) over every driver that has one.  A slot that did not follow (a window that is not
+    full at a slide, POOL_FULL) would be out of step with its driver, so it raises."""
+    todo = [d for d in drivers if d._est_queue]
+    while todo:
+        steps = [(d, d._est_queue.pop(0)) for d in todo]
+        for part, name in enumerate(("slide_batch", "imu_batch", "image_batch")):
+            who = [d for d, st in steps if st[part] is not None]
+            if not who:
+                continue
+            res = getattr(who[0].est, name)([(d.est_slot,) + st[part] for d, st in steps if st[part] is not None])
+            for d, r in zip(who, res):
+                if r["status"] != 0 or (part == 0 and not r["slid"]):
+                    raise RuntimeError("StreamDriver: vio_est_%s did not serve slot %d (status %d, frame_count %d)" % (name, d.est_slot, r["status"], r["frame_count"]))
+        todo = [d for d in todo if d._est_queue]
+
+
+def est_init_apply(drivers, results):
+    """visualInitialAlign's state change of every driver that initialised, in its slot: one init_apply_batch on each try's poses,
+    speed_bias, g and rot (include/vio_est_init.h), with commit_last: the reference runs no failureDetection behind the first solve
+    (estimator.cpp:192-201), update_batch always does, so last_P starts at the initialisation's newest frame and not at whatever the
+    slot held."""
+    res = drivers[0].est.init_apply_batch([(d.est_slot, np.asarray(r["poses"], dtype=np.float64).reshape(NUM_FRAMES, 7),
+                                            np.asarray(r["speed_bias"], dtype=np.float64).reshape(NUM_FRAMES, 9), r["g"], r["rot"], True)
+                                           for d, r in zip(drivers, results)])
+    for d, r in zip(drivers, res):
+        if r["status"] != 0:
+            raise RuntimeError("StreamDriver: vio_est_init_apply_batch refused slot %d with status %d (frame_count %d)" % (d.est_slot, r["status"], r["frame_count"]))
+
+
+def est_relinearize(drivers):
+    """repropagate in the slots of the drivers that ask for it (state=dict(relinearize=)): one relinearize_batch; each driver's count
+    goes to its `repropagated`."""
+    who = [d for d in drivers if d.est_relin is not None]
+    if who:
+        for d, r in zip(who, who[0].est.relinearize_batch([(d.est_slot,) + d.est_relin for d in who])):
+            d.repropagated.append(int(r["n_relinearized"]))
+
+
+def _parse_state(state):
+    """(handle, slot, relinearize thresholds or None) of a state= argument: a tuple (handle, slot), or a dict(handle=, slot=,
+    relinearize=(ba_thresh, bg_thresh))."""
+    if isinstance(state, dict):
+        relin = state.get("relinearize")
+        return state["handle"], int(state["slot"]), None if relin is None else (float(relin[0]), float(relin[1]))
+    return state[0], int(state[1]), None
+
+
 # ---- the FeatureManager of `drivers` (all on one fm.FmHandle, features=) in one call each ------------------------
 FM_DEPTH_SET, FM_BACK_SHIFT_DEPTH, FM_BACK, FM_FRONT = 0, 0, 1, 2        # include/vio_fm.h
 
@@ -487,13 +537,24 @@ class StreamDriver:
         InitHandle.initialize_batch over the driver's lists; a key walk or PnP that fails is a failed try with status
         sfm.TRY_FAILED_SFM.  The slot is fed in steps that are queued and sent in front of a try, for every driver of a group in
         one call each (aif_flush).  The handle's IMU noise is the caller's to set (AifHandle.set_config) and must equal the
-        stream's; an `aligner` cannot be combined with `all_frames` (both raise ValueError).  None: the
-        ground-truth start below.
+        stream's; an `aligner` cannot be combined with `all_frames` (both raise ValueError).  A `state` entry, (est_handle, slot) or
+        the dict form of state= below: the stream lives in slot `slot` of an est.EstHandle from its first IMU sample.  The slot is reset
+        and fed as processIMU / processImage would feed it (one sample in front of the first image for acc_0 / gyr_0, then each window
+        frame's samples and its header), in queued steps that est_flush sends for every driver of a group in one call each; a failed try
+        queues slideWindow (MARG_OLD), the next frame's samples and its header; a successful one ends in init_apply_batch
+        (include/vio_est_init.h, with commit_last) on the try's poses, speed_bias, g and rot, and from then on the driver is a state=
+        driver: the first update_batch commits last_R / last_P / last_R0 / last_P0 again (estimator.cpp:234-237).  It composes with `all_frames` and
+        features=.  None: the ground-truth start below.
         state=(est_handle, slot): the window states, the intervals' samples and pre-integrations live in slot `slot` of an
         est.EstHandle (include/vio_est.h; or anything with its batched methods): the ground-truth start is written there as an
         initialisation result would be, every step reads the window from it (vector2double and the ten records), re-anchors through it
         (double2vector, with failureDetection's verdict appended to self.failures; a failure raises, there is no reboot policy here),
         slides through it and feeds the next interval's samples to its processIMU.  Not with initialize= or bias_relinearize=.
+        state=dict(handle=, slot=, relinearize=(ba_thresh, bg_thresh)): the same, and with `relinearize` the slot's pre-integrations follow
+        the bias estimates as bias_relinearize= makes the driver's own do: one relinearize_batch (include/vio_est_init.h) in front of every
+        window pull; self.repropagated: the count of every step.  No IMU-library handle is created.  (After a non-keyframe slide the slot's
+        merged interval keeps its linearisation biases, as the reference's push_back does, where bias_relinearize= re-integrates it at
+        the frame's bias.)
         features=(fm_handle, slot), or dict(handle=, slot=, remove_failures=False): the FeatureManager lives in slot `slot` of an
         fm.FmHandle (include/vio_fm.h and vio_fm_stream.h; or anything with its batched methods) and the driver holds no tracks /
         depth dicts.  The slot is reset and fed every stream observation of the eleven window frames (add_batch, frame_count 0 .. 10;
@@ -597,19 +658,20 @@ class StreamDriver:
             if held is not None and tuple(float(nz[k]) for k in ("acc_n", "gyr_n", "acc_w", "gyr_w")) != tuple(float(v) for v in held):
                 raise ValueError("StreamDriver: the stream's IMU noise differs from the all_frames handle's (AifHandle.set_config); the slot's records would not be the driver's")
             self._aif_seed()
-        self.est, self.est_slot = (None, None) if state is None else (state[0], int(state[1]))
+        init_state = None if self.initialize is None else self.initialize.get("state")
+        self.est, self.est_slot, self.est_relin = (None, None, None) if state is None and init_state is None else _parse_state(state if state is not None else init_state)
         self.failures = []          # failureDetection's verdict of every step (state set): the update's result dicts
-        if self.est is not None:
+        if init_state is not None:  # the slot in the INITIAL state: fed by est_flush, handed over by est_init_apply
+            self._est_seed_initial()
+        elif self.est is not None:
             self._seed_state()
 
     # ---- the window state in an estimator-state slot (state) -------------------------------------------
     def _seed_state(self):
         """The ground-truth start as a full window in the slot: frame_count = WINDOW_SIZE, interval j + 1 = self.intervals[j] at zero
         linearisation biases, last_R / last_P / last_R0 / last_P0 as after a first solve (estimator.cpp:198-201)."""
-        nz = dict(acc_n=synth.ACC_N, gyr_n=synth.GYR_N, acc_w=synth.ACC_W, gyr_w=synth.GYR_W)
-        nz.update(self.noise)
+        self._est_config()
         g = (0.0, 0.0, self.g_norm)
-        self.est.set_config(self.ext[0:3], self.ext[3:7], g, nz)
         ivs = self.intervals
         off = np.concatenate([[0, 0], np.cumsum([len(iv["dt"]) for iv in ivs])]).astype(np.int64)
         S = int(off[-1])
@@ -625,6 +687,26 @@ class StreamDriver:
             tic=self.ext[0:3], ric=synth.quat_to_rot(self.ext[3:7]).reshape(9), g=np.array(g), acc_0=acc[-1], gyr_0=gyr[-1], first=first,
             lin_bias=np.zeros((NUM_FRAMES, 6)), last_R=R[WINDOW_SIZE], last_P=self.poses[WINDOW_SIZE, 0:3], last_R0=R[0],
             last_P0=self.poses[0, 0:3], off=off, dt=cat("dt", 1).reshape(S), acc=acc, gyr=gyr))
+
+    def _est_config(self):
+        nz = dict(acc_n=synth.ACC_N, gyr_n=synth.GYR_N, acc_w=synth.ACC_W, gyr_w=synth.GYR_W)
+        nz.update(self.noise)
+        self.est.set_config(self.ext[0:3], self.ext[3:7], (0.0, 0.0, self.g_norm), nz)
+
+    @staticmethod
+    def _est_samples(iv):
+        return (np.array(iv["dt"], dtype=np.float64), np.array(iv["acc"], dtype=np.float64).reshape(-1, 3), np.array(iv["gyr"], dtype=np.float64).reshape(-1, 3))
+
+    def _est_seed_initial(self):
+        """The slot reset, and the window as the INITIAL state has seen it queued for it (slide, imu, image per step): one sample in
+        front of the first image, which gives acc_0 / gyr_0 and constructs interval 0; then every window frame's samples and header."""
+        self._est_config()
+        self.est.reset(self.est_slot)
+        iv0 = self.intervals[0]
+        self._est_queue = [(None, (np.zeros(1), np.array(iv0["acc0"], dtype=np.float64).reshape(1, 3), np.array(iv0["gyr0"], dtype=np.float64).reshape(1, 3)),
+                            (float(self.s.times[self.frames[0]]), True))]
+        for k in range(1, len(self.frames)):
+            self._est_queue.append((None, self._est_samples(self.intervals[k - 1]), (float(self.s.times[self.frames[k]]), True)))
 
     def pull_window(self, win=None):
         """poses, speed-biases and the ten pre-integrations from the slot (win: this slot's entry of a batched window call)."""
@@ -817,13 +899,18 @@ class StreamDriver:
             self._init_imu = load_imu().create(device=self.ctx.cfg.device)
         return self._init_h.initialize_batch(items, intervals, self._init_imu, self.ext[0:3].copy(), self.g_norm, self.noise)
 
-    def init_apply(self, item, res, fm_batched=False):
+    def init_apply(self, item, res, fm_batched=False, est_batched=False):
         """One try's outcome: visualInitialAlign's state change on success, else the INITIAL slide and the next frame.  fm_batched
         (features set): the slot's part is the caller's, for a group in one call each (batch_stream.initialize_batched):
-        fm_init_depths after a success; fm_slide(FM_BACK), fm_add of the new frame and the all_image_frame push after a failure."""
+        fm_init_depths after a success; fm_slide(FM_BACK), fm_add of the new frame and the all_image_frame push after a failure.
+        est_batched (initialize=dict(state=)): likewise est_flush and est_init_apply after a success; a failure's slide and next frame
+        are queued for the slot either way."""
         self.init_tries += 1
         if res["status"] == 0:
             s = float(res["s"])
+            if self.est is not None and not est_batched:
+                est_flush([self])
+                est_init_apply([self], [res])
             self.poses = np.asarray(res["poses"], dtype=np.float64).reshape(NUM_FRAMES, 7).copy()
             self.sb = np.asarray(res["speed_bias"], dtype=np.float64).reshape(NUM_FRAMES, 9).copy()
             self.preint = list(res["pre"])
@@ -876,6 +963,8 @@ class StreamDriver:
         self.preint.pop(0)
         self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
         self.take_next_frame(observe=not fm_batched)
+        if self.est is not None:    # slideWindow, processIMU over the new interval, processImage: frame_count stays WINDOW_SIZE
+            self._est_queue.append(((MARG_OLD, False), self._est_samples(self.intervals[-1]), (float(self.s.times[self.frames[-1]]), True)))
         if fm_batched:
             self._fm_gone = gone        # (for the caller's all_image_frame push, behind its add)
         elif self.aif is not None:
@@ -1016,6 +1105,7 @@ class StreamDriver:
         if self.bias_relinearize is not None:
             self.repropagated.append(self.relinearize_biases())
         if self.est is not None:
+            est_relinearize([self])
             self.pull_window()
         if self.fm is not None:
             w, ids = fm_windows([self], True)[0]
@@ -1148,7 +1238,7 @@ class StreamDriver:
 
     def take_next_frame(self, observe=True):
         """The next image: processIMU's propagation of the newest state, then the frame's observations."""
-        if self.est is not None:            # processIMU over the interval's samples, Headers[frame_count], in the slot
+        if self.est is not None and self.initialized:   # processIMU over the interval's samples, Headers[frame_count], in the slot
             f, imu_item, image_item = self.begin_next_frame()
             self.est.imu_batch([imu_item])
             self.est.image_batch([image_item])
