@@ -4,20 +4,17 @@ and within its tolerances of the host's vio_preintegrate, double2vector to 1e-12
 failureDetection at their thresholds, the pool limit, independence of batch and slot index, and the argument errors.  A missing
 library is a failure, not a skip."""
 import ctypes as C
-import math
 
 import numpy as np
 import pytest
 
 import est_reference as er
+from est_scenes import G, NOISE, RIC_Q, TIC, UPDATE_CASES, UPDATE_TOL, make_state, rot, samples, solved_window, update_case, ypr  # noqa: F401  (the builders live there)
 
 pytestmark = pytest.mark.gpu
 
 SLOTS = (0, 7, 255)
 VEC_TOL, BLOCK_TOL = 1e-13, 1e-12       # tests/test_gpu_imu.py's
-UPDATE_TOL = 1e-12                      # relative to max(1, the compared array's largest magnitude)
-NOISE = dict(acc_n=0.08, gyr_n=0.004, acc_w=4.0e-5, gyr_w=2.0e-6)
-TIC, RIC_Q, G = (0.02, -0.06, 0.01), (0.5, -0.5, 0.5, 0.5), (0.0, 0.0, 9.81007)
 
 
 @pytest.fixture(scope="module")
@@ -31,49 +28,6 @@ def eh(est_lib):
     h.set_config(TIC, RIC_Q, G, NOISE)
     yield h
     h.close()
-
-
-def rot(axis, deg):
-    a = np.asarray(axis, dtype=np.float64)
-    a = a / np.linalg.norm(a)
-    t = math.radians(deg)
-    K = np.array([[0, -a[2], a[1]], [a[2], 0, -a[0]], [-a[1], a[0], 0]])
-    return np.eye(3) + math.sin(t) * K + (1 - math.cos(t)) * (K @ K)
-
-
-def ypr(y, p, r):
-    return rot([0, 0, 1], y) @ rot([0, 1, 0], p) @ rot([1, 0, 0], r)
-
-
-def samples(rng, n):
-    return rng.uniform(0.004, 0.006, n), rng.normal(0.0, 2.0, (n, 3)) + [0.0, 0.0, 9.81], rng.uniform(-1.0, 1.0, (n, 3))
-
-
-def make_state(seed, counts, fc=10, missing=()):
-    """A state written down directly: frame_count fc, counts[j] samples in interval j (none behind fc), every interval up to fc
-    constructed but those in `missing`; non-zero biases, an Rs that is not orthonormal, Rs[2] / Rs[5] / Rs[8] turned by 179 degrees
-    about x / y / z (the quaternion's three diagonal branches)."""
-    rng = np.random.RandomState(seed)
-    s = er.new_state(TIC, RIC_Q, G)
-    s.update(frame_count=fc, first_imu=1)
-    for i in range(11):
-        s["Rs"][i] = (ypr(*rng.uniform(-60, 60, 3)) * (1.0 + 1e-3 * rng.uniform(-1, 1))).reshape(9)
-    for i, ax in ((2, [1, 0, 0]), (5, [0, 1, 0]), (8, [0, 0, 1])):
-        s["Rs"][i] = (rot(ax, 179.0) @ ypr(1.0, 2.0, 3.0)).reshape(9)
-    s["Ps"], s["Vs"] = rng.uniform(-3, 3, (11, 3)), rng.uniform(-1, 1, (11, 3))
-    s["Bas"], s["Bgs"] = rng.uniform(-0.2, 0.2, (11, 3)), rng.uniform(-0.02, 0.02, (11, 3))
-    s["Headers"] = 100.0 + 0.05 * np.arange(11)
-    counts = list(counts) + [0] * (11 - len(counts))
-    assert all(c == 0 for c in counts[fc + 1:]) and all(counts[j] == 0 for j in missing)
-    s["exists"] = np.array([int(j <= fc and j not in missing) for j in range(11)], dtype=np.int32)
-    s["first"] = rng.normal(0.0, 2.0, (11, 6)) * s["exists"][:, None]
-    s["lin_bias"] = np.concatenate([rng.uniform(-0.2, 0.2, (11, 3)), rng.uniform(-0.02, 0.02, (11, 3))], axis=1) * s["exists"][:, None]
-    s["off"] = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
-    s["dt"], s["acc"], s["gyr"] = samples(rng, int(s["off"][11]))
-    s["acc_0"], s["gyr_0"] = rng.normal(0.0, 2.0, 3), rng.uniform(-1, 1, 3)
-    s["last_R"], s["last_P"] = ypr(*rng.uniform(-60, 60, 3)).reshape(9), rng.uniform(-3, 3, 3)
-    s["last_R0"], s["last_P0"] = ypr(*rng.uniform(-60, 60, 3)).reshape(9), rng.uniform(-3, 3, 3)
-    return s
 
 
 FIELDS = list(er.new_state().keys())
@@ -239,43 +193,6 @@ def test_window_batch_states_and_preintegrations(vio, hip_lib, eh):
 
 
 # ---- 4. update_batch ---------------------------------------------------------------------------------------------------------------
-def solved_window(rng, s, gauge, scale_q=False):
-    """What a solve could return for state s: every frame moved by the gauge drift `gauge` and a shift, quaternions not unit if asked."""
-    poses, sb, _ = er.vector2double(s)
-    out = poses.copy()
-    for i in range(11):
-        R = gauge @ np.array(er.quat_to_rot(er.F(poses[i, 3:7] / np.linalg.norm(poses[i, 3:7])))).reshape(3, 3)
-        out[i, 0:3] = gauge @ poses[i, 0:3] + [0.3, -0.2, 0.1]
-        out[i, 3:7] = np.array(er.rot_to_quat(er.F(R))[0]) * ((1.0 + 0.02 * i) if scale_q else 1.0)
-    sb = sb + rng.uniform(-0.01, 0.01, sb.shape)
-    ext = np.concatenate([rng.uniform(-0.1, 0.1, 3), np.array(RIC_Q) * 1.01])
-    return out, sb, ext
-
-
-def update_case(name):
-    rng = np.random.RandomState(sum(map(ord, name)))
-    s = make_state(70 + len(name), [0, 2, 2])
-    for i in range(11):                                      # a window of rotations (Rs[0] decides the branch)
-        s["Rs"][i] = ypr(*rng.uniform(-40, 40, 3)).reshape(9)
-    s["last_P"] = s["Ps"][10].copy()                         # (no gate fires: these cases are about double2vector)
-    gauge = ypr(25.0, 0.0, 0.0)
-    if name == "singular_old":
-        s["Rs"][0] = ypr(30.0, 89.5, 10.0).reshape(9)
-        gauge = ypr(25.0, 0.0, 0.0) @ rot([0, 1, 0], -40.0)   # the solved frame 0 is well away from the pole
-    if name == "singular_new":
-        s["Rs"][0] = ypr(30.0, 40.0, 10.0).reshape(9)
-        gauge = ypr(70.0, -89.5, 0.0) @ ypr(30.0, 40.0, 10.0).T        # the solved frame 0 is ypr(70, -89.5, 0) ypr-wise near the pole
-    if name == "failure_occur":
-        s["failure_occur"] = 1
-    out = solved_window(rng, s, gauge, scale_q=(name == "non_unit"))
-    if name == "failure_occur":                              # (the window lands on last_R0 / last_P0: keep the gates quiet there too)
-        s["last_P"] = er.double2vector(s, *out, False)[0]["Ps"][10].copy()
-    return s, out
-
-
-UPDATE_CASES = ["yaw_only", "singular_old", "singular_new", "failure_occur", "non_unit"]
-
-
 def test_update_batch_against_the_restatement(eh):
     """double2vector: Rs / Ps / Vs and last_* within 1e-12 of max(1, |array|) (device atan2 / sin / cos through two 3 x 3 products);
     Bas / Bgs / tic / ric bit for bit.  The measured maximum is printed (DESIGN.md section 30 records it)."""
