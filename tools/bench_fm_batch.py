@@ -14,6 +14,14 @@ times with the order of the legs alternating, for the spread.  Both legs see the
 decisions and the track counts of the last frame are compared (`same`).
 
     python tools/bench_fm_batch.py [--batches 1,16,64,256] [--reps 20] [--warmup 3] [--repeats 3] [--out profiles/NAME.json]
+
+--remove measures erasing a tenth of the rows of B slots by feature id instead, B = 1, 16, 64 (--batches) and
+150 and 2048 tracks per slot:
+
+  leg batch  one FmHandle.remove_batch over the B slots (include/vio_fm_outlier.h): one launch and one wait
+  leg host   per slot tracks_get, the erase on the host (a numpy mask over the arrays) and tracks_set: the route without the call
+
+Every repetition seeds the slots afresh (not timed); the two legs alternate as above and must leave the same tables (`same`).
 """
 import argparse
 import ctypes as C
@@ -65,16 +73,87 @@ def make_stream(seed, frames):
     return out
 
 
+def remove_tracks(n, seed):
+    """n rows as arrays (ids, start, depth, flag, off, pts): 1 .. 11 observations, ids above 2^31 and not sorted."""
+    rng = np.random.RandomState(seed)
+    k = rng.randint(1, 12, size=n)
+    start = (rng.uniform(size=n) * (12 - k)).astype(np.int32)
+    off = np.concatenate([[0], np.cumsum(k)]).astype(np.int64)
+    return (rng.permutation(n).astype(np.int64) * 2500013 + 2 ** 31 + 11, start, rng.uniform(2.0, 9.0, n), np.zeros(n, dtype=np.int32), off,
+            rng.uniform(-0.7, 0.7, (int(off[-1]), 2)))
+
+
+def host_erase(tr, gone):
+    """tracks_get's dict without the rows whose id is in `gone`, as tracks_set's arguments."""
+    keep = ~np.isin(tr["ids"], gone)
+    k = np.diff(tr["off"])
+    off = np.concatenate([[0], np.cumsum(k[keep])]).astype(np.int64)
+    return tr["ids"][keep], tr["start"][keep], tr["depth"][keep], tr["flag"][keep], off, tr["pts"][np.repeat(keep, k)]
+
+
+def measure_remove(vio, args):
+    batches = [int(b) for b in args.batches.split(",")]
+    rows = []
+    fh = vio.load_fm().create()
+    for rep in range(args.repeats):
+        for n in (150, 2048):
+            for B in batches:
+                tables = [remove_tracks(n, 100 * s + n) for s in range(B)]
+                gone = [np.random.RandomState(s).choice(t[0], size=n // 10, replace=False) for s, t in enumerate(tables)]
+                after = {}
+                for leg in (("batch", "host") if rep % 2 == 0 else ("host", "batch")):
+                    wall, lib, parts = [], [], []
+                    for t in range(args.warmup + args.reps):
+                        for s in range(B):
+                            fh.tracks_set(s, *tables[s])
+                        t0 = time.perf_counter()
+                        if leg == "batch":
+                            res = fh.remove_batch(list(zip(range(B), gone)))
+                        else:
+                            for s in range(B):
+                                fh.tracks_set(s, *host_erase(fh.tracks_get(s), gone[s]))
+                        dt = 1e3 * (time.perf_counter() - t0)
+                        if leg == "batch":
+                            assert all(r["n_rows"] == n // 10 for r in res)
+                        if t >= args.warmup:
+                            wall.append(dt)
+                            if leg == "batch":
+                                parts.append(fh.timing())
+                    after[leg] = [fh.tracks_get(s) for s in range(B)]
+                    row = dict(repeat=rep, tracks=n, batch=B, leg=leg, call_ms=float(np.median(wall)), call_ms_min=float(np.min(wall)),
+                               call_ms_max=float(np.max(wall)), us_per_slot=1e3 * float(np.median(wall)) / B)
+                    if leg == "batch":
+                        row["stages_ms"] = {k: float(np.median([p[k] for p in parts])) for k in ("host_ms", "kernel_ms", "readback_ms", "total_ms")}
+                    rows.append(row)
+                    print("repeat %d  tracks %4d  B %3d  leg %-5s  %9.3f ms (%.3f .. %.3f)  %9.1f us/slot  %s"
+                          % (rep, n, B, leg, row["call_ms"], row["call_ms_min"], row["call_ms_max"], row["us_per_slot"],
+                             "lib %(total_ms).3f  h %(host_ms).3f k %(kernel_ms).3f r %(readback_ms).3f" % row["stages_ms"] if leg == "batch" else ""), flush=True)
+                same = all(a[k].tobytes() == b[k].tobytes() for a, b in zip(after["batch"], after["host"]) for k in a)
+                rows.append(dict(repeat=rep, tracks=n, batch=B, same=bool(same)))
+                print("repeat %d  tracks %4d  B %3d  the two legs leave identical tables: %s" % (rep, n, B, same), flush=True)
+    fh.close()
+    res = dict(bench="fm_remove", erased_fraction=0.1, reps=args.reps, warmup=args.warmup, repeats=args.repeats, rows=rows)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="1,16,64,256")
+    ap.add_argument("--remove", action="store_true")
+    ap.add_argument("--batches", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
+    if args.batches is None:
+        args.batches = "1,16,64" if args.remove else "1,16,64,256"
     vio = g.load_package()
     vio.load_hip()
+    if args.remove:
+        return measure_remove(vio, args)
     host = build_host_leg(os.path.join(ROOT, "visual-inertial-odometry_amd", "csrc"))
     batches = [int(b) for b in args.batches.split(",")]
     frames = WINDOW + args.warmup + args.reps

@@ -14,13 +14,14 @@ import numpy as np
 
 from .capi import MARG_OLD, MARG_SECOND_NEW, WINDOW_SIZE
 from .stream import (FM_BACK, FM_BACK_SHIFT_DEPTH, FM_FRONT, anchor_gauge, est_flush, est_init_apply, est_relinearize, fm_add, fm_init_depths,
-                     fm_set_depths, fm_slide, fm_tracks, fm_windows)
+                     fm_remove, fm_set_depths, fm_slide, fm_tracks, fm_windows)
 
 
 def _check(drivers):
     for i, d in enumerate(drivers):
-        if d.outlier_px is not None:
-            raise ValueError("run_batched: driver %d was created with outlier_px (the residual query is not batched here)" % i)
+        if d.outlier_px is not None and (d.fm is None or not hasattr(d.fm, "remove_batch")):
+            raise ValueError("run_batched: driver %d was created with outlier_px and without features= on a handle with remove_batch "
+                             "(the residual query is batched here for FeatureManagers in slots only)" % i)
         if d.bias_relinearize is not None:
             raise ValueError("run_batched: driver %d was created with bias_relinearize (not batched here)" % i)
     libs = {id(d.lib) for d in drivers}
@@ -44,7 +45,10 @@ def step_batched(drivers, marg):
     created with state= share a handle (_check): the frame then makes one window, one update, one slide and one processIMU call (and
     one for the headers) for all of them.  Drivers created with features= share a handle too: the frame then makes one export, one
     set-depth, one second export, one slide and one add call for all of them.  Where a driver was created with
-    state=dict(relinearize=), one relinearize_batch goes in front of the window call."""
+    state=dict(relinearize=), one relinearize_batch goes in front of the window call.  Where drivers were created with outlier_px
+    (features= too, _check), the frame makes one batched residual query per distinct threshold over them behind the solve, flags only,
+    and one remove_batch of the flagged landmarks' feature ids behind the marginalisation and in front of the slides; the drivers
+    without a threshold take part in neither."""
     est, fm = drivers[0].est, drivers[0].fm
     if est is not None:
         est_relinearize(drivers)    # (state=dict(relinearize=): one relinearize_batch in front of the window call)
@@ -71,6 +75,7 @@ def step_batched(drivers, marg):
     invds = [d.ctx.get_landmarks() for d in drivers]
     if fm is not None:
         fm_set_depths(drivers, invds)
+    bad = _flagged(drivers, loaded)
     for d, (w, ids), rep, (poses, sb, _), invd in zip(drivers, loaded, reps, solved, invds):
         if d.prior is not None:      # estimator.cpp:1040-1049: b/err prior come back updated, H/Jt stay
             b, e = d.ctx.get_prior()
@@ -92,6 +97,10 @@ def step_batched(drivers, marg):
     if fm is not None:
         jobs = [(kind, w2, prior) for (kind, _, prior), (w2, _) in zip(jobs, fm_windows(drivers, False))]
     priors = marg.compute_batch(jobs)
+    if bad:                         # removeOutlier + removeFailures, before the slides
+        for d, ids in bad:
+            d.record_rejected(ids)
+        fm_remove([d for d, _ in bad], [ids for _, ids in bad])
     more = []
     if est is not None:             # slideWindow, then processIMU and the headers of the next frame, one call each
         for d, p in zip(drivers, priors):
@@ -140,6 +149,20 @@ def step_batched(drivers, marg):
         d.take_next_frame()
         more.append(True)
     return more
+
+
+def _flagged(drivers, loaded):
+    """(driver, feature ids the residual query condemns) of every driver created with outlier_px: FeaturePerId::is_outlier /
+    solve_flag = 2 from the solved states the contexts hold, on the windows they were loaded with.  One batch_residuals per distinct
+    threshold, flags only."""
+    out = {}
+    for px in sorted({d.outlier_px for d in drivers if d.outlier_px is not None}):
+        who = [i for i, d in enumerate(drivers) if d.outlier_px == px]
+        res = drivers[0].lib.batch_residuals([drivers[i].ctx for i in who], [loaded[i][0] for i in who], outlier_px=px, outputs=("flags",))
+        for i, r in zip(who, res):
+            ids = loaded[i][1]
+            out[i] = [ids[k] for k in np.nonzero(r["flags"] & 7)[0]]
+    return [(drivers[i], out[i]) for i in sorted(out)]
 
 
 def _fm_slide_group(go, mats):

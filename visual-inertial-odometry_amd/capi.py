@@ -234,11 +234,12 @@ class VioLib:
         from . import load_cov
         return load_cov().compute_batch(ctxs, windows, gauge)
 
-    def batch_residuals(self, ctxs, windows, focal=None, outlier_px=3.0):
+    def batch_residuals(self, ctxs, windows, focal=None, outlier_px=3.0, outputs=None):
         """VioContext.residuals of every window of `ctxs` with one launch per kernel for the batch (vio_res_compute_batch): one dict
-        per window, bitwise what the single call gives."""
+        per window, bitwise what the single call gives.  outputs: the entries wanted of obs, lm, flags, summary (None: all)."""
         from . import load_res, synth
-        return load_res().compute_batch(ctxs, windows, synth.FOCAL if focal is None else focal, outlier_px)
+        kw = {} if outputs is None else dict(outputs=tuple(outputs))
+        return load_res().compute_batch(ctxs, windows, synth.FOCAL if focal is None else focal, outlier_px, **kw)
 
     def has(self, name):
         return hasattr(self.dll, self.prefix + name)

@@ -1,7 +1,8 @@
 // vio_fm.hip — libvio_fm_hip.so: the FeatureManager of many streams in one call, each stream's track list resident on the device
 // (include/vio_fm.h).
 // Contraction is off (vio_fm_math.h): the parallax term and the depth shift are evaluated as written.  No floating-point atomics.
-// The kernels, described where they are, are in vio_fm_body.inc and (include/vio_fm_stream.h's two) vio_fm_stream_body.inc; the triangulation is vio_triangulate_body.h, a function around the
+// The kernels, described where they are, are in vio_fm_body.inc, (include/vio_fm_stream.h's two) vio_fm_stream_body.inc and
+// (include/vio_fm_outlier.h's one) vio_fm_outlier_body.inc; the triangulation is vio_triangulate_body.h, a function around the
 // text (vio_triangulate_body.inc) that k_triangulate of libvio_hip includes.
 #include <hip/hip_runtime.h>
 
@@ -14,6 +15,7 @@
 
 #include "../../include/vio_fm.h"
 #include "../../include/vio_fm_stream.h"
+#include "../../include/vio_fm_outlier.h"
 #include "vio_companion.h"
 #include "vio_device_math.h"
 #include "vio_types.h"
@@ -24,6 +26,8 @@
 
 #include "vio_fm_body.inc"
 #include "vio_fm_stream_body.inc"
+#include "vio_fm_outlier_math.h"
+#include "vio_fm_outlier_body.inc"
 
 static_assert(FM_MAX_TRACKS == VIO_FM_MAX_TRACKS && FM_MAX_OBS == VIO_FM_MAX_OBS && FM_MAX_POINTS == VIO_FM_MAX_POINTS &&
               FM_BACK_SHIFT_DEPTH == VIO_FM_BACK_SHIFT_DEPTH && FM_BACK == VIO_FM_BACK && FM_FRONT == VIO_FM_FRONT &&
@@ -49,6 +53,7 @@ struct vio_fm {
     double timing[4] = {NAN, NAN, NAN, NAN};
     std::vector<FmItemD> its;
     std::vector<int64_t> scratch_ids;
+    std::vector<int32_t> scratch_perm;                   // vio_fm_remove_batch: every item's sort permutation
 };
 
 namespace {
@@ -496,6 +501,48 @@ vio_status vio_fm_tracks_batch(vio_fm *h, int32_t count, const vio_fm_tracks_ite
                             if (total) std::memcpy(it.pts, p, 16 * total);
                             p += 16 * no;
                             if (n) { std::memcpy(it.start, p, 4 * n); std::memcpy(it.flag, p + 4 * nt, 4 * n); }
+                        }
+                    });
+}
+
+// ---- include/vio_fm_outlier.h --------------------------------------------------------------------------------
+
+vio_status vio_fm_remove_batch(vio_fm *h, int32_t count, const vio_fm_remove_item *items, vio_fm_result *results) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    const Tick t0 = std::chrono::steady_clock::now();
+    vio_status st = begin_call(h, "vio_fm_remove_batch", count, items, results);
+    if (st != VIO_OK || count == 0) return st;
+    size_t total = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_fm_remove_item &it = items[i];
+        if (it.n < 0 || it.n > VIO_FM_MAX_TRACKS) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_remove_batch: item %d: n = %d outside [0, %d]", i, it.n, VIO_FM_MAX_TRACKS);
+        if (it.n > 0 && !it.ids) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_remove_batch: item %d: ids is required", i);
+        total += (size_t)it.n;
+    }
+    h->scratch_ids.resize(total);                        // every item's ids, sorted, one item behind the other (c: where)
+    h->scratch_perm.resize(total);
+    size_t b_in = 0, b_out = 0, at = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_fm_remove_item &it = items[i];
+        if (!fm_sort_ids(it.ids, it.n, h->scratch_ids.data() + at, h->scratch_perm.data() + at))
+            return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_remove_batch: item %d: an id is listed twice", i);
+        FmItemD &d = h->its[(size_t)i];
+        d.b = it.n; d.c = (int32_t)at;
+        d.o_in = (int64_t)b_in; d.o_out = (int64_t)b_out;
+        b_in += align256(8 * (size_t)it.n);
+        b_out += align256((size_t)it.n);
+        at += (size_t)it.n;
+    }
+    return run_call(h, t0, count, items, results, b_in, b_out, k_fm_remove, FM_NT,
+                    [&](char *in) {
+                        for (int i = 0; i < count; ++i)
+                            if (items[i].n) std::memcpy(in + h->its[(size_t)i].o_in, h->scratch_ids.data() + h->its[(size_t)i].c, 8 * (size_t)items[i].n);
+                    },
+                    [&](const char *out) {
+                        for (int i = 0; i < count; ++i) {
+                            const FmItemD &d = h->its[(size_t)i];
+                            results[i].n_rows = fm_clamp(results[i].n_rows, 0, d.n_tracks < d.b ? d.n_tracks : d.b);
+                            if (items[i].erased) fm_unpermute_hits((const uint8_t *)out + d.o_out, h->scratch_perm.data() + d.c, d.b, items[i].erased);
                         }
                     });
 }

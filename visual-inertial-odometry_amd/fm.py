@@ -1,4 +1,4 @@
-"""ctypes binding of include/vio_fm.h (csrc/libvio_fm_hip.so): the reference's FeatureManager for many streams at once, each stream's
+"""ctypes binding of include/vio_fm.h, vio_fm_stream.h and vio_fm_outlier.h (csrc/libvio_fm_hip.so): the reference's FeatureManager for many streams at once, each stream's
 track list resident on the device.
 
     fh = vio.load_fm().create()                                      # (device 0, its own stream)
@@ -6,6 +6,7 @@ track list resident on the device.
     res = fm.add_feature_frames(bt.feature_frames(), frame_counts)   # addFeatureCheckParallax: res[i]["keyframe"]
     wins = fm.windows(poses, ext)                                    # triangulate + the arrays vio_set_landmarks / _observations take
     fm.set_depths([w["inv_depth"] for w in solved])                  # setDepth + removeFailures
+    fm.remove([w["feature_ids"][flags & 7 != 0] for w, flags in zip(wins, lm_flags)])    # removeOutlier by id (vio_fm_outlier.h)
     fm.slide([BACK_SHIFT_DEPTH] * 64, marg_R=..., marg_P=..., new_R=..., new_P=...)
 
 A track list as arrays is tests/fm_util.tracks_to_arrays' layout: ids, start, depth, flag, off (n + 1), pts (off[-1], 2).
@@ -67,6 +68,10 @@ class VioFmTracksItem(C.Structure):
                 ("depth", C.c_void_p), ("flag", C.c_void_p), ("off", C.c_void_p), ("pts", C.c_void_p)]
 
 
+class VioFmRemoveItem(C.Structure):                                     # include/vio_fm_outlier.h
+    _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("ids", C.c_void_p), ("erased", C.c_void_p)]
+
+
 def _result(r):
     return {k: getattr(r, k) for k, _ in VioFmResult._fields_}
 
@@ -77,6 +82,7 @@ class FmLib:
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "reset", "counts", "add_batch", "export_batch",
                "set_depth_batch", "slide_batch", "corresponding_batch", "tracks_set", "tracks_get", "timing"]
     STREAM_SYMBOLS = ["init_depth_batch", "tracks_batch"]                                  # include/vio_fm_stream.h
+    OUTLIER_SYMBOLS = ["remove_batch"]                                                     # include/vio_fm_outlier.h
 
     def __init__(self, path):
         self.path = path
@@ -91,7 +97,8 @@ class FmLib:
         self.fn["tracks_get"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int64] + [C.c_void_p] * 7
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
         self.fn.update(open_lib(path, "vio_fm_", self.STREAM_SYMBOLS)[1])
-        for k in self.STREAM_SYMBOLS:
+        self.fn.update(open_lib(path, "vio_fm_", self.OUTLIER_SYMBOLS)[1])
+        for k in self.STREAM_SYMBOLS + self.OUTLIER_SYMBOLS:
             self.fn[k].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
@@ -266,6 +273,30 @@ class FmHandle(CompanionHandle):
                      pts=o["pts"][:o["off"][n]].copy())
         return res
 
+    def remove_batch(self, items):
+        """removeOutlier by id per item (slot, ids (n,)): every row of the slot whose feature id is listed is erased, the others keep
+        their order and content; an id no row has is not an error.  ids: distinct, at most MAX_TRACKS, any order (the feature_ids an
+        export_batch returned).  The result dicts (the three counts after the call; n_rows: the rows erased) plus `erased`, a bool
+        array in the order of ids: which of them named a row."""
+        arr, keep, outs = (VioFmRemoveItem * max(len(items), 1))(), [], []
+        for i, (slot, ids) in enumerate(items):
+            ids = np.asarray(ids)
+            if ids.ndim != 1 or (ids.size and ids.dtype.kind not in "iu"):
+                raise ValueError("item %d: ids must be a one-dimensional array of integers" % i)
+            ids = np.ascontiguousarray(ids, dtype=np.int64)
+            if len(ids) > MAX_TRACKS:
+                raise ValueError("item %d: %d ids, a slot has at most %d rows" % (i, len(ids), MAX_TRACKS))
+            if len(np.unique(ids)) != len(ids):
+                raise ValueError("item %d: an id is listed twice" % i)
+            erased = np.zeros(len(ids), dtype=np.uint8)
+            keep.append(ids)
+            outs.append(erased)
+            arr[i] = VioFmRemoveItem(int(slot), len(ids), ids.ctypes.data if len(ids) else None, erased.ctypes.data if len(ids) else None)
+        res = self._call("remove_batch", arr, len(items))
+        for r, e in zip(res, outs):
+            r["erased"] = e.astype(bool)
+        return res
+
     def timing(self):
         """ms of the last batched call that launched: host checks, packing and upload; the kernel; the read-back; the whole call."""
         t = (C.c_double * 4)()
@@ -337,3 +368,7 @@ class BatchFeatureManager:
     def tracks(self):
         """Every slot's list (sfm_f) in one call."""
         return self.fm.tracks_batch(self.slots)
+
+    def remove(self, ids_per_slot):
+        """removeOutlier / removeFailures by id: per slot the feature ids whose tracks go (FmHandle.remove_batch)."""
+        return self.fm.remove_batch(list(zip(self.slots, self._per_slot(ids_per_slot, "ids_per_slot"))))

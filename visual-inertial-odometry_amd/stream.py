@@ -466,6 +466,15 @@ def fm_set_depths(drivers, inv_depths):
             _fm_checked(ds, ds[0].fm.set_depth_batch([(d.fm_slot, x) for d, x in who], FM_DEPTH_SET, flag), "set_depth_batch")
 
 
+def fm_remove(drivers, ids_lists):
+    """removeOutlier / removeFailures by feature id in every driver's slot: one remove_batch.  Each call's erased rows go to the
+    driver's fm_erased."""
+    res = _fm_checked(drivers, drivers[0].fm.remove_batch([(d.fm_slot, np.asarray(ids, dtype=np.int64).reshape(-1)) for d, ids in zip(drivers, ids_lists)]),
+                      "remove_batch")
+    for d, r in zip(drivers, res):
+        d.fm_erased.append(int(r["n_rows"]))
+
+
 def fm_slide(drivers, kinds, mats=None):
     """kinds[i]: FM_BACK_SHIFT_DEPTH with mats[i] = (marg_R, marg_P, new_R, new_P), FM_BACK, or FM_FRONT (frame_count WINDOW_SIZE): one
     slide_batch."""
@@ -563,15 +572,16 @@ class StreamDriver:
         removeFailures does), exports the marginalisation's edges, slides (slide_batch: BACK_SHIFT_DEPTH on the four arrays of
         slideWindowOld, FRONT for a non-keyframe) and adds the next frame.  An INITIAL try reads sfm_f with tracks_batch, a failed
         one slides with BACK, a successful one ends in init_depth_batch on the SfM poses with tic = 0 and s.  The library's own
-        keyframe decision of every add is recorded in self.fm_keyframe and not used.  A slot status other than OK raises.  Not with
-        outlier_px, and not with triangulate=False unless initialize= is given (both raise ValueError): erasing by id and the perturbed
-        ground-truth depths are not FeatureManager behaviour."""
+        keyframe decision of every add is recorded in self.fm_keyframe and not used.  A slot status other than OK raises.  With
+        outlier_px the flagged landmarks' feature ids (the export's) go to remove_batch (include/vio_fm_outlier.h) after the
+        marginalisation and before the slide; self.fm_erased: the rows each call erased (an id that remove_failures=True had erased
+        already counts in self.rejected and not here).  A handle without remove_batch raises ValueError with outlier_px.  Not with
+        triangulate=False unless initialize= is given (ValueError): the perturbed ground-truth depths are not FeatureManager
+        behaviour."""
         if state is not None and (initialize is not None or bias_relinearize is not None):
             raise ValueError("StreamDriver: state= cannot be combined with initialize= or bias_relinearize=")
         self.fm, self.fm_slot, self.fm_remove_failures = None, None, False
         if features is not None:
-            if outlier_px is not None:
-                raise ValueError("StreamDriver: features= cannot be combined with outlier_px (removeOutlier by id is not in the slot)")
             if not triangulate and initialize is None:
                 raise ValueError("StreamDriver: features= needs triangulate=True or initialize= (the perturbed ground-truth depths are not a FeatureManager behaviour)")
             if isinstance(features, dict):
@@ -579,6 +589,9 @@ class StreamDriver:
                 self.fm_remove_failures = bool(features.get("remove_failures", False))
             else:
                 self.fm, self.fm_slot = features[0], int(features[1])
+            if outlier_px is not None and not hasattr(self.fm, "remove_batch"):
+                raise ValueError("StreamDriver: features= with outlier_px needs a handle with remove_batch (removeOutlier by id, include/vio_fm_outlier.h)")
+        self._rejected = set()      # landmarks whose tracks were erased (outlier_px set): frame_points leaves them out
         self.fm_keyframe = []       # addFeatureCheckParallax's own decision of every frame added (features set): recorded, not used
         self.lib, self.s = lib, stream
         self.noise = dict(getattr(stream, "noise", None) or {})      # sensor noise of re-integrated intervals (default: synth's)
@@ -628,6 +641,7 @@ class StreamDriver:
         self.outlier_px = outlier_px
         self.rejected = []          # tracks erased at every step (outlier_px set)
         self.rejected_ids = []      # ... and which
+        self.fm_erased = []         # rows every remove_batch erased (features and outlier_px set)
         self.bias_relinearize = None if bias_relinearize is None else (float(bias_relinearize[0]), float(bias_relinearize[1]))
         self.repropagated = []      # intervals re-propagated before every solve (bias_relinearize set)
         if self.bias_relinearize is not None:
@@ -980,10 +994,13 @@ class StreamDriver:
     # ---- feature bookkeeping (FeatureManager) ---------------------------------------------------------
     def frame_points(self, f):
         """Every stream observation of global frame f as the front end would hand it over: (ids, points), ids the landmark numbers,
-        the point lm_px for the frame that hosts the landmark, else lm_obs[l][f]."""
+        the point lm_px for the frame that hosts the landmark, else lm_obs[l][f].  A landmark whose track was rejected (outlier_px)
+        is left out from then on, as add_frame_observations leaves it out of the dicts: an erased track is not begun again."""
         st = self.s
         ids, pts = [], []
         for l, h in enumerate(st.lm_host):
+            if l in self._rejected:
+                continue
             if h == f:
                 ids.append(l); pts.append(st.lm_px[l])
             elif f in st.lm_obs[l]:
@@ -1143,11 +1160,9 @@ class StreamDriver:
         self.ctx.load(w2)
         self.prior = self.ctx.marginalize(MARG_OLD if margin_old else MARG_SECOND_NEW)
         if self.outlier_px is not None:         # removeOutlier + removeFailures, before the slide
-            for l in bad:
-                del self.tracks[l]
-                self.depth.pop(l, None)
-            self.rejected.append(len(bad))
-            self.rejected_ids.extend(bad)
+            self.record_rejected(bad)
+            if self.fm is not None:
+                fm_remove([self], [bad])
         if self.next_frame >= st.n_frames:
             return False
         if self.est is not None:
@@ -1158,6 +1173,17 @@ class StreamDriver:
             self.slide_window_new()
         self.take_next_frame()
         return True
+
+    def record_rejected(self, bad):
+        """The tracks the residual query's flags condemn at this step: erased from the dicts where the driver holds them (the slot's
+        rows go in the caller's remove_batch), counted and listed."""
+        if self.fm is None:
+            for l in bad:
+                del self.tracks[l]
+                self.depth.pop(l, None)
+        self.rejected.append(len(bad))
+        self.rejected_ids.extend(bad)
+        self._rejected.update(bad)
 
     def apply_slide(self, res, margin_old, fm_done=False):
         """The FeatureManager side of a slide the slot has made: res is this slot's entry of slide_batch's results."""
