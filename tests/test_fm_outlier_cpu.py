@@ -12,6 +12,7 @@ import pytest
 
 import fm_outlier_reference as fo
 import fm_stream_reference as fsr
+from stream_group_util import OracleMarg, patch_batched, stub_driver
 from test_fm_stream_cpu import STREAMS, make
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,21 +96,6 @@ def test_duplicate_ids_are_found_wherever_they_stand(driver):
 
 
 # ---- the drivers' wiring ------------------------------------------------------------------------------------------------
-def stub_flags(w):
-    """The residual query's flags as a function of the window alone: bit 0 (outlier) for every seventh landmark index, bit 1 (behind a
-    camera) for every eleventh."""
-    n = int(w.n_landmarks)
-    f = np.zeros(n, dtype=np.uint8)
-    f[3::7] |= 1
-    f[5::11] |= 2
-    return f
-
-
-def stub_driver(d):
-    d.ctx.residuals = lambda w, focal=None, outlier_px=3.0: dict(flags=stub_flags(w))
-    return d
-
-
 @pytest.mark.parametrize("seed,nonkey,n_frames", STREAMS)
 def test_slot_path_rejects_what_the_dict_path_rejects(vio, oracle_lib, seed, nonkey, n_frames):
     vs = vio.stream
@@ -160,32 +146,10 @@ def test_an_id_remove_failures_took_counts_as_rejected_and_not_as_erased(vio, or
     assert not set(drv.rejected_ids) & set(ids)
 
 
-class OracleMarg:
-    """MargHandle.compute_batch on the CPU backend: each job through a context's load + marginalize."""
-
-    def __init__(self, lib):
-        self.lib = lib
-
-    def compute_batch(self, jobs):
-        out = []
-        for kind, w, prior in jobs:
-            assert w.prior is prior
-            c = self.lib.context()
-            c.load(w)
-            out.append(c.marginalize(kind))
-        return out
-
-
 def batch_group(vio, oracle_lib, monkeypatch, thresholds, fm):
     from vio_amd import batch_stream
     vs = vio.stream
-    seen = []
-
-    def batch_residuals(ctxs, windows, focal=None, outlier_px=3.0, outputs=None):
-        seen.append((len(ctxs), outlier_px, outputs))
-        return [dict(flags=stub_flags(w)) for w in windows]
-    monkeypatch.setattr(oracle_lib, "batch_solve", lambda ctxs, iterations=10: [c.solve(iterations) for c in ctxs], raising=False)
-    monkeypatch.setattr(oracle_lib, "batch_residuals", batch_residuals, raising=False)
+    seen = patch_batched(monkeypatch, oracle_lib)
     drivers = []
     for k, ((seed, nonkey, n_frames), px) in enumerate(zip(STREAMS, thresholds)):
         d = vs.StreamDriver(oracle_lib, make(vs, seed, n_frames), triangulate=True, nonkey_every=nonkey, outlier_px=px, features=(fm, 10 + k))

@@ -360,18 +360,10 @@ def aif_flush(drivers):
     """Feeds the INITIAL-state steps that `drivers` (all on one aif.AifHandle) have queued into their all_image_frame slots: per step
     one slide_batch, one imu_batch and one image_batch over every driver that has one.  A refused item (POOL_FULL, FRAMES_FULL,
     NO_FRAME) would leave its slot out of step with the driver's lists, so it raises."""
-    todo = [d for d in drivers if d._aif_queue]
-    while todo:
-        steps = [(d, d._aif_queue.pop(0)) for d in todo]
-        for part, name in enumerate(("slide_batch", "imu_batch", "image_batch")):
-            who = [d for d, st in steps if st[part] is not None]
-            if not who:
-                continue
-            res = getattr(who[0].aif, name)([(d.aif_slot,) + st[part] for d, st in steps if st[part] is not None])
-            for d, r in zip(who, res):
-                if r["status"] != 0:
-                    raise RuntimeError("StreamDriver: vio_aif_%s refused slot %d with status %d" % (name, d.aif_slot, r["status"]))
-        todo = [d for d in todo if d._aif_queue]
+    def check(d, name, r):
+        if r["status"] != 0:
+            raise RuntimeError("StreamDriver: vio_aif_%s refused slot %d with status %d" % (name, d.aif_slot, r["status"]))
+    _flush(drivers, "aif", check)
 
 
 def est_flush(drivers):
@@ -379,18 +371,27 @@ def est_flush(drivers):
     estimator-state slots, as aif_flush does for all_image_frame: per step one slide_batch (a failed try's slideWindow), one imu_batch
     (processIMU) and one image_batch (processImage) over every driver that has one.  A slot that did not follow (a window that is not
     full at a slide, POOL_FULL) would be out of step with its driver, so it raises."""
-    todo = [d for d in drivers if d._est_queue]
+    def check(d, name, r):
+        if r["status"] != 0 or (name == "slide_batch" and not r["slid"]):
+            raise RuntimeError("StreamDriver: vio_est_%s did not serve slot %d (status %d, frame_count %d)" % (name, d.est_slot, r["status"], r["frame_count"]))
+    _flush(drivers, "est", check)
+
+
+def _flush(drivers, kind, check):
+    """The queued (slide, imu, image) steps of `drivers` into their `kind` ("aif" or "est") slots, the oldest step of every driver
+    first: one call per part over the drivers whose step has it; check(driver, method, result) raises where a slot did not follow."""
+    queue, slot = "_%s_queue" % kind, "%s_slot" % kind
+    todo = [d for d in drivers if getattr(d, queue)]
     while todo:
-        steps = [(d, d._est_queue.pop(0)) for d in todo]
+        steps = [(d, getattr(d, queue).pop(0)) for d in todo]
         for part, name in enumerate(("slide_batch", "imu_batch", "image_batch")):
-            who = [d for d, st in steps if st[part] is not None]
+            who = [(d, st[part]) for d, st in steps if st[part] is not None]
             if not who:
                 continue
-            res = getattr(who[0].est, name)([(d.est_slot,) + st[part] for d, st in steps if st[part] is not None])
-            for d, r in zip(who, res):
-                if r["status"] != 0 or (part == 0 and not r["slid"]):
-                    raise RuntimeError("StreamDriver: vio_est_%s did not serve slot %d (status %d, frame_count %d)" % (name, d.est_slot, r["status"], r["frame_count"]))
-        todo = [d for d in todo if d._est_queue]
+            res = getattr(getattr(who[0][0], kind), name)([(getattr(d, slot),) + item for d, item in who])
+            for (d, _), r in zip(who, res):
+                check(d, name, r)
+        todo = [d for d in todo if getattr(d, queue)]
 
 
 def est_init_apply(drivers, results):
@@ -492,15 +493,180 @@ def fm_tracks(drivers):
 def fm_init_depths(drivers, items, scales):
     """visualInitialAlign's depth hand-over of every driver that initialised: clearDepth, triangulate on items[i]'s SfM poses with
     tic = 0, estimated_depth *= scales[i] (estimator.cpp:406-442): one init_depth_batch."""
-    args = []
-    for d, it, s in zip(drivers, items, scales):
-        sfm = np.zeros((NUM_FRAMES, 7))
-        sfm[:, 0:3] = it["T"]
-        for i in range(NUM_FRAMES):
-            sfm[i, 3:7] = synth.rot_to_quat(it["R"][i])
-        args.append((d.fm_slot, sfm, np.concatenate([np.zeros(3), d.ext[3:7]]), float(s)))
+    args = [(d.fm_slot, sfm_poses(it), np.concatenate([np.zeros(3), d.ext[3:7]]), float(s)) for d, it, s in zip(drivers, items, scales)]
     for d, r in zip(drivers, _fm_checked(drivers, drivers[0].fm.init_depth_batch(args), "init_depth_batch")):
         d.n_triangulated += int(r["n_triangulated"])
+
+
+def sfm_poses(item):
+    """An alignment item's SfM poses (R, T) as the (NUM_FRAMES, 7) array a triangulation takes."""
+    sfm = np.zeros((NUM_FRAMES, 7))
+    sfm[:, 0:3] = item["T"]
+    for i in range(NUM_FRAMES):
+        sfm[i, 3:7] = synth.rot_to_quat(item["R"][i])
+    return sfm
+
+
+# ---- one frame and one INITIAL round of a group of drivers (a StreamDriver alone is a group of one) ---------------
+class OwnContexts:
+    """The frame's three heavy calls, each driver's on its own context: what StreamDriver.step issues.  (batch_stream.BatchedCalls
+    issues them once for the group.)"""
+
+    def solve(self, drivers):
+        """Problem::Solve(10) of every loaded window; the reports."""
+        return [d.ctx.solve(10) for d in drivers]
+
+    def flags(self, drivers, windows):
+        """The residual query's landmark flags on the solved states, per driver; None for a driver without outlier_px."""
+        return [None if d.outlier_px is None else d.ctx.residuals(w, outlier_px=d.outlier_px)["flags"] for d, w in zip(drivers, windows)]
+
+    def marginalize(self, drivers, jobs):
+        """jobs[i] = (flag, re-anchored window, prior): the new priors, through vio_marginalize on the reloaded context."""
+        out = []
+        for d, (kind, w2, _) in zip(drivers, jobs):
+            d.ctx.load(w2)
+            out.append(d.ctx.marginalize(kind))
+        return out
+
+
+def step_group(drivers, backend):
+    """One frame of every driver in `drivers` (all initialised and not finished; one library, and one handle each where they have
+    estimator-state or FeatureManager slots): solve the current window, marginalise, slide, take in the next frame.  backend: how
+    the solve, the residual query and the marginalisation are issued (OwnContexts, batch_stream.BatchedCalls).  Every slot call is
+    made once for the group.  Returns, per driver, whether it has another frame."""
+    est, fm = drivers[0].est, drivers[0].fm
+    for d in drivers:
+        if d.bias_relinearize is not None:
+            d.repropagated.append(d.relinearize_biases())
+    if est is not None:             # (state=dict(relinearize=): one relinearize_batch in front of the window call)
+        est_relinearize(drivers)
+        for d, win in zip(drivers, est.window_batch([d.est_slot for d in drivers])):
+            d.pull_window(win)
+    # [f_manager.triangulate,] vector2double, Solve(10)
+    loaded = fm_windows(drivers, True) if fm is not None else [d.dict_windows(True) for d in drivers]
+    for d, (w, _) in zip(drivers, loaded):
+        d.ctx.load(w)
+    reps = backend.solve(drivers)
+    solved = [d.ctx.get_window() for d in drivers]
+    if est is not None:             # double2vector + failureDetection of every window in one call
+        for d, r in zip(drivers, est.update_batch([(d.est_slot, s[0], s[1], d.ext, True) for d, s in zip(drivers, solved)])):
+            d.apply_update(r)
+    else:
+        for d, (w, _), (poses, sb, _) in zip(drivers, loaded, solved):
+            d.poses, d.sb = anchor_gauge(w.poses, poses, sb)
+    invds = [d.ctx.get_landmarks() for d in drivers]
+    if fm is not None:
+        fm_set_depths(drivers, invds)
+    else:
+        for d, (_, ids), invd in zip(drivers, loaded, invds):
+            d.dict_set_depths(ids, invd)
+    # FeaturePerId::is_outlier / solve_flag = 2 from the solved states the contexts hold, on the windows they were loaded with
+    bad = [(d, [ids[k] for k in np.nonzero(f & 7)[0]])
+           for d, (_, ids), f in zip(drivers, loaded, backend.flags(drivers, [w for w, _ in loaded])) if f is not None]
+    kinds = []
+    for d, rep in zip(drivers, reps):
+        if d.prior is not None:      # estimator.cpp:1040-1049: b/err prior come back updated, H/Jt stay
+            b, e = d.ctx.get_prior()
+            d.prior = dict(d.prior, b=b[:156].copy(), err=e.copy())
+        d.trajectory.append((d.s.times[d.frames[WINDOW_SIZE]], d.poses[WINDOW_SIZE].copy()))
+        d.reports.append(rep)
+        second_new = d.frames[WINDOW_SIZE - 1]
+        margin_old = not (d.nonkey_every and second_new % d.nonkey_every == d.nonkey_every - 1)
+        kinds.append(MARG_OLD if margin_old else MARG_SECOND_NEW)
+        d.flags.append(kinds[-1])
+    # backendOptimization marginalises on the re-anchored states (estimator.cpp:1086-1102)
+    again = fm_windows(drivers, False) if fm is not None else [d.dict_windows(False) for d in drivers]
+    priors = backend.marginalize(drivers, [(kind, w2, d.prior) for d, kind, (w2, _) in zip(drivers, kinds, again)])
+    if bad:                         # removeOutlier + removeFailures, before the slides
+        for d, ids in bad:
+            d.record_rejected(ids)
+        if fm is not None:
+            fm_remove([d for d, _ in bad], [ids for _, ids in bad])
+        else:
+            for d, ids in bad:
+                d.dict_remove(ids)
+    more = []
+    for d, p in zip(drivers, priors):
+        d.prior = p
+        more.append(d.next_frame < d.s.n_frames)
+    go = [(d, kind == MARG_OLD) for d, m, kind in zip(drivers, more, kinds) if m]
+    if not go:
+        return more
+    # slideWindow, then processIMU and the image of the next frame
+    ds = [d for d, _ in go]
+    if est is not None:
+        slid = est.slide_batch([(d.est_slot, MARG_OLD if old else MARG_SECOND_NEW, True) for d, old in go])
+        for d, r in zip(ds, slid):
+            if not r["slid"]:
+                raise RuntimeError("StreamDriver: the slot's window is not full (frame_count %d)" % r["frame_count"])
+        mats = [(r["marg_R"], r["marg_P"], r["new_R"], r["new_P"]) if old else None for (_, old), r in zip(go, slid)]
+    else:
+        mats = [d.slide_mats() if old else None for d, old in go]
+    if fm is not None:              # (both slide kinds ride in one slide_batch)
+        fm_slide(ds, [FM_BACK_SHIFT_DEPTH if old else FM_FRONT for _, old in go], mats)
+    else:
+        for (d, old), m in zip(go, mats):
+            if old:
+                d.dict_slide_back_shift(m)
+            else:
+                d.dict_slide_front()
+    for d, old in go:
+        d.slide_lists(old)
+    if est is not None:
+        begun = [d.begin_next_frame() for d in ds]
+        est.imu_batch([b[1] for b in begun])
+        est.image_batch([b[2] for b in begun])
+        new = [b[0] for b in begun]
+    else:
+        new = [d.propagate_next_frame() for d in ds]
+    if fm is not None:
+        fm_add(ds, new)
+    else:
+        for d, f in zip(ds, new):
+            d.dict_add(f)
+    return more
+
+
+def init_round(group):
+    """One INITIAL try of every driver in `group` (all created with `initialize`, not initialised yet, and alike in what one
+    alignment call shares: batch_stream._init_group_key), every call made once for the group: the slots' queued feeding (est_flush),
+    sfm_f (one tracks_batch), the alignment, each driver's own bookkeeping (init_apply), then visualInitialAlign's depth hand-over
+    for the successes, the INITIAL slide, the next frame and its all_image_frame push for the failures, and the state hand-over
+    (est_init_apply) for the successes."""
+    lead = group[0]
+    est, fm = lead.est, lead.fm
+    if est is not None:             # the window in the first round, the last round's failures afterwards
+        est_flush(group)
+    tracks = fm_tracks(group) if fm is not None and lead.initialize.get("sfm") else [None] * len(group)
+    reqs = [d.init_request(tr) for d, tr in zip(group, tracks)]
+    res = lead.init_align([r[0] for r in reqs], [r[1] for r in reqs])
+    won, lost = [], []
+    for d, (item, _), r in zip(group, reqs, res):
+        gone = d.init_apply(r)
+        if gone is None:
+            won.append((d, item, r))
+        else:
+            lost.append((d, gone))
+    if won and fm is not None:
+        fm_init_depths([d for d, _, _ in won], [item for _, item, _ in won], [float(r["s"]) for _, _, r in won])
+    elif won:
+        for d, item, r in won:
+            d.dict_init_depths(item, float(r["s"]))
+    if lost:                        # slideWindow in the INITIAL state: no prior, no depth shift (f_manager.removeBack); the next frame
+        ds = [d for d, _ in lost]
+        if fm is not None:
+            fm_slide(ds, [FM_BACK] * len(ds))
+            fm_add(ds, [d.frames[-1] for d in ds])
+        else:
+            for d, gone in lost:
+                d.dict_slide_back(gone)
+                d.dict_add(d.frames[-1])
+        aif = [(d, gone) for d, gone in lost if d.aif is not None]
+        rows = fm_tracks([d for d, _ in aif]) if aif and fm is not None else [None] * len(aif)
+        for (d, gone), tr in zip(aif, rows):
+            d._aif_push(len(d.frames) - 1, slide=d.s.times[gone], tracks=tr)
+    if won and est is not None:
+        est_init_apply([d for d, _, _ in won], [r for _, _, r in won])
 
 
 class StreamDriver:
@@ -629,7 +795,7 @@ class StreamDriver:
         else:
             self.tracks = {}
             for f in self.frames:
-                self.add_frame_observations(f)
+                self.dict_add(f)
             self.depth = {}                                # landmark -> estimated depth in its current host frame
         self.init_depth = np.array(st.lm_depth) * (1.0 + depth_noise * st.init_noise)
         self.triangulate = triangulate
@@ -666,8 +832,7 @@ class StreamDriver:
             if self.initialize.get("aligner") is not None:
                 raise ValueError("StreamDriver: all_frames takes the try from the library (aif.initialize_from_frames); it cannot be combined with an aligner")
             self.aif, self.aif_slot = self.initialize["all_frames"][0], int(self.initialize["all_frames"][1])
-            nz = dict(acc_n=synth.ACC_N, gyr_n=synth.GYR_N, acc_w=synth.ACC_W, gyr_w=synth.GYR_W)
-            nz.update(self.noise)
+            nz = self._noise()
             held = getattr(self.aif, "noise", None)         # (an AifHandle remembers its set_config; a stand-in without one is not checked)
             if held is not None and tuple(float(nz[k]) for k in ("acc_n", "gyr_n", "acc_w", "gyr_w")) != tuple(float(v) for v in held):
                 raise ValueError("StreamDriver: the stream's IMU noise differs from the all_frames handle's (AifHandle.set_config); the slot's records would not be the driver's")
@@ -702,10 +867,14 @@ class StreamDriver:
             lin_bias=np.zeros((NUM_FRAMES, 6)), last_R=R[WINDOW_SIZE], last_P=self.poses[WINDOW_SIZE, 0:3], last_R0=R[0],
             last_P0=self.poses[0, 0:3], off=off, dt=cat("dt", 1).reshape(S), acc=acc, gyr=gyr))
 
-    def _est_config(self):
+    def _noise(self):
+        """The four IMU noise figures a slot's handle is configured with: synth's, overridden by the stream's."""
         nz = dict(acc_n=synth.ACC_N, gyr_n=synth.GYR_N, acc_w=synth.ACC_W, gyr_w=synth.GYR_W)
         nz.update(self.noise)
-        self.est.set_config(self.ext[0:3], self.ext[3:7], (0.0, 0.0, self.g_norm), nz)
+        return nz
+
+    def _est_config(self):
+        self.est.set_config(self.ext[0:3], self.ext[3:7], (0.0, 0.0, self.g_norm), self._noise())
 
     @staticmethod
     def _est_samples(iv):
@@ -748,18 +917,17 @@ class StreamDriver:
     def _aif_push(self, k, slide=None, first=None, tracks=None):
         """Queues window frame k for the all_image_frame slot as one step (slide, imu, image): the erase up to header `slide`
         (slideWindow) if given, the samples since frame k - 1 (processIMU; `first`: one sample in front of the first image), then the
-        image (processImage).  aif_flush feeds the queued steps of many drivers in one call each."""
+        image (processImage).  tracks (features set): this slot's entry of a tracks call; None: the driver's own dicts.  aif_flush
+        feeds the queued steps of many drivers in one call each."""
         f = self.frames[k]
         iv = first if k == 0 else self.intervals[k - 1]
         imu = None if iv is None else (np.array(iv["dt"], dtype=np.float64), np.array(iv["acc"], dtype=np.float64), np.array(iv["gyr"], dtype=np.float64))
         # a track's observations are consecutive window frames from its first one, so frame k's is entry k - (index of that first frame):
         # one look per track, not a scan of its list
-        if self.fm is not None:     # the slot's rows that have window frame k
-            tr = fm_tracks([self])[0] if tracks is None else tracks
-            n_obs = np.diff(tr["off"])
-            has = (tr["start"] <= k) & (k < tr["start"] + n_obs)
-            ids = np.array(tr["ids"][has], dtype=np.int64)
-            pts = np.array(tr["pts"][(tr["off"][:-1] + k - tr["start"])[has]], dtype=np.float64).reshape(-1, 2)
+        if tracks is not None:      # the slot's rows that have window frame k
+            has = (tracks["start"] <= k) & (k < tracks["start"] + np.diff(tracks["off"]))
+            ids = np.array(tracks["ids"][has], dtype=np.int64)
+            pts = np.array(tracks["pts"][(tracks["off"][:-1] + k - tracks["start"])[has]], dtype=np.float64).reshape(-1, 2)
         else:
             pos = {fr: i for i, fr in enumerate(self.frames)}
             obs = []
@@ -913,89 +1081,43 @@ class StreamDriver:
             self._init_imu = load_imu().create(device=self.ctx.cfg.device)
         return self._init_h.initialize_batch(items, intervals, self._init_imu, self.ext[0:3].copy(), self.g_norm, self.noise)
 
-    def init_apply(self, item, res, fm_batched=False, est_batched=False):
-        """One try's outcome: visualInitialAlign's state change on success, else the INITIAL slide and the next frame.  fm_batched
-        (features set): the slot's part is the caller's, for a group in one call each (batch_stream.initialize_batched):
-        fm_init_depths after a success; fm_slide(FM_BACK), fm_add of the new frame and the all_image_frame push after a failure.
-        est_batched (initialize=dict(state=)): likewise est_flush and est_init_apply after a success; a failure's slide and next frame
-        are queued for the slot either way."""
+    def init_apply(self, res):
+        """The driver's own bookkeeping of one try's outcome, none of it on a handle (init_round makes the slots' calls and the
+        FeatureManager's part).  Success: visualInitialAlign's state change; returns None.  Failure: the INITIAL slideWindow of the
+        window lists (the oldest frame leaves, no prior), the next frame's propagation and, with initialize=dict(state=), the queue
+        entry that brings both into the slot; returns the global frame that left the window."""
         self.init_tries += 1
         if res["status"] == 0:
-            s = float(res["s"])
-            if self.est is not None and not est_batched:
-                est_flush([self])
-                est_init_apply([self], [res])
             self.poses = np.asarray(res["poses"], dtype=np.float64).reshape(NUM_FRAMES, 7).copy()
             self.sb = np.asarray(res["speed_bias"], dtype=np.float64).reshape(NUM_FRAMES, 9).copy()
             self.preint = list(res["pre"])
             self.init_result = res
             self.init_frame = self.frames[WINDOW_SIZE]
             self.initialized = True
-            if self.fm is not None:
-                if not fm_batched:
-                    fm_init_depths([self], [item], [s])
-                return True
-            # f_manager.clearDepth; triangulate on the SfM poses with TIC_TMP = 0 and RIC; estimated_depth *= s (estimator.cpp:407-439)
-            self.depth = {}
-            sfm = np.zeros((NUM_FRAMES, 7))
-            sfm[:, 0:3] = item["T"]
-            for i in range(NUM_FRAMES):
-                sfm[i, 3:7] = synth.rot_to_quat(item["R"][i])
-            todo = self.usable()
-            if todo:
-                sf, off, pts = [], [0], []
-                for l, start in todo:
-                    sf.append(start); pts.extend(p for _, p in self.tracks[l]); off.append(off[-1] + len(self.tracks[l]))
-                ext0 = np.concatenate([np.zeros(3), self.ext[3:7]])
-                d = self.ctx.triangulate(np.array(sf, dtype=np.int32), np.array(off, dtype=np.int64), np.array(pts).reshape(-1, 2),
-                                         sfm, ext0, -np.ones(len(todo)))
-                for (l, _), v in zip(todo, d):
-                    self.depth[l] = float(v) * s
-                self.n_triangulated += len(todo)
-            self.init_result = res
-            self.init_frame = self.frames[WINDOW_SIZE]
-            self.initialized = True
-            return True
+            return None
         if self.init_tries >= self.initialize["max_tries"]:
             raise RuntimeError("StreamDriver: no initialisation after %d tries (last status %d)" % (self.init_tries, res["status"]))
         if self.next_frame >= self.s.n_frames:
             raise RuntimeError("StreamDriver: the stream ended before the initialisation succeeded")
-        # slideWindow in the INITIAL state: the oldest frame leaves, no prior, no depth shift (f_manager.removeBack)
         gone = self.frames[0]
-        if self.fm is not None:
-            if not fm_batched:
-                fm_slide([self], [FM_BACK])
-        else:
-            for l in list(self.tracks.keys()):
-                tr = self.tracks[l]
-                if tr[0][0] == gone:
-                    del tr[0]
-                    if not tr:
-                        del self.tracks[l]
-        self.frames.pop(0)
-        self.intervals.pop(0)
-        self.preint.pop(0)
-        self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
-        self.take_next_frame(observe=not fm_batched)
+        self._drop_oldest()
+        self.propagate_next_frame()
         if self.est is not None:    # slideWindow, processIMU over the new interval, processImage: frame_count stays WINDOW_SIZE
             self._est_queue.append(((MARG_OLD, False), self._est_samples(self.intervals[-1]), (float(self.s.times[self.frames[-1]]), True)))
-        if fm_batched:
-            self._fm_gone = gone        # (for the caller's all_image_frame push, behind its add)
-        elif self.aif is not None:
-            self._aif_push(len(self.frames) - 1, slide=self.s.times[gone])
-        return False
+        return gone
 
     def ensure_initialized(self):
-        """Tries until the window is initialised (a no-op for a driver created without `initialize`, or already initialised)."""
+        """Tries until the window is initialised (a no-op for a driver created without `initialize`, or already initialised): rounds
+        of a group of one.  With initialize=dict(state=) the queued feeding of the slot goes out at the head of every round, so a
+        driver that raises after max_tries has fed its slot."""
         while not self.initialized:
-            item, ivs = self.init_request()
-            self.init_apply(item, self.init_align([item], [ivs])[0])
+            init_round([self])
 
     # ---- feature bookkeeping (FeatureManager) ---------------------------------------------------------
     def frame_points(self, f):
         """Every stream observation of global frame f as the front end would hand it over: (ids, points), ids the landmark numbers,
         the point lm_px for the frame that hosts the landmark, else lm_obs[l][f].  A landmark whose track was rejected (outlier_px)
-        is left out from then on, as add_frame_observations leaves it out of the dicts: an erased track is not begun again."""
+        is left out from then on, as dict_add leaves it out of the dicts: an erased track is not begun again."""
         st = self.s
         ids, pts = [], []
         for l, h in enumerate(st.lm_host):
@@ -1007,16 +1129,91 @@ class StreamDriver:
                 ids.append(l); pts.append(st.lm_obs[l][f])
         return np.array(ids, dtype=np.int64), np.array(pts, dtype=np.float64).reshape(-1, 2)
 
-    def add_frame_observations(self, f):
-        if self.fm is not None:
-            fm_add([self], [f])
-            return
+    # The FeatureManager a driver without features= keeps in its own tracks / depth dicts: one method per operation, beside the fm_*
+    # helpers that make the same operation in the slots of a group (step_group and init_round choose once per operation).
+    def dict_add(self, f):
+        """fm_add: global frame f's observations begin or extend their tracks."""
         st = self.s
         for l, h in enumerate(st.lm_host):
             if h == f:
                 self.tracks[l] = [(f, np.asarray(st.lm_px[l], dtype=np.float64))]
             elif l in self.tracks and f in st.lm_obs[l] and self.tracks[l][-1][0] == self.prev_of(f):
                 self.tracks[l].append((f, np.asarray(st.lm_obs[l][f], dtype=np.float64)))
+
+    def dict_windows(self, triangulate):
+        """fm_windows: (Window, feature ids) on the current poses, the tracks without a depth given one first (triangulate)."""
+        if triangulate:
+            self.ensure_depths()
+        return self.window_arrays()
+
+    def dict_set_depths(self, ids, inv_depths):
+        """fm_set_depths: setDepth from the solved inverse depths of landmarks `ids`."""
+        for l, v in zip(ids, inv_depths):
+            self.depth[l] = 1.0 / v
+
+    def dict_remove(self, ids):
+        """fm_remove: removeOutlier / removeFailures by landmark."""
+        for l in ids:
+            del self.tracks[l]
+            self.depth.pop(l, None)
+
+    def dict_slide_back(self, gone):
+        """fm_slide(FM_BACK): removeBack, global frame `gone` leaves the front of its tracks (the INITIAL slideWindow)."""
+        for l in list(self.tracks.keys()):
+            tr = self.tracks[l]
+            if tr[0][0] == gone:
+                del tr[0]
+                if not tr:
+                    del self.tracks[l]
+
+    def dict_slide_back_shift(self, mats):
+        """fm_slide(FM_BACK_SHIFT_DEPTH): removeBackShiftDepth (feature_manager.cpp:276-312) on slideWindowOld's four arrays, before
+        the window lists slide.  (numpy's products: fm_shift_depth evaluates the shift in another order.)"""
+        gone = self.frames[0]
+        mR, mP, nR, nP = mats
+        for l in list(self.tracks.keys()):
+            tr = self.tracks[l]
+            if tr[0][0] != gone:
+                continue
+            uv = np.array([tr[0][1][0], tr[0][1][1], 1.0])
+            del tr[0]
+            if len(tr) < 2:
+                del self.tracks[l]
+                self.depth.pop(l, None)
+                continue
+            if l in self.depth:
+                pj = nR.T @ (mR @ (uv * self.depth[l]) + mP - nP)
+                self.depth[l] = float(pj[2]) if pj[2] > 0 else 5.0       # INIT_DEPTH
+
+    def dict_slide_front(self):
+        """fm_slide(FM_FRONT): removeFront (feature_manager.cpp:331-350) of the second-newest frame, before the window lists slide."""
+        gone = self.frames[WINDOW_SIZE - 1]
+        for l in list(self.tracks.keys()):
+            tr = [o for o in self.tracks[l] if o[0] != gone]
+            if not tr:
+                del self.tracks[l]
+                self.depth.pop(l, None)
+            else:
+                self.tracks[l] = tr
+
+    def dict_init_depths(self, item, s):
+        """fm_init_depths: f_manager.clearDepth; triangulate on the SfM poses with TIC_TMP = 0 and RIC; estimated_depth *= s
+        (estimator.cpp:407-439)."""
+        self.depth = {}
+        todo = self.usable()
+        for (l, _), v in zip(todo, self._triangulate(todo, sfm_poses(item), np.concatenate([np.zeros(3), self.ext[3:7]]))):
+            self.depth[l] = float(v) * s
+
+    def _triangulate(self, todo, poses, ext):
+        """The depths of tracks todo = [(landmark, window index of its host)] by the context's triangulation on `poses` and `ext`."""
+        if not todo:
+            return []
+        sf, off, pts = [], [0], []
+        for l, start in todo:
+            sf.append(start); pts.extend(p for _, p in self.tracks[l]); off.append(off[-1] + len(self.tracks[l]))
+        self.n_triangulated += len(todo)
+        return self.ctx.triangulate(np.array(sf, dtype=np.int32), np.array(off, dtype=np.int64), np.array(pts).reshape(-1, 2),
+                                    poses, ext, -np.ones(len(todo)))
 
     def prev_of(self, f):
         """The window frame in front of global frame f (tracks are consecutive in window frames)."""
@@ -1043,14 +1240,8 @@ class StreamDriver:
             for l, _ in todo:
                 self.depth[l] = float(self.init_depth[l])
             return
-        sf, off, pts = [], [0], []
-        for l, start in todo:
-            sf.append(start); pts.extend(p for _, p in self.tracks[l]); off.append(off[-1] + len(self.tracks[l]))
-        d = self.ctx.triangulate(np.array(sf, dtype=np.int32), np.array(off, dtype=np.int64), np.array(pts).reshape(-1, 2),
-                                 self.poses, self.ext, -np.ones(len(todo)))
-        for (l, _), v in zip(todo, d):
+        for (l, _), v in zip(todo, self._triangulate(todo, self.poses, self.ext)):
             self.depth[l] = float(v)
-        self.n_triangulated += len(todo)
 
     def window_arrays(self):
         ids, lm, host, target, pi, pj, invd = [], [], [], [], [], [], []
@@ -1073,24 +1264,23 @@ class StreamDriver:
     def inv_depth(self):
         """Inverse depths by landmark id (NaN where the landmark never got one) — what the tests compare."""
         out = np.full(len(self.s.lm_host), np.nan)
-        if self.fm is not None:     # (a row's depth is -1 until it gets one)
-            tr = fm_tracks([self])[0]
-            got = tr["depth"] != -1.0
-            out[tr["ids"][got]] = 1.0 / tr["depth"][got]
-            return out
-        for l, d in self.depth.items():
-            out[l] = 1.0 / d
+        ids, depths = self._depths()
+        out[ids] = 1.0 / depths
         return out
 
     @property
     def have_depth(self):
         out = np.zeros(len(self.s.lm_host), dtype=bool)
-        if self.fm is not None:
-            tr = fm_tracks([self])[0]
-            out[tr["ids"][tr["depth"] != -1.0]] = True
-            return out
-        out[list(self.depth.keys())] = True
+        out[self._depths()[0]] = True
         return out
+
+    def _depths(self):
+        """(landmark ids, depths) of the landmarks that have a depth: the dicts', or the slot's rows (-1 until a row gets one)."""
+        if self.fm is None:
+            return np.array(list(self.depth.keys()), dtype=np.int64), np.array(list(self.depth.values()), dtype=np.float64)
+        tr = fm_tracks([self])[0]
+        got = tr["depth"] != -1.0
+        return tr["ids"][got], tr["depth"][got]
 
     # ---- IMU pre-integration at the bias estimates (bias_relinearize) ---------------------------------
     def _repropagate(self, ks):
@@ -1116,137 +1306,41 @@ class StreamDriver:
     # ---- one frame ------------------------------------------------------------------------------------
     def step(self):
         """Solve the current window, marginalise, slide, take in the next frame.  Returns False at the end."""
-        st = self.s
-        if not self.initialized:
-            self.ensure_initialized()
-        if self.bias_relinearize is not None:
-            self.repropagated.append(self.relinearize_biases())
-        if self.est is not None:
-            est_relinearize([self])
-            self.pull_window()
-        if self.fm is not None:
-            w, ids = fm_windows([self], True)[0]
-        else:
-            self.ensure_depths()
-            w, ids = self.window_arrays()
-        self.ctx.load(w)
-        rep = self.ctx.solve(10)
-        poses, sb, _ = self.ctx.get_window()
-        invd = self.ctx.get_landmarks()
-        if self.prior is not None:      # estimator.cpp:1040-1049: b/err prior come back updated, H/Jt stay
-            b, e = self.ctx.get_prior()
-            self.prior = dict(self.prior, b=b[:156].copy(), err=e.copy())
-        if self.est is not None:
-            self.apply_update(self.est.update_batch([(self.est_slot, poses, sb, self.ext, True)])[0])
-        else:
-            self.poses, self.sb = anchor_gauge(w.poses, poses, sb)
-        if self.fm is not None:
-            fm_set_depths([self], [invd])
-        else:
-            for l, v in zip(ids, invd):
-                self.depth[l] = 1.0 / v
-        newest = self.frames[WINDOW_SIZE]
-        self.trajectory.append((st.times[newest], self.poses[WINDOW_SIZE].copy()))
-        self.reports.append(rep)
-        bad = []
-        if self.outlier_px is not None:         # FeaturePerId::is_outlier / solve_flag = 2 from the solved window
-            flags = self.ctx.residuals(w, outlier_px=self.outlier_px)["flags"]
-            bad = [ids[k] for k in np.nonzero(flags & 7)[0]]
-        second_new = self.frames[WINDOW_SIZE - 1]
-        margin_old = not (self.nonkey_every and second_new % self.nonkey_every == self.nonkey_every - 1)
-        self.flags.append(MARG_OLD if margin_old else MARG_SECOND_NEW)
-        # backendOptimization marginalises on the re-anchored states (estimator.cpp:1086-1102)
-        w2, _ = fm_windows([self], False)[0] if self.fm is not None else self.window_arrays()
-        self.ctx.load(w2)
-        self.prior = self.ctx.marginalize(MARG_OLD if margin_old else MARG_SECOND_NEW)
-        if self.outlier_px is not None:         # removeOutlier + removeFailures, before the slide
-            self.record_rejected(bad)
-            if self.fm is not None:
-                fm_remove([self], [bad])
-        if self.next_frame >= st.n_frames:
-            return False
-        if self.est is not None:
-            self.apply_slide(self.est.slide_batch([(self.est_slot, MARG_OLD if margin_old else MARG_SECOND_NEW, True)])[0], margin_old)
-        elif margin_old:
-            self.slide_window_old()
-        else:
-            self.slide_window_new()
-        self.take_next_frame()
-        return True
+        self.ensure_initialized()
+        return step_group([self], OwnContexts())[0]
 
     def record_rejected(self, bad):
-        """The tracks the residual query's flags condemn at this step: erased from the dicts where the driver holds them (the slot's
-        rows go in the caller's remove_batch), counted and listed."""
-        if self.fm is None:
-            for l in bad:
-                del self.tracks[l]
-                self.depth.pop(l, None)
+        """The tracks the residual query's flags condemn at this step, counted and listed (their erasure is the FeatureManager's:
+        fm_remove or dict_remove)."""
         self.rejected.append(len(bad))
         self.rejected_ids.extend(bad)
         self._rejected.update(bad)
 
-    def apply_slide(self, res, margin_old, fm_done=False):
-        """The FeatureManager side of a slide the slot has made: res is this slot's entry of slide_batch's results."""
-        if not res["slid"]:
-            raise RuntimeError("StreamDriver: the slot's window is not full (frame_count %d)" % res["frame_count"])
-        if margin_old:
-            self.slide_window_old((res["marg_R"], res["marg_P"], res["new_R"], res["new_P"]), fm_done)
-        else:
-            self.slide_window_new(fm_done)
-
-    def slide_mats(self, mats=None):
-        """The four arrays of slideWindowOld (marg_R, marg_P, new_R, new_P): the slot's where it computed them (state set), else from
-        the poses of the two oldest frames."""
-        if mats is not None:
-            return mats
+    def slide_mats(self):
+        """The four arrays of slideWindowOld (marg_R, marg_P, new_R, new_P) from the poses of the two oldest frames (a state= driver
+        takes the slot's)."""
         R0 = synth.quat_to_rot(self.poses[0, 3:7]); R1 = synth.quat_to_rot(self.poses[1, 3:7])
         ric, tic = synth.quat_to_rot(self.ext[3:7]), self.ext[0:3]
         return R0 @ ric, self.poses[0, 0:3] + R0 @ tic, R1 @ ric, self.poses[1, 0:3] + R1 @ tic
 
-    def slide_window_old(self, mats=None, fm_done=False):
-        """slideWindowOld (estimator.cpp:1144-1199) + removeBackShiftDepth (feature_manager.cpp:276-312).  mats: the four arrays of
-        slideWindowOld where the slot computed them (state set).  fm_done (features set): the caller has slid the slot already, in a
-        group's one call."""
-        gone = self.frames[0]
-        mR, mP, nR, nP = self.slide_mats(mats)
-        if self.fm is not None and not fm_done:
-            fm_slide([self], [FM_BACK_SHIFT_DEPTH], [(mR, mP, nR, nP)])
-        for l in list(self.tracks.keys()) if self.fm is None else ():
-            tr = self.tracks[l]
-            if tr[0][0] != gone:
-                continue
-            uv = np.array([tr[0][1][0], tr[0][1][1], 1.0])
-            del tr[0]
-            if len(tr) < 2:
-                del self.tracks[l]
-                self.depth.pop(l, None)
-                continue
-            if l in self.depth:
-                pj = nR.T @ (mR @ (uv * self.depth[l]) + mP - nP)
-                self.depth[l] = float(pj[2]) if pj[2] > 0 else 5.0       # INIT_DEPTH
+    def _drop_oldest(self):
+        """The oldest frame leaves the window lists and the states move up."""
         self.frames.pop(0)
-        if self.est is not None:            # (the states and the intervals slid in the slot; the next step pulls them)
-            return
         self.intervals.pop(0)
         self.preint.pop(0)
         if self.bias_relinearize is not None:
             self._imu_stale = True
         self.poses[:-1], self.sb[:-1] = self.poses[1:].copy(), self.sb[1:].copy()
 
-    def slide_window_new(self, fm_done=False):
-        """slideWindowNew (estimator.cpp:1201-1206, the frame_count - 1 branch of :1163-1186) + removeFront."""
-        gone = self.frames[WINDOW_SIZE - 1]
-        if self.fm is not None and not fm_done:
-            fm_slide([self], [FM_FRONT])
-        for l in list(self.tracks.keys()) if self.fm is None else ():
-            tr = [o for o in self.tracks[l] if o[0] != gone]
-            if not tr:
-                del self.tracks[l]
-                self.depth.pop(l, None)
-            else:
-                self.tracks[l] = tr
-        if self.est is not None:            # (the slot merged the intervals and copied the state)
-            self.frames.pop(WINDOW_SIZE - 1)
+    def slide_lists(self, margin_old):
+        """The window lists' side of slideWindowOld (estimator.cpp:1144-1199) or slideWindowNew (:1201-1206, the frame_count - 1
+        branch of :1163-1186), behind the FeatureManager's.  A state= driver keeps only the frame numbers: the states and the
+        intervals slid in the slot, and the next step pulls them."""
+        if self.est is not None:
+            self.frames.pop(0 if margin_old else WINDOW_SIZE - 1)
+            return
+        if margin_old:
+            self._drop_oldest()
             return
         # the IMU samples of the newest interval are appended to the one before it
         a, b = self.intervals[WINDOW_SIZE - 2], self.intervals[WINDOW_SIZE - 1]
@@ -1262,15 +1356,9 @@ class StreamDriver:
         self.frames.pop(WINDOW_SIZE - 1)
         self.poses[WINDOW_SIZE - 1], self.sb[WINDOW_SIZE - 1] = self.poses[WINDOW_SIZE].copy(), self.sb[WINDOW_SIZE].copy()
 
-    def take_next_frame(self, observe=True):
-        """The next image: processIMU's propagation of the newest state, then the frame's observations."""
-        if self.est is not None and self.initialized:   # processIMU over the interval's samples, Headers[frame_count], in the slot
-            f, imu_item, image_item = self.begin_next_frame()
-            self.est.imu_batch([imu_item])
-            self.est.image_batch([image_item])
-            if observe:
-                self.add_frame_observations(f)
-            return
+    def propagate_next_frame(self):
+        """The next image on the host: its interval joins the lists and processIMU's propagation predicts its state from the newest
+        one.  Returns its number.  (An initialised state= driver's next frame comes into the slot instead: begin_next_frame.)"""
         st = self.s
         f = self.next_frame
         self.next_frame += 1
@@ -1294,8 +1382,7 @@ class StreamDriver:
         self.poses[WINDOW_SIZE, 3:7] = synth.quat_mul(self.poses[i, 3:7], pre["delta_q"])
         self.sb[WINDOW_SIZE, 0:3] = Vi - g * dt + Ri @ pre["delta_v"]
         self.sb[WINDOW_SIZE, 3:9] = self.sb[i, 3:9]
-        if observe:                         # (False, features set: the caller adds a group's frames in one call)
-            self.add_frame_observations(f)
+        return f
 
     def run(self):
         while self.step():
