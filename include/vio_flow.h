@@ -6,6 +6,7 @@
  *   vio_flow_track_batch      the pyramids of every image of the call (k_flow_pyr_down, one launch per level), then every keypoint of
  *                             every pair, one wavefront per keypoint                                            (k_flow_track)
  *   vio_flow_pyramid          the pyramid levels of one image
+ *   vio_flow_set_back         the forward-backward check inside k_flow_track, off by default        (include/vio_flow_back.h)
  * It works from host arrays and needs nothing from libvio_hip but the vio_status type.  DESIGN.md section 19 has the layout and the
  * measurements.
  *
@@ -83,6 +84,7 @@ extern "C" {
 #define VIO_FLOW_DEFAULT_MAX_ITER 10                /* MAX_ITERATIONS */
 #define VIO_FLOW_DEFAULT_BORDER 1                   /* BORDER_SIZE */
 #define VIO_FLOW_GRADIENT_DIVISOR 26.0
+#define VIO_FLOW_HAS_BACK 1                         /* include/vio_flow_back.h is there: the forward-backward check */
 
 /* Per-keypoint outcomes besides VIO_OK and VIO_ERR_NOT_FINITE. */
 #define VIO_FLOW_FAIL_LOST 1            /* the reference's success = false at level 0 */
@@ -140,4 +142,7 @@ vio_status vio_flow_timing(const vio_flow *h, double *out4);
 #ifdef __cplusplus
 }
 #endif
+
+#include "vio_flow_back.h"
+
 #endif

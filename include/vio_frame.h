@@ -64,6 +64,7 @@ extern "C" {
 #define VIO_FRAME_PREV 0                            /* `which` of vio_frame_download */
 #define VIO_FRAME_NEXT 1
 #define VIO_FRAME_HAS_READ 1                        /* include/vio_frame_read.h is there */
+#define VIO_FRAME_HAS_BACK 1                        /* include/vio_frame_back.h is there: the forward-backward check */
 
 typedef struct vio_frame vio_frame;
 
@@ -135,5 +136,6 @@ vio_status vio_frame_timing(vio_frame *h, double *out8);
 
 #include "vio_frame_read.h"
 #include "vio_frame_camera.h"
+#include "vio_frame_back.h"
 
 #endif

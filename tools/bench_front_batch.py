@@ -11,12 +11,15 @@ the median of --reps frames after --warmup, with the least and the most; for leg
 same images and times from the same empty state, and the outputs of the last frame are compared byte for byte (`same`).
 
     python tools/bench_front_batch.py [--batches 1,16,64] [--reps 20] [--warmup 3] [--repeats 3] [--slot-cameras none|pinhole|mixed]
-                                      [--out profiles/NAME.json]
+                                      [--flow-back [--back-levels 2]] [--no-reject] [--legs read,loop] [--out profiles/NAME.json]
 
 --slot-cameras (include/vio_frame_camera.h): none: the handle's camera alone, the PINHOLE kernels; pinhole: every
 slot has that same camera as its own, so the same arithmetic runs through the general kernels and the camera table; mixed: slot s has
 the handle's camera, a KANNALA_BRANDT, a MEI or a SCARAMUZZA camera of its own by s mod 4, and leg loop's rejecter is a
 camera.CameraHandle.bind(s) with the same cameras.
+
+--flow-back (include/vio_frame_back.h): the forward-backward check of the tracker over --back-levels levels, in both
+legs; --no-reject: no rejectWithF in a published frame, in both legs.  --legs read: leg read alone (no comparison).
 
 Stream k sees the fixture pair (tests/golden/flow_image_1.npz, flow_image_2.npz) alternating, shifted down by k rows (wrapped).
 """
@@ -54,6 +57,10 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--slot-cameras", choices=("none", "pinhole", "mixed"), default="none")
+    ap.add_argument("--flow-back", action="store_true")
+    ap.add_argument("--back-levels", type=int, default=2)
+    ap.add_argument("--no-reject", action="store_true")
+    ap.add_argument("--legs", default="read,loop")
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     vio = g.load_package()
@@ -62,6 +69,8 @@ def main():
     batches = [int(b) for b in args.batches.split(",")]
     raw = [[np.roll(im, k, axis=0) for k in range(max(batches))] for im in pair]                   # raw[parity][stream]
     frames = args.warmup + args.reps
+    legs = tuple(args.legs.split(","))
+    extra = dict(flow_back=dict(levels=args.back_levels) if args.flow_back else None, reject_with_f=not args.no_reject)
     rows = []
     for rep in range(args.repeats):
         for B in batches:
@@ -80,13 +89,13 @@ def main():
                 ch = vio.load_camera().create()
                 for s in range(B):
                     ch.set_camera(slot=s, **own.get(s, dict(model=0, **EUROC)))
-            for leg in (("read", "loop") if rep % 2 == 0 else ("loop", "read")):
+            for leg in (legs if rep % 2 == 0 else legs[::-1]):
                 wall, parts, moved = [], [], None
                 if leg == "read":
-                    bt = vio.BatchFeatureTracker(fr, range(B), max_cnt=MAX_CNT, min_dist=MIN_DIST, cameras=own)
+                    bt = vio.BatchFeatureTracker(fr, range(B), max_cnt=MAX_CNT, min_dist=MIN_DIST, cameras=own, **extra)
                 else:
                     fts = [vio.FeatureTracker(None, None, max_cnt=MAX_CNT, min_dist=MIN_DIST, rejecter=ch.bind(s) if args.slot_cameras == "mixed" else rh,
-                                              frames=lo, slot=s) for s in range(B)]
+                                              frames=lo, slot=s, **extra) for s in range(B)]
                 for t in range(frames):
                     imgs = raw[t & 1][:B]
                     c0 = fr.counters() if leg == "read" else None
@@ -118,12 +127,14 @@ def main():
                 print("repeat %d  B %3d  leg %-4s  frame %9.3f ms (%.3f .. %.3f)  %9.1f us/stream  points %.1f  %s"
                       % (rep, B, leg, row["frame_ms"], row["frame_ms_min"], row["frame_ms_max"], row["us_per_stream"], row["points_per_stream"],
                          " ".join("%s %.3f" % (k[:-3], v) for k, v in row.get("stages_ms", {}).items())), flush=True)
-            same = all(a[k].tobytes() == b[k].tobytes() for a, b in zip(last["read"], last["loop"]) for k in KEYS)
-            rows.append(dict(repeat=rep, batch=B, same=bool(same)))
-            print("repeat %d  B %3d  outputs of the two legs identical: %s" % (rep, B, same), flush=True)
+            if len(last) == 2:
+                same = all(a[k].tobytes() == b[k].tobytes() for a, b in zip(last["read"], last["loop"]) for k in KEYS)
+                rows.append(dict(repeat=rep, batch=B, same=bool(same)))
+                print("repeat %d  B %3d  outputs of the two legs identical: %s" % (rep, B, same), flush=True)
             for h in (fr, lo, rh) + ((ch,) if args.slot_cameras == "mixed" else ()):
                 h.close()
-    res = dict(bench="front_batch", slot_cameras=args.slot_cameras, image="%dx%d" % (pair[0].shape[1], pair[0].shape[0]), max_cnt=MAX_CNT, min_dist=MIN_DIST, reps=args.reps,
+    res = dict(bench="front_batch", slot_cameras=args.slot_cameras, flow_back=bool(args.flow_back), back_levels=args.back_levels if args.flow_back else None,
+               reject_with_f=not args.no_reject, image="%dx%d" % (pair[0].shape[1], pair[0].shape[0]), max_cnt=MAX_CNT, min_dist=MIN_DIST, reps=args.reps,
                warmup=args.warmup, repeats=args.repeats, rows=rows)
     print(json.dumps(res))
     if args.out:

@@ -33,6 +33,8 @@ struct vio_flow {
     Twin<char> tab;                                      // item descriptors | keypoint descriptors
     Twin<uint8_t> pyr;                                   // level 0 of every image (the part uploaded) | the levels above
     Twin<FlowOut> out;
+    vio_flow_back_config bcfg = FLOW_BACK_DEFAULTS;      // the forward-backward check (include/vio_flow_back.h), off
+    Twin<FlowBackOut> bout;
     StreamEvents<4> q;                                   // events: upload start, pyramid start, tracking start, end
     double timing[4] = {NAN, NAN, NAN, NAN};
 };
@@ -48,38 +50,12 @@ vio_status check_image(vio_flow *h, int i, int width, int height, int stride) {
     return VIO_OK;
 }
 
-}  // namespace
-
-extern "C" {
-
-int32_t vio_flow_version(void) { return VIO_FLOW_VERSION; }
-
-const char *vio_flow_last_error(const vio_flow *h) { return h ? h->err : "NULL handle"; }
-
-vio_status vio_flow_create(int32_t device, void *stream, vio_flow **out) { return create_handle(device, stream, out, vio_flow_destroy); }
-
-void vio_flow_destroy(vio_flow *h) { destroy_handle(h); }
-
-vio_status vio_flow_set_config(vio_flow *h, const vio_flow_config *cfg) {
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->err[0] = 0;
-    const vio_status st = flow_check_config(h->err, "vio_flow_set_config", cfg);
-    if (st != VIO_OK) return st;
-    h->cfg = *cfg;
-    return VIO_OK;
-}
-
-vio_status vio_flow_timing(const vio_flow *h, double *out4) {
-    if (!h || !out4) return VIO_ERR_BAD_ARG;
-    std::memcpy(out4, h->timing, sizeof(h->timing));
-    return VIO_OK;
-}
-
-vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item *items, float *next_pts, vio_flow_pt_info *info) {
-    if (!h) return VIO_ERR_BAD_ARG;
-    h->err[0] = 0;
+// vio_flow_track_batch, and with the check enabled vio_flow_track_back_batch (back may be NULL): fn names the call in errors
+vio_status track_run(vio_flow *h, const char *fn, int32_t count, const vio_flow_item *items, float *next_pts, vio_flow_pt_info *info,
+                     vio_flow_back_info *back) {
+    const bool check = h->bcfg.enabled != 0;
     if (count < 0 || count > MAX_ITEMS || (count > 0 && (!items || !next_pts)))
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_flow_track_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
+        return fail(h->err, VIO_ERR_BAD_ARG, "%s: count outside [0, %d] or a NULL array", fn, MAX_ITEMS);
     if (count == 0) return VIO_OK;
     const auto t0 = std::chrono::steady_clock::now();
     const int L = h->cfg.levels;
@@ -126,7 +102,8 @@ vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item 
     const size_t b_it = align256(sizeof(FlowItemD) * (size_t)count), b_tab = b_it + sizeof(FlowPt) * total;
     vio_status st;
     if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->pyr.ensure(h->err, (size_t)off)) != VIO_OK ||
-        (st = h->out.ensure(h->err, sizeof(FlowOut) * total)) != VIO_OK)
+        (st = h->out.ensure(h->err, sizeof(FlowOut) * total)) != VIO_OK ||
+        (check && back && (st = h->bout.ensure(h->err, sizeof(FlowBackOut) * total)) != VIO_OK))
         return st;
     for (int i = 0; i < count; ++i) {                    // (the pyramid buffer is where it stays now)
         FlowItemD &d = its[(size_t)i];
@@ -155,19 +132,75 @@ vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item 
     (void)hipEventRecord(h->q.ev[1], q);
     flow_launch_pyramids(q, a.items, 2 * count, 1, L, max_px);
     (void)hipEventRecord(h->q.ev[2], q);
-    flow_launch_track(q, a, h->cfg.inverse != 0);
+    if (check) flow_launch_track_back(q, flow_back_args(a.items, a.pts, a.out, back ? h->bout.d : nullptr, total, L, h->cfg, h->bcfg), h->cfg.inverse != 0);
+    else flow_launch_track(q, a, h->cfg.inverse != 0);
     (void)hipEventRecord(h->q.ev[3], q);
     if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
     const size_t outb = sizeof(FlowOut) * total;
-    if (hipMemcpyAsync(h->out.h, h->out.d, outb, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+    if (hipMemcpyAsync(h->out.h, h->out.d, outb, hipMemcpyDeviceToHost, q) != hipSuccess ||
+        (check && back && hipMemcpyAsync(h->bout.h, h->bout.d, sizeof(FlowBackOut) * total, hipMemcpyDeviceToHost, q) != hipSuccess) ||
+        hipStreamSynchronize(q) != hipSuccess)
         return fail_synced(h, "kernel or read-back failed");
     const vio_status ret = flow_unpack(h->err, h->out.h, count, items, next_pts, info);
+    if (check && back) flow_unpack_back(h->bout.h, count, items, back);
     const auto t2 = std::chrono::steady_clock::now();
     h->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count() + elapsed_ms(h->q.ev[0], h->q.ev[1]);
     h->timing[1] = elapsed_ms(h->q.ev[1], h->q.ev[2]);
     h->timing[2] = elapsed_ms(h->q.ev[2], h->q.ev[3]);
     h->timing[3] = std::chrono::duration<double, std::milli>(t2 - t0).count();
     return ret;
+}
+
+}  // namespace
+
+extern "C" {
+
+int32_t vio_flow_version(void) { return VIO_FLOW_VERSION; }
+
+const char *vio_flow_last_error(const vio_flow *h) { return h ? h->err : "NULL handle"; }
+
+vio_status vio_flow_create(int32_t device, void *stream, vio_flow **out) { return create_handle(device, stream, out, vio_flow_destroy); }
+
+void vio_flow_destroy(vio_flow *h) { destroy_handle(h); }
+
+vio_status vio_flow_set_config(vio_flow *h, const vio_flow_config *cfg) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    const vio_status st = flow_check_config(h->err, "vio_flow_set_config", cfg);
+    if (st != VIO_OK) return st;
+    if (h->bcfg.enabled && h->bcfg.levels > cfg->levels)
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_flow_set_config: %d levels are fewer than the %d of the forward-backward check", cfg->levels, h->bcfg.levels);
+    h->cfg = *cfg;
+    return VIO_OK;
+}
+
+vio_status vio_flow_set_back(vio_flow *h, const vio_flow_back_config *cfg) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    const vio_status st = flow_check_back(h->err, "vio_flow_set_back", cfg, h->cfg.levels);
+    if (st != VIO_OK) return st;
+    h->bcfg = cfg ? *cfg : FLOW_BACK_DEFAULTS;
+    return VIO_OK;
+}
+
+vio_status vio_flow_timing(const vio_flow *h, double *out4) {
+    if (!h || !out4) return VIO_ERR_BAD_ARG;
+    std::memcpy(out4, h->timing, sizeof(h->timing));
+    return VIO_OK;
+}
+
+vio_status vio_flow_track_batch(vio_flow *h, int32_t count, const vio_flow_item *items, float *next_pts, vio_flow_pt_info *info) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    return track_run(h, "vio_flow_track_batch", count, items, next_pts, info, nullptr);
+}
+
+vio_status vio_flow_track_back_batch(vio_flow *h, int32_t count, const vio_flow_item *items, float *next_pts, vio_flow_pt_info *info,
+                                     vio_flow_back_info *back) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (!h->bcfg.enabled) return fail(h->err, VIO_ERR_BAD_ARG, "vio_flow_track_back_batch: the check is off (vio_flow_set_back)");
+    return track_run(h, "vio_flow_track_back_batch", count, items, next_pts, info, back);
 }
 
 vio_status vio_flow_pyramid(vio_flow *h, const uint8_t *img, int32_t width, int32_t height, int32_t stride, uint8_t *out) {

@@ -4,6 +4,8 @@
 // a plain C++ compiler.  It includes nothing itself: the including file has included <cstdint>, ../../include/vio_flow.h and
 // vio_host_base.h.
 // An Item is a vio_flow_item or a vio_frame_track_item (n_pts, prev_pts, guess).
+// The forward-backward check (include/vio_flow_back.h) adds FlowBackOut, FlowBackArgs, flow_check_back, flow_back_args and
+// flow_unpack_back beside what the forward pass has; tests/cpp/flow_back_host_main.cpp builds them with a plain C++ compiler.
 constexpr int MAXL = VIO_FLOW_MAX_LEVELS;
 
 struct FlowItemD {
@@ -24,6 +26,13 @@ struct FlowOut {
     double cost;
 };
 
+// the backward row of a keypoint (include/vio_flow_back.h): vio_flow_back_info's fields
+struct FlowBackOut {
+    float x, y;
+    int32_t status, iterations;
+    double cost, d2;
+};
+
 struct PyrArgs {
     const FlowItemD *items;
     int32_t level;                      // the source level
@@ -38,6 +47,16 @@ struct FlowArgs {
     int32_t npts, levels, half_patch, max_iter, border, early_stop;
 };
 
+// k_flow_track<INV, true>'s arguments: the forward pass's, the backward rows (NULL: none are written), the top level of the backward pass and max_dist squared
+struct FlowBackArgs {
+    FlowArgs f;
+    FlowBackOut *back;
+    int32_t back_levels, pad;
+    double max_d2;
+};
+
+constexpr vio_flow_back_config FLOW_BACK_DEFAULTS = {0, 0, VIO_FLOW_BACK_DEFAULT_MAX_DIST};
+
 constexpr vio_flow_config FLOW_DEFAULTS = {VIO_FLOW_DEFAULT_LEVELS, VIO_FLOW_DEFAULT_HALF_PATCH, VIO_FLOW_DEFAULT_MAX_ITER, 0, VIO_FLOW_DEFAULT_BORDER, 0};
 
 inline vio_status flow_check_config(ErrText &err, const char *fn, const vio_flow_config *c) {
@@ -47,6 +66,17 @@ inline vio_status flow_check_config(ErrText &err, const char *fn, const vio_flow
                     "inverse and early_stop 0 or 1, border >= 0", fn, VIO_FLOW_MAX_LEVELS, VIO_FLOW_MAX_HALF_PATCH);
     return VIO_OK;
 }
+
+// the settings of the check against the flow levels they run under; c NULL is the check off
+inline vio_status flow_check_back(ErrText &err, const char *fn, const vio_flow_back_config *c, int flow_levels) {
+    if (!c) return VIO_OK;
+    if ((c->enabled != 0 && c->enabled != 1) || c->levels < 0 || c->levels > flow_levels || !(c->max_dist >= 0.0) || !(c->max_dist <= 1.7976931348623157e308))
+        return fail(err, VIO_ERR_BAD_ARG, "%s: the check's enabled 0 or 1, its levels in [0, %d] (the flow levels), max_dist finite and >= 0", fn, flow_levels);
+    return VIO_OK;
+}
+
+// the levels the backward pass runs over under `flow_levels` flow levels
+inline int flow_back_levels(const vio_flow_back_config &b, int flow_levels) { return b.levels > 0 ? b.levels : flow_levels; }
 
 // the sizes of the levels of a width x height image; false if one is smaller than 2 x 2
 inline bool flow_level_dims(int width, int height, int levels, int32_t *w, int32_t *hh) {
@@ -85,6 +115,15 @@ inline FlowArgs flow_args(const FlowItemD *items, const FlowPt *pts, FlowOut *ou
     return a;
 }
 
+inline FlowBackArgs flow_back_args(const FlowItemD *items, const FlowPt *pts, FlowOut *out, FlowBackOut *back, size_t total, int levels,
+                                   const vio_flow_config &cfg, const vio_flow_back_config &bcfg) {
+    FlowBackArgs a;
+    a.f = flow_args(items, pts, out, total, levels, cfg);
+    a.back = back; a.back_levels = flow_back_levels(bcfg, levels); a.pad = 0;
+    a.max_d2 = bcfg.max_dist * bcfg.max_dist;
+    return a;
+}
+
 // The results in the order of the keypoints of the call, into next_pts and (unless NULL) info.  VIO_ERR_NOT_FINITE, with the first
 // such keypoint named in err, if one or its guess was not finite.
 template <class Item> vio_status flow_unpack(ErrText &err, const FlowOut *out_h, int count, const Item *items, float *next_pts, vio_flow_pt_info *info) {
@@ -106,4 +145,17 @@ template <class Item> vio_status flow_unpack(ErrText &err, const FlowOut *out_h,
         row += (size_t)items[i].n_pts;
     }
     return ret;
+}
+
+// The backward rows in the order of the keypoints of the call, into back (one vio_flow_back_info per keypoint).
+template <class Item> void flow_unpack_back(const FlowBackOut *back_h, int count, const Item *items, vio_flow_back_info *back) {
+    size_t row = 0;
+    for (int i = 0; i < count; ++i) {
+        for (int k = 0; k < items[i].n_pts; ++k) {
+            const FlowBackOut &o = back_h[row + (size_t)k];
+            vio_flow_back_info &bi = back[row + (size_t)k];
+            bi.x = o.x; bi.y = o.y; bi.status = o.status; bi.iterations = o.iterations; bi.cost = o.cost; bi.d2 = o.d2;
+        }
+        row += (size_t)items[i].n_pts;
+    }
 }

@@ -127,3 +127,13 @@ __device__ __forceinline__ void solve2(double h00, double h01, double h11, doubl
     d0 = c ? v1 : v0;
     d1 = c ? v0 : v1;
 }
+
+// The verdict of the forward-backward check (include/vio_flow_back.h) for a keypoint at (px, py) whose backward pass ended at
+// (bx, by): d2 is formed whenever the pass ran; a lost pass is VIO_FLOW_FAIL_BACK_LOST, a comparison that is false (NaN included)
+// VIO_FLOW_FAIL_BACK_FAR.  max_d2: the host's max_dist * max_dist.
+__device__ __forceinline__ int flow_back_verdict(bool back_ok, float px, float py, float bx, float by, double max_d2, double &d2) {
+    const double dx = (double)bx - (double)px, dy = (double)by - (double)py;
+    d2 = dx * dx + dy * dy;
+    if (!back_ok) return VIO_FLOW_FAIL_BACK_LOST;
+    return d2 <= max_d2 ? VIO_OK : VIO_FLOW_FAIL_BACK_FAR;
+}

@@ -109,6 +109,7 @@ struct vio_frame {
     // track and detect wait for their results, so their buffers are free again when they return
     Twin<char> ttab;                                     // track: FlowItemD per item | FlowPt per keypoint
     Twin<kf::FlowOut> tout;
+    Twin<kf::FlowBackOut> tbout;                         // the backward rows of a track with the check (include/vio_frame_back.h)
     Twin<char> dtab;                                     // detect: DetItemD per item | DetTrk per tracked point
     Twin<char> dout;                                     // DetRes per item | keep_order | new_pts
     DevBuf<double> r;
@@ -134,6 +135,11 @@ struct vio_frame {
     // the slots' own cameras (vio_frame_cameras.h) and the table's twin, which goes up ahead of a read that needs it when it has changed
     FrameCameras cams;
     Twin<CamDev> camtab;
+    // include/vio_frame_back.h: the forward-backward check of the tracker, whether a published read runs rejectWithF, and per slot the
+    // check's counts of its last read (checked, lost on the way back, too far)
+    vio_flow_back_config bcfg = kf::FLOW_BACK_DEFAULTS;
+    int32_t reject_f = 1;
+    int32_t back_info[VIO_FRAME_MAX_SLOTS][3] = {};
 };
 
 namespace {
@@ -340,6 +346,67 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
                                          std::chrono::steady_clock::time_point t0, const std::vector<int32_t> &sl, const std::vector<int32_t> &ww,
                                          const std::vector<int32_t> &hh, const std::vector<double> &tt, const std::vector<vio_frame_push_item> &push);
 
+// vio_frame_track_batch, and with the check enabled vio_frame_track_back_batch (back may be NULL): fn names the call in errors
+vio_status track_run(vio_frame *h, const char *fn, int32_t count, const vio_frame_track_item *items, float *next_pts, vio_flow_pt_info *info,
+                     vio_flow_back_info *back) {
+    const bool check = h->bcfg.enabled != 0;
+    if (count < 0 || count > MAX_ITEMS || (count > 0 && (!items || !next_pts)))
+        return fail(h->err, VIO_ERR_BAD_ARG, "%s: count outside [0, %d] or a NULL array", fn, MAX_ITEMS);
+    if (count == 0) return VIO_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    const int L = h->tab.levels;
+    size_t total = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_frame_track_item &it = items[i];
+        if (it.n_pts < 0 || it.n_pts > VIO_FLOW_MAX_POINTS)
+            return fail(h->err, VIO_ERR_BAD_ARG, "%s: item %d: n_pts must be in [0, %d]", fn, i, VIO_FLOW_MAX_POINTS);
+        const FrameCheck ck = h->tab.check_track(it.slot);
+        if (ck != FRAME_OK) return fail_check(h, fn, ck, i, it.slot);
+        if (it.n_pts > 0 && !it.prev_pts) return fail(h->err, VIO_ERR_BAD_ARG, "%s: item %d: prev_pts is required", fn, i);
+        total += (size_t)it.n_pts;
+    }
+    if (total == 0) return VIO_OK;
+    DeviceScope dev(h->device);
+    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+    const size_t b_it = align256(sizeof(kf::FlowItemD) * (size_t)count), b_tab = b_it + sizeof(kf::FlowPt) * total;
+    vio_status st;
+    if ((st = h->ttab.ensure(h->err, b_tab)) != VIO_OK || (st = h->tout.ensure(h->err, sizeof(kf::FlowOut) * total)) != VIO_OK ||
+        (check && back && (st = h->tbout.ensure(h->err, sizeof(kf::FlowBackOut) * total)) != VIO_OK))
+        return st;
+    std::memset(h->ttab.h, 0, b_it);
+    kf::FlowItemD *fi = (kf::FlowItemD *)h->ttab.h;
+    kf::FlowPt *hp = (kf::FlowPt *)(h->ttab.h + b_it);
+    size_t row = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_frame_track_item &it = items[i];
+        if (it.n_pts == 0) continue;
+        const FrameSlot &s = h->tab.slots[it.slot];
+        FrameLayout Y;
+        frame_layout(s.width, s.height, L, Y);
+        flow_item_of(h, fi[i], Y, s.prev, s.next);
+        kf::flow_fill_pts(hp + row, i, it);
+        row += (size_t)it.n_pts;
+    }
+    const kf::FlowArgs a = kf::flow_args((const kf::FlowItemD *)h->ttab.d, (const kf::FlowPt *)(h->ttab.d + b_it), h->tout.d, total, L, h->fcfg);
+    hipStream_t q = h->q.stream;
+    if (hipMemcpyAsync(h->ttab.d, h->ttab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
+    (void)hipEventRecord(h->q.ev[4], q);
+    if (check) kf::flow_launch_track_back(q, kf::flow_back_args(a.items, a.pts, a.out, back ? h->tbout.d : nullptr, total, L, h->fcfg, h->bcfg), h->fcfg.inverse != 0);
+    else kf::flow_launch_track(q, a, h->fcfg.inverse != 0);
+    (void)hipEventRecord(h->q.ev[5], q);
+    if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
+    const size_t outb = sizeof(kf::FlowOut) * total, backb = check && back ? sizeof(kf::FlowBackOut) * total : 0;
+    if (hipMemcpyAsync(h->tout.h, h->tout.d, outb, hipMemcpyDeviceToHost, q) != hipSuccess ||
+        (backb && hipMemcpyAsync(h->tbout.h, h->tbout.d, backb, hipMemcpyDeviceToHost, q) != hipSuccess) || hipStreamSynchronize(q) != hipSuccess)
+        return fail_synced(h, "kernel or read-back failed");
+    h->counters[2] += b_tab; h->counters[3] += outb + backb;
+    const vio_status ret = kf::flow_unpack(h->err, h->tout.h, count, items, next_pts, info);
+    if (backb) kf::flow_unpack_back(h->tbout.h, count, items, back);
+    h->timing[4] = elapsed_ms(h->q.ev[4], h->q.ev[5]);
+    h->timing[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ret;
+}
+
 }  // namespace
 
 extern "C" {
@@ -379,6 +446,8 @@ vio_status vio_frame_set_config(vio_frame *h, int32_t equalize, const vio_clahe_
     if ((st = kc::clahe_check_config(h->err, "vio_frame_set_config", &c)) != VIO_OK || (st = kf::flow_check_config(h->err, "vio_frame_set_config", &f)) != VIO_OK ||
         (st = kd::det_check_config(h->err, "vio_frame_set_config", &d)) != VIO_OK)
         return st;
+    if (h->bcfg.enabled && h->bcfg.levels > f.levels)
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_config: %d flow levels are fewer than the %d of the forward-backward check", f.levels, h->bcfg.levels);
     d.reserved = 0;
     h->equalize = equalize; h->ccfg = c; h->fcfg = f; h->dcfg = d;
     h->tab.set_levels(f.levels);
@@ -405,6 +474,7 @@ vio_status vio_frame_reset(vio_frame *h, int32_t slot) {
     if (!FrameTable::slot_ok(slot)) return fail_check(h, "vio_frame_reset", FRAME_BAD_SLOT, 0, slot);
     h->tab.reset(slot);
     h->cams.lift_info_set(slot, 0, 0);
+    for (int32_t &v : h->back_info[slot]) v = 0;
     return VIO_OK;
 }
 
@@ -472,56 +542,40 @@ vio_status vio_frame_download(vio_frame *h, int32_t slot, int32_t which, int32_t
 vio_status vio_frame_track_batch(vio_frame *h, int32_t count, const vio_frame_track_item *items, float *next_pts, vio_flow_pt_info *info) {
     if (!h) return VIO_ERR_BAD_ARG;
     h->err[0] = 0;
-    if (count < 0 || count > MAX_ITEMS || (count > 0 && (!items || !next_pts)))
-        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_track_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
-    if (count == 0) return VIO_OK;
-    const auto t0 = std::chrono::steady_clock::now();
-    const int L = h->tab.levels;
-    size_t total = 0;
-    for (int i = 0; i < count; ++i) {
-        const vio_frame_track_item &it = items[i];
-        if (it.n_pts < 0 || it.n_pts > VIO_FLOW_MAX_POINTS)
-            return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_track_batch: item %d: n_pts must be in [0, %d]", i, VIO_FLOW_MAX_POINTS);
-        const FrameCheck ck = h->tab.check_track(it.slot);
-        if (ck != FRAME_OK) return fail_check(h, "vio_frame_track_batch", ck, i, it.slot);
-        if (it.n_pts > 0 && !it.prev_pts) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_track_batch: item %d: prev_pts is required", i);
-        total += (size_t)it.n_pts;
-    }
-    if (total == 0) return VIO_OK;
-    DeviceScope dev(h->device);
-    if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
-    const size_t b_it = align256(sizeof(kf::FlowItemD) * (size_t)count), b_tab = b_it + sizeof(kf::FlowPt) * total;
-    vio_status st;
-    if ((st = h->ttab.ensure(h->err, b_tab)) != VIO_OK || (st = h->tout.ensure(h->err, sizeof(kf::FlowOut) * total)) != VIO_OK) return st;
-    std::memset(h->ttab.h, 0, b_it);
-    kf::FlowItemD *fi = (kf::FlowItemD *)h->ttab.h;
-    kf::FlowPt *hp = (kf::FlowPt *)(h->ttab.h + b_it);
-    size_t row = 0;
-    for (int i = 0; i < count; ++i) {
-        const vio_frame_track_item &it = items[i];
-        if (it.n_pts == 0) continue;
-        const FrameSlot &s = h->tab.slots[it.slot];
-        FrameLayout Y;
-        frame_layout(s.width, s.height, L, Y);
-        flow_item_of(h, fi[i], Y, s.prev, s.next);
-        kf::flow_fill_pts(hp + row, i, it);
-        row += (size_t)it.n_pts;
-    }
-    const kf::FlowArgs a = kf::flow_args((const kf::FlowItemD *)h->ttab.d, (const kf::FlowPt *)(h->ttab.d + b_it), h->tout.d, total, L, h->fcfg);
-    hipStream_t q = h->q.stream;
-    if (hipMemcpyAsync(h->ttab.d, h->ttab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
-    (void)hipEventRecord(h->q.ev[4], q);
-    kf::flow_launch_track(q, a, h->fcfg.inverse != 0);
-    (void)hipEventRecord(h->q.ev[5], q);
-    if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
-    const size_t outb = sizeof(kf::FlowOut) * total;
-    if (hipMemcpyAsync(h->tout.h, h->tout.d, outb, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
-        return fail_synced(h, "kernel or read-back failed");
-    h->counters[2] += b_tab; h->counters[3] += outb;
-    const vio_status ret = kf::flow_unpack(h->err, h->tout.h, count, items, next_pts, info);
-    h->timing[4] = elapsed_ms(h->q.ev[4], h->q.ev[5]);
-    h->timing[5] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    return ret;
+    return track_run(h, "vio_frame_track_batch", count, items, next_pts, info, nullptr);
+}
+
+vio_status vio_frame_track_back_batch(vio_frame *h, int32_t count, const vio_frame_track_item *items, float *next_pts, vio_flow_pt_info *info,
+                                      vio_flow_back_info *back) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (!h->bcfg.enabled) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_track_back_batch: the check is off (vio_frame_set_flow_back)");
+    return track_run(h, "vio_frame_track_back_batch", count, items, next_pts, info, back);
+}
+
+vio_status vio_frame_set_flow_back(vio_frame *h, const vio_flow_back_config *cfg) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    const vio_status st = kf::flow_check_back(h->err, "vio_frame_set_flow_back", cfg, h->fcfg.levels);
+    if (st != VIO_OK) return st;
+    h->bcfg = cfg ? *cfg : kf::FLOW_BACK_DEFAULTS;
+    return VIO_OK;
+}
+
+vio_status vio_frame_set_reject_with_f(vio_frame *h, int32_t enabled) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (enabled != 0 && enabled != 1) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_reject_with_f: enabled 0 or 1");
+    h->reject_f = enabled;
+    return VIO_OK;
+}
+
+vio_status vio_frame_read_back_info(const vio_frame *h, int32_t slot, int32_t *n_checked, int32_t *n_back_lost, int32_t *n_back_far) {
+    if (!h || !FrameTable::slot_ok(slot)) return VIO_ERR_BAD_ARG;
+    if (n_checked) *n_checked = h->back_info[slot][0];
+    if (n_back_lost) *n_back_lost = h->back_info[slot][1];
+    if (n_back_far) *n_back_far = h->back_info[slot][2];
+    return VIO_OK;
 }
 
 vio_status vio_frame_detect_batch(vio_frame *h, int32_t count, const vio_frame_detect_item *items, vio_detect_result *results) {
@@ -778,6 +832,7 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
     const size_t w_lstage = carve(sizeof(float) * 4 * rowsN), w_lids = carve(sizeof(long long) * 2 * rowsN);
     const size_t w_un = carve(sizeof(float) * 2 * rowsN), w_vel = carve(sizeof(float) * 2 * rowsN), w_cntm = carve(sizeof(int32_t) * rowsN);
     const size_t w_lflag = CAMS ? carve(rowsN) : 0;        // k_reject_lift's flag byte per point
+    const bool check = h->bcfg.enabled != 0;
     const size_t row_bytes = (36 * (size_t)rows_cap + 7) & ~(size_t)7;
     const size_t b_res = align256(sizeof(FrontRes) * B), b_out = b_res + row_bytes * B;
     for (size_t i = 0; i < B; ++i) {
@@ -844,6 +899,7 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
     a.un = (const float *)(W + w_un); a.vel = (const float *)(W + w_vel); a.cntm = (int32_t *)(W + w_cntm);
     a.res = (FrontRes *)h->rout.d; a.rows = h->rout.d + b_res; a.row_bytes = (int64_t)row_bytes; a.rows_cap = rows_cap;
     a.count = count; a.publish = publish; a.border = h->border;
+    a.reject = h->reject_f; a.flow_back = check ? 1 : 0;
     if constexpr (CAMS) a.lflags = (const uint8_t *)(W + w_lflag);
     hipStream_t q = h->q.stream;
     if (hipMemcpyAsync(h->rtab.d, h->rtab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess || hipMemsetAsync(W, 0, b_zero, q) != hipSuccess)
@@ -864,12 +920,21 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
     // 2 - 4. the slot's points into the new frame, and those that stay
     if (total > 0) {
         front(P::begin);
-        kf::flow_launch_track(q, kf::flow_args((const kf::FlowItemD *)(h->rtab.d + o_flow), a.fpts, (kf::FlowOut *)(W + w_fout), (size_t)total, L, h->fcfg),
-                              h->fcfg.inverse != 0);
+        const kf::FlowItemD *fid = (const kf::FlowItemD *)(h->rtab.d + o_flow);
+        if (check)
+            kf::flow_launch_track_back(q, kf::flow_back_args(fid, a.fpts, (kf::FlowOut *)(W + w_fout), nullptr, (size_t)total, L,
+                                                             h->fcfg, h->bcfg), h->fcfg.inverse != 0);
+        else
+            kf::flow_launch_track(q, kf::flow_args(fid, a.fpts, (kf::FlowOut *)(W + w_fout), (size_t)total, L, h->fcfg), h->fcfg.inverse != 0);
     }
     front(P::filter);
     (void)hipEventRecord(h->rev[0], q);
-    if (publish) {
+    if (publish && !h->reject_f) {
+        // no rejectWithF: the reject stage is an unpublished read's, and k_front_after_reject, which keeps every row of an inactive pair
+        // and makes the detection's table, runs in the detection stage
+        (void)hipEventRecord(h->rev[1], q);
+        front(P::after_reject);
+    } else if (publish) {
         // 5, 6. rejectWithF and what it keeps
         typename P::RansacArgs ra;
         if constexpr (CAMS) {
@@ -885,6 +950,8 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
         if (total > 0) hipLaunchKernelGGL(P::ransac, per_item, dim3(kr::NT), 0, q, ra);
         front(P::after_reject);
         (void)hipEventRecord(h->rev[1], q);
+    }
+    if (publish) {
         // 7. setMask and the detection
         kd::DetArgs da = kd::det_args(h->dcfg, count);
         da.items = a.ditems; da.trk = a.dtrk;
@@ -937,6 +1004,8 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
         const bool bad_lift = n_bad > 0 || r.reject_status == VIO_ERR_NOT_FINITE;       // (in undistortedPoints, in rejectWithF)
         if (bad_lift && ret == VIO_OK) ret = fail(h->err, VIO_ERR_NOT_FINITE, "item %d: slot %d: a lift is not finite", (int)i, it.slot);
         h->cams.lift_info_set(it.slot, n_clamped, n_bad);
+        h->back_info[it.slot][0] = front_clamp(r.n_checked, 0, FRONT_CAP); h->back_info[it.slot][1] = front_clamp(r.n_back_lost, 0, FRONT_CAP);
+        h->back_info[it.slot][2] = front_clamp(r.n_back_far, 0, FRONT_CAP);
         o.status = bad_lift ? VIO_ERR_NOT_FINITE : VIO_OK; o.n = (int32_t)n; o.n_new = front_clamp(r.n_new, 0, (int32_t)n);
         o.n_tracked_in = r.n_tracked_in; o.n_after_track = r.n_after_track; o.n_after_reject = r.n_after_reject;
         o.reject_status = r.reject_status; o.reject_hyp = r.reject_hyp; o.n_candidates = r.n_candidates; o.reserved = 0;

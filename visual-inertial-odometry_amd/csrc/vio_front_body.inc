@@ -5,7 +5,8 @@
 // One workgroup of FRONT_CAP = 1024 threads per item of the call (blockIdx.x), one thread per row of the slot's point table.
 //   k_front_begin          the FlowPt rows of the slot's cur_pts (no guess), at the item's offset of the call's flat keypoint list
 //   k_front_filter         keep a row when the tracker found it (status 0) and it rounds inside the border; compact; track_cnt + 1;
-//                          the pair's RejPair (n, active, finite) and its staged cur | forw floats
+//                          the pair's RejPair (n, active, finite) and its staged cur | forw floats; with the forward-backward check
+//                          (include/vio_frame_back.h) the counts of the rows it ran on and of those it failed
 //   k_front_after_reject   compact by k_reject_ransac's mask (an inactive pair keeps every row); DetItemD.n_tracked and the DetTrk rows
 //   k_front_merge          the kept rows in keep_order, then new_pts with id -1 and count 1; the LiftItem (n, m) with its staged points
 //                          and ids, the slot's prev_un behind them
@@ -44,6 +45,7 @@ struct FrontRes {
 #ifdef FRONT_CAMERAS
     int32_t n_clamped, n_bad;           // of the undistort stage: the clamped points (0 where a lift is bad), the bad lifts
 #endif
+    int32_t n_checked, n_back_lost, n_back_far, pad_back;      // of the forward-backward check (0 with it off)
 };
 
 struct FrontArgs {
@@ -75,6 +77,7 @@ struct FrontArgs {
     int64_t row_bytes;
     int32_t rows_cap;                   // rows of an item's result arrays
     int32_t count, publish, border;
+    int32_t reject, flow_back;          // 0: a published read runs no rejectWithF; 1: the tracker ran the forward-backward check
 #ifdef FRONT_CAMERAS
     const uint8_t *lflags;              // k_reject_lift's flag byte per point: CAM_FLAG_BAD | CAM_FLAG_CLAMPED
 #endif
@@ -109,10 +112,17 @@ __global__ __launch_bounds__(FNT) void k_front_filter(FrontArgs a) {
     const int n = front_clamp(I.n, 0, FRONT_CAP);
     float fx = 0.f, fy = 0.f;
     bool keep = false;
+    int st = -1;
     if (t < n) {
         const kf::FlowOut o = a.fout[I.flow_off + t];
-        fx = o.x; fy = o.y;
+        fx = o.x; fy = o.y; st = o.status;
         keep = o.status == 0 && front_in_border(fx, fy, I.w, I.h, a.border);
+    }
+    int n_ok = 0, n_lost = 0, n_far = 0;
+    if (a.flow_back) {                                      // (uniform: every thread of the workgroup takes the barriers)
+        (void)front_scan(st == 0, s_w, n_ok);
+        (void)front_scan(st == VIO_FLOW_FAIL_BACK_LOST, s_w, n_lost);
+        (void)front_scan(st == VIO_FLOW_FAIL_BACK_FAR, s_w, n_far);
     }
     int nk;
     const int dst = front_scan(keep, s_w, nk);
@@ -128,8 +138,9 @@ __global__ __launch_bounds__(FNT) void k_front_filter(FrontArgs a) {
     }
     if (t == 0) {
         P.n = nk; P.finite = 1;
-        P.active = a.publish && nk >= VIO_REJECT_MIN_POINTS;
+        P.active = a.publish && a.reject && nk >= VIO_REJECT_MIN_POINTS;
         FrontRes &R = a.res[item];
+        R.n_checked = n_ok + n_lost + n_far; R.n_back_lost = n_lost; R.n_back_far = n_far; R.pad_back = 0;
         R.n = nk; R.n_new = 0; R.n_tracked_in = n; R.n_after_track = nk; R.n_after_reject = nk;
         R.reject_status = VIO_OK; R.reject_hyp = -1; R.n_candidates = 0; R.next_id = 0;
     }

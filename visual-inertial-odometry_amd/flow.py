@@ -7,6 +7,9 @@ on the GPU, the step of FeatureTracker::readImage that makes the tracks (feature
     outs = fh.track_batch([dict(img_prev=a, img_next=b, prev_pts=p, guess=None), ...])
     levels = fh.pyramid(img)                                         # the uint8 levels of one image
 
+    fh.set_back(levels=2, max_dist=0.5)                              # the forward-backward check (include/vio_flow_back.h)
+    out = fh.track(img_prev, img_next, prev_pts, back=True)          # ... and its rows: back_pts, back_status, back_d2, ...
+
 An item is a dict: img_prev, img_next (height, width) uint8 of one shape (rows may be strided), prev_pts (n, 2) float32 as (x, y),
 guess (n, 2) or None.  A result is a dict: next_pts (n, 2) float32, status (n,), iterations (n,), cost (n,).
 """
@@ -20,7 +23,10 @@ MAX_LEVELS, MAX_HALF_PATCH, MAX_POINTS, MAX_DIM = 8, 16, 4096, 16384
 DEFAULT_LEVELS, DEFAULT_HALF_PATCH, DEFAULT_MAX_ITER, DEFAULT_BORDER = 4, 4, 10, 1
 OK, NOT_FINITE = 0, -3
 FAIL_LOST, FAIL_BORDER = 1, 2
-STATUS_NAMES = {OK: "ok", NOT_FINITE: "not finite", FAIL_LOST: "lost", FAIL_BORDER: "outside the border"}
+FAIL_BACK_LOST, FAIL_BACK_FAR, BACK_NOT_RUN = 3, 4, -1               # include/vio_flow_back.h
+DEFAULT_BACK_MAX_DIST = 0.5
+STATUS_NAMES = {OK: "ok", NOT_FINITE: "not finite", FAIL_LOST: "lost", FAIL_BORDER: "outside the border",
+                FAIL_BACK_LOST: "lost on the way back", FAIL_BACK_FAR: "came back too far off"}
 
 
 class VioFlowConfig(C.Structure):
@@ -37,10 +43,41 @@ class VioFlowPtInfo(C.Structure):
     _fields_ = [("status", C.c_int32), ("iterations", C.c_int32), ("cost", C.c_double)]
 
 
+class VioFlowBackConfig(C.Structure):
+    _fields_ = [("enabled", C.c_int32), ("levels", C.c_int32), ("max_dist", C.c_double)]
+
+
+class VioFlowBackInfo(C.Structure):
+    _fields_ = [("x", C.c_float), ("y", C.c_float), ("status", C.c_int32), ("iterations", C.c_int32), ("cost", C.c_double), ("d2", C.c_double)]
+
+
+PT_INFO_DTYPE = np.dtype([("status", np.int32), ("iterations", np.int32), ("cost", np.float64)])
+BACK_INFO_DTYPE = np.dtype([("x", np.float32), ("y", np.float32), ("status", np.int32), ("iterations", np.int32), ("cost", np.float64),
+                            ("d2", np.float64)])
+
+
+def track_results(base, nxt, info, back=None):
+    """The dicts of track_batch from the flat arrays a track call filled; base: the items' first rows and the total."""
+    total = max(int(base[-1]), 1)
+    rec = np.frombuffer(info, dtype=PT_INFO_DTYPE, count=total)
+    brec = None if back is None else np.frombuffer(back, dtype=BACK_INFO_DTYPE, count=total)
+    out = []
+    for i in range(len(base) - 1):
+        lo, hi = int(base[i]), int(base[i + 1])
+        d = dict(next_pts=nxt[lo:hi].copy(), status=rec["status"][lo:hi].copy(), iterations=rec["iterations"][lo:hi].copy(),
+                 cost=rec["cost"][lo:hi].copy())
+        if brec is not None:
+            d.update(back_pts=np.stack([brec["x"][lo:hi], brec["y"][lo:hi]], axis=1), back_status=brec["status"][lo:hi].copy(),
+                     back_iterations=brec["iterations"][lo:hi].copy(), back_cost=brec["cost"][lo:hi].copy(), back_d2=brec["d2"][lo:hi].copy())
+        out.append(d)
+    return out
+
+
 class FlowLib:
     """libvio_flow_hip.so: vio_flow_*."""
 
     SYMBOLS = ["create", "destroy", "last_error", "version", "set_config", "track_batch", "pyramid", "timing"]
+    BACK_SYMBOLS = ["set_back", "track_back_batch"]                  # include/vio_flow_back.h
 
     def __init__(self, path):
         self.path = path
@@ -50,6 +87,9 @@ class FlowLib:
         self.fn["track_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         self.fn["pyramid"].argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p]
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_flow_", self.BACK_SYMBOLS)[1])
+        self.fn["set_back"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn["track_back_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_flow handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -113,26 +153,33 @@ class FlowHandle(CompanionHandle):
         self._ck(self.lib.fn["set_config"](self.h, C.byref(cfg)), "set_config")
         self.levels = int(levels)
 
-    def track_batch(self, items):
+    def set_back(self, enabled=True, levels=0, max_dist=DEFAULT_BACK_MAX_DIST):
+        """The forward-backward check (include/vio_flow_back.h): every keypoint that tracked is followed back over `levels` levels (0: the
+        handle's) and kept only if it ends within max_dist of where it started.  With it on, track and track_batch apply it."""
+        cfg = VioFlowBackConfig(1 if enabled else 0, int(levels), float(max_dist))
+        self._ck(self.lib.fn["set_back"](self.h, C.byref(cfg)), "set_back")
+
+    def track_batch(self, items, back=False):
         """The keypoints of every pair followed from img_prev into img_next: a list of dicts (next_pts (n, 2) float32: the position the
-        reference leaves, tracked or not; status (n,): OK, FAIL_LOST, FAIL_BORDER or NOT_FINITE; iterations (n,) and cost (n,) of level
-        0).  Non-finite keypoints do not raise."""
+        reference leaves, tracked or not; status (n,): OK, FAIL_LOST, FAIL_BORDER or NOT_FINITE, and with the check FAIL_BACK_LOST or
+        FAIL_BACK_FAR; iterations (n,) and cost (n,) of level 0).  Non-finite keypoints do not raise.  back=True (the check must be
+        on: set_back): also back_pts (n, 2) float32, back_status (n,): OK, FAIL_LOST or BACK_NOT_RUN, back_iterations, back_cost and
+        back_d2 (n,), the squared distance the verdict compares."""
         B = len(items)
         pk = _Packed(items)
         nxt = np.full((max(pk.total, 1), 2), np.nan, dtype=np.float32)
         info = (VioFlowPtInfo * max(pk.total, 1))()
-        st = self.lib.fn["track_batch"](self.h, C.c_int32(B), C.addressof(pk.items), nxt.ctypes.data, C.addressof(info))
-        self._ck(st, "track_batch", allow_not_finite=True)
-        rec = np.frombuffer(info, dtype=np.dtype([("status", np.int32), ("iterations", np.int32), ("cost", np.float64)]), count=max(pk.total, 1))
-        out = []
-        for i in range(B):
-            lo, hi = int(pk.base[i]), int(pk.base[i + 1])
-            out.append(dict(next_pts=nxt[lo:hi].copy(), status=rec["status"][lo:hi].copy(), iterations=rec["iterations"][lo:hi].copy(),
-                            cost=rec["cost"][lo:hi].copy()))
-        return out
+        binfo = None
+        if back:
+            binfo = (VioFlowBackInfo * max(pk.total, 1))()
+            st = self.lib.fn["track_back_batch"](self.h, C.c_int32(B), C.addressof(pk.items), nxt.ctypes.data, C.addressof(info), C.addressof(binfo))
+        else:
+            st = self.lib.fn["track_batch"](self.h, C.c_int32(B), C.addressof(pk.items), nxt.ctypes.data, C.addressof(info))
+        self._ck(st, "track_back_batch" if back else "track_batch", allow_not_finite=True)
+        return track_results(pk.base, nxt, info, binfo)
 
-    def track(self, img_prev, img_next, prev_pts, guess=None):
-        return self.track_batch([dict(img_prev=img_prev, img_next=img_next, prev_pts=prev_pts, guess=guess)])[0]
+    def track(self, img_prev, img_next, prev_pts, guess=None, back=False):
+        return self.track_batch([dict(img_prev=img_prev, img_next=img_next, prev_pts=prev_pts, guess=guess)], back=back)[0]
 
     def pyramid(self, img):
         """The configured levels of one image, level 0 first: a list of uint8 arrays."""

@@ -20,6 +20,9 @@ the image steps of FeatureTracker::readImage (feature_tracker.cpp:87-149) for ma
     fr.set_slot_camera(4, **camera.parse_camodocal_yaml(text)); fr.clear_slot_camera(4); fr.slot_camera(3)               # (include/vio_frame_camera.h)
     fr.set_reject_config(seed=0, ransac_hypotheses=128); fr.read_lift_info(3)                 # dict(n_clamped, n_bad) of slot 3's last read
 
+    fr.set_flow_back(levels=2, max_dist=0.5); fr.track(prev_pts, back=True)                   # the forward-backward check (include/vio_frame_back.h)
+    fr.set_reject_with_f(False); fr.read_back_info(0)                                          # no rejectWithF in a published read; the check's counts
+
 A handle is what frontend.FeatureTracker takes as `frames`, and what frontend.BatchFeatureTracker drives through read_batch.
 """
 import ctypes as C
@@ -31,7 +34,8 @@ from .capi import CompanionHandle, VioError, open_lib
 from .clahe import DEFAULT_CLIP_LIMIT, DEFAULT_TILES, VioClaheConfig
 from .detect import DEFAULT_MAX_TOTAL, DEFAULT_MIN_DISTANCE, DEFAULT_QUALITY, VioDetectConfig, VioDetectResult
 from .reject import DEFAULT_F_THRESHOLD, DEFAULT_FOCAL_LENGTH, DEFAULT_HYPOTHESES, MODEL_PINHOLE, VioRejectCamera, VioRejectConfig
-from .flow import DEFAULT_BORDER, DEFAULT_HALF_PATCH, DEFAULT_LEVELS, DEFAULT_MAX_ITER, VioFlowConfig, VioFlowPtInfo, _image
+from .flow import (DEFAULT_BACK_MAX_DIST, DEFAULT_BORDER, DEFAULT_HALF_PATCH, DEFAULT_LEVELS, DEFAULT_MAX_ITER, VioFlowBackConfig, VioFlowBackInfo,
+                   VioFlowConfig, VioFlowPtInfo, _image, track_results)
 
 MAX_SLOTS, MAX_DIM = 256, 16384
 PREV, NEXT = 0, 1
@@ -70,6 +74,7 @@ class FrameLib:
                "download", "reset", "counters", "timing"]
     READ_SYMBOLS = ["set_camera", "set_tracker", "read_batch", "points_set", "points_get", "read_timing"]      # include/vio_frame_read.h
     CAMERA_SYMBOLS = ["set_slot_camera", "get_slot_camera", "set_reject_config", "read_lift_info"]            # include/vio_frame_camera.h
+    BACK_SYMBOLS = ["set_flow_back", "track_back_batch", "set_reject_with_f", "read_back_info"]                # include/vio_frame_back.h
 
     def __init__(self, path):
         self.path = path
@@ -96,6 +101,11 @@ class FrameLib:
         self.fn["get_slot_camera"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["set_reject_config"].argtypes = [C.c_void_p, C.c_void_p]
         self.fn["read_lift_info"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_frame_", self.BACK_SYMBOLS)[1])
+        self.fn["set_flow_back"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn["track_back_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.fn["set_reject_with_f"].argtypes = [C.c_void_p, C.c_int32]
+        self.fn["read_back_info"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_frame handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -183,8 +193,14 @@ class FrameHandle(CompanionHandle):
         return out
 
     # ---- tracking -------------------------------------------------------------------------
-    def track_batch(self, items):
-        """items: dicts of slot, prev_pts (n, 2) float32, guess (n, 2) or None.  FlowHandle.track_batch's list of dicts."""
+    def set_flow_back(self, enabled=True, levels=0, max_dist=DEFAULT_BACK_MAX_DIST):
+        """FlowHandle.set_back for the handle's tracker: track, track_batch and read_batch apply the forward-backward check."""
+        cfg = VioFlowBackConfig(1 if enabled else 0, int(levels), float(max_dist))
+        self._ck(self.lib.fn["set_flow_back"](self.h, C.byref(cfg)), "set_flow_back")
+
+    def track_batch(self, items, back=False):
+        """items: dicts of slot, prev_pts (n, 2) float32, guess (n, 2) or None.  FlowHandle.track_batch's list of dicts (back=True: with
+        the check's rows; the check must be on)."""
         B = len(items)
         arr = (VioFrameTrackItem * max(B, 1))()
         keep, n = [], []
@@ -201,18 +217,17 @@ class FrameHandle(CompanionHandle):
         base = np.concatenate([[0], np.cumsum(n)]).astype(np.int64)
         nxt = np.full((max(total, 1), 2), np.nan, dtype=np.float32)
         info = (VioFlowPtInfo * max(total, 1))()
-        st = self.lib.fn["track_batch"](self.h, C.c_int32(B), C.addressof(arr), nxt.ctypes.data, C.addressof(info))
-        self._ck(st, "track_batch", allow_not_finite=True)
-        rec = np.frombuffer(info, dtype=np.dtype([("status", np.int32), ("iterations", np.int32), ("cost", np.float64)]), count=max(total, 1))
-        out = []
-        for i in range(B):
-            lo, hi = int(base[i]), int(base[i + 1])
-            out.append(dict(next_pts=nxt[lo:hi].copy(), status=rec["status"][lo:hi].copy(), iterations=rec["iterations"][lo:hi].copy(),
-                            cost=rec["cost"][lo:hi].copy()))
-        return out
+        binfo = None
+        if back:
+            binfo = (VioFlowBackInfo * max(total, 1))()
+            st = self.lib.fn["track_back_batch"](self.h, C.c_int32(B), C.addressof(arr), nxt.ctypes.data, C.addressof(info), C.addressof(binfo))
+        else:
+            st = self.lib.fn["track_batch"](self.h, C.c_int32(B), C.addressof(arr), nxt.ctypes.data, C.addressof(info))
+        self._ck(st, "track_back_batch" if back else "track_batch", allow_not_finite=True)
+        return track_results(base, nxt, info, binfo)
 
-    def track(self, prev_pts, guess=None, slot=0):
-        return self.track_batch([dict(slot=slot, prev_pts=prev_pts, guess=guess)])[0]
+    def track(self, prev_pts, guess=None, slot=0, back=False):
+        return self.track_batch([dict(slot=slot, prev_pts=prev_pts, guess=guess)], back=back)[0]
 
     # ---- detection ------------------------------------------------------------------------
     def detect_batch(self, items):
@@ -289,6 +304,16 @@ class FrameHandle(CompanionHandle):
         c, b = C.c_int32(0), C.c_int32(0)
         self._ck(self.lib.fn["read_lift_info"](self.h, C.c_int32(int(slot)), C.addressof(c), C.addressof(b)), "read_lift_info")
         return dict(n_clamped=int(c.value), n_bad=int(b.value))
+
+    def set_reject_with_f(self, enabled=True):
+        """False: a published read_batch runs no rejectWithF (n_after_reject = n_after_track, reject_hyp -1); the default is True."""
+        self._ck(self.lib.fn["set_reject_with_f"](self.h, C.c_int32(1 if enabled else 0)), "set_reject_with_f")
+
+    def read_back_info(self, slot=0):
+        """dict(n_checked, n_back_lost, n_back_far) of the forward-backward check in the slot's last read_batch (zeros with it off)."""
+        c, l, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+        self._ck(self.lib.fn["read_back_info"](self.h, C.c_int32(int(slot)), C.addressof(c), C.addressof(l), C.addressof(f)), "read_back_info")
+        return dict(n_checked=int(c.value), n_back_lost=int(l.value), n_back_far=int(f.value))
 
     def set_tracker(self, max_cnt=DEFAULT_MAX_CNT, border=DEFAULT_TRACK_BORDER):
         """The reference's MAX_CNT (at most MAX_TRACK_POINTS) and inBorder's margin."""

@@ -40,17 +40,32 @@ against the reference: the fisheye circle mask as a built-in (it is the `mask` i
 BatchFeatureTracker is the same front end for many streams at once over a frame.FrameHandle's read_batch: the points stay on the
 device, one call reads one new image of every stream.
 
+`flow_back` is None, or a dict of FlowHandle.set_back's arguments (levels, max_dist): the forward-backward check of VINS-Fusion's front
+end (include/vio_flow_back.h), set on `frames` if given and else on `tracker`.  A point that fails it has a status other than 0, so it
+leaves with those the tracker lost; back_info holds the check's counts of the last read_image.  reject_with_f=False skips
+rejecter.reject on a published frame, as VINS-Fusion does, and keeps rejecter.undistort.  BatchFeatureTracker takes the same two.  With
+both left at their defaults the classes make exactly the calls they made without them.
+
 One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
 """
 import numpy as np
 
+from .flow import FAIL_BACK_FAR, FAIL_BACK_LOST
+
 
 class FeatureTracker:
     def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None, equalizer=None, frames=None,
-                 slot=0):
+                 slot=0, flow_back=None, reject_with_f=True):
         self.tracker, self.detector = tracker, detector
         self.frames, self.slot = frames, int(slot)
+        self.flow_back, self.reject_with_f = flow_back, bool(reject_with_f)
+        self.back_info = dict(n_checked=0, n_back_lost=0, n_back_far=0)
+        if flow_back is not None:
+            if frames is not None:
+                frames.set_flow_back(**dict(flow_back))
+            else:
+                tracker.set_back(**dict(flow_back))
         self.max_cnt, self.min_dist, self.border, self.reject, self.mask = int(max_cnt), int(min_dist), int(border), reject, mask
         if frames is not None:
             if hasattr(frames, "set_config"):
@@ -101,9 +116,15 @@ class FeatureTracker:
             self.prev_img = self.cur_img = img
         cur, forw = self.cur_pts, np.zeros((0, 2), dtype=np.float32)
         ids, cnt = self.ids, self.track_cnt
+        if self.flow_back is not None:
+            self.back_info = dict(n_checked=0, n_back_lost=0, n_back_far=0)
         if len(cur) > 0:
             out = self.frames.track(cur, slot=self.slot) if self.frames is not None else self.tracker.track(self.cur_img, img, cur)
             forw = np.asarray(out["next_pts"], dtype=np.float32).reshape(-1, 2)
+            if self.flow_back is not None:
+                st = np.asarray(out["status"])
+                self.back_info = dict(n_checked=int(np.sum((st == 0) | (st == FAIL_BACK_LOST) | (st == FAIL_BACK_FAR))),
+                                      n_back_lost=int(np.sum(st == FAIL_BACK_LOST)), n_back_far=int(np.sum(st == FAIL_BACK_FAR)))
             ok = (np.asarray(out["status"]) == 0) & self.in_border(forw, img.shape)
             cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
         cnt = cnt + 1
@@ -112,7 +133,7 @@ class FeatureTracker:
             if self.reject is not None and len(forw) > 0:
                 ok = np.asarray(self.reject(cur, forw), dtype=bool).reshape(-1)
                 cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
-            if self.rejecter is not None and len(forw) > 0:
+            if self.rejecter is not None and self.reject_with_f and len(forw) > 0:
                 ok = np.asarray(self.rejecter.reject(cur, forw, self.n_frames), dtype=bool).reshape(-1)
                 cur, forw, ids, cnt = self._reduce(ok, cur, forw, ids, cnt)
             if self.frames is not None:
@@ -174,9 +195,10 @@ class BatchFeatureTracker:
 
     masks: None, or {slot: mask}.  cameras: None, or {slot: set_slot_camera's keywords}: the slot's own camera, of any model; a slot
     without one lifts through the handle's (frames.set_camera).  The handle's detector gets min_distance = min_dist (its other settings return to their defaults), as
-    in FeatureTracker."""
+    in FeatureTracker.  flow_back, reject_with_f: FeatureTracker's (frame.FrameHandle.set_flow_back, set_reject_with_f); frames.read_back_info(slot)
+    has the check's counts."""
 
-    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None, cameras=None):
+    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None, cameras=None, flow_back=None, reject_with_f=True):
         self.frames, self.slots = frames, [int(s) for s in slots]
         if len(set(self.slots)) != len(self.slots):
             raise ValueError("a slot is listed twice")
@@ -187,6 +209,10 @@ class BatchFeatureTracker:
             frames.set_mask(m, slot=int(s))
         for s, cam in (cameras or {}).items():
             frames.set_slot_camera(int(s), **cam)
+        if flow_back is not None:
+            frames.set_flow_back(**dict(flow_back))
+        if not reject_with_f:
+            frames.set_reject_with_f(False)
         self.last = [None] * len(self.slots)
 
     def read_images(self, imgs, t, publish=True):
