@@ -18,7 +18,7 @@
  *   PINHOLE          k1 k2 p1 p2 fx fy cx cy                          (PinholeCamera.cc:170-180)      fx, fy not 0
  *   MEI              xi k1 k2 p1 p2 gamma1 gamma2 u0 v0               (CataCamera.cc:186-199)         gamma1, gamma2 not 0
  *   SCARAMUZZA       p0 p1 p2 p3 p4 ac ad ae cx cy                    (ScaramuzzaCamera.cc:89-103; the 20 inv_poly entries are
- *                                                                      spaceToPlane's, which is not built)     ac - ad ae not 0
+ *                                                                      spaceToPlane's: vio_camera_set_inv_poly)  ac - ad ae not 0
  *   KANNALA_BRANDT   k2 k3 k4 k5 mu mv u0 v0 theta_max                (EquidistantCamera.cc:171-179)  mu, mv not 0
  * theta_max is this library's (see the root solve): in (0, pi], 0 for the default VIO_CAMERA_KB_DEFAULT_THETA_MAX = pi.
  *
@@ -69,8 +69,9 @@
  * result depends neither on its batch nor on its slot's number; the calling thread's current HIP device is restored; one handle is
  * used by one caller thread at a time.
  *
- * Not built: spaceToPlane (and with it SCARAMUZZA's inv_poly); the fisheye circle mask, which is the mask image the tracker already
- * takes.  The resident read_batch path of include/vio_frame_read.h takes these cameras per slot through include/vio_frame_camera.h
+ * spaceToPlane of the four models, with SCARAMUZZA's inv_poly, is include/vio_camera_project.h's, in this library and on these slots
+ * (vio_camera_project_batch, vio_camera_set_inv_poly).  Not built: the fisheye circle mask, which is the mask
+ * image the tracker already takes.  The resident read_batch path of include/vio_frame_read.h takes these cameras per slot through include/vio_frame_camera.h
  * (vio_frame_set_slot_camera; its handle-wide vio_frame_set_camera stays PINHOLE).
  */
 #ifndef VIO_CAMERA_H

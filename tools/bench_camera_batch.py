@@ -4,6 +4,7 @@ packing + upload, the kernel (HIP events through vio_camera_timing / vio_reject_
 calls after --warmup.
 
     python tools/bench_camera_batch.py [--out profiles/NAME.json]
+    python tools/bench_camera_batch.py --project [--batches 1,64] [--out profiles/NAME.json]      # spaceToPlane (measure_project)
 
 The pairs are synthetic two-view scenes (tests/camera_reference.two_view_scene: landmarks through the model from two poses, 0.1 px of
 noise, 20 % planted outliers), scene k of a batch drawn with seed k mod 8; undistort matches every point against the other frame's
@@ -41,14 +42,68 @@ def timed(handle, pairs, und, warmup, reps):
     return median(tr), median(tu), out
 
 
+def measure_project(vio, args):
+    """--project: spaceToPlane of B items of N points (include/vio_camera_project.h), B = 1 and 64 (--batches),
+    per model and mixed: leg batch is one CameraHandle.project_batch, leg numpy a loop over tests/camera_project_reference.project, the
+    route without the call.  Both legs must give the same bytes (`same`)."""
+    import time
+
+    import camera_project_reference as cp
+    import camera_reference as cr
+    models = [("PINHOLE", cr.EUROC), ("KANNALA_BRANDT", cr.KB_FOUR), ("MEI", cr.MEI), ("SCARAMUZZA", cr.SCARAMUZZA)]
+    cams = [cr.Camera(**p) for _, p in models]
+    invs = [cp.fit_inv_poly(c) if c.model == cr.MODEL_SCARAMUZZA else None for c in cams]
+    ch = vio.load_camera().create()
+    for slot, (_, params) in enumerate(models):
+        ch.set_camera(slot=slot, **params)
+        if invs[slot] is not None:
+            ch.set_inv_poly(slot, invs[slot])
+    rng = np.random.RandomState(0)
+    th, ph = rng.uniform(0.0, 0.45, (8, N)), rng.uniform(-np.pi, np.pi, (8, N))
+    pts = np.stack([np.sin(th) * np.cos(ph), np.sin(th) * np.sin(ph), np.cos(th)], axis=2) * rng.uniform(0.5, 25.0, (8, N, 1))
+    rows = []
+    for B in [int(b) for b in (args.batches or "1,64").split(",")]:
+        for name, slot_of in [(n, (lambda k, s=s: s)) for s, (n, _) in enumerate(models)] + [("mixed", lambda k: k % 4)]:
+            items = [dict(points=pts[k % 8], slot=slot_of(k)) for k in range(B)]
+            wall, parts, ref = [], [], []
+            for r in range(args.warmup + args.reps):
+                t0 = time.perf_counter()
+                out = ch.project_batch(items)
+                dt = 1e3 * (time.perf_counter() - t0)
+                if r >= args.warmup:
+                    wall.append(dt)
+                    parts.append(ch.timing())
+            for r in range(max(args.reps // 4, 2)):
+                t0 = time.perf_counter()
+                want = [cp.project(cams[it["slot"]], it["points"], invs[it["slot"]]) for it in items]
+                ref.append(1e3 * (time.perf_counter() - t0))
+            same = all(o["pixels"].tobytes() == w[0].tobytes() and o["flags"].tobytes() == w[1].tobytes() for o, w in zip(out, want))
+            row = dict(batch=B, n=N, model=name, call_ms=float(np.median(wall)), us_per_item=1e3 * float(np.median(wall)) / B, stages_ms=median(parts),
+                       numpy_ms=float(np.median(ref)), numpy_us_per_item=1e3 * float(np.median(ref)) / B, same=bool(same))
+            rows.append(row)
+            print("B %3d  %-14s  call %8.3f ms  %8.2f us/item  (upload %.3f kernel %.3f total %.3f)   numpy loop %8.3f ms  %8.2f us/item   same bytes: %s"
+                  % (B, name, row["call_ms"], row["us_per_item"], row["stages_ms"]["upload_ms"], row["stages_ms"]["kernel_ms"], row["stages_ms"]["total_ms"],
+                     row["numpy_ms"], row["numpy_us_per_item"], same), flush=True)
+    ch.close()
+    res = dict(bench="camera_project", n=N, reps=args.reps, warmup=args.warmup, rows=rows)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--batches", default="1,16,64,256")
+    ap.add_argument("--project", action="store_true")
+    ap.add_argument("--batches", default=None)
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     vio = g.load_package()
+    if args.project:
+        return measure_project(vio, args)
+    args.batches = args.batches or "1,16,64,256"
     import camera_reference as cr
     import reject_reference as rr
     models = [("PINHOLE", cr.EUROC), ("KANNALA_BRANDT", cr.KB_FOUR), ("MEI", cr.MEI), ("SCARAMUZZA", cr.SCARAMUZZA)]

@@ -22,6 +22,9 @@ decisions and the track counts of the last frame are compared (`same`).
   leg host   per slot tracks_get, the erase on the host (a numpy mask over the arrays) and tracks_set: the route without the call
 
 Every repetition seeds the slots afresh (not timed); the two legs alternate as above and must leave the same tables (`same`).
+
+--predict measures predictPtsInNextFrame of B slots of 150 tracks, B = 1 and 64 (--batches), against a loop over
+the numpy restatement (measure_predict).
 """
 import argparse
 import ctypes as C
@@ -139,8 +142,53 @@ def measure_remove(vio, args):
             json.dump(res, f, indent=1)
 
 
+def measure_predict(vio, args):
+    """--predict: predictPtsInNextFrame of B slots of 150 tracks (include/vio_fm_predict.h), B = 1 and 64
+    (--batches): leg batch is one FmHandle.predict_batch, leg numpy per slot tracks_get and tests/fm_predict_reference.predict, the
+    route without the call.  Both legs must give the same bytes (`same`)."""
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    import fm_predict_reference as fp
+    import predict_inputs as pi
+    fh = vio.load_fm().create()
+    rows = []
+    for B in [int(b) for b in args.batches.split(",")]:
+        tabs = [pi.table(POINTS, WINDOW, seed=s)[0] for s in range(B)]
+        poses = [pi.poses(s) for s in range(B)]
+        for s in range(B):
+            fh.tracks_set(s, *[tabs[s][k] for k in ("ids", "start", "depth", "flag", "off", "pts")])
+        items = [(s, WINDOW, poses[s][0], poses[s][1], None) for s in range(B)]
+        wall, parts, ref = [], [], []
+        for r in range(args.warmup + args.reps):
+            t0 = time.perf_counter()
+            out = fh.predict_batch(items)
+            dt = 1e3 * (time.perf_counter() - t0)
+            if r >= args.warmup:
+                wall.append(dt)
+                parts.append(fh.timing())
+        for r in range(max(args.reps // 4, 2)):
+            t0 = time.perf_counter()
+            want = [fp.predict(fh.tracks_get(s), WINDOW, poses[s][0], poses[s][1], None) for s in range(B)]
+            ref.append(1e3 * (time.perf_counter() - t0))
+        same = all(o["ids"].tobytes() == w[0].tobytes() and o["pts_cam"].tobytes() == w[1].tobytes() for o, w in zip(out, want))
+        row = dict(batch=B, tracks=POINTS, rows_per_slot=float(np.mean([o["n_rows"] for o in out])), call_ms=float(np.median(wall)),
+                   us_per_slot=1e3 * float(np.median(wall)) / B,
+                   stages_ms={k: float(np.median([p[k] for p in parts])) for k in ("host_ms", "kernel_ms", "readback_ms", "total_ms")},
+                   numpy_ms=float(np.median(ref)), numpy_us_per_slot=1e3 * float(np.median(ref)) / B, same=bool(same))
+        rows.append(row)
+        print("B %3d  tracks %d  rows %.1f  call %8.3f ms  %8.2f us/slot  (lib %.3f  h %.3f k %.3f r %.3f)   numpy loop %8.3f ms  %8.2f us/slot   same bytes: %s"
+              % (B, POINTS, row["rows_per_slot"], row["call_ms"], row["us_per_slot"], row["stages_ms"]["total_ms"], row["stages_ms"]["host_ms"],
+                 row["stages_ms"]["kernel_ms"], row["stages_ms"]["readback_ms"], row["numpy_ms"], row["numpy_us_per_slot"], same), flush=True)
+    fh.close()
+    res = dict(bench="fm_predict", tracks=POINTS, reps=args.reps, warmup=args.warmup, rows=rows)
+    print(json.dumps(res))
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump(res, f, indent=1)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--predict", action="store_true")
     ap.add_argument("--remove", action="store_true")
     ap.add_argument("--batches", default=None)
     ap.add_argument("--reps", type=int, default=20)
@@ -149,9 +197,11 @@ def main():
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
     if args.batches is None:
-        args.batches = "1,16,64" if args.remove else "1,16,64,256"
+        args.batches = "1,64" if args.predict else "1,16,64" if args.remove else "1,16,64,256"
     vio = g.load_package()
     vio.load_hip()
+    if args.predict:
+        return measure_predict(vio, args)
     if args.remove:
         return measure_remove(vio, args)
     host = build_host_leg(os.path.join(ROOT, "visual-inertial-odometry_amd", "csrc"))

@@ -12,6 +12,9 @@ reference's four camera models (PINHOLE, KANNALA_BRANDT, MEI, SCARAMUZZA), for m
     outs = ch.undistort_batch([dict(pts=, ids=, prev_ids=, prev_un_pts=, dt=, slot=), ...])   # status, n_clamped, un_pts, velocity
     outs = ch.reject_batch([dict(cur_pts=, forw_pts=, pair=, slot=), ...])                    # status, hyp, n_inliers, F, mask
     other = ch.bind(3)                                               # the same handle with slot 3 as its default slot
+    ch.set_inv_poly(slot, coeffs)                                    # SCARAMUZZA's inv_poly_parameters (include/vio_camera_project.h)
+    pixels = ch.project(points, slot=0)                              # spaceToPlane: (n, 3) float64 -> (n, 2) float64
+    outs = ch.project_batch([dict(points=, slot=), ...])             # dicts: status, n_flagged, pixels (n, 2), flags (n,) uint8
 
 A CameraHandle (or a bind() view) is a FeatureTracker rejecter: FeatureTracker(rejecter=ch, frames=, slot=).  An item whose lift the
 tracker cannot use (a pixel that is not finite, P2 == 0 on a fisheye) gets status NOT_FINITE and does not raise.
@@ -29,6 +32,9 @@ MAX_SLOTS, MAX_PARAMS, MAX_POINTS, MAX_ITEMS = 256, 16, 4096, 4096
 KB_BISECTIONS, KB_NEWTON, KB_GRID = 12, 8, 4096
 KB_DEFAULT_THETA_MAX = math.pi
 KB_RAY_C = 3.6
+INV_POLY_MAX = 20                                                      # include/vio_camera_project.h
+PROJECT_NOT_FINITE, PROJECT_BEHIND = 1, 2
+PROJECT_C = 3e-13
 MODEL_PINHOLE, MODEL_KANNALA_BRANDT, MODEL_MEI, MODEL_SCARAMUZZA = 0, 1, 2, 3
 MODEL_NAMES = {"PINHOLE": MODEL_PINHOLE, "KANNALA_BRANDT": MODEL_KANNALA_BRANDT, "MEI": MODEL_MEI, "SCARAMUZZA": MODEL_SCARAMUZZA}
 
@@ -66,6 +72,14 @@ class VioCameraRejectItem(C.Structure):
                 ("reserved", C.c_int32)]
 
 
+class VioCameraProjectItem(C.Structure):                                # include/vio_camera_project.h
+    _fields_ = [("n", C.c_int32), ("slot", C.c_int32), ("points", C.c_void_p), ("pixels", C.c_void_p), ("flags", C.c_void_p)]
+
+
+class VioCameraProjectResult(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_flagged", C.c_int32)]
+
+
 def model_params(model, **params):
     """The params[] array of `model` from keywords named as the reference's calibration files name them (SCARAMUZZA's polynomial is
     poly0 .. poly4).  A missing keyword without a default and an unknown keyword raise."""
@@ -85,7 +99,7 @@ def model_params(model, **params):
 def parse_camodocal_yaml(text):
     """set_camera's keywords from the calibration text the reference's readFromYamlFile reads: `%YAML:1.0`, model_type, image_width,
     image_height and the model's parameter sections (distortion_parameters, projection_parameters, mirror_parameters,
-    poly_parameters, affine_parameters; inv_poly_parameters is read past).  Only `key: value` lines are understood: a section is a key
+    poly_parameters, affine_parameters; inv_poly_parameters is parse_camodocal_inv_poly's).  Only `key: value` lines are understood: a section is a key
     without a value followed by indented keys.  Everything else of the file (topics, extrinsics, matrices) is ignored."""
     top, sections, cur = {}, {}, None
     for raw in text.splitlines():
@@ -124,10 +138,33 @@ def parse_camodocal_yaml(text):
     return out
 
 
+def parse_camodocal_inv_poly(text):
+    """SCARAMUZZA's inv_poly_parameters (p0, p1, ...) of the calibration text parse_camodocal_yaml reads, as a list of floats, lowest
+    power first, for CameraHandle.set_inv_poly; [] where the text has no such section.  A function of its own: parse_camodocal_yaml's
+    dict is set_camera's keywords and nothing else."""
+    sec, inside = {}, False
+    for raw in text.splitlines():
+        line = raw.split("#", 1)[0].rstrip()
+        if not line.strip() or line.lstrip().startswith("%") or line.strip() == "---" or ":" not in line:
+            continue
+        key, val = line.split(":", 1)
+        if key[:1] not in " \t":
+            inside = key.strip() == "inv_poly_parameters" and val.strip() == ""
+        elif inside:
+            sec[key.strip()] = float(val.strip().strip('"'))
+    out = []
+    while "p%d" % len(out) in sec:
+        out.append(sec["p%d" % len(out)])
+    if len(out) != len(sec):
+        raise ValueError("inv_poly_parameters must be p0, p1, ... without a gap")
+    return out
+
+
 class CameraLib:
     """libvio_camera_hip.so: vio_camera_*."""
 
     SYMBOLS = ["create", "destroy", "last_error", "version", "set", "set_config", "lift_batch", "undistort_batch", "reject_batch", "timing"]
+    PROJECT_SYMBOLS = ["set_inv_poly", "project_batch"]                                    # include/vio_camera_project.h
 
     def __init__(self, path):
         from .capi import open_lib
@@ -140,6 +177,9 @@ class CameraLib:
         self.fn["undistort_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
         self.fn["reject_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_camera_", self.PROJECT_SYMBOLS)[1])
+        self.fn["set_inv_poly"].argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]
+        self.fn["project_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_camera handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -253,6 +293,35 @@ class CameraHandle(CompanionHandle):
     def reject(self, cur_pts, forw_pts, pair=0):
         """The pairs to keep on the default slot: (n,) bool (FeatureTracker's rejecter interface)."""
         return self.reject_batch([dict(cur_pts=cur_pts, forw_pts=forw_pts, pair=pair)])[0]["mask"]
+
+    def set_inv_poly(self, slot, coeffs):
+        """SCARAMUZZA's inv_poly_parameters of camera slot `slot`: 1 to INV_POLY_MAX finite coefficients, lowest power first.  The slot
+        must hold a SCARAMUZZA camera; a later set_camera on it clears them."""
+        c = np.ascontiguousarray(coeffs, dtype=np.float64).reshape(-1)
+        self._ck(self.lib.fn["set_inv_poly"](self.h, C.c_int32(int(slot)), C.c_int32(len(c)), c.ctypes.data if len(c) else None), "set_inv_poly")
+
+    def project_batch(self, items):
+        """spaceToPlane of every item (points (n, 3) float64 in the camera frame, slot): a list of dicts status, n_flagged, pixels (n, 2)
+        float64, flags (n,) uint8 (0: usable; PROJECT_NOT_FINITE, PROJECT_BEHIND).  A point that is not finite gives its item
+        NOT_FINITE and does not raise."""
+        B = len(items)
+        arr = (VioCameraProjectItem * max(B, 1))()
+        keep, outs = [], []
+        for i, it in enumerate(items):
+            p = np.ascontiguousarray(it["points"], dtype=np.float64).reshape(-1, 3)
+            pix = np.zeros((max(len(p), 1), 2), dtype=np.float64)
+            fl = np.zeros(max(len(p), 1), dtype=np.uint8)
+            keep.append(p)
+            outs.append((pix, fl, len(p)))
+            arr[i] = VioCameraProjectItem(len(p), int(it.get("slot", self.slot)), p.ctypes.data, pix.ctypes.data, fl.ctypes.data)
+        res = (VioCameraProjectResult * max(B, 1))()
+        st = self.lib.fn["project_batch"](self.h, C.c_int32(B), C.addressof(arr), C.addressof(res))
+        self._ck(st, "project_batch", allow_not_finite=True)
+        return [dict(status=int(res[i].status), n_flagged=int(res[i].n_flagged), pixels=pix[:n], flags=fl[:n]) for i, (pix, fl, n) in enumerate(outs)]
+
+    def project(self, points, slot=None):
+        """The pixels of one point set: (n, 2) float64 (NaN where a point has no finite pixel)."""
+        return self.project_batch([dict(points=points, slot=self.slot if slot is None else slot)])[0]["pixels"]
 
     def timing(self):
         """ms of the last call that launched: host packing + upload, the kernel, the whole call."""

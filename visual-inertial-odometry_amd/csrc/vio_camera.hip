@@ -6,6 +6,9 @@
 // normalised point divide by the ray's z.  The RANSAC behind the prologue is untouched.  The camera table (VIO_CAMERA_MAX_SLOTS CamDev)
 // lives in device memory; a workgroup of k_reject_ransac reads its pair's camera once, uniformly, k_reject_lift per point.
 // Contraction is off; no floating-point atomics; every sum has a fixed order.
+// spaceToPlane (include/vio_camera_project.h) is k_camera_project of vio_camera_project_body.inc over
+// vio_camera_project_math.h, with a device table of its own (VIO_CAMERA_MAX_SLOTS CamProj): CamDev is shared with libvio_frame_hip
+// and stays as it is.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -16,11 +19,13 @@
 #include <vector>
 
 #include "../../include/vio_camera.h"
+#include "../../include/vio_camera_project.h"
 #include "vio_companion.h"
 
 #pragma clang fp contract(off)
 
 #include "vio_camera_math.h"
+#include "vio_camera_project_math.h"
 #include "vio_sfm_math.h"
 
 constexpr int MAX_ITEMS = VIO_CAMERA_MAX_ITEMS;
@@ -28,6 +33,7 @@ static_assert(VIO_CAMERA_MAX_POINTS == VIO_REJECT_MAX_POINTS && VIO_CAMERA_MAX_I
 
 #include "vio_camera_host.h"
 #include "vio_reject_body.inc"
+#include "vio_camera_project_body.inc"
 
 // ---------------------------------------------------------------------------------------------------------
 // host side
@@ -38,6 +44,8 @@ struct vio_camera {
     vio_reject_config cfg = REJ_DEFAULTS;
     Twin<CamDev> cams;                                       // the camera table
     bool cams_dirty = true;
+    Twin<CamProj> proj;                                      // the projection table (include/vio_camera_project.h)
+    bool proj_dirty = true;
     Twin<char> tab;                                          // descriptors | staged floats | staged ids
     Twin<char> out;                                          // results | masks, or un_pts | velocity | flags, or rays | angles | flags
     DevBuf<char> scratch;                                    // corr | flags
@@ -164,6 +172,8 @@ vio_status vio_camera_create(int32_t device, void *stream, vio_camera **out) {
     return create_handle(device, stream, out, vio_camera_destroy, [](vio_camera *h) {
         if (h->cams.ensure(h->err, sizeof(CamDev) * VIO_CAMERA_MAX_SLOTS) != VIO_OK) return false;
         std::memset(h->cams.h, 0, sizeof(CamDev) * VIO_CAMERA_MAX_SLOTS);
+        if (h->proj.ensure(h->err, sizeof(CamProj) * VIO_CAMERA_MAX_SLOTS) != VIO_OK) return false;
+        std::memset(h->proj.h, 0, sizeof(CamProj) * VIO_CAMERA_MAX_SLOTS);
         return true;
     });
 }
@@ -178,6 +188,8 @@ vio_status vio_camera_set(vio_camera *h, int32_t slot, const vio_camera_model *c
     if (st != VIO_OK) return st;
     h->cams.h[slot] = cam_device_form(*cam);
     h->cams_dirty = true;
+    h->proj.h[slot] = cam_project_form(*cam);               // (inv_poly of the slot is cleared)
+    h->proj_dirty = true;
     return VIO_OK;
 }
 
@@ -381,6 +393,109 @@ vio_status vio_camera_reject_batch(vio_camera *h, int32_t count, const vio_camer
         }
     }
     if (any) h->timing[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+    return ret;
+}
+
+// ---- include/vio_camera_project.h ----------------------------------------------------------------------------
+
+vio_status vio_camera_set_inv_poly(vio_camera *h, int32_t slot, int32_t n, const double *inv_poly) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (!slot_set(h, slot)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_camera_set_inv_poly: camera slot %d is outside [0, %d) or not set", slot, VIO_CAMERA_MAX_SLOTS);
+    if (h->proj.h[slot].model != VIO_CAMERA_MODEL_SCARAMUZZA) return fail(h->err, VIO_ERR_BAD_ARG, "vio_camera_set_inv_poly: slot %d does not hold a SCARAMUZZA camera", slot);
+    if (n < 1 || n > VIO_CAMERA_INV_POLY_MAX || !inv_poly) return fail(h->err, VIO_ERR_BAD_ARG, "vio_camera_set_inv_poly: n must be in [1, %d] and inv_poly given", VIO_CAMERA_INV_POLY_MAX);
+    for (int i = 0; i < n; ++i)
+        if (!std::isfinite(inv_poly[i])) return fail(h->err, VIO_ERR_BAD_ARG, "vio_camera_set_inv_poly: coefficient %d is not finite", i);
+    CamProj &C = h->proj.h[slot];
+    for (int i = 0; i < VIO_CAMERA_INV_POLY_MAX; ++i) C.inv[i] = i < n ? inv_poly[i] : 0.0;
+    C.n_inv = n;
+    h->proj_dirty = true;
+    return VIO_OK;
+}
+
+vio_status vio_camera_project_batch(vio_camera *h, int32_t count, const vio_camera_project_item *items, vio_camera_project_result *results) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (count < 0 || count > MAX_ITEMS || (count > 0 && (!items || !results)))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_camera_project_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
+    if (count == 0) return VIO_OK;
+    const auto t0 = std::chrono::steady_clock::now();
+    std::vector<ProjItem> its((size_t)count);
+    int64_t n_pts = 0;
+    int max_n = 0;
+    for (int i = 0; i < count; ++i) {
+        const vio_camera_project_item &it = items[i];
+        if (it.n < 0 || it.n > VIO_CAMERA_MAX_POINTS) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: n must be in [0, %d]", i, VIO_CAMERA_MAX_POINTS);
+        if (it.n > 0 && (!it.points || !it.pixels)) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: points and pixels are required", i);
+        if (!slot_set(h, it.slot)) return fail(h->err, VIO_ERR_BAD_ARG, "item %d: camera slot %d is outside [0, %d) or not set", i, it.slot, VIO_CAMERA_MAX_SLOTS);
+        const CamProj &C = h->proj.h[it.slot];
+        if (C.model == VIO_CAMERA_MODEL_SCARAMUZZA && C.n_inv < 1)
+            return fail(h->err, VIO_ERR_BAD_ARG, "item %d: SCARAMUZZA slot %d has no inv_poly (vio_camera_set_inv_poly)", i, it.slot);
+        ProjItem &d = its[(size_t)i];
+        d.n = it.n; d.slot = it.slot; d.o_pt = n_pts;
+        n_pts += it.n;
+        max_n = std::max(max_n, it.n);
+    }
+    const size_t n_total = (size_t)n_pts;
+    if (max_n > 0) {
+        DeviceScope dev(h->device);
+        if (!dev.ok) return fail(h->err, VIO_ERR_HIP, "hipSetDevice(%d)", h->device);
+        const size_t b_it = align256(sizeof(ProjItem) * (size_t)count), b_tab = b_it + sizeof(double) * 3 * n_total;
+        const size_t b_pix = sizeof(double) * 2 * n_total, b_out = b_pix + n_total;
+        vio_status st;
+        if ((st = h->tab.ensure(h->err, b_tab)) != VIO_OK || (st = h->out.ensure(h->err, b_out)) != VIO_OK) return st;
+        std::memcpy(h->tab.h, its.data(), sizeof(ProjItem) * (size_t)count);
+        double *hp = (double *)(h->tab.h + b_it);
+        for (int i = 0; i < count; ++i)
+            if (items[i].n > 0) std::memcpy(hp + 3 * its[(size_t)i].o_pt, items[i].points, sizeof(double) * 3 * (size_t)items[i].n);
+        ProjArgs a;
+        std::memset(&a, 0, sizeof(a));
+        a.items = (const ProjItem *)h->tab.d;
+        a.pts = (const double *)(h->tab.d + b_it);
+        a.pix = (double *)h->out.d;
+        a.flags = (uint8_t *)(h->out.d + b_pix);
+        a.cams = h->proj.d; a.count = count;
+        const auto t1 = std::chrono::steady_clock::now();
+        hipStream_t q = h->q.stream;
+        (void)hipEventRecord(h->q.ev[0], q);
+        if (h->proj_dirty) {
+            if (hipMemcpyAsync(h->proj.d, h->proj.h, sizeof(CamProj) * VIO_CAMERA_MAX_SLOTS, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
+            h->proj_dirty = false;
+        }
+        if (hipMemcpyAsync(h->tab.d, h->tab.h, b_tab, hipMemcpyHostToDevice, q) != hipSuccess) return fail_synced(h, "upload failed");
+        (void)hipEventRecord(h->q.ev[1], q);
+        hipLaunchKernelGGL(k_camera_project, dim3((unsigned)((max_n + NT - 1) / NT), (unsigned)count), dim3(NT), 0, q, a);
+        (void)hipEventRecord(h->q.ev[2], q);
+        if (hipGetLastError() != hipSuccess) return fail_synced(h, "kernel launch failed");
+        if (hipMemcpyAsync(h->out.h, h->out.d, b_out, hipMemcpyDeviceToHost, q) != hipSuccess || hipStreamSynchronize(q) != hipSuccess)
+            return fail_synced(h, "kernel or read-back failed");
+        h->timing[0] = std::chrono::duration<double, std::milli>(t1 - t0).count() + elapsed_ms(h->q.ev[0], h->q.ev[1]);
+        h->timing[1] = elapsed_ms(h->q.ev[1], h->q.ev[2]);
+    }
+    const double *pix = (const double *)h->out.h;
+    const uint8_t *flags = max_n > 0 ? (const uint8_t *)(h->out.h + sizeof(double) * 2 * n_total) : nullptr;
+    vio_status ret = VIO_OK;
+    for (int i = 0; i < count; ++i) {
+        const ProjItem &d = its[(size_t)i];
+        int flagged = 0;
+        bool bad = false;
+        if (d.n > 0) {
+            std::memcpy(items[i].pixels, pix + 2 * (size_t)d.o_pt, sizeof(double) * 2 * (size_t)d.n);
+            if (items[i].flags) std::memcpy(items[i].flags, flags + d.o_pt, (size_t)d.n);
+            for (int k = 0; k < d.n; ++k) {
+                const uint8_t f = flags[d.o_pt + k];
+                flagged += f != 0;
+                bad |= (f & VIO_CAMERA_PROJECT_NOT_FINITE) != 0;
+            }
+        }
+        results[i].status = bad ? VIO_ERR_NOT_FINITE : VIO_OK;
+        results[i].n_flagged = flagged;
+        if (bad) {
+            if (ret == VIO_OK) fail(h->err, VIO_ERR_NOT_FINITE, "item %d: a point or its pixel is not finite", i);
+            ret = VIO_ERR_NOT_FINITE;
+        }
+    }
+    if (max_n > 0) h->timing[2] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     return ret;
 }
 

@@ -2,7 +2,7 @@
 // (include/vio_fm.h).
 // Contraction is off (vio_fm_math.h): the parallax term and the depth shift are evaluated as written.  No floating-point atomics.
 // The kernels, described where they are, are in vio_fm_body.inc, (include/vio_fm_stream.h's two) vio_fm_stream_body.inc and
-// (include/vio_fm_outlier.h's one) vio_fm_outlier_body.inc; the triangulation is vio_triangulate_body.h, a function around the
+// (include/vio_fm_outlier.h's one) vio_fm_outlier_body.inc and (include/vio_fm_predict.h's one) vio_fm_predict_body.inc; the triangulation is vio_triangulate_body.h, a function around the
 // text (vio_triangulate_body.inc) that k_triangulate of libvio_hip includes.
 #include <hip/hip_runtime.h>
 
@@ -16,6 +16,7 @@
 #include "../../include/vio_fm.h"
 #include "../../include/vio_fm_stream.h"
 #include "../../include/vio_fm_outlier.h"
+#include "../../include/vio_fm_predict.h"
 #include "vio_companion.h"
 #include "vio_device_math.h"
 #include "vio_types.h"
@@ -28,6 +29,8 @@
 #include "vio_fm_stream_body.inc"
 #include "vio_fm_outlier_math.h"
 #include "vio_fm_outlier_body.inc"
+#include "vio_fm_predict_math.h"
+#include "vio_fm_predict_body.inc"
 
 static_assert(FM_MAX_TRACKS == VIO_FM_MAX_TRACKS && FM_MAX_OBS == VIO_FM_MAX_OBS && FM_MAX_POINTS == VIO_FM_MAX_POINTS &&
               FM_BACK_SHIFT_DEPTH == VIO_FM_BACK_SHIFT_DEPTH && FM_BACK == VIO_FM_BACK && FM_FRONT == VIO_FM_FRONT &&
@@ -543,6 +546,52 @@ vio_status vio_fm_remove_batch(vio_fm *h, int32_t count, const vio_fm_remove_ite
                             const FmItemD &d = h->its[(size_t)i];
                             results[i].n_rows = fm_clamp(results[i].n_rows, 0, d.n_tracks < d.b ? d.n_tracks : d.b);
                             if (items[i].erased) fm_unpermute_hits((const uint8_t *)out + d.o_out, h->scratch_perm.data() + d.c, d.b, items[i].erased);
+                        }
+                    });
+}
+
+// ---- include/vio_fm_predict.h --------------------------------------------------------------------------------
+
+vio_status vio_fm_predict_batch(vio_fm *h, int32_t count, const vio_fm_predict_item *items, vio_fm_result *results) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    const Tick t0 = std::chrono::steady_clock::now();
+    vio_status st = begin_call(h, "vio_fm_predict_batch", count, items, results);
+    if (st != VIO_OK || count == 0) return st;
+    size_t b_out = 0;
+    const size_t b_pose = align256(8 * FMP_IN);
+    for (int i = 0; i < count; ++i) {
+        const vio_fm_predict_item &it = items[i];
+        const int n = h->slots[it.slot].n_tracks;
+        if (it.frame_count < 0 || it.frame_count > FM_WINDOW) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_predict_batch: item %d: frame_count must be in [0, %d]", i, FM_WINDOW);
+        if (!it.poses || !it.ext) return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_predict_batch: item %d: poses and ext are required", i);
+        if (!all_finite(it.poses, 7 * VIO_NF) || !all_finite(it.ext, 7) || (it.next_pose && !all_finite(it.next_pose, 7)))
+            return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_predict_batch: item %d: a pose is not finite", i);
+        if (it.cap_rows < n || (n > 0 && (!it.ids || !it.pts_cam)))
+            return fail(h->err, VIO_ERR_BAD_ARG, "vio_fm_predict_batch: item %d: ids and pts_cam hold %d rows, the slot has %d tracks", i, it.cap_rows, n);
+        FmItemD &d = h->its[(size_t)i];
+        d.a = it.frame_count; d.b = n; d.c = it.next_pose != nullptr;
+        d.o_in = (int64_t)(b_pose * (size_t)i);
+        d.o_out = (int64_t)b_out;
+        b_out += align256(32 * (size_t)n);
+    }
+    return run_call(h, t0, count, items, results, b_pose * (size_t)count, b_out, k_fm_predict, FM_NT,
+                    [&](char *in) {
+                        for (int i = 0; i < count; ++i) {
+                            double *p = (double *)(in + h->its[(size_t)i].o_in);
+                            std::memcpy(p, items[i].poses, 8 * 7 * VIO_NF);
+                            std::memcpy(p + 7 * VIO_NF, items[i].ext, 8 * 7);
+                            if (items[i].next_pose) std::memcpy(p + 7 * VIO_NF + 7, items[i].next_pose, 8 * 7);
+                            else std::memset(p + 7 * VIO_NF + 7, 0, 8 * 7);
+                        }
+                    },
+                    [&](const char *out) {
+                        for (int i = 0; i < count; ++i) {
+                            const FmItemD &d = h->its[(size_t)i];
+                            const size_t n = (size_t)d.b;                        // (the kernel's layout: the rows the call began with)
+                            const int nr = fm_clamp(results[i].n_rows, 0, d.b);
+                            results[i].n_rows = nr;
+                            const char *p = out + d.o_out;
+                            if (nr) { std::memcpy(items[i].ids, p, 8 * (size_t)nr); std::memcpy(items[i].pts_cam, p + 8 * n, 24 * (size_t)nr); }
                         }
                     });
 }

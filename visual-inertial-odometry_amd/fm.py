@@ -1,4 +1,4 @@
-"""ctypes binding of include/vio_fm.h, vio_fm_stream.h and vio_fm_outlier.h (csrc/libvio_fm_hip.so): the reference's FeatureManager for many streams at once, each stream's
+"""ctypes binding of include/vio_fm.h, vio_fm_stream.h, vio_fm_outlier.h and vio_fm_predict.h (csrc/libvio_fm_hip.so): the reference's FeatureManager for many streams at once, each stream's
 track list resident on the device.
 
     fh = vio.load_fm().create()                                      # (device 0, its own stream)
@@ -8,6 +8,7 @@ track list resident on the device.
     fm.set_depths([w["inv_depth"] for w in solved])                  # setDepth + removeFailures
     fm.remove([w["feature_ids"][flags & 7 != 0] for w, flags in zip(wins, lm_flags)])    # removeOutlier by id (vio_fm_outlier.h)
     fm.slide([BACK_SHIFT_DEPTH] * 64, marg_R=..., marg_P=..., new_R=..., new_P=...)
+    pred = fm.predict(frame_count, poses, ext)                       # predictPtsInNextFrame: pred[i]["ids"], ["pts_cam"] (vio_fm_predict.h)
 
 A track list as arrays is tests/fm_util.tracks_to_arrays' layout: ids, start, depth, flag, off (n + 1), pts (off[-1], 2).
 """
@@ -72,6 +73,11 @@ class VioFmRemoveItem(C.Structure):                                     # includ
     _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("ids", C.c_void_p), ("erased", C.c_void_p)]
 
 
+class VioFmPredictItem(C.Structure):                                    # include/vio_fm_predict.h
+    _fields_ = [("slot", C.c_int32), ("frame_count", C.c_int32), ("cap_rows", C.c_int32), ("reserved", C.c_int32), ("poses", C.c_void_p),
+                ("ext", C.c_void_p), ("next_pose", C.c_void_p), ("ids", C.c_void_p), ("pts_cam", C.c_void_p)]
+
+
 def _result(r):
     return {k: getattr(r, k) for k, _ in VioFmResult._fields_}
 
@@ -83,6 +89,7 @@ class FmLib:
                "set_depth_batch", "slide_batch", "corresponding_batch", "tracks_set", "tracks_get", "timing"]
     STREAM_SYMBOLS = ["init_depth_batch", "tracks_batch"]                                  # include/vio_fm_stream.h
     OUTLIER_SYMBOLS = ["remove_batch"]                                                     # include/vio_fm_outlier.h
+    PREDICT_SYMBOLS = ["predict_batch"]                                                    # include/vio_fm_predict.h
 
     def __init__(self, path):
         self.path = path
@@ -98,7 +105,8 @@ class FmLib:
         self.fn["timing"].argtypes = [C.c_void_p, C.c_void_p]
         self.fn.update(open_lib(path, "vio_fm_", self.STREAM_SYMBOLS)[1])
         self.fn.update(open_lib(path, "vio_fm_", self.OUTLIER_SYMBOLS)[1])
-        for k in self.STREAM_SYMBOLS + self.OUTLIER_SYMBOLS:
+        self.fn.update(open_lib(path, "vio_fm_", self.PREDICT_SYMBOLS)[1])
+        for k in self.STREAM_SYMBOLS + self.OUTLIER_SYMBOLS + self.PREDICT_SYMBOLS:
             self.fn[k].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
@@ -297,6 +305,28 @@ class FmHandle(CompanionHandle):
             r["erased"] = e.astype(bool)
         return res
 
+    def predict_batch(self, items):
+        """predictPtsInNextFrame per item (slot, frame_count, poses (11, 7), ext (7,), next_pose (7,) or None for the constant-velocity
+        pose): the tracks with a depth that end at frame_count as points in the next frame's camera.  The result dicts (the three
+        counts; n_rows: the rows predicted) plus ids (n_rows,) int64 and pts_cam (n_rows, 3) float64, in list order."""
+        arr, keep, outs = (VioFmPredictItem * max(len(items), 1))(), [], []
+        for i, (slot, fc, poses, ext, nxt) in enumerate(items):
+            n = self.counts(slot)[0]
+            poses = np.ascontiguousarray(poses, dtype=np.float64)
+            ext = np.ascontiguousarray(ext, dtype=np.float64)
+            nxt = None if nxt is None else np.ascontiguousarray(nxt, dtype=np.float64)
+            if poses.shape != (11, 7) or ext.shape != (7,) or (nxt is not None and nxt.shape != (7,)):
+                raise ValueError("item %d: poses (11, 7), ext (7,), next_pose (7,) or None" % i)
+            ids, pts = np.zeros(max(n, 1), dtype=np.int64), np.zeros((max(n, 1), 3))
+            keep += [poses, ext, nxt]
+            outs.append((ids, pts))
+            arr[i] = VioFmPredictItem(int(slot), int(fc), n, 0, poses.ctypes.data, ext.ctypes.data, None if nxt is None else nxt.ctypes.data,
+                                      ids.ctypes.data, pts.ctypes.data)
+        res = self._call("predict_batch", arr, len(items))
+        for r, (ids, pts) in zip(res, outs):
+            r.update(ids=ids[:r["n_rows"]].copy(), pts_cam=pts[:r["n_rows"]].copy())
+        return res
+
     def timing(self):
         """ms of the last batched call that launched: host checks, packing and upload; the kernel; the read-back; the whole call."""
         t = (C.c_double * 4)()
@@ -368,6 +398,16 @@ class BatchFeatureManager:
     def tracks(self):
         """Every slot's list (sfm_f) in one call."""
         return self.fm.tracks_batch(self.slots)
+
+    def predict(self, frame_count, poses, ext, next_poses=None):
+        """predictPtsInNextFrame of every slot: frame_count one for all or per slot, poses per slot (11, 7), ext (7,) for all or per
+        slot, next_poses None (constant velocity) or per slot (7,) / None (FmHandle.predict_batch)."""
+        poses = self._per_slot(poses, "poses")
+        fcs = [int(frame_count)] * len(self.slots) if np.ndim(frame_count) == 0 else self._per_slot(frame_count, "frame_count")
+        ext = np.asarray(ext, dtype=np.float64)
+        exts = [ext] * len(self.slots) if ext.ndim == 1 else self._per_slot(ext, "ext")
+        nxt = [None] * len(self.slots) if next_poses is None else self._per_slot(next_poses, "next_poses")
+        return self.fm.predict_batch(list(zip(self.slots, fcs, poses, exts, nxt)))
 
     def remove(self, ids_per_slot):
         """removeOutlier / removeFailures by id: per slot the feature ids whose tracks go (FmHandle.remove_batch)."""

@@ -46,6 +46,14 @@ leaves with those the tracker lost; back_info holds the check's counts of the la
 rejecter.reject on a published frame, as VINS-Fusion does, and keeps rejecter.undistort.  BatchFeatureTracker takes the same two.  With
 both left at their defaults the classes make exactly the calls they made without them.
 
+Prediction (VINS-Fusion's predictPtsInNextFrame / setPrediction): predict_pixels(fm, camera, ...) gives the pixels
+the tracks with a depth are expected at in the next image, set_prediction(ids, pixels) hands them to the next read_image, which passes
+guess= to the tracker (FlowHandle.track, or FrameHandle.track with frames=): the predicted pixel for a current point whose id is
+listed, the point's current pixel for every other.  A prediction is used for one frame.  prediction=dict(min_tracked=10) is
+VINS-Fusion's fallback: fewer than min_tracked points with status 0 from the guessed call, and the frame is tracked again without a
+guess.  pred_info holds n_guessed and fell_back of the last read_image.  Without a prediction the tracker is called as before, with no
+guess keyword.  BatchFeatureTracker's resident path takes no prediction.
+
 One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
 """
@@ -56,8 +64,11 @@ from .flow import FAIL_BACK_FAR, FAIL_BACK_LOST
 
 class FeatureTracker:
     def __init__(self, tracker, detector, max_cnt=150, min_dist=30, border=1, reject=None, mask=None, rejecter=None, equalizer=None, frames=None,
-                 slot=0, flow_back=None, reject_with_f=True):
+                 slot=0, flow_back=None, reject_with_f=True, prediction=None):
         self.tracker, self.detector = tracker, detector
+        self.min_tracked = None if prediction is None else int(dict(prediction).get("min_tracked", 0))
+        self.pred_ids, self.pred_pts = None, None          # set_prediction's, until the next read_image
+        self.pred_info = dict(n_guessed=0, fell_back=False)
         self.frames, self.slot = frames, int(slot)
         self.flow_back, self.reject_with_f = flow_back, bool(reject_with_f)
         self.back_info = dict(n_checked=0, n_back_lost=0, n_back_far=0)
@@ -101,6 +112,40 @@ class FeatureTracker:
     def _reduce(self, keep, *arrays):
         return [a[keep] for a in arrays]
 
+    def set_prediction(self, ids, pixels):
+        """VINS-Fusion's setPrediction: the pixels (n, 2) the tracks `ids` (n,) are expected at in the next image (predict_pixels).  The
+        next read_image starts the Lucas-Kanade search of a current point whose id is listed from its predicted pixel and of every
+        other point from its current pixel; the prediction is used for that one frame and then dropped."""
+        ids = np.asarray(ids, dtype=np.int64).reshape(-1)
+        pix = np.asarray(pixels, dtype=np.float32).reshape(-1, 2)
+        if len(ids) != len(pix):
+            raise ValueError("ids and pixels must have the same length")
+        self.pred_ids, self.pred_pts = ids.copy(), pix.copy()
+
+    def _take_guess(self, cur, ids):
+        """The guess array of the frame from the prediction (None without one), which is dropped."""
+        pred_ids, pred_pts = self.pred_ids, self.pred_pts
+        self.pred_ids = self.pred_pts = None
+        self.pred_info = dict(n_guessed=0, fell_back=False)
+        if pred_ids is None:
+            return None
+        guess = np.array(cur, dtype=np.float32).reshape(-1, 2)
+        order = np.argsort(pred_ids, kind="stable")
+        at = np.searchsorted(pred_ids[order], ids)
+        hit = (at < len(order)) & (ids >= 0)
+        hit[hit] = pred_ids[order][at[hit]] == ids[hit]
+        guess[hit] = pred_pts[order][at[hit]]
+        self.pred_info["n_guessed"] = int(np.sum(hit))
+        return guess
+
+    def _track(self, img, cur, guess):
+        """One call of the tracker; without a guess exactly the call made before there were predictions."""
+        if guess is None:
+            return self.frames.track(cur, slot=self.slot) if self.frames is not None else self.tracker.track(self.cur_img, img, cur)
+        if self.frames is not None:
+            return self.frames.track(cur, guess=guess, slot=self.slot)
+        return self.tracker.track(self.cur_img, img, cur, guess=guess)
+
     def read_image(self, img, t, publish=True):
         img = np.asarray(img)
         if img.dtype != np.uint8 or img.ndim != 2:
@@ -118,9 +163,13 @@ class FeatureTracker:
         ids, cnt = self.ids, self.track_cnt
         if self.flow_back is not None:
             self.back_info = dict(n_checked=0, n_back_lost=0, n_back_far=0)
+        guess = self._take_guess(cur, ids)
         if len(cur) > 0:
-            out = self.frames.track(cur, slot=self.slot) if self.frames is not None else self.tracker.track(self.cur_img, img, cur)
-            forw = np.asarray(out["next_pts"], dtype=np.float32).reshape(-1, 2)
+            out = self._track(img, cur, guess)
+            if guess is not None and self.min_tracked is not None and int(np.sum(np.asarray(out["status"]) == 0)) < self.min_tracked:
+                out = self._track(img, cur, None)           # VINS-Fusion's fallback: the frame again from the old pixels
+                self.pred_info["fell_back"] = True
+            forw =np.asarray(out["next_pts"], dtype=np.float32).reshape(-1, 2)
             if self.flow_back is not None:
                 st = np.asarray(out["status"])
                 self.back_info = dict(n_checked=int(np.sum((st == 0) | (st == FAIL_BACK_LOST) | (st == FAIL_BACK_FAR))),
@@ -241,3 +290,22 @@ class BatchFeatureTracker:
             rows[:, 5:7] = o["velocity"][k]
             out.append((o["ids"][k].copy(), rows))
         return out
+
+
+def predict_pixels(fm, camera, frame_count, poses, ext, next_pose=None, fm_slot=0, camera_slot=None, width=None, height=None):
+    """VINS-Fusion's predictPtsInNextFrame and setPrediction's projection composed: the tracks of slot `fm_slot` of the fm.FmHandle
+    `fm` that have a depth and end at frame_count, moved into the camera of the next pose (FmHandle.predict_batch; next_pose None: the
+    constant-velocity pose) and projected by camera slot `camera_slot` of the camera.CameraHandle `camera` (project_batch).  Returns
+    (ids (m,) int64, pixels (m, 2) float64) of the predictions whose flag is 0 and, where width and height are given, whose pixel lies
+    inside the image (0 <= u <= width - 1, 0 <= v <= height - 1): FeatureTracker.set_prediction's arguments."""
+    pred = fm.predict_batch([(fm_slot, frame_count, poses, ext, next_pose)])[0]
+    item = dict(points=pred["pts_cam"])
+    if camera_slot is not None:
+        item["slot"] = int(camera_slot)
+    proj = camera.project_batch([item])[0]
+    pix = proj["pixels"]
+    ok = proj["flags"] == 0
+    if width is not None and height is not None:
+        with np.errstate(invalid="ignore"):
+            ok &= (pix[:, 0] >= 0) & (pix[:, 0] <= width - 1) & (pix[:, 1] >= 0) & (pix[:, 1] <= height - 1)
+    return pred["ids"][ok].copy(), pix[ok].copy()
