@@ -40,7 +40,9 @@
  *
  * Resident points (VIO_FRAME_HAS_READ): include/vio_frame_read.h, which this header includes, declares vio_frame_read_batch and what
  * goes with it: all of readImage for one new image per slot, the points kept on the device.  include/vio_frame_camera.h, included behind
- * it (VIO_FRAME_HAS_SLOT_CAMERAS), gives every slot a camera of its own, of any model of include/vio_camera.h.
+ * it (VIO_FRAME_HAS_SLOT_CAMERAS), gives every slot a camera of its own, of any model of include/vio_camera.h.  include/vio_frame_back.h
+ * (VIO_FRAME_HAS_BACK) adds the tracker's forward-backward check, include/vio_frame_predict.h (VIO_FRAME_HAS_PREDICT) predicted pixels
+ * for the tracking step of a read.
  */
 #ifndef VIO_FRAME_H
 #define VIO_FRAME_H
@@ -65,6 +67,7 @@ extern "C" {
 #define VIO_FRAME_NEXT 1
 #define VIO_FRAME_HAS_READ 1                        /* include/vio_frame_read.h is there */
 #define VIO_FRAME_HAS_BACK 1                        /* include/vio_frame_back.h is there: the forward-backward check */
+#define VIO_FRAME_HAS_PREDICT 1                     /* include/vio_frame_predict.h is there: predicted pixels for a read's tracking step */
 
 typedef struct vio_frame vio_frame;
 
@@ -137,5 +140,6 @@ vio_status vio_frame_timing(vio_frame *h, double *out8);
 #include "vio_frame_read.h"
 #include "vio_frame_camera.h"
 #include "vio_frame_back.h"
+#include "vio_frame_predict.h"
 
 #endif

@@ -12,6 +12,7 @@ same images and times from the same empty state, and the outputs of the last fra
 
     python tools/bench_front_batch.py [--batches 1,16,64] [--reps 20] [--warmup 3] [--repeats 3] [--slot-cameras none|pinhole|mixed]
                                       [--flow-back [--back-levels 2]] [--no-reject] [--legs read,loop] [--out profiles/NAME.json]
+                                      [--predict [--min-tracked K]]
 
 --slot-cameras (include/vio_frame_camera.h): none: the handle's camera alone, the PINHOLE kernels; pinhole: every
 slot has that same camera as its own, so the same arithmetic runs through the general kernels and the camera table; mixed: slot s has
@@ -20,6 +21,12 @@ camera.CameraHandle.bind(s) with the same cameras.
 
 --flow-back (include/vio_frame_back.h): the forward-backward check of the tracker over --back-levels levels, in both
 legs; --no-reject: no rejectWithF in a published frame, in both legs.  --legs read: leg read alone (no comparison).
+
+--predict (include/vio_frame_predict.h): from the second frame on every stream gets a prediction for each of its
+points, the point's own pixel moved by half a pixel, inside the timed frame: leg read through BatchFeatureTracker.set_predictions (one
+call), leg loop through FeatureTracker.set_prediction.  --min-tracked K arms the fallback in both legs: 1 never falls back here (the
+second pass runs over rows that leave at once), 1024 makes every stream fall back.  Rows gain `fell_back`, the streams that did in the
+last frame.
 
 Stream k sees the fixture pair (tests/golden/flow_image_1.npz, flow_image_2.npz) alternating, shifted down by k rows (wrapped).
 """
@@ -62,6 +69,8 @@ def main():
     ap.add_argument("--no-reject", action="store_true")
     ap.add_argument("--legs", default="read,loop")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--predict", action="store_true")
+    ap.add_argument("--min-tracked", type=int, default=0)
     args = ap.parse_args()
     vio = g.load_package()
     cfg = dict(equalize=True, clahe=dict(clip_limit=3.0, tiles=(8, 8)), flow={}, detect=dict(min_distance=MIN_DIST))
@@ -71,6 +80,8 @@ def main():
     frames = args.warmup + args.reps
     legs = tuple(args.legs.split(","))
     extra = dict(flow_back=dict(levels=args.back_levels) if args.flow_back else None, reject_with_f=not args.no_reject)
+    if args.predict:
+        extra["prediction"] = dict(min_tracked=args.min_tracked)
     rows = []
     for rep in range(args.repeats):
         for B in batches:
@@ -99,12 +110,17 @@ def main():
                 for t in range(frames):
                     imgs = raw[t & 1][:B]
                     c0 = fr.counters() if leg == "read" else None
+                    guesses = [(o["ids"], o["pts"] + np.float32(0.5)) for o in outs] if args.predict and t > 0 else None
                     t0 = time.perf_counter()
                     if leg == "read":
+                        if guesses is not None:
+                            bt.set_predictions(dict(enumerate(guesses)))
                         outs = bt.read_images(imgs, DT * t)
                     else:
                         outs = []
                         for s in range(B):
+                            if guesses is not None:
+                                fts[s].set_prediction(*guesses[s])
                             o = fts[s].read_image(imgs[s], DT * t)
                             o["ids"] = fts[s].update_ids()
                             outs.append(o)
@@ -120,6 +136,8 @@ def main():
                 row = dict(repeat=rep, batch=B, leg=leg, frame_ms=float(np.median(wall)), frame_ms_min=float(np.min(wall)),
                            frame_ms_max=float(np.max(wall)), us_per_stream=1e3 * float(np.median(wall)) / B,
                            points_per_stream=float(np.mean([len(o["pts"]) for o in outs])))
+                if args.predict:
+                    row["fell_back"] = int(sum(p["fell_back"] for p in (bt.pred_info if leg == "read" else [ft.pred_info for ft in fts])))
                 if leg == "read":
                     row["stages_ms"] = {k: float(np.median([p[k] for p in parts])) for k in STAGES}
                     row["bytes_per_frame"] = moved
@@ -134,7 +152,7 @@ def main():
             for h in (fr, lo, rh) + ((ch,) if args.slot_cameras == "mixed" else ()):
                 h.close()
     res = dict(bench="front_batch", slot_cameras=args.slot_cameras, flow_back=bool(args.flow_back), back_levels=args.back_levels if args.flow_back else None,
-               reject_with_f=not args.no_reject, image="%dx%d" % (pair[0].shape[1], pair[0].shape[0]), max_cnt=MAX_CNT, min_dist=MIN_DIST, reps=args.reps,
+               reject_with_f=not args.no_reject, predict=bool(args.predict), min_tracked=args.min_tracked if args.predict else None, image="%dx%d" % (pair[0].shape[1], pair[0].shape[0]), max_cnt=MAX_CNT, min_dist=MIN_DIST, reps=args.reps,
                warmup=args.warmup, repeats=args.repeats, rows=rows)
     print(json.dumps(res))
     if args.out:

@@ -3,7 +3,8 @@
 //
 // The numeric kernels are those of libvio_clahe_hip, libvio_flow_hip, libvio_detect_hip and libvio_reject_hip, compiled from the same
 // four files (vio_clahe_body.inc, vio_flow_body.inc, vio_detect_body.inc, vio_reject_body.inc), each inside a namespace since their
-// constants share names.  The five kernels that join them in vio_frame_read_batch are in vio_front_body.inc.
+// constants share names.  The five kernels that join them in vio_frame_read_batch are in vio_front_body.inc, the
+// three that bring a slot's prediction into its tracking step in vio_front_guess_body.inc (include/vio_frame_predict.h, section 39).
 // vio_frame_set_slot_camera (include/vio_frame_camera.h) gives a slot a camera of its own, of any of the four models:
 // a read that lists such a slot runs a second instantiation of vio_reject_body.inc (namespace kq, against vio_camera_math.h through
 // vio_camera_host.h, as libvio_camera_hip compiles it) and of vio_front_body.inc (namespace fq), every descriptor carrying its slot.
@@ -32,6 +33,7 @@
 #include "vio_detect_math.h"
 #include "vio_flow_math.h"
 #include "vio_front_math.h"
+#include "vio_front_guess_math.h"
 #include "vio_reject_math.h"
 #include "vio_sfm_math.h"
 
@@ -53,6 +55,7 @@ namespace kr {
 }
 #define FRONT_REJ kr
 #include "vio_front_body.inc"
+#include "vio_front_guess_body.inc"
 #undef FRONT_REJ
 
 // the same two texts against the four camera models and a camera per slot: the lift's customisation points change hands
@@ -75,6 +78,7 @@ namespace fq {
 #define FRONT_REJ kq
 #define FRONT_CAMERAS
 #include "vio_front_body.inc"
+#include "vio_front_guess_body.inc"
 #undef FRONT_CAMERAS
 #undef FRONT_REJ
 }
@@ -82,6 +86,7 @@ namespace fq {
 
 static_assert(FRAME_CAM_SLOTS == VIO_FRAME_MAX_SLOTS && FRAME_CAM_SLOTS == VIO_CAMERA_MAX_SLOTS, "a camera per slot");
 static_assert(sizeof(fq::FrontItem) == sizeof(FrontItem), "one item table for both sets of joining kernels");
+static_assert(sizeof(GuessItem) == 16 && sizeof(GuessRes) == 16 && sizeof(fq::GuessArgs) == sizeof(GuessArgs), "the prediction's tables are the same in both");
 static_assert(FRAME_MAX_SLOTS == VIO_FRAME_MAX_SLOTS && FRAME_MAX_LEVELS == VIO_FLOW_MAX_LEVELS && FRAME_MAX_DIM == VIO_FRAME_MAX_DIM,
               "vio_frame_slots.h restates the header's limits");
 static_assert(FRAME_MAX_TRACK_POINTS == VIO_FRAME_MAX_TRACK_POINTS && FRONT_CAP == VIO_FRAME_MAX_TRACK_POINTS, "one capacity");
@@ -89,6 +94,15 @@ static_assert(VIO_FRAME_MAX_TRACK_POINTS <= VIO_DETECT_MAX_POINTS && VIO_FRAME_M
               VIO_FRAME_MAX_TRACK_POINTS <= VIO_FLOW_MAX_POINTS, "a slot's table fits every library's limits");
 static_assert(VIO_FRAME_MAX_DIM == VIO_FLOW_MAX_DIM && VIO_FRAME_MAX_DIM == VIO_DETECT_MAX_DIM && VIO_FRAME_MAX_DIM == VIO_CLAHE_MAX_DIM,
               "one size limit");
+
+// a slot's pending prediction (include/vio_frame_predict.h), as it goes up: front_guess_normalise's rows
+struct FramePrediction {
+    bool pending = false;
+    int32_t n_listed = 0;
+    std::vector<long long> ids;
+    std::vector<float> px;
+    void drop() { pending = false; n_listed = 0; ids.clear(); px.clear(); }
+};
 
 struct vio_frame {
     int device = 0;
@@ -140,6 +154,11 @@ struct vio_frame {
     vio_flow_back_config bcfg = kf::FLOW_BACK_DEFAULTS;
     int32_t reject_f = 1;
     int32_t back_info[VIO_FRAME_MAX_SLOTS][3] = {};
+    // include/vio_frame_predict.h: the slots' pending predictions, the fallback's threshold, and per slot what its last read made of
+    // its prediction (listed, guessed, status 0 after the guessed pass, fell back)
+    std::vector<FramePrediction> pred = std::vector<FramePrediction>((size_t)VIO_FRAME_MAX_SLOTS);
+    int32_t min_tracked = 0;
+    int32_t pred_info[VIO_FRAME_MAX_SLOTS][4] = {};
 };
 
 namespace {
@@ -331,6 +350,8 @@ template <> struct ReadPath<false> {
     using Item = ::FrontItem; using Res = ::FrontRes; using Args = ::FrontArgs;
     static constexpr auto begin = ::k_front_begin, filter = ::k_front_filter, after_reject = ::k_front_after_reject, merge = ::k_front_merge,
                           finish = ::k_front_finish;
+    using GuessItem = ::GuessItem; using GuessRes = ::GuessRes; using GuessArgs = ::GuessArgs;
+    static constexpr auto guess = ::k_front_guess, fallback = ::k_front_fallback, take = ::k_front_take;
     static constexpr auto ransac = kr::k_reject_ransac;
 };
 template <> struct ReadPath<true> {
@@ -339,6 +360,8 @@ template <> struct ReadPath<true> {
     using Item = fq::FrontItem; using Res = fq::FrontRes; using Args = fq::FrontArgs;
     static constexpr auto begin = fq::k_front_begin, filter = fq::k_front_filter, after_reject = fq::k_front_after_reject, merge = fq::k_front_merge,
                           finish = fq::k_front_finish;
+    using GuessItem = fq::GuessItem; using GuessRes = fq::GuessRes; using GuessArgs = fq::GuessArgs;
+    static constexpr auto guess = fq::k_front_guess, fallback = fq::k_front_fallback, take = fq::k_front_take;
     static constexpr auto ransac = kq::k_reject_ransac;
 };
 
@@ -450,6 +473,8 @@ vio_status vio_frame_set_config(vio_frame *h, int32_t equalize, const vio_clahe_
         return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_config: %d flow levels are fewer than the %d of the forward-backward check", f.levels, h->bcfg.levels);
     d.reserved = 0;
     h->equalize = equalize; h->ccfg = c; h->fcfg = f; h->dcfg = d;
+    if (f.levels != h->tab.levels)                          // (the slots' points go with their frames, and the predictions with the points)
+        for (FramePrediction &p : h->pred) p.drop();
     h->tab.set_levels(f.levels);
     return VIO_OK;
 }
@@ -475,6 +500,8 @@ vio_status vio_frame_reset(vio_frame *h, int32_t slot) {
     h->tab.reset(slot);
     h->cams.lift_info_set(slot, 0, 0);
     for (int32_t &v : h->back_info[slot]) v = 0;
+    h->pred[(size_t)slot].drop();
+    for (int32_t &v : h->pred_info[slot]) v = 0;
     return VIO_OK;
 }
 
@@ -491,8 +518,10 @@ vio_status vio_frame_push_batch(vio_frame *h, int32_t count, const vio_frame_pus
     int32_t bad = -1;
     const FrameCheck ck = h->tab.check_push(count, sl.data(), ww.data(), hh.data(), &bad);
     if (ck != FRAME_OK) return fail_check(h, "vio_frame_push_batch", ck, bad, sl[(size_t)bad]);
-    const vio_status st = check_images(h, "vio_frame_push_batch", count, items);
-    return st != VIO_OK ? st : push_run(h, count, items, t0);
+    vio_status st = check_images(h, "vio_frame_push_batch", count, items);
+    if (st != VIO_OK || (st = push_run(h, count, items, t0)) != VIO_OK) return st;
+    for (int i = 0; i < count; ++i) h->pred[(size_t)items[i].slot].drop();     // (as the roll drops the slot's points)
+    return VIO_OK;
 }
 
 vio_status vio_frame_set_mask(vio_frame *h, int32_t slot, const uint8_t *mask, int32_t width, int32_t height, int32_t stride) {
@@ -575,6 +604,65 @@ vio_status vio_frame_read_back_info(const vio_frame *h, int32_t slot, int32_t *n
     if (n_checked) *n_checked = h->back_info[slot][0];
     if (n_back_lost) *n_back_lost = h->back_info[slot][1];
     if (n_back_far) *n_back_far = h->back_info[slot][2];
+    return VIO_OK;
+}
+
+vio_status vio_frame_set_prediction_batch(vio_frame *h, int32_t count, const vio_frame_prediction_item *items) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (count < 0 || count > MAX_ITEMS || (count > 0 && !items))
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_prediction_batch: count outside [0, %d] or a NULL array", MAX_ITEMS);
+    // every argument of every item first: nothing is stored on an error
+    std::vector<uint8_t> seen((size_t)VIO_FRAME_MAX_SLOTS, 0);
+    for (int i = 0; i < count; ++i) {
+        const vio_frame_prediction_item &it = items[i];
+        if (!FrameTable::slot_ok(it.slot)) return fail_check(h, "vio_frame_set_prediction_batch", FRAME_BAD_SLOT, i, it.slot);
+        if (seen[(size_t)it.slot]) return fail_check(h, "vio_frame_set_prediction_batch", FRAME_TWICE, i, it.slot);
+        seen[(size_t)it.slot] = 1;
+        if (it.n < 0 || it.n > VIO_FRAME_MAX_TRACK_POINTS)
+            return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_prediction_batch: item %d: n must be in [0, %d]", i, VIO_FRAME_MAX_TRACK_POINTS);
+        if (it.n > 0 && (!it.ids || !it.pixels)) return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_prediction_batch: item %d: ids and pixels are required", i);
+        for (int k = 0; k < 2 * it.n; ++k)
+            if (!std::isfinite(it.pixels[k]))
+                return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_prediction_batch: item %d: pixel %d is not finite", i, k / 2);
+    }
+    for (int i = 0; i < count; ++i) {
+        const vio_frame_prediction_item &it = items[i];
+        FramePrediction &p = h->pred[(size_t)it.slot];
+        std::vector<long long> ids((size_t)it.n);
+        for (int k = 0; k < it.n; ++k) ids[(size_t)k] = (long long)it.ids[k];
+        p.ids.resize((size_t)it.n); p.px.resize(2 * (size_t)it.n);
+        const int32_t m = front_guess_normalise(ids.data(), it.pixels, it.n, p.ids.data(), p.px.data());
+        p.ids.resize((size_t)m); p.px.resize(2 * (size_t)m);
+        p.pending = true; p.n_listed = it.n;
+    }
+    return VIO_OK;
+}
+
+vio_status vio_frame_clear_prediction(vio_frame *h, int32_t slot) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (!FrameTable::slot_ok(slot)) return fail_check(h, "vio_frame_clear_prediction", FRAME_BAD_SLOT, 0, slot);
+    h->pred[(size_t)slot].drop();
+    return VIO_OK;
+}
+
+vio_status vio_frame_set_prediction_fallback(vio_frame *h, int32_t min_tracked) {
+    if (!h) return VIO_ERR_BAD_ARG;
+    h->err[0] = 0;
+    if (min_tracked < 0 || min_tracked > VIO_FRAME_MAX_TRACK_POINTS)
+        return fail(h->err, VIO_ERR_BAD_ARG, "vio_frame_set_prediction_fallback: min_tracked in [0, %d]", VIO_FRAME_MAX_TRACK_POINTS);
+    h->min_tracked = min_tracked;
+    return VIO_OK;
+}
+
+vio_status vio_frame_read_predict_info(const vio_frame *h, int32_t slot, int32_t *n_listed, int32_t *n_guessed, int32_t *n_ok_guessed,
+                                       int32_t *fell_back) {
+    if (!h || !FrameTable::slot_ok(slot)) return VIO_ERR_BAD_ARG;
+    if (n_listed) *n_listed = h->pred_info[slot][0];
+    if (n_guessed) *n_guessed = h->pred_info[slot][1];
+    if (n_ok_guessed) *n_ok_guessed = h->pred_info[slot][2];
+    if (fell_back) *fell_back = h->pred_info[slot][3];
     return VIO_OK;
 }
 
@@ -816,7 +904,20 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
     // the tables that travel: their size depends on the count of items alone
     const size_t o_flow = align256(sizeof(FrontItem) * B), o_det = o_flow + align256(sizeof(kf::FlowItemD) * B);
     const size_t o_pair = o_det + align256(sizeof(kd::DetItemD) * B), o_lift = o_pair + align256(sizeof(RejPair) * B);
-    const size_t b_tab = o_lift + align256(sizeof(LiftItem) * B);
+    // ... and with them the predictions of the listed slots that have points to track (include/vio_frame_predict.h): an item table,
+    // the ids, the pixels.  Without one the tables, the work space and the results are laid out as they always were.
+    using GuessItem = typename P::GuessItem;
+    using GuessRes = typename P::GuessRes;
+    std::vector<uint8_t> guessed(B, 0);
+    size_t g_rows = 0;
+    for (size_t i = 0; i < B; ++i) {
+        guessed[i] = h->pred[(size_t)sl[i]].pending && was[i].n_pts > 0;
+        if (guessed[i]) g_rows += h->pred[(size_t)sl[i]].ids.size();
+    }
+    const bool guess = std::find(guessed.begin(), guessed.end(), 1) != guessed.end(), again = guess && h->min_tracked > 0;
+    const size_t o_gitem = o_lift + align256(sizeof(LiftItem) * B), o_gids = o_gitem + (guess ? align256(sizeof(GuessItem) * B) : 0);
+    const size_t o_gpx = o_gids + (guess ? align256(sizeof(long long) * g_rows) : 0);
+    const size_t b_tab = o_gpx + (guess ? align256(sizeof(float) * 2 * g_rows) : 0);
     // the device work space, every per-point array at FRONT_CAP rows per item
     size_t b_work = 0;
     const auto carve = [&](size_t bytes) { const size_t at = b_work; b_work += align256(bytes); return at; };
@@ -832,9 +933,11 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
     const size_t w_lstage = carve(sizeof(float) * 4 * rowsN), w_lids = carve(sizeof(long long) * 2 * rowsN);
     const size_t w_un = carve(sizeof(float) * 2 * rowsN), w_vel = carve(sizeof(float) * 2 * rowsN), w_cntm = carve(sizeof(int32_t) * rowsN);
     const size_t w_lflag = CAMS ? carve(rowsN) : 0;        // k_reject_lift's flag byte per point
+    const size_t w_fpts2 = again ? carve(sizeof(kf::FlowPt) * rowsN) : 0, w_fout2 = again ? carve(sizeof(kf::FlowOut) * rowsN) : 0;    // the fallback's pass
     const bool check = h->bcfg.enabled != 0;
     const size_t row_bytes = (36 * (size_t)rows_cap + 7) & ~(size_t)7;
-    const size_t b_res = align256(sizeof(FrontRes) * B), b_out = b_res + row_bytes * B;
+    const size_t b_res = align256(sizeof(FrontRes) * B), o_gres = align256(b_res + row_bytes * B);
+    const size_t b_out = guess ? o_gres + sizeof(GuessRes) * B : b_res + row_bytes * B;       // (GuessRes per item behind the rows)
     for (size_t i = 0; i < B; ++i) {
         n_r += (int64_t)ww[i] * hh[i];
         n_cand += (int64_t)std::max(ww[i] - 2, 0) * std::max(hh[i] - 2, 0);
@@ -883,6 +986,24 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
         if constexpr (CAMS) { r.slot = sl[i]; u.slot = sl[i]; }
     }
     total = flow_off;
+    // the listed slots' predictions are consumed here, whatever becomes of them: the slots have rolled
+    std::vector<int32_t> n_listed(B, 0);
+    size_t g_at = 0;
+    for (size_t i = 0; i < B; ++i) {
+        FramePrediction &p = h->pred[(size_t)sl[i]];
+        if (p.pending) n_listed[i] = p.n_listed;
+        if (guessed[i]) {
+            GuessItem &g = ((GuessItem *)(h->rtab.h + o_gitem))[i];
+            const size_t m = p.ids.size();
+            g.off = (int32_t)g_at; g.m = (int32_t)m; g.guessed = 1;
+            if (m > 0) {
+                std::memcpy(h->rtab.h + o_gids + sizeof(long long) * g_at, p.ids.data(), sizeof(long long) * m);
+                std::memcpy(h->rtab.h + o_gpx + sizeof(float) * 2 * g_at, p.px.data(), sizeof(float) * 2 * m);
+            }
+            g_at += m;
+        }
+        p.drop();
+    }
     char *W = h->rwork.d;
     FrontArgs a;
     std::memset(&a, 0, sizeof(a));
@@ -918,7 +1039,33 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
     const dim3 per_item((unsigned)count), fnt(FNT);
     const auto front = [&](auto kernel) { hipLaunchKernelGGL(kernel, per_item, fnt, 0, q, a); };
     // 2 - 4. the slot's points into the new frame, and those that stay
-    if (total > 0) {
+    if (guess) {
+        // a listed slot has a prediction (include/vio_frame_predict.h): the guesses into k_front_begin's rows, the tracker; the count
+        // of each item's status-0 rows and the decision; with a fallback armed the tracker again over the second list (its rows are
+        // NaN for every item that keeps its guessed pass), and the rows of the items that fell back over the first pass's
+        typename P::GuessArgs g;
+        std::memset(&g, 0, sizeof(g));
+        g.items = a.items; g.gitems = (const GuessItem *)(h->rtab.d + o_gitem);
+        g.gids = (const long long *)(h->rtab.d + o_gids); g.gpx = (const float *)(h->rtab.d + o_gpx);
+        g.fpts = a.fpts; g.fpts2 = again ? (kf::FlowPt *)(W + w_fpts2) : nullptr;
+        g.fout = (kf::FlowOut *)(W + w_fout); g.fout2 = again ? (const kf::FlowOut *)(W + w_fout2) : nullptr;
+        g.gres = (GuessRes *)(h->rout.d + o_gres);
+        g.g_rows = (int32_t)g_rows; g.min_tracked = h->min_tracked;
+        const kf::FlowItemD *fid = (const kf::FlowItemD *)(h->rtab.d + o_flow);
+        const auto track = [&](const kf::FlowPt *pts, kf::FlowOut *out) {
+            if (check) kf::flow_launch_track_back(q, kf::flow_back_args(fid, pts, out, nullptr, (size_t)total, L, h->fcfg, h->bcfg), h->fcfg.inverse != 0);
+            else kf::flow_launch_track(q, kf::flow_args(fid, pts, out, (size_t)total, L, h->fcfg), h->fcfg.inverse != 0);
+        };
+        const auto joined = [&](auto kernel) { hipLaunchKernelGGL(kernel, per_item, fnt, 0, q, g); };
+        front(P::begin);
+        joined(P::guess);
+        track(g.fpts, g.fout);
+        joined(P::fallback);
+        if (again) {
+            track(g.fpts2, (kf::FlowOut *)(W + w_fout2));
+            joined(P::take);
+        }
+    } else if (total > 0) {
         front(P::begin);
         const kf::FlowItemD *fid = (const kf::FlowItemD *)(h->rtab.d + o_flow);
         if (check)
@@ -1006,6 +1153,12 @@ template <bool CAMS> vio_status read_run(vio_frame *h, int32_t count, const vio_
         h->cams.lift_info_set(it.slot, n_clamped, n_bad);
         h->back_info[it.slot][0] = front_clamp(r.n_checked, 0, FRONT_CAP); h->back_info[it.slot][1] = front_clamp(r.n_back_lost, 0, FRONT_CAP);
         h->back_info[it.slot][2] = front_clamp(r.n_back_far, 0, FRONT_CAP);
+        int32_t *pinfo = h->pred_info[it.slot];
+        pinfo[0] = n_listed[i]; pinfo[1] = pinfo[2] = pinfo[3] = 0;
+        if (guess) {
+            const GuessRes &gr = ((const GuessRes *)(h->rout.h + o_gres))[i];
+            pinfo[1] = front_clamp(gr.n_guessed, 0, FRONT_CAP); pinfo[2] = front_clamp(gr.n_ok_guessed, 0, FRONT_CAP); pinfo[3] = gr.fell_back != 0;
+        }
         o.status = bad_lift ? VIO_ERR_NOT_FINITE : VIO_OK; o.n = (int32_t)n; o.n_new = front_clamp(r.n_new, 0, (int32_t)n);
         o.n_tracked_in = r.n_tracked_in; o.n_after_track = r.n_after_track; o.n_after_reject = r.n_after_reject;
         o.reject_status = r.reject_status; o.reject_hyp = r.reject_hyp; o.n_candidates = r.n_candidates; o.reserved = 0;

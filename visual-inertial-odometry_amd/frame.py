@@ -23,6 +23,9 @@ the image steps of FeatureTracker::readImage (feature_tracker.cpp:87-149) for ma
     fr.set_flow_back(levels=2, max_dist=0.5); fr.track(prev_pts, back=True)                   # the forward-backward check (include/vio_frame_back.h)
     fr.set_reject_with_f(False); fr.read_back_info(0)                                          # no rejectWithF in a published read; the check's counts
 
+    fr.set_prediction_batch([(slot, ids, pixels), ...]); fr.set_prediction_fallback(10)         # predicted pixels for the next read_batch's
+    fr.clear_prediction(slot); fr.read_predict_info(slot)                                      # tracking step (include/vio_frame_predict.h)
+
 A handle is what frontend.FeatureTracker takes as `frames`, and what frontend.BatchFeatureTracker drives through read_batch.
 """
 import ctypes as C
@@ -67,6 +70,10 @@ class VioFrameReadResult(C.Structure):
                                          "reject_hyp", "n_candidates", "reserved")]
 
 
+class VioFramePredictionItem(C.Structure):
+    _fields_ = [("slot", C.c_int32), ("n", C.c_int32), ("ids", C.c_void_p), ("pixels", C.c_void_p)]
+
+
 class FrameLib:
     """libvio_frame_hip.so: vio_frame_*."""
 
@@ -75,6 +82,7 @@ class FrameLib:
     READ_SYMBOLS = ["set_camera", "set_tracker", "read_batch", "points_set", "points_get", "read_timing"]      # include/vio_frame_read.h
     CAMERA_SYMBOLS = ["set_slot_camera", "get_slot_camera", "set_reject_config", "read_lift_info"]            # include/vio_frame_camera.h
     BACK_SYMBOLS = ["set_flow_back", "track_back_batch", "set_reject_with_f", "read_back_info"]                # include/vio_frame_back.h
+    PREDICT_SYMBOLS = ["set_prediction_batch", "clear_prediction", "set_prediction_fallback", "read_predict_info"]   # include/vio_frame_predict.h
 
     def __init__(self, path):
         self.path = path
@@ -106,6 +114,11 @@ class FrameLib:
         self.fn["track_back_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
         self.fn["set_reject_with_f"].argtypes = [C.c_void_p, C.c_int32]
         self.fn["read_back_info"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p]
+        self.fn.update(open_lib(path, "vio_frame_", self.PREDICT_SYMBOLS)[1])
+        self.fn["set_prediction_batch"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p]
+        self.fn["clear_prediction"].argtypes = [C.c_void_p, C.c_int32]
+        self.fn["set_prediction_fallback"].argtypes = [C.c_void_p, C.c_int32]
+        self.fn["read_predict_info"].argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
 
     def create(self, device=0, stream=None):
         """A vio_frame handle on `device`; stream: a hipStream_t (int) to enqueue on, or None for one of the library's own."""
@@ -314,6 +327,38 @@ class FrameHandle(CompanionHandle):
         c, l, f = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         self._ck(self.lib.fn["read_back_info"](self.h, C.c_int32(int(slot)), C.addressof(c), C.addressof(l), C.addressof(f)), "read_back_info")
         return dict(n_checked=int(c.value), n_back_lost=int(l.value), n_back_far=int(f.value))
+
+    def set_prediction_batch(self, items):
+        """items: (slot, ids (n,), pixels (n, 2)) each: the pixels the tracks `ids` are expected at in the slot's next image
+        (frontend.predict_pixels_batch).  The next read_batch that lists the slot starts those points' search there and every other
+        point's at its own pixel; the prediction is used by that one read.  It replaces the slot's pending prediction; nothing is
+        stored if an item is refused (a pixel that is not finite, more than MAX_TRACK_POINTS rows, a slot listed twice)."""
+        B = len(items)
+        arr = (VioFramePredictionItem * max(B, 1))()
+        keep = []
+        for i, (slot, ids, pixels) in enumerate(items):
+            d = np.ascontiguousarray(ids, dtype=np.int64).reshape(-1)
+            p = np.ascontiguousarray(pixels, dtype=np.float32).reshape(-1, 2)
+            if len(d) != len(p):
+                raise ValueError("item %d: ids and pixels must have the same length" % i)
+            keep += [d, p]
+            arr[i] = VioFramePredictionItem(int(slot), len(d), d.ctypes.data, p.ctypes.data)
+        self._ck(self.lib.fn["set_prediction_batch"](self.h, C.c_int32(B), C.addressof(arr)), "set_prediction_batch")
+
+    def clear_prediction(self, slot=0):
+        """Drops the slot's pending prediction, if it has one."""
+        self._ck(self.lib.fn["clear_prediction"](self.h, C.c_int32(int(slot))), "clear_prediction")
+
+    def set_prediction_fallback(self, min_tracked=0):
+        """VINS-Fusion's fallback: a slot whose guessed pass leaves fewer than min_tracked points with status 0 is tracked again without
+        a guess, on the device.  0, the default: never."""
+        self._ck(self.lib.fn["set_prediction_fallback"](self.h, C.c_int32(int(min_tracked))), "set_prediction_fallback")
+
+    def read_predict_info(self, slot=0):
+        """dict(n_listed, n_guessed, n_ok_guessed, fell_back) of the prediction in the slot's last read_batch (zeros without one)."""
+        v = [C.c_int32(0) for _ in range(4)]
+        self._ck(self.lib.fn["read_predict_info"](self.h, C.c_int32(int(slot)), *[C.addressof(x) for x in v]), "read_predict_info")
+        return dict(n_listed=int(v[0].value), n_guessed=int(v[1].value), n_ok_guessed=int(v[2].value), fell_back=bool(v[3].value))
 
     def set_tracker(self, max_cnt=DEFAULT_MAX_CNT, border=DEFAULT_TRACK_BORDER):
         """The reference's MAX_CNT (at most MAX_TRACK_POINTS) and inBorder's margin."""

@@ -52,7 +52,9 @@ guess= to the tracker (FlowHandle.track, or FrameHandle.track with frames=): the
 listed, the point's current pixel for every other.  A prediction is used for one frame.  prediction=dict(min_tracked=10) is
 VINS-Fusion's fallback: fewer than min_tracked points with status 0 from the guessed call, and the frame is tracked again without a
 guess.  pred_info holds n_guessed and fell_back of the last read_image.  Without a prediction the tracker is called as before, with no
-guess keyword.  BatchFeatureTracker's resident path takes no prediction.
+guess keyword.  BatchFeatureTracker takes the same: set_predictions({slot: (ids, pixels)}) hands them to the next read_images
+(frame.FrameHandle.set_prediction_batch, include/vio_frame_predict.h), the ids are joined and the fallback is decided on the device, and
+every array still equals the per-stream loop's.  predict_pixels_batch is predict_pixels for many slots in two library calls.
 
 One thing differs on purpose: prev_pts stays aligned with the points through setMask's
 reordering (the reference reorders forw_pts, ids and track_cnt and leaves prev_pts as it was).
@@ -245,9 +247,12 @@ class BatchFeatureTracker:
     masks: None, or {slot: mask}.  cameras: None, or {slot: set_slot_camera's keywords}: the slot's own camera, of any model; a slot
     without one lifts through the handle's (frames.set_camera).  The handle's detector gets min_distance = min_dist (its other settings return to their defaults), as
     in FeatureTracker.  flow_back, reject_with_f: FeatureTracker's (frame.FrameHandle.set_flow_back, set_reject_with_f); frames.read_back_info(slot)
-    has the check's counts."""
+    has the check's counts.  prediction: None, or dict(min_tracked=k): FeatureTracker's fallback, armed on the handle
+    (frame.FrameHandle.set_prediction_fallback); None leaves the handle as it is.  set_predictions hands predicted pixels to the next
+    read_images, and pred_info holds, per slot, n_guessed and fell_back of the last one."""
 
-    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None, cameras=None, flow_back=None, reject_with_f=True):
+    def __init__(self, frames, slots, max_cnt=150, min_dist=30, border=1, masks=None, cameras=None, flow_back=None, reject_with_f=True,
+                 prediction=None):
         self.frames, self.slots = frames, [int(s) for s in slots]
         if len(set(self.slots)) != len(self.slots):
             raise ValueError("a slot is listed twice")
@@ -262,7 +267,22 @@ class BatchFeatureTracker:
             frames.set_flow_back(**dict(flow_back))
         if not reject_with_f:
             frames.set_reject_with_f(False)
+        if prediction is not None:
+            frames.set_prediction_fallback(int(dict(prediction).get("min_tracked", 0)))
+        self.predicted = set()                                  # the slots set_predictions named since the last read_images
+        self.pred_info = [dict(n_guessed=0, fell_back=False) for _ in self.slots]
         self.last = [None] * len(self.slots)
+
+    def set_predictions(self, predictions):
+        """{slot: (ids (n,), pixels (n, 2))}: FeatureTracker.set_prediction for each named slot, in one call.  The next read_images uses
+        them and drops them; a slot named again before it takes the later prediction."""
+        items = [(int(s), ids, pix) for s, (ids, pix) in dict(predictions).items()]
+        unknown = [s for s, _, _ in items if s not in self.slots]
+        if unknown:
+            raise ValueError("slot %d is not one of this tracker's" % unknown[0])
+        if items:
+            self.frames.set_prediction_batch(items)
+            self.predicted.update(s for s, _, _ in items)
 
     def read_images(self, imgs, t, publish=True):
         """One new image per slot, in the order of `slots`; t: one time stamp for all, or one per image.  Returns read_batch's dicts."""
@@ -273,6 +293,12 @@ class BatchFeatureTracker:
             if a.dtype != np.uint8 or a.ndim != 2:
                 raise ValueError("an image must be a 2-d uint8 array")
         self.last = self.frames.read_batch(imgs, t, slots=self.slots, publish=publish)
+        predicted, self.predicted = self.predicted, set()       # (the read consumed them)
+        self.pred_info = [dict(n_guessed=0, fell_back=False) for _ in self.slots]
+        for k, s in enumerate(self.slots):
+            if s in predicted:
+                info = self.frames.read_predict_info(s)
+                self.pred_info[k] = dict(n_guessed=int(info["n_guessed"]), fell_back=bool(info["fell_back"]))
         return self.last
 
     def feature_frames(self):
@@ -292,20 +318,37 @@ class BatchFeatureTracker:
         return out
 
 
+def predict_pixels_batch(fm, camera, items, width=None, height=None):
+    """predict_pixels for many slots in one fm.predict_batch and one camera.project_batch, two library calls whatever len(items) is.
+    items: dicts of frame_count, poses, ext and, optionally, next_pose (None), fm_slot (0), camera_slot (None: the camera handle's
+    own), width and height (default: this call's).  Returns one (ids, pixels) per item, each what predict_pixels gives for it:
+    BatchFeatureTracker.set_predictions takes {slot: pair}."""
+    items = [dict(it) for it in items]
+    preds = fm.predict_batch([(it.get("fm_slot", 0), it["frame_count"], it["poses"], it["ext"], it.get("next_pose")) for it in items])
+    pitems = []
+    for it, pred in zip(items, preds):
+        item = dict(points=pred["pts_cam"])
+        if it.get("camera_slot") is not None:
+            item["slot"] = int(it["camera_slot"])
+        pitems.append(item)
+    projs = camera.project_batch(pitems)
+    out = []
+    for it, pred, proj in zip(items, preds, projs):
+        pix = proj["pixels"]
+        ok = proj["flags"] == 0
+        w, h = it.get("width", width), it.get("height", height)
+        if w is not None and h is not None:
+            with np.errstate(invalid="ignore"):
+                ok &= (pix[:, 0] >= 0) & (pix[:, 0] <= w - 1) & (pix[:, 1] >= 0) & (pix[:, 1] <= h - 1)
+        out.append((pred["ids"][ok].copy(), pix[ok].copy()))
+    return out
+
+
 def predict_pixels(fm, camera, frame_count, poses, ext, next_pose=None, fm_slot=0, camera_slot=None, width=None, height=None):
     """VINS-Fusion's predictPtsInNextFrame and setPrediction's projection composed: the tracks of slot `fm_slot` of the fm.FmHandle
     `fm` that have a depth and end at frame_count, moved into the camera of the next pose (FmHandle.predict_batch; next_pose None: the
     constant-velocity pose) and projected by camera slot `camera_slot` of the camera.CameraHandle `camera` (project_batch).  Returns
     (ids (m,) int64, pixels (m, 2) float64) of the predictions whose flag is 0 and, where width and height are given, whose pixel lies
     inside the image (0 <= u <= width - 1, 0 <= v <= height - 1): FeatureTracker.set_prediction's arguments."""
-    pred = fm.predict_batch([(fm_slot, frame_count, poses, ext, next_pose)])[0]
-    item = dict(points=pred["pts_cam"])
-    if camera_slot is not None:
-        item["slot"] = int(camera_slot)
-    proj = camera.project_batch([item])[0]
-    pix = proj["pixels"]
-    ok = proj["flags"] == 0
-    if width is not None and height is not None:
-        with np.errstate(invalid="ignore"):
-            ok &= (pix[:, 0] >= 0) & (pix[:, 0] <= width - 1) & (pix[:, 1] >= 0) & (pix[:, 1] <= height - 1)
-    return pred["ids"][ok].copy(), pix[ok].copy()
+    return predict_pixels_batch(fm, camera, [dict(frame_count=frame_count, poses=poses, ext=ext, next_pose=next_pose, fm_slot=fm_slot,
+                                                  camera_slot=camera_slot)], width=width, height=height)[0]
